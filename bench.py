@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- XFeat front-end throughput on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--height 480 --width 640]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--height 480 --width 640] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -12,8 +12,10 @@ A "step" is one pass of the extraction hot path (XFextractor::operator(), refere
 one batch of B distinct synthetic VGA frames per GPU, with the frames already resident in HBM and the 4096-row
 (keypoints, descriptors) records left in HBM (the task's rule for `value`); with N > 1 the step also moves the records
 with RCCL (frame i -> GPU i mod N; xfh_allgather_records by default, --gather root|compact for the cheaper
-forms) on the ctx's communication stream, overlapped with the next step.  `value` = frames/s over all GPUs.  In the same
-JSON line:
+forms) on the ctx's communication stream, overlapped with the next step.  `value` = frames/s over all GPUs, `ms_per_step` =
+milliseconds per timed step (K of them after W untimed ones).  A plain run does only that: set up, warm up, time the K steps,
+print the JSON line.  --dump-outputs DIR also writes the records of the last timed step as .npy files (dump_outputs below; the
+inputs are the same from run to run, so two builds can be compared output for output).  With --full the same JSON line carries:
   host_visible  SURVEY.md 8d read literally: the same frames from (pinned) HOST memory to records in HOST memory through
                 xfh_extract_batch_submit / _wait (csrc/pipeline.cpp), PCIe inside the clock, with the fraction of the PCIe rate
   roofline      dominant extraction kernel (3x3 64->64 at 1/8 resolution): algorithmic flops / average launch duration of the
@@ -137,7 +139,12 @@ def main():
                          "root = send/recv group into rank 0 only (rank 0 is the only consumer; an all-gather lands N x 298 MB per step in EVERY GPU), "
                          "compact = header + valid rows to rank 0")
     ap.add_argument("--force-comm", action="store_true", help="run the RCCL exchange also with one rank")
-    ap.add_argument("--no-legs", action="store_true", help="timed region only (no host_visible / configs3 / host_api / match / aux / cpu legs)")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline as well: the conv roofline (dispatch events inside the timed region, then an "
+                                                        "isolated run), the multi-rank legs and the extra legs (host_visible / configs3 / host_api / match / aux / cpu / parity); "
+                                                        "without it a run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write the records the last timed step produced as .npy files into DIR "
+                                                                        "(rank 0; float32 / float64, a fixed sample of frames, < 64 MB)")
+    ap.add_argument("--no-legs", action="store_true", help="with --full: timed region and conv roofline only (no host_visible / configs3 / host_api / match / aux / cpu legs)")
     ap.add_argument("--host-steps", type=int, default=24, help="steps of the host-visible leg (each: the same frames per GPU as a timed step)")
     ap.add_argument("--libtorch-leg", type=str, default="", help=argparse.SUPPRESS)        # child process of the cpu_baseline leg: "threads,threads,..."
     ap.add_argument("--only-match-leg", action="store_true", help="of the extra legs run the matcher ones only (short traces for the PMC passes)")
@@ -149,6 +156,8 @@ def main():
     args = ap.parse_args()
     if args.libtorch_leg:
         return libtorch_leg(args)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     rank = int(os.environ.get("RANK", 0)); local_rank = int(os.environ.get("LOCAL_RANK", 0))
     world = int(os.environ.get("WORLD_SIZE", 1))
@@ -252,7 +261,7 @@ def main():
     # reports the same average.  With several sub-batches in flight a launch shares the CUs with the other ctx' kernels, so
     # its duration is longer than the kernel's own speed: that one is measured after the region (`isolated`, one ctx alone).
     layer_mask = sum(1 << l for l in DOMINANT_LAYERS)
-    in_region = K * len(DOMINANT_LAYERS) <= 4096
+    in_region = args.full and K * len(DOMINANT_LAYERS) <= 4096
     if in_region:
         for c_ in ctxs:
             c_.timing_enable(capi.K["CONV_MFMA"], layer_mask)
@@ -265,18 +274,22 @@ def main():
     if use_comm:
         comm.synchronize()
     elapsed = sync(time.perf_counter() - t0)               # barrier; MAX over ranks
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, ctx, d_rec[(step_no[0] - 1) & 1 if use_comm else 0], S * B)
     n_conv, ms_conv = 0, 0.0
     if in_region:
         for c_ in ctxs:
             n_, ms_ = c_.timing_read()
             n_conv += n_; ms_conv += ms_
             c_.timing_enable(0)
-    ctx.timing_enable(capi.K["CONV_MFMA"], layer_mask)
-    for _ in range(min(K, 40)):
-        capi.check(lib.xfh_extract_batch_device(ctx.h, in_ptr, B, H, W, 0, 0, rec_ptr), ctx.h)
-    ctx.synchronize()
-    n_iso, ms_iso = ctx.timing_read()
-    ctx.timing_enable(0)
+    n_iso, ms_iso = 0, 0.0
+    if args.full:
+        ctx.timing_enable(capi.K["CONV_MFMA"], layer_mask)
+        for _ in range(min(K, 40)):
+            capi.check(lib.xfh_extract_batch_device(ctx.h, in_ptr, B, H, W, 0, 0, rec_ptr), ctx.h)
+        ctx.synchronize()
+        n_iso, ms_iso = ctx.timing_read()
+        ctx.timing_enable(0)
     frames_per_s = N * B * S * K / elapsed
 
     def timed(fn, k, warm=2):
@@ -294,7 +307,7 @@ def main():
         return sync(time.perf_counter() - t_) / k
 
     multi = None
-    if use_comm and not args.no_legs:
+    if use_comm and args.full and not args.no_legs:
         multi = multi_rank_legs(args, lib, capi, synth, Context, xd, comm, ctx, blob, rank, N, dev, nf, rec_bytes, step, timed, gather, gather_target, B * S, step_no)
 
     if rank != 0:
@@ -311,7 +324,7 @@ def main():
         "value": frames_per_s, "unit": "frames/s", "n_gpus": N, "steps": K, "warmup": args.warmup,
         "ms_per_step": elapsed / K * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
         "dtype": "f32", "data": "synthetic",
-        "config": {"workload": f"configs[1], HBM-resident (host-visible: config.host_visible_frames_per_s): {H}x{W} u8 frames, XFeat extract, nfeatures {nf}, {B * S} distinct frames per GPU per step "
+        "config": {"workload": f"configs[1], HBM-resident (host-visible: {'config.host_visible_frames_per_s' if args.full else 'bench.py --full'}): {H}x{W} u8 frames, XFeat extract, nfeatures {nf}, {B * S} distinct frames per GPU per step "
                                f"({S} sub-batch(es) of {B}, each on its own ctx / HIP streams) ({BN_TEXT[args.bn]}), inputs and 4096-row records resident in HBM"
                                + (f", RCCL {GATHER_TEXT[args.gather]} through the C ABI (xfh_comm_*), overlapped with the next step" if use_comm else ""),
                    "frames_per_gpu_per_step": B * S, "sub_batches_in_flight": S, "height": H, "width": W, "nfeatures": nf,
@@ -346,22 +359,23 @@ def main():
                                    "measured_GBps": (meas * frames_per_s / N / 1e9) if meas else None,
                                    "measured_frac": (meas * frames_per_s / N / 8e12) if meas else None,
                                    "note": "the step is bound by the vector / matrix pipe (frac above), not by HBM"}
-    kname = ("k_conv_mfma<64,64,3,...>" if B > 32 else "k_conv_mfma16<64,64,1,16,2,...> (16x16x4 tiles, the form for batches <= 32)") + " (block3.1, block_fusion.1: 3x3 64->64 at 1/8 res)" + ("" if args.bn != "folded" else ", bias+ReLU epilogue")
-    out["roofline"] = {"kernel": kname,
-                       "measured": f"HIP events attached to every dispatch of the kernel (hipExtLaunchKernelGGL): the same launches ({B} frames each) with ONE ctx alone on the GPU "
-                                   "right after the timed region -- the kernel's own duration, the view rocprofv3 --kernel-trace gives of a serial run (profiles/r06_roofline_table_B64.md: "
-                                   "`bench.py --streams 1 --batch 64 --serial-branch --only-match-leg` under rocprofv3, 191 us per launch on the box whose events read 192)",
-                       "bound": "mfma", "achieved": iso_tf, "peak": PEAK_F32_MFMA_TFLOPS, "unit": "TFLOP/s", "frac": iso_tf / PEAK_F32_MFMA_TFLOPS,
-                       "traffic": conv_traffic, "traffic_source": pmc_src if conv_traffic else None,
-                       "mfma_busy": pmc_busy("k_conv_mfma<64, 64, 3, 1, 4, 2, 1, 16, 1, 0") if B > 32 else None, "mfma_busy_source": PMC_BUSY_SRC,
-                       "avg_launch_us": iso_us, "launches": n_iso, "flops_per_launch": conv_flops(H, W) * B,
-                       "in_timed_region": {"note": "the same events inside the timed region, all ctx" + (f": {S} sub-batches are in flight, a launch shares the CUs with the other ctx' kernels, so this "
-                                                   "span is longer than the kernel's own speed (it measures neither the kernel nor the step)" if S > 1 else ""),
-                                           "achieved": conv_tf, "frac": conv_tf / PEAK_F32_MFMA_TFLOPS, "avg_launch_us": conv_us, "launches": n_conv}}
+    if args.full:
+        kname = ("k_conv_mfma<64,64,3,...>" if B > 32 else "k_conv_mfma16<64,64,1,16,2,...> (16x16x4 tiles, the form for batches <= 32)") + " (block3.1, block_fusion.1: 3x3 64->64 at 1/8 res)" + ("" if args.bn != "folded" else ", bias+ReLU epilogue")
+        out["roofline"] = {"kernel": kname,
+                           "measured": f"HIP events attached to every dispatch of the kernel (hipExtLaunchKernelGGL): the same launches ({B} frames each) with ONE ctx alone on the GPU "
+                                       "right after the timed region -- the kernel's own duration, the view rocprofv3 --kernel-trace gives of a serial run (profiles/r06_roofline_table_B64.md: "
+                                       "`bench.py --full --streams 1 --batch 64 --serial-branch --only-match-leg` under rocprofv3, 191 us per launch on the box whose events read 192)",
+                           "bound": "mfma", "achieved": iso_tf, "peak": PEAK_F32_MFMA_TFLOPS, "unit": "TFLOP/s", "frac": iso_tf / PEAK_F32_MFMA_TFLOPS,
+                           "traffic": conv_traffic, "traffic_source": pmc_src if conv_traffic else None,
+                           "mfma_busy": pmc_busy("k_conv_mfma<64, 64, 3, 1, 4, 2, 1, 16, 1, 0") if B > 32 else None, "mfma_busy_source": PMC_BUSY_SRC,
+                           "avg_launch_us": iso_us, "launches": n_iso, "flops_per_launch": conv_flops(H, W) * B,
+                           "in_timed_region": {"note": "the same events inside the timed region, all ctx" + (f": {S} sub-batches are in flight, a launch shares the CUs with the other ctx' kernels, so this "
+                                                       "span is longer than the kernel's own speed (it measures neither the kernel nor the step)" if S > 1 else ""),
+                                               "achieved": conv_tf, "frac": conv_tf / PEAK_F32_MFMA_TFLOPS, "avg_launch_us": conv_us, "launches": n_conv}}
     if multi is not None:
         out.update(multi)
 
-    if not args.no_legs:
+    if args.full and not args.no_legs:
         legs(out, args, lib, capi, synth, Context, ctx, blob, frames, d_in, d_rec[0], B, H, W, nf, rec_bytes, traffic, N)
 
     flat_scalars(out, N)
@@ -380,7 +394,7 @@ def flat_scalars(out, N):
     objects and drops nested ones: BENCH_r04.json lost `host_visible`, `match` and `step_roofline`).  `value` stays the HBM-resident regime -- the bench
     contract: "inputs already resident in HBM when the timed region starts ... the PCIe-inclusive rate is never `value`" -- and SURVEY.md 8d's host-visible
     reading of the same metric sits next to it."""
-    c, r = out["config"], out["roofline"]
+    c, r = out["config"], out.get("roofline", {})                                      # `roofline`: --full only
     c["hbm_resident_fps_per_gpu"] = out["value"] / N
     if "host_visible" in out:
         hv = out["host_visible"]
@@ -447,6 +461,26 @@ def flat_scalars(out, N):
              "frames_per_gpu_per_step", "sub_batches_in_flight", "bn_mode", "library"]
     out["config"] = {**{k: c[k] for k in first if k in c}, **{k: v for k, v in c.items() if k not in first}}
     assert all(len(k) <= 32 for k in out["config"]), [k for k in out["config"] if len(k) > 32]
+
+
+DUMP_FRAMES = 32      # frames of the last timed step whose keypoints and descriptors --dump-outputs writes (37 MB at 4096 rows)
+
+
+def dump_outputs(path, ctx, d_records, n_frames):
+    """--dump-outputs DIR: what a caller of the timed path receives from its last step, the 4096-row records of the step's frames, as
+    .npy files: header.npy float64 [n_frames, 3] (n_valid, mono_index, n_candidates of every frame); for a fixed, seeded sample of
+    DUMP_FRAMES frames (frame_index.npy, float64) keypoints.npy float32 [n, rows, 7] (x, y, size, angle, response, octave, class_id)
+    and descriptors.npy float32 [n, rows, 64].  The rows past n_valid are the record's padding, written by the kernels too."""
+    os.makedirs(path, exist_ok=True)
+    rb = ctx.rec_bytes
+    head = np.stack([d_records.download(np.int32, 3, i * rb) for i in range(n_frames)]).astype(np.float64)
+    pick = np.sort(np.random.default_rng(0).choice(n_frames, min(n_frames, DUMP_FRAMES), replace=False))
+    recs = [ctx.parse_records(d_records.download(np.uint8, rb, int(i) * rb), 1)[0] for i in pick]
+    kps = np.stack([np.stack([k[f].astype(np.float32) for f in k.dtype.names], -1) for k, *_ in recs])
+    np.save(os.path.join(path, "header.npy"), head)
+    np.save(os.path.join(path, "frame_index.npy"), pick.astype(np.float64))
+    np.save(os.path.join(path, "keypoints.npy"), kps)
+    np.save(os.path.join(path, "descriptors.npy"), np.stack([d for _, d, *_ in recs]).astype(np.float32))
 
 
 PCIE_GBPS = 63.0      # PCIe 5.0 x16, one direction, after 128b/130b (tools/pcie_probe.py on the bench box: 56.5 GB/s for one copy stream)

@@ -124,8 +124,8 @@ def test_scale_tables_match_reference_formula():
     assert sf.dtype == np.float32 and len(sf) == 8
 
 
-def test_cpp_dropin_compiles_and_links():
-    out = "/tmp/xfh_dropin_test"
+def test_cpp_dropin_compiles_and_links(tmp_path):
+    out = str(tmp_path / "xfh_dropin_test")
     cmd = ["g++", "-std=c++17", "-O1", "-Wall", "-I" + os.path.join(ROOT, "include"),
            os.path.join(ROOT, "tests", "cpp", "dropin_test.cpp"), "-L" + os.path.join(ROOT, "xfeatslam_amd"), "-lxfeat_hip",
            "-Wl,-rpath," + os.path.join(ROOT, "xfeatslam_amd"), "-Wl,-rpath,/opt/rocm/lib", "-o", out]
@@ -133,11 +133,11 @@ def test_cpp_dropin_compiles_and_links():
     assert r.returncode == 0, r.stderr
 
 
-def test_cpp_dropin_opencv_branch_compiles():
+def test_cpp_dropin_opencv_branch_compiles(tmp_path):
     """the wrappers' `#if XFEAT_HAVE_OPENCV` branch (the reference's cv::InputArray / cv::OutputArray signature, include/XFextractor.h:41-43) is
     type-checked by a compiler: tests/cpp/cv_branch_test.cpp against tests/stubs/opencv_api, an API-shaped stand-in for the few cv:: members
     the branch uses (NOT OpenCV: the image has none; tests/test_gpu_dropin_cpp.py runs the program)"""
-    out = "/tmp/xfh_cv_branch_test"
+    out = str(tmp_path / "xfh_cv_branch_test")
     cmd = ["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "tests", "stubs", "opencv_api"),
            os.path.join(ROOT, "tests", "cpp", "cv_branch_test.cpp"), "-L" + os.path.join(ROOT, "xfeatslam_amd"), "-lxfeat_hip",
            "-Wl,-rpath," + os.path.join(ROOT, "xfeatslam_amd"), "-Wl,-rpath,/opt/rocm/lib", "-o", out]

@@ -116,7 +116,7 @@ def test_bench_runs_with_n_ranks(gpu_lib, tmp_path, world):
     for r in range(world):
         env = dict(os.environ, RANK=str(r), LOCAL_RANK=str(r), WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
         env["XFH_RCCL_LIB"] = os.path.join(stub_dir, "librccl.so.1")           # explicit (comm.cpp: no fallback behind it)
-        procs.append(subprocess.Popen([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "3", "--warmup", "1", "--batch", "3", "--streams", "2",
+        procs.append(subprocess.Popen([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", str(world), "--steps", "3", "--warmup", "1", "--batch", "3", "--streams", "2",
                                        "--height", "96", "--width", "128", "--cpu-frames", "0", "--match-iters", "5", "--match-pairs", "2", "--host-steps", "3"],
                                       env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True))
     outs = []

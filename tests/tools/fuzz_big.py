@@ -1,6 +1,6 @@
 """larger seeded fuzz campaign against the oracle (development tool; `python tests/tools/fuzz_big.py SEED` on the GPU box)"""
-import sys, numpy as np
-sys.path.insert(0, "/root/repo")
+import os, sys, numpy as np
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 from xfeatslam_amd import capi, synth, weights as WT
 from xfeatslam_amd.extractor import Context
 from oracle import oracle as O

@@ -5,7 +5,7 @@ cp xfeatslam_amd/libxfeat_hip.so /tmp/keep_abs.so
 for v in A B; do
   cp tools/ab/$v.so xfeatslam_amd/libxfeat_hip.so
   rm -rf $O/prof_abs_$v
-  ( cd /tmp && timeout 300 rocprofv3 --kernel-trace --output-format csv -d $O/prof_abs_$v -o t -- python $R/bench.py --streams 1 --batch ${AB_BATCH:-256} --serial-branch --no-legs --steps 6 --warmup 2 ) > $O/prof_abs_$v.log 2>&1
+  ( cd /tmp && timeout 300 rocprofv3 --kernel-trace --output-format csv -d $O/prof_abs_$v -o t -- python $R/bench.py --full --streams 1 --batch ${AB_BATCH:-256} --serial-branch --no-legs --steps 6 --warmup 2 ) > $O/prof_abs_$v.log 2>&1
 done
 cp /tmp/keep_abs.so xfeatslam_amd/libxfeat_hip.so
 python - <<'PY'

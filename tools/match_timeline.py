@@ -1,5 +1,5 @@
 """GEMM / post durations and the gaps between them in the prepared-image match loop of a rocprofv3 kernel trace of
-`bench.py --only-match-leg` (the last 200 k_mnn_post launches that directly follow a k_mnn_gemm_img launch)."""
+`bench.py --full --only-match-leg` (the last 200 k_mnn_post launches that directly follow a k_mnn_gemm_img launch)."""
 import csv, sys
 rows = sorted(csv.DictReader(open(sys.argv[1])), key=lambda r: int(r["Start_Timestamp"]))
 seq = [(r["Kernel_Name"], int(r["Start_Timestamp"]), int(r["End_Timestamp"])) for r in rows if "k_mnn" in r["Kernel_Name"] or "k_rownorm" in r["Kernel_Name"]]

@@ -9,8 +9,8 @@ echo "[$(date +%T)] done: ( timeout 900 python -m pytest tests -m gpu -q 2>&1 | 
 ( timeout 100 tools/probes/dist_probe; python tools/dist_probe.py; python tools/dist_probe.py 1000 | tail -1 ) > $O/dist_probe.log 2>&1
 ( timeout 120 python -c "import __graft_entry__ as g; g.smoke()" ) > $O/smoke.log 2>&1
 echo "[$(date +%T)] done: ( timeout 120 python -c 'import __graft_entry__ as g; g.smok" >> $O/round_times.log
-( timeout 600 python bench.py ) > $O/bench_default.json 2> $O/bench_default.err
-echo "[$(date +%T)] done: ( timeout 600 python bench.py ) > O/bench_default.json 2> " >> $O/round_times.log
+( timeout 600 python bench.py --full ) > $O/bench_default.json 2> $O/bench_default.err
+echo "[$(date +%T)] done: ( timeout 600 python bench.py --full ) > O/bench_default.json 2> " >> $O/round_times.log
 ( timeout 200 tools/probes/mnn_seg_probe 200 ) > $O/mnn_seg_probe.log 2>&1
 echo "[$(date +%T)] done: ( timeout 200 tools/probes/mnn_seg_probe 200 ) > O/mnn_seg_" >> $O/round_times.log
 ( timeout 200 tools/probes/mnn_probe 200 ) > $O/mnn_probe.log 2>&1
@@ -22,15 +22,15 @@ echo "[$(date +%T)] done: ( timeout 300 bash tools/gemm_b2b.sh ) > /dev/null 2>&
 ( timeout 100 python tools/b1_modes.py ) > $O/b1_modes.log 2>&1
 echo "[$(date +%T)] done: ( timeout 100 python tools/b1_modes.py ) > O/b1_modes.log 2" >> $O/round_times.log
 rm -rf $O/prof $O/pmc_fetch $O/pmc_write $O/prof_serial $O/prof_serial64
-( cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o bench -- python $R/bench.py --steps 20 --match-warm-ms 10 --cpu-frames 0 ) > $O/bench_prof.json 2> $O/bench_prof.err
+( cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o bench -- python $R/bench.py --full --steps 20 --match-warm-ms 10 --cpu-frames 0 ) > $O/bench_prof.json 2> $O/bench_prof.err
 echo "[$(date +%T)] done: ( cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats --" >> $O/round_times.log
-( cd /tmp && timeout 600 rocprofv3 --kernel-trace --output-format csv -d $O/prof_serial -o bench -- python $R/bench.py --streams 1 --batch 256 --serial-branch --only-match-leg --steps 10 --warmup 3 --cpu-frames 0 ) > $O/bench_prof_serial.json 2> $O/bench_prof_serial.err
+( cd /tmp && timeout 600 rocprofv3 --kernel-trace --output-format csv -d $O/prof_serial -o bench -- python $R/bench.py --full --streams 1 --batch 256 --serial-branch --only-match-leg --steps 10 --warmup 3 --cpu-frames 0 ) > $O/bench_prof_serial.json 2> $O/bench_prof_serial.err
 echo "[$(date +%T)] done: ( cd /tmp && timeout 600 rocprofv3 --kernel-trace --output-f" >> $O/round_times.log
-( cd /tmp && timeout 600 rocprofv3 --kernel-trace --output-format csv -d $O/prof_serial64 -o bench -- python $R/bench.py --streams 1 --batch 64 --serial-branch --only-match-leg --steps 20 --warmup 3 --cpu-frames 0 ) > $O/bench_prof_serial64.json 2> $O/bench_prof_serial64.err
+( cd /tmp && timeout 600 rocprofv3 --kernel-trace --output-format csv -d $O/prof_serial64 -o bench -- python $R/bench.py --full --streams 1 --batch 64 --serial-branch --only-match-leg --steps 20 --warmup 3 --cpu-frames 0 ) > $O/bench_prof_serial64.json 2> $O/bench_prof_serial64.err
 echo "[$(date +%T)] done: ( cd /tmp && timeout 600 rocprofv3 --kernel-trace --output-f" >> $O/round_times.log
-( cd /tmp && timeout 600 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $O/pmc_fetch -o bench -- python $R/bench.py --steps 3 --warmup 1 --match-iters 10 --match-warm-ms 0 --cpu-frames 0 --only-match-leg ) > $O/pmc_fetch.json 2> $O/pmc_fetch.err
+( cd /tmp && timeout 600 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $O/pmc_fetch -o bench -- python $R/bench.py --full --steps 3 --warmup 1 --match-iters 10 --match-warm-ms 0 --cpu-frames 0 --only-match-leg ) > $O/pmc_fetch.json 2> $O/pmc_fetch.err
 echo "[$(date +%T)] done: ( cd /tmp && timeout 600 rocprofv3 --kernel-trace --pmc FETC" >> $O/round_times.log
-( cd /tmp && timeout 600 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $O/pmc_write -o bench -- python $R/bench.py --steps 3 --warmup 1 --match-iters 10 --match-warm-ms 0 --cpu-frames 0 --only-match-leg ) > $O/pmc_write.json 2> $O/pmc_write.err
+( cd /tmp && timeout 600 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $O/pmc_write -o bench -- python $R/bench.py --full --steps 3 --warmup 1 --match-iters 10 --match-warm-ms 0 --cpu-frames 0 --only-match-leg ) > $O/pmc_write.json 2> $O/pmc_write.err
 echo "[$(date +%T)] done: ( cd /tmp && timeout 600 rocprofv3 --kernel-trace --pmc WRIT" >> $O/round_times.log
 bash tools/pmc_calib.sh > $O/pmc_calib.out 2>&1
 echo "[$(date +%T)] done: bash tools/pmc_calib.sh > O/pmc_calib.out 2>&1" >> $O/round_times.log

@@ -1,8 +1,8 @@
 #!/usr/bin/env python
 """profiles/<tag>_roofline_table.md: every kernel of one bench step (256 frames, one ctx, one stream) against its bound.
 
-Input: the rocprofv3 kernel trace of `python bench.py --streams 1 --batch 256 --serial-branch` (gpurun_out/prof_serial/
-*kernel_trace.csv, tools/gpu_round.sh): one ctx with the keypoint branch on the main stream, so no two kernels overlap and a
+Input: the rocprofv3 kernel trace of `python bench.py --full --streams 1 --batch 256 --serial-branch` (prof_serial/*kernel_trace.csv
+in the output folder of tools/gpu_round.sh): one ctx with the keypoint branch on the main stream, so no two kernels overlap and a
 launch's duration is the kernel's own speed (the default bench runs four 64-frame ctx side by side, which is faster as a
 whole -- profiles/<tag>_bench_sweep.md -- but stretches every single launch).
 Launches are attributed to the batched steps by their grid (grid.z == B, or grid.x == B for the per-frame
@@ -122,7 +122,7 @@ def pmc_of(n):
     return None
 with open(out, "w") as o:
     o.write(f"# Every kernel of one bench step against its bound (B = {B} frames of {H}x{W}, one ctx, one stream, 1 x MI355X)\n\n"
-            f"Source: rocprofv3 --kernel-trace of `python bench.py --streams 1 --batch {B} --serial-branch` (all kernels serial on one stream; tools/gpu_round.sh), launches with the batched grid only; {steps} steps.  The matcher kernels (k_mnn_*, k_rownorm_img, k_dist_mfma, k_best2_csr, k_distinctive_csr) are the 4096 x 4096 legs of the same run.\n"
+            f"Source: rocprofv3 --kernel-trace of `python bench.py --full --streams 1 --batch {B} --serial-branch` (all kernels serial on one stream; tools/gpu_round.sh), launches with the batched grid only; {steps} steps.  The matcher kernels (k_mnn_*, k_rownorm_img, k_dist_mfma, k_best2_csr, k_distinctive_csr) are the 4096 x 4096 legs of the same run.\n"
             f"`alg` = algorithmic flops / HBM bytes per launch (raw input map read once + raw output map written once; no halo, no weights);\n"
             f"achieved = alg / average duration; % of the bound's peak (f32 MFMA {PEAK_TF} TFLOP/s, HBM {PEAK_TB} TB/s).  `latency` = per-frame single\n"
             f"workgroup or dependent-launch bound kernels (no meaningful roofline); `cache` = k_mnn_post[_batch], k_best2_csr, k_distinctive_csr: gathered rows / key planes out of tables that sit in L2 / Infinity Cache (no compulsory HBM bytes; the percentage is against the HBM rate for scale only).  Extraction kernels sum to {tot:.0f} us per step = {tot / B:.1f} us per frame.\n"
@@ -163,7 +163,7 @@ try:
         ksum = sum(sum(d) for n, d in agg2.items() if len(d) >= 0.9 * nsub) / 1e3 / nsub * S2
         with open(out, "a") as o:
             o.write(f"\n## The same step as the bench runs it: {S2} ctx of {B2} frames side by side\n\n"
-                    f"rocprofv3 --kernel-trace of the default `python bench.py` ({nsub} sub-batches of {B2} frames traced): the durations of one step's launches ({S2} sub-batches) add up to "
+                    f"rocprofv3 --kernel-trace of `python bench.py --full` ({nsub} sub-batches of {B2} frames traced): the durations of one step's launches ({S2} sub-batches) add up to "
                     f"**{ksum:.0f} us**, the step takes **{l2['ms_per_step'] * 1e3:.0f} us** of wall time in that run ({l2['value']:.0f} frames/s): with {S2} streams a launch shares the CUs with the other "
                     f"sub-batches' kernels, so every single launch is longer than in the serial table above ({tot:.0f} us for {B} frames on one stream = {tot / B * B2 * S2:.0f} us per {B2 * S2} frames), "
                     f"and the overlap of the streams (memory-bound kernels of one sub-batch beside the MFMA-bound ones of another) is what brings the wall time below the serial sum.\n")
