@@ -977,6 +977,7 @@ int xfh_debug_tensor(xfh_ctx* c, int id, int frame, float* out, size_t cap, size
     const size_t xs = (size_t)c->Hmax * c->Wmax;
     const int H = c->H, W = c->W, h8 = H / 8, w8 = W / 8, h4 = H / 4, w4 = W / 4;
     const float* src = nullptr; size_t n = 0;
+    if (!was_written(c, id)) return XFH_ERR_INVALID_ARG;          // block1.0's map, or a tensor the last call's regime did not write
     switch (id) {
         case XFH_T_X: src = c->X + frame * xs; n = (size_t)H * W; break;
         case XFH_T_XSTAT: src = c->xstat + frame * 2; n = 2; break;
@@ -987,7 +988,7 @@ int xfh_debug_tensor(xfh_ctx* c, int id, int frame, float* out, size_t cap, size
         default:
             if (id >= XFH_T_RAW0 && id < XFH_T_RAW0 + XFH_NUM_LAYERS) {
                 const int i = id - XFH_T_RAW0;
-                if (!c->raw[i]) return XFH_ERR_INVALID_ARG;                    // block1.0
+                if (!c->raw[i]) return XFH_ERR_INVALID_ARG;
                 src = c->raw[i] + frame * c->raw_stride[i]; n = (size_t)c->lh[i] * c->lw[i] * XFH_LAYERS[i].cout;
             } else if (id >= XFH_T_STAT0 && id < XFH_T_STAT0 + XFH_NUM_LAYERS) {
                 const int i = id - XFH_T_STAT0;

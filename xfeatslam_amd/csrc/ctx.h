@@ -68,6 +68,9 @@ struct xfh_ctx {
     int B = 0, H0 = 0, W0 = 0, H = 0, W = 0;
     int lh[XFH_NUM_LAYERS] = {}, lw[XFH_NUM_LAYERS] = {};     // output dims per layer
     int npart[XFH_NUM_LAYERS] = {};                            // stat partials per frame per layer
+    // debug tensor ids (XFH_T_*, < 128) that the last extract call wrote: set where the writing launch is issued, cleared at the start of
+    // every call; xfh_debug_tensor refuses the others (a buffer the regime skips still holds an earlier call's values)
+    unsigned long long written[2] = {0ull, 0ull};
 
     // device buffers, all [max_batch][...]
     uint8_t* d_gray = nullptr;                  // staging of host frames
@@ -154,6 +157,9 @@ inline void launch_k(xfh_ctx* c, int kernel_id, int layer, K kern, dim3 grid, di
             done_mask_.fetch_or(bit_, std::memory_order_release);                                              \
         }                                                                                                      \
     } while (0)
+
+inline void mark_written(xfh_ctx* c, int id) { c->written[id >> 6] |= 1ull << (id & 63); }
+inline bool was_written(const xfh_ctx* c, int id) { return id >= 0 && id < 128 && ((c->written[id >> 6] >> (id & 63)) & 1ull); }
 
 // launchers (kernels_*.hip)
 bool ride_mode(const xfh_ctx* c, int B);      // batches <= 8, batch statistics: the keypoint branch rides on block1.3 .. block3.0 (kernels_conv.hip)

@@ -1753,6 +1753,7 @@ StatSrc stat_src(xfh_ctx* c, int j, int B) {
     if (c->cfg.bn_mode == XFH_BN_BATCH_STATS && consumer_fold(B)) {
         s.part = c->part[j]; s.part_stride = c->part_stride[j]; s.npart = c->npart[j];
         s.count = (double)c->lh[j] * (double)c->lw[j]; s.stat_out = c->stat[j];
+        mark_written(c, XFH_T_STAT0 + j);           // workgroup 0 of each frame of the consumer publishes the folded statistics
     }
     return s;
 }
@@ -1885,9 +1886,11 @@ static hipError_t launch_basic_layer_t(xfh_ctx* c, int li, const float* in, size
     }
     if (e != hipSuccess) return e;
     c->npart[li] = np;
+    mark_written(c, XFH_T_RAW0 + li);
     if (running || consumer_fold(B)) return hipGetLastError();     // statistics from the weight file / folded by the consumers
     hipLaunchKernelGGL(k_bn_finalize, dim3(B), dim3(256), 0, c->stream, (const double*)c->part[li], c->part_stride[li], np,
                        L.cout, (double)Hout * (double)Wout, c->stat[li]);
+    mark_written(c, XFH_T_STAT0 + li);
     return hipGetLastError();
 }
 
@@ -1913,6 +1916,7 @@ static ConvArgs stats_layer_args(xfh_ctx* c, int li, const float* in, size_t in_
     a.tiles_x = (Wout + TW - 1) / TW;
     *ntile = a.tiles_x * ((Hout + TH - 1) / TH);
     c->npart[li] = *ntile;
+    mark_written(c, XFH_T_RAW0 + li);              // host and rider layers alike write their map
     return a;
 }
 template <int CIN, int COUT, int KS, int ST, int WM, int WN, int NT, int WW, int PRO, int CBMAX, int TPC, int RIDER, int EPI = EPI_STATS>
@@ -1986,8 +1990,10 @@ hipError_t launch_block1_stats(xfh_ctx* c, const StatSrc& xs, int H, int W, int 
     launch_k(c, XFH_K_CONV_DIRECT, 0, k_block1_stats, dim3(np, 1, B), dim3(256), 0, (const float*)c->X, xsz, xs, H, W,
              (W + L0S_TW - 1) / L0S_TW, (const float*)c->w.direct[0], c->part[0], c->part_stride[0], c->skip_pool, xsz / 16);
     hipError_t e = hipGetLastError();
+    mark_written(c, XFH_T_SKIP_POOL);
     if (e != hipSuccess || consumer_fold(B)) return e;
     hipLaunchKernelGGL(k_bn_finalize, dim3(B), dim3(256), 0, c->stream, (const double*)c->part[0], c->part_stride[0], np, 4, (double)H * (double)W, c->stat[0]);
+    mark_written(c, XFH_T_STAT0);
     return hipGetLastError();
 }
 
@@ -2030,6 +2036,7 @@ hipError_t launch_fusion_chain(xfh_ctx* c, int Hh, int Wh, int B, int* done) {
         a.out = c->raw[19]; a.out_stride = c->raw_stride[19];
         e = chain_launch<3, 4, PRO_BN, MID_BIAS_STORE, EPI_BIAS_RELU>(c, ca, B, &np, 19);
         if (e != hipSuccess) return e;
+        mark_written(c, XFH_T_FEATS); mark_written(c, XFH_T_RAW0 + 19);          // heatmap_head.0's map is handed on only
         c->lh[18] = Hh; c->lw[18] = Wh; c->npart[18] = np; c->lh[19] = Hh; c->lw[19] = Wh; c->npart[19] = np;
         *done = 2;
         return hipSuccess;
@@ -2040,6 +2047,7 @@ hipError_t launch_fusion_chain(xfh_ctx* c, int Hh, int Wh, int B, int* done) {
         a.out = c->raw[18]; a.out_stride = c->raw_stride[18]; a.part = c->part[18]; a.part_stride = c->part_stride[18];
         e = chain_launch<2, 4, PRO_BN, MID_BIAS_STORE, EPI_STATS, true>(c, ca, B, &np, 18);
         if (e != hipSuccess) return e;
+        mark_written(c, XFH_T_FEATS); mark_written(c, XFH_T_RAW0 + 18);
         c->lh[18] = Hh; c->lw[18] = Wh; c->npart[18] = np;
         *done = 1;
         return hipSuccess;
@@ -2048,10 +2056,13 @@ hipError_t launch_fusion_chain(xfh_ctx* c, int Hh, int Wh, int B, int* done) {
         a.out = c->raw[18]; a.out_stride = c->raw_stride[18]; a.part = c->part[18]; a.part_stride = c->part_stride[18];
         e = chain_launch<2, 4, PRO_BN, MID_BIAS_STORE, EPI_STATS>(c, ca, B, &np, 18);
         if (e != hipSuccess) return e;
+        mark_written(c, XFH_T_FEATS); mark_written(c, XFH_T_RAW0 + 18);
         c->lh[18] = Hh; c->lw[18] = Wh; c->npart[18] = np;
         *done = 1;
-        if (c->cfg.bn_mode == XFH_BN_BATCH_STATS)
+        if (c->cfg.bn_mode == XFH_BN_BATCH_STATS) {
             hipLaunchKernelGGL(k_bn_finalize, dim3(B), dim3(256), 0, c->stream, (const double*)c->part[18], c->part_stride[18], np, 64, (double)Hh * (double)Wh, c->stat[18]);
+            mark_written(c, XFH_T_STAT0 + 18);
+        }
         return hipGetLastError();
     }
     // folded BatchNorms: more layers could follow in the same pass (heatmap_head.1 here; keypoint_head.0 -> .1 -> .2).  Measured at
@@ -2062,6 +2073,7 @@ hipError_t launch_fusion_chain(xfh_ctx* c, int Hh, int Wh, int B, int* done) {
     a.out = c->raw[18]; a.out_stride = c->raw_stride[18];
     e = chain_launch<2, 4, PRO_BN, MID_BIAS_STORE, EPI_BIAS_RELU>(c, ca, B, &np, 18);
     if (e != hipSuccess) return e;
+    mark_written(c, XFH_T_FEATS); mark_written(c, XFH_T_RAW0 + 18);
     c->lh[18] = Hh; c->lw[18] = Wh; c->npart[18] = np;
     *done = 1;
     return hipSuccess;
@@ -2071,5 +2083,6 @@ hipError_t launch_fusion_chain(xfh_ctx* c, int Hh, int Wh, int B, int* done) {
 hipError_t launch_finalize_image(xfh_ctx* c, int B, int npart, double count) {
     hipLaunchKernelGGL(k_bn_finalize, dim3(B), dim3(256), 0, c->stream, (const double*)c->pre_part,
                        (size_t)c->pre_npart * 2, npart, 1, count, c->xstat);
+    mark_written(c, XFH_T_XSTAT);
     return hipGetLastError();
 }

@@ -918,14 +918,19 @@ hipError_t run_extract(xfh_ctx* c, const uint8_t* d_gray, int B, int H0, int W0,
     const size_t rec = xfh_record_bytes(nf);
     const bool resc = (c->cfg.flags & XFH_FLAG_RESCALE_KEYPOINTS) != 0;
     const float rw = resc ? (float)((double)W0 / (double)W) : 1.0f, rh = resc ? (float)((double)H0 / (double)H) : 1.0f;
+    c->written[0] = c->written[1] = 0ull;
+    if (c->cfg.bn_mode != XFH_BN_BATCH_STATS)                    // eval() modes: every frame's statistics slots hold the weight file's values (or the identity)
+        for (int i = 0; i < XFH_NUM_LAYERS; ++i) mark_written(c, XFH_T_STAT0 + i);
 
     // image -> float, resize, InstanceNorm statistics
     const int npre = (H * W + 1023) / 1024;
     launch_k(c, XFH_K_PREPROC, -1, k_preproc, dim3(npre, 1, B), dim3(256), 0, d_gray, (size_t)H0 * W0, H0, W0, H, W, c->X, xs, c->pre_part, c->pre_npart, c->cand_count);
     CK(hipGetLastError());
+    mark_written(c, XFH_T_X);
     StatSrc xsrc{};
     xsrc.stat = c->xstat;
-    if (consumer_fold(B)) { xsrc.part = c->pre_part; xsrc.part_stride = (size_t)c->pre_npart * 2; xsrc.npart = npre; xsrc.count = (double)H * (double)W; xsrc.stat_out = c->xstat; }
+    if (consumer_fold(B)) { xsrc.part = c->pre_part; xsrc.part_stride = (size_t)c->pre_npart * 2; xsrc.npart = npre; xsrc.count = (double)H * (double)W; xsrc.stat_out = c->xstat;
+                            mark_written(c, XFH_T_XSTAT); }      // published by k_block1_stats / k_norm_aux
     else CK(launch_finalize_image(c, B, npre, (double)H * (double)W));
     // skip1's AvgPool4 of the normalised image (and, for B <= 8, the published image statistics): in the reference's batch-statistics
     // mode k_block1_stats produces both on its one pass over the image; with eval() statistics that kernel is not needed and
@@ -934,6 +939,7 @@ hipError_t run_extract(xfh_ctx* c, const uint8_t* d_gray, int B, int H0, int W0,
     else {
         hipLaunchKernelGGL(k_norm_aux, dim3((h4 * w4 + 255) / 256, 1, B), dim3(256), 0, s, c->X, xs, xsrc, H, W, c->skip_pool, xs / 16);
         CK(hipGetLastError());
+        mark_written(c, XFH_T_SKIP_POOL);
     }
     // keypoint branch (keypoint_head.0-3 on unfold2d(x), softmax, depth-to-space) on the second stream: it only needs
     // the normalised image, so it runs beside the backbone (memory-bound 1x1 layers next to MFMA-bound 3x3 layers)
@@ -956,6 +962,7 @@ hipError_t run_extract(xfh_ctx* c, const uint8_t* d_gray, int B, int H0, int W0,
             launch_k(c, XFH_K_HEADS, -1, k_heads_kp, dim3((h8 * w8 + HF_PX - 1) / HF_PX, 1, B), dim3(HF_PX), 0,
                      (const float*)c->raw[22], stat_src(c, 22, B), c->raw_stride[22], (const float*)c->w.kp3_w, (const float*)c->w.kp3_b, h8, w8, c->K1h, xs);
             e = hipGetLastError();
+            mark_written(c, XFH_T_K1H);
         }
         c->stream = s;
         // the fork is always joined, also on an error path: the main stream must not run ahead of (or be destroyed before) the branch
@@ -973,6 +980,7 @@ hipError_t run_extract(xfh_ctx* c, const uint8_t* d_gray, int B, int H0, int W0,
         CK(launch_layer_with_rider(c, 4, c->raw[3], c->raw_stride[3], 3, PRO_B2IN, h4, w4, B, c->K1h, xs));
         CK(launch_layer_with_rider(c, 5, c->raw[4], c->raw_stride[4], 4, PRO_BN, h4, w4, B, c->K1h, xs));
         CK(launch_layer_with_rider(c, 6, c->raw[5], c->raw_stride[5], 5, PRO_BN, h4, w4, B, c->K1h, xs));
+        mark_written(c, XFH_T_K1H);                                          // keypoint_head.3 + softmax ride on block3.0
     } else {
     CK(launch_basic_layer(c, 3, c->raw[2], c->raw_stride[2], 2, PRO_BN, c->lh[2], c->lw[2], B));
     // block2 (block2.0 adds skip1(x) to x1 while staging), block3
@@ -1001,6 +1009,7 @@ hipError_t run_extract(xfh_ctx* c, const uint8_t* d_gray, int B, int H0, int W0,
     if (consumer_fold(B) && !c->no_nms_heat) return hipGetLastError();           // small batches: heatmap_head.2 + sigmoid are computed inside k_nms_score
     hipLaunchKernelGGL(k_heads_heat, dim3((h8 * w8 + HF_PX - 1) / HF_PX, 1, B), dim3(HF_PX), 0, s,
                        (const float*)c->raw[19], stat_src(c, 19, B), c->raw_stride[19], (const float*)c->w.heat2_w, (const float*)c->w.heat2_b, h8 * w8, c->H1, xs / 64);
+    mark_written(c, XFH_T_H1);
     return hipGetLastError();
     };
     {
@@ -1011,12 +1020,13 @@ hipError_t run_extract(xfh_ctx* c, const uint8_t* d_gray, int B, int H0, int W0,
     // NMS + score, top-k + placement, descriptors
     const int nms_blocks = ((W + NMS_TW - 1) / NMS_TW) * ((H + NMS_TH - 1) / NMS_TH);
     const int fn_blocks = consumer_fold(B) ? (h8 * w8 + 255) / 256 : 0;          // small batches: the feature norms ride on this launch
-    if (fn_blocks && !c->no_nms_heat)
+    if (fn_blocks && !c->no_nms_heat) {
+        mark_written(c, XFH_T_H1);                                           // heatmap_head.2 + sigmoid inside the NMS launch
         launch_k(c, XFH_K_NMS, -1, k_nms_score<true>, dim3(nms_blocks + fn_blocks, 1, B), dim3(256), 0, c->K1h, xs, c->H1, xs / 64,
                        H, W, c->cfg.nms_threshold, c->cand, c->cand_cap, c->cand_count,
                        nms_blocks, (const float*)c->feats, c->raw_stride[17], h8 * w8, c->feat_nrm, xs / 64,
                        fn_blocks ? (const float*)c->raw[19] : (const float*)nullptr, stat_src(c, 19, B), c->raw_stride[19], (const float*)c->w.heat2_w, (const float*)c->w.heat2_b, c->H1);
-    else
+    } else
         launch_k(c, XFH_K_NMS, -1, k_nms_score<false>, dim3(nms_blocks + fn_blocks, 1, B), dim3(256), 0, c->K1h, xs, c->H1, xs / 64,
                        H, W, c->cfg.nms_threshold, c->cand, c->cand_cap, c->cand_count,
                        nms_blocks, (const float*)c->feats, c->raw_stride[17], h8 * w8, c->feat_nrm, xs / 64,
@@ -1032,6 +1042,7 @@ hipError_t run_extract(xfh_ctx* c, const uint8_t* d_gray, int B, int H0, int W0,
                  lap0, lap1, rw, c->slot_src, c->sel_key, c->sel_n, d_records, rec);
     }
     CK(hipGetLastError());
+    mark_written(c, XFH_T_SEL);
     if (!fn_blocks) {
         hipLaunchKernelGGL(k_feat_norm, dim3((h8 * w8 + 255) / 256, 1, B), dim3(256), 0, s, (const float*)c->feats, c->raw_stride[17], h8 * w8, c->feat_nrm, xs / 64);
         CK(hipGetLastError());
