@@ -17,6 +17,9 @@ kernels_misc.hip, run_extract):
                                                 bias + ReLU epilogue) | 720p B = 1 folded (k_conv_mfma16 tall tiles, folded riders)
   ctx reused at smaller sizes                   one ctx of 720x1280 x 8: 720p B8 -> 170x230 B3 -> 480x640 B1 -> 720p B2
 
+Every checked frame's tail (tests/fp64_tail.py) is checked too, from the same device tensors and the call's records with a lapping
+area: k_nms_score<true> (B <= 8) and <false> (B > 8), k_select at nfeatures = 512, k_desc with its padding slots.
+
 Every call gets frames no earlier call of its ctx has seen (a seed per call), mixed image families and a constant frame in every
 batched case, so a tensor the regime did not write, or a statistic / tile taken from the wrong frame, cannot pass.  The log prints
 max err/tol per stage and case and the module's wall time.
@@ -27,6 +30,7 @@ import numpy as np
 import pytest
 
 import fp64_layers as F
+import fp64_tail as FT
 from xfeatslam_amd import capi, synth, weights as WT
 from xfeatslam_amd.extractor import Context
 
@@ -89,16 +93,24 @@ def _getter(ctx, b):
 
 
 def run_case(ctx, case, frames, wt, mode):
-    """one extract call on `ctx`, then every checked frame against the reference; returns the stages the call refused"""
+    """one extract call on `ctx`, then every checked frame against the reference -- the forward pass (fp64_layers) and the tail
+    from the same tensors and the call's records (fp64_tail: NMS, scores, selection, record, descriptors); returns the stages the
+    call refused"""
     B, H, W = frames.shape
-    ctx.extract_batch(frames)
+    lap = (W // 4, W // 2)                                  # a lapping area: front and back slots
+    recs = ctx.extract_batch(frames, lap)
     refused = set()
+    ties = []
     for b in _check_frames(B, H, W):
-        fc = F.FrameCheck(_getter(ctx, b), frames[b], wt, mode, REPORT, case, b)
+        get = _getter(ctx, b)
+        fc = F.FrameCheck(get, frames[b], wt, mode, REPORT, case, b)
         fc.run()
         refused |= set(fc.missing)
         with pytest.raises(capi.XfhError):
             ctx.debug_tensor(capi.T["RAW0"], b)             # block1.0's map is never written
+        tc = FT.check_frame(get, recs[b], ctx.nfeatures, lap, (H, W), report=REPORT, case=case, frame=b)
+        ties.append(f"{b}:C={tc.n_candidates},N={len(tc.ss)},near-ties={tc.near_ties}")
+    print(f"{case}: tail " + " ".join(ties))
     for line in REPORT.lines(case):
         print(line)
     bad = [(c, s, v) for (c, s), v in REPORT.failures() if c == case]
@@ -163,7 +175,7 @@ def test_one_ctx_at_changing_sizes(gpu_lib):
 def test_zz_margins_over_the_matrix():
     """worst err/tol per stage over every case above (runs last in this module), and the module's wall time"""
     print(f"\nworst err/tol per stage over {len({c for c, _ in REPORT.rows})} cases:")
-    for st, (case, v) in sorted(REPORT.worst_by_stage().items(), key=lambda kv: F.STAGES.index(kv[0])):
+    for st, (case, v) in sorted(REPORT.worst_by_stage().items(), key=lambda kv: (F.STAGES + FT.STAGES).index(kv[0])):
         print(F.Report.fmt(case, st, v))
     print(f"test_gpu_layers wall time {time.time() - _t0:.1f} s")
     REPORT.assert_ok()
