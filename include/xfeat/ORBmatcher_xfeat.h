@@ -6,6 +6,9 @@
  *   void match(cv::Mat d1, cv::Mat d2, std::vector<cv::DMatch>& out)    -- declared :77, the
  *        definition is commented out in the reference (ORBmatcher.cc:340-405); this supplies it.
  *   TH_LOW / TH_HIGH                                                    -- ORBmatcher.cc:34-35
+ *   XFgrid / XFmatcher::searchWindow: Frame::AssignFeaturesToGrid + GetFeaturesInArea (Frame.cc:569-599, 850-916) and the
+ *        loop of SearchByProjection (ORBmatcher.cc:1925-1955) on the GPU: a frame grid in device memory and one fused
+ *        window -> candidates -> best two call for all queries
  *   best2 / distinctive: the batched inner loops of SearchBy* (ORBmatcher.cc:75-119) and of
  *        MapPoint::ComputeDistinctiveDescriptors (MapPoint.cc:329-403)
  *
@@ -16,6 +19,10 @@
 #define XFEAT_ORBMATCHER_XFEAT_H
 
 #include "XFextractor.h"
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
 
 namespace xfeat {
 #if !XFEAT_HAVE_OPENCV
@@ -30,6 +37,112 @@ struct DMatch {
 }  // namespace xfeat
 
 namespace ORB_SLAM3 {
+
+// The frame grid of one frame in device memory (xfh_grid_build_device; Frame::AssignFeaturesToGrid, Frame.cc:569-599): owns the
+// blob.  build() uploads a host keypoint vector (all slots are binned, padding included, as the reference does);
+// buildFromRecord() takes the keypoints straight from an extraction record that is already in device memory (flags:
+// XFH_GRID_SKIP_PADDING leaves the padding slots out).  featuresInArea() is Frame::GetFeaturesInArea (Frame.cc:850-916) on a host
+// copy of the grid, for callers that still want the index list; XFmatcher::searchWindow never needs it.
+class XFgrid {
+public:
+    using KeyPoint = xfeat::cvx::KeyPoint;
+    explicit XFgrid(xfh_ctx* shared_ctx) : ctx(shared_ctx) {}
+    ~XFgrid() { if (d_grid) xfh_dev_free(d_grid); if (d_kps) xfh_dev_free(d_kps); }
+    XFgrid(const XFgrid&) = delete;
+    XFgrid& operator=(const XFgrid&) = delete;
+
+    void build(const std::vector<KeyPoint>& keys, const xfh_grid_bounds& bounds) {
+        static_assert(sizeof(KeyPoint) == sizeof(xfh_keypoint), "KeyPoint must mirror xfh_keypoint");
+        const int count = (int)keys.size();
+        reserve(count, true);
+        if (count > 0 && xfh_memcpy_h2d(d_kps, keys.data(), (size_t)count * sizeof(xfh_keypoint)) != XFH_OK) throw std::runtime_error("XFgrid::build: upload failed");
+        finish(xfh_grid_build_device(ctx, (const xfh_keypoint*)d_kps, count, nullptr, &bounds, 0, d_grid), count, bounds);
+        host_x.resize(count); host_y.resize(count);
+        for (int i = 0; i < count; ++i) { host_x[i] = keys[i].pt.x; host_y[i] = keys[i].pt.y; }
+    }
+    // d_record: one record of `nfeatures` slots in device memory (xfh_extract_batch_device)
+    void buildFromRecord(const void* d_record, int nfeatures, const xfh_grid_bounds& bounds, int flags = 0) {
+        reserve(nfeatures, false);
+        finish(xfh_grid_build_device(ctx, (const xfh_keypoint*)((const char*)d_record + xfh_record_kps_offset()), nfeatures, d_record, &bounds, flags, d_grid),
+               nfeatures, bounds);
+        host_x.clear(); host_y.clear();
+    }
+    const void* device() const { return d_grid; }
+    int size() const { return n; }
+
+    // Frame::GetFeaturesInArea on the host copy (downloaded and unpacked at the first call after a build): indices in the
+    // reference's visiting order
+    std::vector<size_t> featuresInArea(float u, float v, float r) {
+        std::vector<size_t> out;
+        if (!d_grid) return out;
+        unpack();
+        if (!(std::isfinite(u) && std::isfinite(v) && std::isfinite(r))) return out;
+        const float inv_w = (float)XFH_GRID_COLS / (b.max_x - b.min_x), inv_h = (float)XFH_GRID_ROWS / (b.max_y - b.min_y);
+        auto sat = [](float f, int hi) { return (int)std::fmin(std::fmax(f, -1.0f), (float)hi); };
+        const int c0x = std::max(0, sat(std::floor((u - b.min_x - r) * inv_w), XFH_GRID_COLS));
+        if (c0x >= XFH_GRID_COLS) return out;
+        const int c1x = std::min(XFH_GRID_COLS - 1, sat(std::ceil((u - b.min_x + r) * inv_w), XFH_GRID_COLS));
+        if (c1x < 0) return out;
+        const int c0y = std::max(0, sat(std::floor((v - b.min_y - r) * inv_h), XFH_GRID_ROWS));
+        if (c0y >= XFH_GRID_ROWS) return out;
+        const int c1y = std::min(XFH_GRID_ROWS - 1, sat(std::ceil((v - b.min_y + r) * inv_h), XFH_GRID_ROWS));
+        if (c1y < 0) return out;
+        for (int ix = c0x; ix <= c1x; ++ix)
+            for (int p = cell_start[ix * XFH_GRID_ROWS + c0y]; c1y >= c0y && p < cell_start[ix * XFH_GRID_ROWS + c1y + 1]; ++p) {
+                const int k = items[p];
+                if (std::fabs(host_x[k] - u) < r && std::fabs(host_y[k] - v) < r) out.push_back((size_t)k);
+            }
+        return out;
+    }
+
+private:
+    void reserve(int count, bool with_kps) {
+        const size_t gb = xfh_grid_bytes(count), kb = (size_t)(count > 0 ? count : 1) * sizeof(xfh_keypoint);
+        if (gb > grid_cap) {
+            if (d_grid) xfh_dev_free(d_grid);
+            d_grid = nullptr; grid_cap = 0;
+            if (xfh_dev_alloc(&d_grid, gb) != XFH_OK) throw std::runtime_error("XFgrid: out of device memory");
+            grid_cap = gb;
+        }
+        if (with_kps && kb > kps_cap) {
+            if (d_kps) xfh_dev_free(d_kps);
+            d_kps = nullptr; kps_cap = 0;
+            if (xfh_dev_alloc(&d_kps, kb) != XFH_OK) throw std::runtime_error("XFgrid: out of device memory");
+            kps_cap = kb;
+        }
+    }
+    void finish(int rc, int count, const xfh_grid_bounds& bounds) {
+        if (rc != XFH_OK) throw std::runtime_error(std::string("XFgrid: ") + xfh_strerror(rc));
+        n = count; b = bounds; unpacked = false;
+    }
+    void unpack() {
+        if (unpacked) return;
+        std::vector<unsigned char> blob(xfh_grid_bytes(n));
+        int rc = xfh_synchronize(ctx);
+        if (rc == XFH_OK) rc = xfh_memcpy_d2h(blob.data(), d_grid, blob.size());
+        cell_start.assign(XFH_GRID_COLS * XFH_GRID_ROWS + 1, 0); items.assign(n > 0 ? n : 1, -1);
+        int nb = 0;
+        if (rc == XFH_OK) rc = xfh_grid_unpack(blob.data(), blob.size(), n, cell_start.data(), items.data(), &nb);
+        if (rc != XFH_OK) throw std::runtime_error(std::string("XFgrid::featuresInArea: ") + xfh_strerror(rc));
+        if (host_x.empty() && n > 0) {                      // built from a record: the coordinates travel in the blob's items (slot, x, y, pad)
+            host_x.assign(n, 0.f); host_y.assign(n, 0.f);
+            for (int p = 0; p < nb; ++p) {
+                float xy[2];
+                memcpy(xy, blob.data() + (blob.size() - (size_t)n * 16) + (size_t)p * 16 + 4, 8);
+                host_x[items[p]] = xy[0]; host_y[items[p]] = xy[1];
+            }
+        }
+        unpacked = true;
+    }
+    xfh_ctx* ctx;
+    void* d_grid = nullptr; size_t grid_cap = 0;
+    void* d_kps = nullptr; size_t kps_cap = 0;
+    int n = 0;
+    xfh_grid_bounds b = {0.f, 0.f, 1.f, 1.f};
+    bool unpacked = false;
+    std::vector<int> cell_start, items;
+    std::vector<float> host_x, host_y;
+};
 
 class XFmatcher {
 public:
@@ -143,6 +256,50 @@ public:
         const int rc = xfh_best2_csr(ctx, queries.template ptr<float>(0), nq, targets.template ptr<float>(0), targets.rows,
                                      offsets.data(), indices.data(), initDist, bestIdx.data(), bestDist.data(), secondIdx.data(), secondDist.data());
         if (rc != XFH_OK) throw std::runtime_error(std::string("XFmatcher::best2: ") + xfh_strerror(rc));
+    }
+
+    // The windowed search of SearchByProjection (ORBmatcher.cc:1925-1955 / :82-119) for ALL queries in one call: query q is row q
+    // of `queries` at (u, v, r) = uvr[3q .. 3q + 2]; its candidates are the keypoints of `grid` inside the window
+    // (Frame::GetFeaturesInArea), minus those with skip[k] != 0 ("already has a map point with observations", :1931-1933) and, when
+    // uright / urQuery are given, minus those with uright[k] > 0 && |urQuery[q] - uright[k]| > r (:1935-1941); best / second best
+    // DescriptorDistance in visiting order as best2().  nCandidates[q] = candidates that were compared (`if (vIndices2.empty()) continue`).
+    // `targets`: the descriptor rows of the grid's frame (rows == grid.size()).  Blocks until the result is on the host.
+    void searchWindow(const Mat& queries, const std::vector<float>& uvr, const XFgrid& grid, const Mat& targets,
+                      std::vector<int>& bestIdx, std::vector<int>& bestDist, std::vector<int>& secondIdx, std::vector<int>& secondDist,
+                      std::vector<int>& nCandidates, int initDist = 256, const std::vector<unsigned char>* skip = nullptr,
+                      const std::vector<float>* uright = nullptr, const std::vector<float>* urQuery = nullptr) {
+        const int nq = queries.rows, nt = targets.rows;
+        bestIdx.assign(nq, -1); bestDist.assign(nq, initDist); secondIdx.assign(nq, -1); secondDist.assign(nq, initDist); nCandidates.assign(nq, 0);
+        if (nq == 0) return;
+        if ((int)uvr.size() != 3 * nq || nt != grid.size() || (skip && (int)skip->size() != nt) || (uright && (int)uright->size() != nt) ||
+            (urQuery && (int)urQuery->size() != nq) || ((uright != nullptr) != (urQuery != nullptr)))
+            throw std::runtime_error("XFmatcher::searchWindow: sizes do not fit");
+        auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+        const size_t bq = al((size_t)nq * 256), bu = al((size_t)nq * 12), bt = al((size_t)nt * 256 + 16), bs = al((size_t)nt + 16), bf = al((size_t)nt * 4 + 16), bn = al((size_t)nq * 4);
+        const size_t bytes = bq + bu + bt + bs + bf + 6 * bn;
+        if (bytes > d_out_bytes) {
+            if (d_out) xfh_dev_free(d_out);
+            d_out = nullptr; d_out_bytes = 0;
+            if (xfh_dev_alloc(&d_out, bytes) != XFH_OK) throw std::runtime_error("XFmatcher::searchWindow: out of device memory");
+            d_out_bytes = bytes;
+        }
+        char* p = (char*)d_out;
+        float* dq = (float*)p; p += bq; float* du = (float*)p; p += bu; float* dt = (float*)p; p += bt; unsigned char* ds = (unsigned char*)p; p += bs;
+        float* dr = (float*)p; p += bf; float* dz = (float*)p; p += bn;
+        int* o[5];
+        for (int k = 0; k < 5; ++k) { o[k] = (int*)p; p += bn; }
+        int rc = xfh_memcpy_h2d(dq, queries.template ptr<float>(0), (size_t)nq * 256);
+        if (rc == XFH_OK) rc = xfh_memcpy_h2d(du, uvr.data(), (size_t)nq * 12);
+        if (rc == XFH_OK && nt > 0) rc = xfh_memcpy_h2d(dt, targets.template ptr<float>(0), (size_t)nt * 256);
+        if (rc == XFH_OK && skip && nt > 0) rc = xfh_memcpy_h2d(ds, skip->data(), (size_t)nt);
+        if (rc == XFH_OK && uright && nt > 0) rc = xfh_memcpy_h2d(dr, uright->data(), (size_t)nt * 4);
+        if (rc == XFH_OK && urQuery) rc = xfh_memcpy_h2d(dz, urQuery->data(), (size_t)nq * 4);
+        if (rc == XFH_OK) rc = xfh_search_window_device(ctx, dq, du, nq, grid.device(), dt, nt, skip ? ds : nullptr, uright ? dr : nullptr, urQuery ? dz : nullptr,
+                                                        initDist, o[0], o[1], o[2], o[3], o[4]);
+        if (rc == XFH_OK) rc = xfh_synchronize(ctx);
+        int* out[5] = {bestIdx.data(), bestDist.data(), secondIdx.data(), secondDist.data(), nCandidates.data()};
+        for (int k = 0; k < 5 && rc == XFH_OK; ++k) rc = xfh_memcpy_d2h(out[k], o[k], (size_t)nq * 4);
+        if (rc != XFH_OK) throw std::runtime_error(std::string("XFmatcher::searchWindow: ") + xfh_strerror(rc));
     }
 
     // MapPoint::ComputeDistinctiveDescriptors (MapPoint.cc:329-403), batched over map points: group g observes the

@@ -250,6 +250,70 @@ int xfh_best2_csr_device(xfh_ctx* ctx, const float* d_queries, int nq, const flo
                          const int* d_offsets, const int* d_indices, int init_dist,
                          int* d_best_idx, int* d_best_dist, int* d_second_idx, int* d_second_dist);
 
+/* ---- frame grid + windowed search, device resident ------------------------------------------------------
+ * What the tracker runs every frame is not the dense match but the WINDOWED search: ORBmatcher::SearchByProjection(Frame, Frame)
+ * (ORBmatcher.cc:1861-1960, from TrackWithMotionModel), SearchByProjection(Frame, vector<MapPoint*>) (:42-130, SearchLocalPoints)
+ * and the relocalisation variants project a point to (u, v), ask Frame::GetFeaturesInArea(u, v, r) (Frame.cc:850-916) for the
+ * keypoints inside the window through the 64 x 48 grid that Frame::AssignFeaturesToGrid (:569-599) built, and run the best /
+ * second-best DescriptorDistance loop over them.  These calls keep all of it on the GPU: a grid per frame in device memory, built
+ * straight from extraction records, and one fused kernel "window -> candidates -> best two" per batch of queries.
+ *
+ * Grid (Frame.cc:569-599, PosInGrid :918-929, bounds and inverse cell sizes :336-341, :985-1001): the caller gives the bounds
+ * (0, 0, cols, rows for an undistorted camera; a caller with distortion passes undistorted keypoints and mnMinX .. mnMaxY);
+ * inv_w = 64.0f / (max_x - min_x), inv_h = 48.0f / (max_y - min_y) in fp32.  Keypoint i goes to cell
+ * (round((x - min_x) * inv_w), round((y - min_y) * inv_h)), round = roundf (half away from zero), and is NOT binned when a
+ * coordinate is < 0, >= 64 resp. >= 48: the reference rounds (it does not floor), so the right-most / bottom half cell of the
+ * image is lost; that is reproduced.  Inside a cell keypoints keep ascending slot order (push_back order).
+ * flags = 0 is the reference: all n slots are binned, padding included -- padding slots are default cv::KeyPoint() at (0, 0) and
+ * all land in cell (0, 0) (N = mvKeys.size(), Frame.cc:318).  With XFH_GRID_SKIP_PADDING and a record header, slots outside
+ * [0, mono_index) U [n - (n_valid - mono_index), n) are left out (the valid slots of xfh_match_records_device); the flag without
+ * a record is XFH_ERR_INVALID_ARG.
+ *
+ * The grid is an opaque, self-contained blob of xfh_grid_bytes(n) bytes in device memory owned by the caller (16-byte aligned):
+ * bounds, inverse cell sizes, cell_start, and per item slot number, x, y in cell order.  Two builds of the same input give
+ * identical bytes.  n <= XFH_GRID_MAX_N.
+ *   xfh_grid_build_device          one grid from n keypoints in device memory (d_record: the record they belong to, or NULL)
+ *   xfh_grid_build_records_device  B grids (grid b at d_grids + b * xfh_grid_bytes(nfeatures)) from B extraction records of this
+ *                                  ctx, ONE launch
+ *   xfh_grid_unpack                host, stateless: a blob copied out of device memory (nbytes of it) -> cell_start[64 * 48 + 1]
+ *                                  (cell = ix * 48 + iy), items[n] (slot numbers in cell order, -1 past *n_binned).  A truncated or
+ *                                  inconsistent blob is XFH_ERR_INVALID_ARG, never an out-of-bounds access.
+ *
+ * Search, per query q with (u, v, r) = d_uvr[3q .. 3q + 2] and descriptor row q of d_queries (GetFeaturesInArea + the loop of
+ * ORBmatcher.cc:1925-1955 / :82-119):
+ *   c0x = max(0, (int)floorf((u - min_x - r) * inv_w)), no candidates if >= 64; c1x = min(63, (int)ceilf((u - min_x + r) * inv_w)),
+ *   none if < 0; the same for y with 48 rows; cells ix = c0x .. c1x (outer), iy = c0y .. c1y (inner), a cell's keypoints in stored
+ *   order; keypoint k is a candidate when fabsf(x_k - u) < r && fabsf(y_k - v) < r (strict);
+ *   d_skip (optional, one byte per target, non-zero = skip): "already has a map point with observations" (:1931-1933), evaluated
+ *   by the caller; d_uright + d_ur_query (optional, both or neither): a candidate with uright[k] > 0 is skipped when
+ *   fabsf(ur_query[q] - uright[k]) > r (:1935-1941);
+ *   over the survivors in visiting order the rule and the result contract of xfh_best2_csr (best = second = init_dist, strict '<',
+ *   exact DescriptorDistance), indices = keypoint slot numbers.  A tie goes to the candidate visited FIRST, which is not the lowest
+ *   slot number.  n_candidates[q] = candidates that passed the window and the optional filters (`if (vIndices.empty()) continue`).
+ * Octave windows (minLevel / maxLevel) are not part of the interface: every XFeat keypoint has octave 0 and every level window the
+ * reference passes contains 0.  Where the reference is undefined -- (int) of a non-finite or huge float -- a query whose u, v or r is
+ * not finite has no candidates, and cell bounds saturate before the conversion; the kernel reads nothing outside the grid and the
+ * nt target rows whatever floats it is given.  d_targets / d_skip / d_uright are indexed by slot number: nt = the n of the grid.
+ * The _device calls take device pointers only and are asynchronous on the ctx stream: no host synchronisation, no allocation.
+ * xfh_search_window is the convenience form for host pointers (like xfh_best2_csr): stages the inputs, builds the grid of the nt
+ * keypoints (flags 0), searches and copies the five result arrays back. */
+#define XFH_GRID_COLS 64              /* FRAME_GRID_COLS, include/Frame.h:48 */
+#define XFH_GRID_ROWS 48              /* FRAME_GRID_ROWS, include/Frame.h:47 */
+#define XFH_GRID_SKIP_PADDING 1
+#define XFH_GRID_MAX_N 16384          /* keypoint slots per grid (the build sorts one frame's keys in the LDS of one workgroup) */
+typedef struct { float min_x, min_y, max_x, max_y; } xfh_grid_bounds;
+size_t xfh_grid_bytes(int n);
+int xfh_grid_build_device(xfh_ctx* ctx, const xfh_keypoint* d_kps, int n, const void* d_record_or_null, const xfh_grid_bounds* bounds,
+                          int flags, void* d_grid);
+int xfh_grid_build_records_device(xfh_ctx* ctx, const void* d_records, int B, const xfh_grid_bounds* bounds, int flags, void* d_grids);
+int xfh_grid_unpack(const void* host_copy_of_grid, size_t nbytes, int n, int* cell_start, int* items, int* n_binned);
+int xfh_search_window_device(xfh_ctx* ctx, const float* d_queries, const float* d_uvr, int nq, const void* d_grid, const float* d_targets, int nt,
+                             const uint8_t* d_skip_or_null, const float* d_uright_or_null, const float* d_ur_query_or_null, int init_dist,
+                             int* d_best_idx, int* d_best_dist, int* d_second_idx, int* d_second_dist, int* d_n_candidates);
+int xfh_search_window(xfh_ctx* ctx, const float* queries, const float* uvr, int nq, const xfh_keypoint* kps, const xfh_grid_bounds* bounds,
+                      const float* targets, int nt, const uint8_t* skip_or_null, const float* uright_or_null, const float* ur_query_or_null,
+                      int init_dist, int* best_idx, int* best_dist, int* second_idx, int* second_dist, int* n_candidates);
+
 /* MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:329-403), batched over map points: group g observes the
  * descriptor rows indices[offsets[g] .. offsets[g+1]) of `table` (n_rows x 64).  Pairwise DescriptorDistance inside
  * the group (diagonal 0), per row the median sorted[(N-1)/2], and the FIRST row with the least median wins:

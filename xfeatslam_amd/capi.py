@@ -29,7 +29,7 @@ ERR_EMPTY_IMAGE = 2
 ERR_NO_DEVICE = 7
 ERR_COMM = 11
 
-K = dict(NONE=0, MNN_GEMM=1, CONV_MFMA=2, CONV_DIRECT=3, NMS=4, SELECT=5, DESC=6, HEADS=7, DIST_I32=8, PREPROC=9, BEST2=10, DISTINCTIVE=11, MNN_GEMM_SEG=12)
+K = dict(NONE=0, MNN_GEMM=1, CONV_MFMA=2, CONV_DIRECT=3, NMS=4, SELECT=5, DESC=6, HEADS=7, DIST_I32=8, PREPROC=9, BEST2=10, DISTINCTIVE=11, MNN_GEMM_SEG=12, GRID_BUILD=13, SEARCH_WINDOW=14)
 T = dict(X=0, XSTAT=1, SKIP_POOL=2, FEATS=6, H1=8, K1H=9, RAW0=16, STAT0=48, SEL=80)
 
 
@@ -38,6 +38,15 @@ class Config(C.Structure):
                 ("nfeatures", C.c_int32), ("max_batch", C.c_int32), ("bn_mode", C.c_int32),
                 ("nms_threshold", C.c_float), ("flags", C.c_int32), ("reserved", C.c_int32 * 7)]
 
+
+class GridBounds(C.Structure):
+    """xfh_grid_bounds: mnMinX, mnMinY, mnMaxX, mnMaxY of the frame (0, 0, cols, rows for an undistorted camera)"""
+    _fields_ = [("min_x", C.c_float), ("min_y", C.c_float), ("max_x", C.c_float), ("max_y", C.c_float)]
+
+
+GRID_COLS, GRID_ROWS = 64, 48
+GRID_SKIP_PADDING = 1
+GRID_MAX_N = 16384
 
 FLAG_RESCALE_KEYPOINTS = 1
 FLAG_SERIAL_BRANCH = 2
@@ -82,6 +91,12 @@ SYMBOLS = [
     ("xfh_distance_i32_device", _i, [_vp, _vp, _i, _vp, _i, _vp]),
     ("xfh_best2_csr", _i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
     ("xfh_best2_csr_device", _i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
+    ("xfh_grid_bytes", _sz, [_i]),
+    ("xfh_grid_build_device", _i, [_vp, _vp, _i, _vp, C.POINTER(GridBounds), _i, _vp]),
+    ("xfh_grid_build_records_device", _i, [_vp, _vp, _i, C.POINTER(GridBounds), _i, _vp]),
+    ("xfh_grid_unpack", _i, [_vp, _sz, _i, _vp, _vp, _pi]),
+    ("xfh_search_window_device", _i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    ("xfh_search_window", _i, [_vp, _vp, _vp, _i, _vp, C.POINTER(GridBounds), _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
     ("xfh_distinctive_csr", _i, [_vp, _vp, _i, _vp, _vp, _i, _vp, _vp]),
     ("xfh_distinctive_csr_device", _i, [_vp, _vp, _i, _vp, _vp, _i, _i, _vp, _vp]),
     ("xfh_comm_unique_id", _i, [_vp]),

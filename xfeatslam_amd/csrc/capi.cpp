@@ -3,6 +3,7 @@
 // compute entry point fails with XFH_ERR_NO_DEVICE / XFH_ERR_HIP.
 #include "ctx.h"
 #include "mnn_seg_plan.h"
+#include "window_layout.h"
 
 #include <dlfcn.h>
 #include <math.h>
@@ -80,7 +81,8 @@ const char* xfh_strerror(int s) {
 
 const char* xfh_kernel_name(int id) {
     static const char* n[XFH_K_COUNT] = {"none", "k_mnn_gemm", "k_conv_mfma", "k_conv_direct", "k_nms_score", "k_select",
-                                         "k_desc", "k_heads_kp", "k_dist_i32", "k_preproc", "k_best2_csr", "k_distinctive_csr", "k_mnn_gemm_seg"};
+                                         "k_desc", "k_heads_kp", "k_dist_i32", "k_preproc", "k_best2_csr", "k_distinctive_csr", "k_mnn_gemm_seg",
+                                         "k_grid_build", "k_search_window"};
     return (id >= 0 && id < XFH_K_COUNT) ? n[id] : "?";
 }
 
@@ -792,6 +794,120 @@ int xfh_best2_csr(xfh_ctx* c, const float* q, int nq, const float* tg, int nt, c
     HIPCK(c, hipMemcpyAsync(best_dist, o1, (size_t)nq * 4, hipMemcpyDeviceToHost, c->stream));
     HIPCK(c, hipMemcpyAsync(second_idx, o2, (size_t)nq * 4, hipMemcpyDeviceToHost, c->stream));
     HIPCK(c, hipMemcpyAsync(second_dist, o3, (size_t)nq * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCK(c, hipStreamSynchronize(c->stream));
+    return XFH_OK;
+}
+
+// ---- frame grid + windowed search (window_search.hip.h, window_layout.h) -----------------------------------
+size_t xfh_grid_bytes(int n) { return n < 0 ? 0 : (size_t)XFH_GRID_ITEMS_OFF + (size_t)n * sizeof(GridItem); }
+
+// mfGridElementWidthInv = FRAME_GRID_COLS / (mnMaxX - mnMinX), mfGridElementHeightInv likewise, in fp32 (Frame.cc:336-341)
+static bool grid_geom(const xfh_grid_bounds* b, GridGeom* g) {
+    if (!b || !isfinite(b->min_x) || !isfinite(b->min_y) || !isfinite(b->max_x) || !isfinite(b->max_y)) return false;
+    if (!(b->max_x > b->min_x) || !(b->max_y > b->min_y)) return false;
+    g->min_x = b->min_x; g->min_y = b->min_y; g->max_x = b->max_x; g->max_y = b->max_y;
+    g->inv_w = (float)XFH_GRID_COLS / (b->max_x - b->min_x);
+    g->inv_h = (float)XFH_GRID_ROWS / (b->max_y - b->min_y);
+    return isfinite(g->inv_w) && isfinite(g->inv_h) && g->inv_w > 0.0f && g->inv_h > 0.0f;
+}
+
+int xfh_grid_build_device(xfh_ctx* c, const xfh_keypoint* d_kps, int n, const void* d_record, const xfh_grid_bounds* bounds, int flags, void* d_grid) {
+    GridGeom g;
+    if (!c || n < 0 || n > XFH_GRID_MAX_N || !d_grid || (n > 0 && !d_kps) || (flags & ~XFH_GRID_SKIP_PADDING)) return XFH_ERR_INVALID_ARG;
+    if ((flags & XFH_GRID_SKIP_PADDING) && !d_record) return XFH_ERR_INVALID_ARG;          // which slots are padding is the record header's knowledge
+    if ((((uintptr_t)d_grid) & 15) || (((uintptr_t)d_kps) & 3) || (((uintptr_t)d_record) & 3) || !grid_geom(bounds, &g)) return XFH_ERR_INVALID_ARG;
+    HIPCK(c, hipSetDevice(c->cfg.device));
+    HIPCK(c, launch_grid_build(c, d_kps, 0, d_record, 0, d_grid, 0, n, 1, g, flags));
+    return XFH_OK;
+}
+
+int xfh_grid_build_records_device(xfh_ctx* c, const void* d_records, int B, const xfh_grid_bounds* bounds, int flags, void* d_grids) {
+    GridGeom g;
+    if (!c || B < 0 || (flags & ~XFH_GRID_SKIP_PADDING) || !grid_geom(bounds, &g)) return XFH_ERR_INVALID_ARG;
+    if (B == 0) return XFH_OK;
+    const int nf = c->cfg.nfeatures;
+    if (!d_records || !d_grids || nf > XFH_GRID_MAX_N || (((uintptr_t)d_grids) & 15) || (((uintptr_t)d_records) & 3)) return XFH_ERR_INVALID_ARG;
+    HIPCK(c, hipSetDevice(c->cfg.device));
+    const size_t rb = xfh_record_bytes(nf);
+    HIPCK(c, launch_grid_build(c, (const char*)d_records + xfh_record_kps_offset(), rb, d_records, rb, d_grids, xfh_grid_bytes(nf), nf, B, g, flags));
+    return XFH_OK;
+}
+
+// host, stateless: a grid blob copied out of device memory -> cell_start[64 * 48 + 1] (cell = ix * 48 + iy), items[n] (slot numbers
+// in cell order; the first *n_binned are meaningful, the rest -1).  Everything the blob claims is checked before it is used.
+int xfh_grid_unpack(const void* blob, size_t nbytes, int n, int* cell_start, int* items, int* n_binned) {
+    if (!blob || n < 0 || !cell_start || (n > 0 && !items)) return XFH_ERR_INVALID_ARG;
+    if (nbytes < xfh_grid_bytes(n)) return XFH_ERR_INVALID_ARG;                            // truncated
+    GridHeader h;
+    memcpy(&h, blob, sizeof h);
+    if (h.magic != XFH_GRID_MAGIC || h.n != n || h.n_binned < 0 || h.n_binned > n) return XFH_ERR_INVALID_ARG;
+    const char* p = (const char*)blob;
+    std::vector<int> cs(XFH_GRID_CELLS + 1);
+    memcpy(cs.data(), p + XFH_GRID_CS_OFF, cs.size() * sizeof(int));
+    if (cs[0] != 0 || cs[XFH_GRID_CELLS] != h.n_binned) return XFH_ERR_INVALID_ARG;
+    for (int k = 0; k < XFH_GRID_CELLS; ++k) if (cs[k] > cs[k + 1]) return XFH_ERR_INVALID_ARG;      // (with the two ends: every entry in [0, n_binned])
+    for (int k = 0; k < h.n_binned; ++k) {
+        GridItem it;
+        memcpy(&it, p + XFH_GRID_ITEMS_OFF + (size_t)k * sizeof it, sizeof it);
+        if (it.index < 0 || it.index >= n) return XFH_ERR_INVALID_ARG;
+    }
+    memcpy(cell_start, cs.data(), cs.size() * sizeof(int));
+    for (int k = 0; k < n; ++k) {
+        GridItem it;
+        memcpy(&it, p + XFH_GRID_ITEMS_OFF + (size_t)k * sizeof it, sizeof it);
+        items[k] = k < h.n_binned ? it.index : -1;
+    }
+    if (n_binned) *n_binned = h.n_binned;
+    return XFH_OK;
+}
+
+int xfh_search_window_device(xfh_ctx* c, const float* q, const float* uvr, int nq, const void* d_grid, const float* tg, int nt,
+                             const uint8_t* skip, const float* uright, const float* ur_query, int init_dist,
+                             int* best_idx, int* best_dist, int* second_idx, int* second_dist, int* n_candidates) {
+    if (!c || nq < 0 || nt < 0 || nt > XFH_GRID_MAX_N) return XFH_ERR_INVALID_ARG;
+    if ((uright != nullptr) != (ur_query != nullptr)) return XFH_ERR_INVALID_ARG;
+    if (nq == 0) return XFH_OK;
+    if (!q || !uvr || !d_grid || (nt > 0 && !tg) || !best_idx || !best_dist || !second_idx || !second_dist || !n_candidates) return XFH_ERR_INVALID_ARG;
+    if (((((uintptr_t)q) | ((uintptr_t)tg) | ((uintptr_t)d_grid)) & 15) || ((((uintptr_t)uvr) | ((uintptr_t)uright) | ((uintptr_t)ur_query)) & 3)) return XFH_ERR_INVALID_ARG;
+    HIPCK(c, hipSetDevice(c->cfg.device));
+    HIPCK(c, launch_search_window(c, q, uvr, nq, d_grid, tg, nt, skip, uright, ur_query, init_dist, best_idx, best_dist, second_idx, second_dist, n_candidates));
+    return XFH_OK;
+}
+
+int xfh_search_window(xfh_ctx* c, const float* q, const float* uvr, int nq, const xfh_keypoint* kps, const xfh_grid_bounds* bounds,
+                      const float* tg, int nt, const uint8_t* skip, const float* uright, const float* ur_query, int init_dist,
+                      int* best_idx, int* best_dist, int* second_idx, int* second_dist, int* n_candidates) {
+    GridGeom g;
+    if (!c || nq < 0 || nt < 0 || nt > XFH_GRID_MAX_N || !grid_geom(bounds, &g)) return XFH_ERR_INVALID_ARG;
+    if ((uright != nullptr) != (ur_query != nullptr)) return XFH_ERR_INVALID_ARG;
+    if (nq == 0) return XFH_OK;
+    if (!q || !uvr || (nt > 0 && (!tg || !kps)) || !best_idx || !best_dist || !second_idx || !second_dist || !n_candidates) return XFH_ERR_INVALID_ARG;
+    HIPCK(c, hipSetDevice(c->cfg.device));
+    MatchWs& w = c->mws;
+    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    const size_t bq = al((size_t)nq * 256), bu = al((size_t)nq * 12), bt = al((size_t)nt * 256 + 16), bk = al((size_t)nt * sizeof(xfh_keypoint) + 16),
+                 bg = al(xfh_grid_bytes(nt)), bs = al((size_t)nt + 16), bf = al((size_t)nt * 4 + 16), bn = al((size_t)nq * 4);
+    int rc = grow(c, &w.b2_buf, &w.cap_b2, bq + bu + bt + bk + bg + bs + bf + 6 * bn);
+    if (rc != XFH_OK) return rc;
+    char* p = (char*)w.b2_buf;
+    float* dq = (float*)p; p += bq; float* du = (float*)p; p += bu; float* dt = (float*)p; p += bt; xfh_keypoint* dk = (xfh_keypoint*)p; p += bk;
+    void* dg = p; p += bg; uint8_t* dsk = (uint8_t*)p; p += bs; float* dur = (float*)p; p += bf; float* duq = (float*)p; p += bn;
+    int* o[5];
+    for (int k = 0; k < 5; ++k) { o[k] = (int*)p; p += bn; }
+    HIPCK(c, hipMemcpyAsync(dq, q, (size_t)nq * 256, hipMemcpyHostToDevice, c->stream));
+    HIPCK(c, hipMemcpyAsync(du, uvr, (size_t)nq * 12, hipMemcpyHostToDevice, c->stream));
+    if (nt > 0) {
+        HIPCK(c, hipMemcpyAsync(dt, tg, (size_t)nt * 256, hipMemcpyHostToDevice, c->stream));
+        HIPCK(c, hipMemcpyAsync(dk, kps, (size_t)nt * sizeof(xfh_keypoint), hipMemcpyHostToDevice, c->stream));
+        if (skip) HIPCK(c, hipMemcpyAsync(dsk, skip, (size_t)nt, hipMemcpyHostToDevice, c->stream));
+        if (uright) HIPCK(c, hipMemcpyAsync(dur, uright, (size_t)nt * 4, hipMemcpyHostToDevice, c->stream));
+    }
+    if (ur_query) HIPCK(c, hipMemcpyAsync(duq, ur_query, (size_t)nq * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCK(c, launch_grid_build(c, dk, 0, nullptr, 0, dg, 0, nt, 1, g, 0));
+    HIPCK(c, launch_search_window(c, dq, du, nq, dg, dt, nt, skip ? dsk : nullptr, uright ? dur : nullptr, ur_query ? duq : nullptr, init_dist,
+                                  o[0], o[1], o[2], o[3], o[4]));
+    int* out[5] = {best_idx, best_dist, second_idx, second_dist, n_candidates};
+    for (int k = 0; k < 5; ++k) HIPCK(c, hipMemcpyAsync(out[k], o[k], (size_t)nq * 4, hipMemcpyDeviceToHost, c->stream));
     HIPCK(c, hipStreamSynchronize(c->stream));
     return XFH_OK;
 }

@@ -205,5 +205,11 @@ hipError_t launch_mnn_gemm(xfh_ctx* c, const float* img1, int n1, const float* i
 hipError_t launch_dist_i32(xfh_ctx* c, const float* d1, int n1, const float* d2, int n2, int32_t* out);
 hipError_t launch_distinctive(xfh_ctx* c, const float* table, const int* offsets, const int* indices, int n_groups, int max_group,
                               int* best_pos, int* best_median);
+struct GridGeom;
+hipError_t launch_grid_build(xfh_ctx* c, const void* kps, size_t kps_stride, const void* hdr, size_t hdr_stride, void* grids, size_t grid_stride,
+                             int n, int B, const GridGeom& g, int flags);                     // window_search.hip.h
+hipError_t launch_search_window(xfh_ctx* c, const float* q, const float* uvr, int nq, const void* grid, const float* tg, int nt,
+                                const uint8_t* skip, const float* uright, const float* ur_query, int init_dist,
+                                int* best_idx, int* best_dist, int* second_idx, int* second_dist, int* n_candidates);
 hipError_t launch_best2(xfh_ctx* c, const float* q, int nq, const float* tg, const int* offsets, const int* indices, int init_dist,
                         int* best_idx, int* best_dist, int* second_idx, int* second_dist);

@@ -9,6 +9,8 @@
 //                   bit-identically), mutual check (:372), min_cossim gate, ordered compaction and distances (:371-403).
 //   k_dist_mfma   : dense (int)(512 * ||a-b||^2), ORBmatcher::DescriptorDistance (:2246-2247): MFMA bulk + exact fix-up.
 //   k_best2_csr   : best / second-best distance over candidate lists (the SearchBy* inner loop, :75-119).
+//   k_grid_build / k_search_window : the frame grid in device memory and the fused window -> candidates -> best two search
+//                   (Frame::AssignFeaturesToGrid / GetFeaturesInArea + the SearchByProjection loop; window_search.hip.h).
 //   k_distinctive_csr : MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:329-403), one wave per map point.
 //
 // Numerics: normalised rows and the 64-term dot products are bit-identical to the oracle
@@ -82,6 +84,8 @@ hipError_t launch_best2(xfh_ctx* c, const float* q, int nq, const float* tg, con
              best_idx, best_dist, second_idx, second_dist);
     return hipGetLastError();
 }
+
+#include "window_search.hip.h"
 
 // ---- k_distinctive_csr: MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:329-403), batched -------
 // One wave per group (map point).  Rows are taken 64 at a time, lane = row: the lane keeps its descriptor in

@@ -170,6 +170,77 @@ class Context:
                                   *[o.ctypes.data for o in out]), self.h)
         return tuple(o[:nq] for o in out)
 
+    # -- frame grid + windowed search (xfh_grid_* / xfh_search_window*) -------------------------
+    @staticmethod
+    def grid_bytes(n: int) -> int:
+        return int(lib().xfh_grid_bytes(n))
+
+    def grid_build_device(self, d_kps, n: int, bounds, flags: int = 0, d_record=None, d_grid=None):
+        """xfh_grid_build_device on device pointers (ints); asynchronous.  -> DeviceBuffer holding the grid (d_grid if given)"""
+        g = d_grid or capi.DeviceBuffer(self.grid_bytes(n))
+        check(lib().xfh_grid_build_device(self.h, d_kps, n, d_record, C.byref(capi.GridBounds(*bounds)), flags, g.ptr), self.h)
+        return g
+
+    def grid_build(self, kps: np.ndarray, bounds, flags: int = 0, header=None):
+        """Frame::AssignFeaturesToGrid on the GPU: keypoints (KP_DTYPE) -> DeviceBuffer with the grid blob.  header = (n_valid,
+        mono_index) of the record the keypoints belong to (needed by GRID_SKIP_PADDING)."""
+        k = np.ascontiguousarray(kps, KP_DTYPE)
+        n = len(k)
+        dk = capi.DeviceBuffer(max(k.nbytes, 16)).upload(k)
+        dh = None
+        if header is not None:
+            dh = capi.DeviceBuffer(16).upload(np.array([header[0], header[1], 0, 0], np.int32))
+        g = self.grid_build_device(dk.ptr, n, bounds, flags, dh.ptr if dh else None)
+        self.synchronize()
+        dk.free()
+        if dh:
+            dh.free()
+        return g
+
+    def grid_build_records(self, d_records, B: int, bounds, flags: int = 0, d_grids=None):
+        """xfh_grid_build_records_device: B grids in one launch straight from B extraction records in device memory (pointer);
+        asynchronous.  Grid b starts at byte b * grid_bytes(nfeatures) of the returned DeviceBuffer."""
+        g = d_grids or capi.DeviceBuffer(max(B, 1) * self.grid_bytes(self.nfeatures))
+        check(lib().xfh_grid_build_records_device(self.h, d_records, B, C.byref(capi.GridBounds(*bounds)), flags, g.ptr), self.h)
+        return g
+
+    @staticmethod
+    def grid_unpack(blob: np.ndarray, n: int):
+        """xfh_grid_unpack (host): a downloaded grid blob -> (cell_start[64 * 48 + 1], items[n_binned])"""
+        b = np.ascontiguousarray(blob, np.uint8)
+        cs = np.zeros(capi.GRID_COLS * capi.GRID_ROWS + 1, np.int32); items = np.zeros(max(n, 1), np.int32); nb = C.c_int(0)
+        check(lib().xfh_grid_unpack(b.ctypes.data, b.nbytes, n, cs.ctypes.data, items.ctypes.data, C.byref(nb)))
+        return cs, items[:nb.value].copy()
+
+    def grid_download(self, grid, n: int, index: int = 0) -> np.ndarray:
+        self.synchronize()
+        nb = self.grid_bytes(n)
+        return grid.download(np.uint8, nb, index * nb)
+
+    def search_window_device(self, d_queries, d_uvr, nq: int, d_grid, d_targets, nt: int, d_out, init_dist: int = 256,
+                             d_skip=None, d_uright=None, d_ur_query=None):
+        """xfh_search_window_device on device pointers; d_out: pointer to 5 * nq ints (best_idx, best_dist, second_idx,
+        second_dist, n_candidates, nq each); asynchronous"""
+        o = [d_out + 4 * nq * k for k in range(5)]
+        check(lib().xfh_search_window_device(self.h, d_queries, d_uvr, nq, d_grid, d_targets, nt, d_skip, d_uright, d_ur_query,
+                                             int(init_dist), *o), self.h)
+
+    def search_window(self, queries, uvr, kps, bounds, targets, init_dist: int = 256, skip=None, uright=None, ur_query=None):
+        """GetFeaturesInArea + the best / second-best loop of SearchByProjection for every query (descriptor row, (u, v, r)) against
+        the keypoints / descriptor rows of one frame -> (best_idx, best_dist, second_idx, second_dist, n_candidates)"""
+        q = np.ascontiguousarray(queries, np.float32); w = np.ascontiguousarray(uvr, np.float32).reshape(-1, 3)
+        k = np.ascontiguousarray(kps, KP_DTYPE); tg = np.ascontiguousarray(targets, np.float32)
+        nq, nt = len(q), len(k)
+        assert len(w) == nq and len(tg) == nt
+        sk = None if skip is None else np.ascontiguousarray(skip, np.uint8)
+        ur = None if uright is None else np.ascontiguousarray(uright, np.float32)
+        uq = None if ur_query is None else np.ascontiguousarray(ur_query, np.float32)
+        out = [np.zeros(max(nq, 1), np.int32) for _ in range(5)]
+        check(lib().xfh_search_window(self.h, q.ctypes.data, w.ctypes.data, nq, k.ctypes.data, C.byref(capi.GridBounds(*bounds)), tg.ctypes.data, nt,
+                                      None if sk is None else sk.ctypes.data, None if ur is None else ur.ctypes.data,
+                                      None if uq is None else uq.ctypes.data, int(init_dist), *[o.ctypes.data for o in out]), self.h)
+        return tuple(o[:nq] for o in out)
+
     def distinctive_csr(self, table, offsets, indices):
         """MapPoint::ComputeDistinctiveDescriptors over CSR groups of descriptor rows ->
         (position inside the group of the descriptor with the least median distance, that median)"""
