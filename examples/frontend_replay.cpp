@@ -21,6 +21,11 @@
 //        behind it: one ORBmatcher::match per pair in the reference, src/ORBmatcher.cc:358-372) in ONE call, xfh_match_mnn_prepared_batch_device.  The
 //        pair (t - 1, t) is what the default mode reports; --dump-window file: per frame the number of partners, then per partner its frame index and
 //        the (idx1 = partner's slot, idx2 = this frame's slot, dist) list.
+//   --rgbd fx,fy,cx,cy,k1,k2,p1,p2,k3,bf,factor: the RGB-D Frame constructor (src/Frame.cc:311-374) for a camera with distortion.  The depth
+//        column of the association list is read (16-bit greyscale PNG, scaled by 1 / factor: RGBD.DepthMapFactor), and every frame is finished on
+//        the device: undistorted keypoints, right coordinates and depths (XFgrid::buildFromRecord with the camera on the record in HBM with --fast,
+//        xfh_frame_finish on the host keypoints otherwise; the same values).  The dump gains, per frame after the match list, xy_un (x, y pairs),
+//        uright and depth, nfeatures entries each.  Without the option the dump is what it was.
 //
 // Build: g++ -std=c++17 -O2 -Iinclude examples/frontend_replay.cpp -Lxfeatslam_amd -lxfeat_hip -lz -o frontend_replay
 #define XFEAT_NO_OPENCV 1
@@ -29,6 +34,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <fstream>
 #include <sstream>
 #include <string>
@@ -67,6 +73,8 @@ int main(int argc, char** argv) {
     FILE* dump = nullptr;
     bool fast = false, valid_only = false;
     int window = 1; FILE* dumpw = nullptr;
+    bool rgbd = false; xfh_camera cam; float depth_factor = 1.f;
+    memset(&cam, 0, sizeof cam);
     for (int i = 4; i < argc; ++i) {
         if (std::string(argv[i]) == "--dump" && i + 1 < argc) dump = fopen(argv[i + 1], "wb");
         if (std::string(argv[i]) == "--rgb" && i + 1 < argc) g_rgb = atoi(argv[i + 1]);
@@ -74,14 +82,22 @@ int main(int argc, char** argv) {
         if (std::string(argv[i]) == "--valid-only") valid_only = true;
         if (std::string(argv[i]) == "--window" && i + 1 < argc) window = atoi(argv[i + 1]);
         if (std::string(argv[i]) == "--dump-window" && i + 1 < argc) dumpw = fopen(argv[i + 1], "wb");
+        if (std::string(argv[i]) == "--rgbd" && i + 1 < argc) {
+            float v[11];
+            if (sscanf(argv[i + 1], "%f,%f,%f,%f,%f,%f,%f,%f,%f,%f,%f", v, v + 1, v + 2, v + 3, v + 4, v + 5, v + 6, v + 7, v + 8, v + 9, v + 10) != 11) {
+                fprintf(stderr, "--rgbd fx,fy,cx,cy,k1,k2,p1,p2,k3,bf,factor\n"); return 2;
+            }
+            cam.fx = v[0]; cam.fy = v[1]; cam.cx = v[2]; cam.cy = v[3]; cam.k1 = v[4]; cam.k2 = v[5]; cam.p1 = v[6]; cam.p2 = v[7]; cam.k3 = v[8]; cam.bf = v[9];
+            depth_factor = v[10]; rgbd = true;
+        }
     }
     const int nfeatures = getenv("XFH_NFEATURES") ? atoi(getenv("XFH_NFEATURES")) : 1000;     // TUM1.yaml: ORBextractor.nFeatures 1000
-    std::vector<std::string> files;
+    std::vector<std::string> files, depth_files;
     int nsyn = 0, H = 480, W = 640;
     if (std::string(argv[2]) == "--synthetic") { nsyn = atoi(argv[3]); if (argc > 5 && argv[4][0] != '-') { H = atoi(argv[4]); W = atoi(argv[5]); } }
     else {
         std::ifstream fa(argv[2]); std::string line;                                           // rgbd_tum.cc LoadImages (:152-179)
-        while (std::getline(fa, line)) { std::stringstream ss(line); std::string t, rgb; if (ss >> t >> rgb) files.push_back(std::string(argv[3]) + "/" + rgb); }
+        while (std::getline(fa, line)) { std::stringstream ss(line); std::string t, rgb, td, dep; if (ss >> t >> rgb) { files.push_back(std::string(argv[3]) + "/" + rgb); depth_files.push_back((ss >> td >> dep) ? std::string(argv[3]) + "/" + dep : std::string()); } }
         if (files.empty()) { fprintf(stderr, "no images in %s\n", argv[2]); return 2; }
     }
     const int n = nsyn ? nsyn : (int)files.size();
@@ -109,6 +125,16 @@ int main(int argc, char** argv) {
         bool ok = xfh_dev_alloc(&d_gray, (size_t)im.rows * im.cols) == XFH_OK && xfh_dev_alloc(&d_out, (size_t)window * ((size_t)nfeatures * 12 + 64)) == XFH_OK;
         for (int g = 0; g < NG; ++g) ok = ok && xfh_dev_alloc(&d_rec[g], rec_bytes) == XFH_OK && xfh_dev_alloc(&d_img[g], img_bytes) == XFH_OK;
         if (!ok) { fprintf(stderr, "out of device memory\n"); return 1; }
+    }
+    // --rgbd: mDepthMapFactor = 1.0f / factor, 1 when the factor is (nearly) zero (Tracking.cc:577-581); bounds once per calibration
+    const float depth_scale = std::fabs(depth_factor) < 1e-5f ? 1.f : 1.0f / depth_factor;
+    xfh_grid_bounds cam_bounds = {0.f, 0.f, 1.f, 1.f};
+    XFgrid frame_grid(ctx);
+    xfeat::Image16 depth_im;
+    std::vector<float> xy_un, u_right, z_depth;
+    if (rgbd) {
+        cam.width = im.cols; cam.height = im.rows;
+        if (xfh_camera_bounds(&cam, &cam_bounds) != XFH_OK) { fprintf(stderr, "--rgbd: bad camera\n"); return 2; }
     }
     int prev_valid = 0;
     for (int ni = 0; ni < n; ++ni) {
@@ -181,6 +207,28 @@ int main(int argc, char** argv) {
             prev_valid = hdr[0];
             gen_valid[g] = hdr[0];
         }
+        if (rgbd) {
+            const void* dimg = nullptr;
+            if (!nsyn) {
+                if (depth_files[ni].empty() || !xfeat::load_png16(depth_files[ni], depth_im) || depth_im.rows != im.rows || depth_im.cols != im.cols) {
+                    fprintf(stderr, "cannot read the depth map of frame %d (16-bit greyscale PNG of the frame's size expected)\n", ni); return 2;
+                }
+                dimg = depth_im.data.data();
+            }
+            const int dt = dimg ? XFH_DEPTH_U16 : XFH_DEPTH_NONE;
+            const size_t pitch = (size_t)im.cols * 2;
+            if (fast) {
+                try {
+                    frame_grid.buildFromRecord(d_rec[ni % NG], nfeatures, cam, cam_bounds, dimg, dt, pitch, depth_scale);
+                    xy_un = frame_grid.keysUn(); u_right = frame_grid.uRight(); z_depth = frame_grid.depth();
+                } catch (const std::exception& e) { fprintf(stderr, "--rgbd: %s\n", e.what()); return 1; }
+            } else {
+                const int nk = (int)keys.size();
+                xy_un.assign(2 * (size_t)nk, 0.f); u_right.assign(nk, 0.f); z_depth.assign(nk, 0.f);
+                const int rc = xfh_frame_finish(ctx, (const xfh_keypoint*)keys.data(), nk, &cam, dimg, dt, pitch, depth_scale, xy_un.data(), u_right.data(), z_depth.data());
+                if (rc != XFH_OK) { fprintf(stderr, "--rgbd: %s (%s)\n", xfh_strerror(rc), xfh_last_hip_error(ctx)); return 1; }
+            }
+        }
         total_matches += (long)matches.size();
         const auto t2 = std::chrono::steady_clock::now();
         vTimesTrack[ni] = std::chrono::duration_cast<std::chrono::duration<double>>(t2 - t1).count();
@@ -208,6 +256,7 @@ int main(int argc, char** argv) {
             for (auto& k : keys) { put(&k.pt.x, 4); put(&k.pt.y, 4); put(&k.size, 4); }
             put(&nm, 4);
             for (auto& m : matches) { put(&m.queryIdx, 4); put(&m.trainIdx, 4); put(&m.distance, 4); }
+            if (rgbd) { put(xy_un.data(), xy_un.size() * 4); put(u_right.data(), u_right.size() * 4); put(z_depth.data(), z_depth.size() * 4); }
         }
         prev = desc; prev_keys = keys;
     }

@@ -8,7 +8,8 @@
  *   TH_LOW / TH_HIGH                                                    -- ORBmatcher.cc:34-35
  *   XFgrid / XFmatcher::searchWindow: Frame::AssignFeaturesToGrid + GetFeaturesInArea (Frame.cc:569-599, 850-916) and the
  *        loop of SearchByProjection (ORBmatcher.cc:1925-1955) on the GPU: a frame grid in device memory and one fused
- *        window -> candidates -> best two call for all queries
+ *        window -> candidates -> best two call for all queries; XFgrid::buildFromRecord(record, n, camera, bounds, depth) is the rest
+ *        of the RGB-D Frame constructor (UndistortKeyPoints, ComputeStereoFromRGBD, the grid on mvKeysUn; Frame.cc:311-374)
  *   best2 / distinctive: the batched inner loops of SearchBy* (ORBmatcher.cc:75-119) and of
  *        MapPoint::ComputeDistinctiveDescriptors (MapPoint.cc:329-403)
  *
@@ -47,7 +48,7 @@ class XFgrid {
 public:
     using KeyPoint = xfeat::cvx::KeyPoint;
     explicit XFgrid(xfh_ctx* shared_ctx) : ctx(shared_ctx) {}
-    ~XFgrid() { if (d_grid) xfh_dev_free(d_grid); if (d_kps) xfh_dev_free(d_kps); }
+    ~XFgrid() { if (d_grid) xfh_dev_free(d_grid); if (d_kps) xfh_dev_free(d_kps); if (d_side) xfh_dev_free(d_side); if (d_img) xfh_dev_free(d_img); }
     XFgrid(const XFgrid&) = delete;
     XFgrid& operator=(const XFgrid&) = delete;
 
@@ -59,16 +60,63 @@ public:
         finish(xfh_grid_build_device(ctx, (const xfh_keypoint*)d_kps, count, nullptr, &bounds, 0, d_grid), count, bounds);
         host_x.resize(count); host_y.resize(count);
         for (int i = 0; i < count; ++i) { host_x[i] = keys[i].pt.x; host_y[i] = keys[i].pt.y; }
+        side_n = -1; side_host = false;
     }
     // d_record: one record of `nfeatures` slots in device memory (xfh_extract_batch_device)
     void buildFromRecord(const void* d_record, int nfeatures, const xfh_grid_bounds& bounds, int flags = 0) {
         reserve(nfeatures, false);
         finish(xfh_grid_build_device(ctx, (const xfh_keypoint*)((const char*)d_record + xfh_record_kps_offset()), nfeatures, d_record, &bounds, flags, d_grid),
                nfeatures, bounds);
-        host_x.clear(); host_y.clear();
+        host_x.clear(); host_y.clear(); side_n = -1; side_host = false;
+    }
+    // The RGB-D Frame constructor between ExtractXF and the first search (Frame.cc:311-374) for a camera WITH distortion, one launch
+    // (xfh_frame_finish_records_device): UndistortKeyPoints -> keysUn(), ComputeStereoFromRGBD -> uRight() / depth(), and
+    // AssignFeaturesToGrid on the undistorted keypoints with `bounds` (xfh_camera_bounds(&cam, &bounds), once per calibration).
+    // d_record: one record of the ctx' nfeatures slots in device memory.  depth: the HOST depth image (cam.height rows, depth_pitch
+    // bytes apart; XFH_DEPTH_F32 metres or XFH_DEPTH_U16 raw values times depth_scale = 1.0f / DepthMapFactor), uploaded into a
+    // buffer of the object; nullptr / XFH_DEPTH_NONE = the monocular constructor (uRight = depth = -1).  The three arrays live in
+    // device memory owned by the object (deviceKeysUn / deviceURight / deviceDepth: what xfh_search_window_device takes); the host
+    // getters download them at the first call after a build.
+    void buildFromRecord(const void* d_record, int nfeatures, const xfh_camera& cam, const xfh_grid_bounds& bounds, const void* depth = nullptr,
+                         int depth_type = XFH_DEPTH_NONE, size_t depth_pitch = 0, float depth_scale = 1.0f, int flags = 0) {
+        reserve(nfeatures, false);
+        const size_t sb = (size_t)(nfeatures > 0 ? nfeatures : 1) * 16;
+        if (sb > side_cap) {
+            if (d_side) xfh_dev_free(d_side);
+            d_side = nullptr; side_cap = 0;
+            if (xfh_dev_alloc(&d_side, sb) != XFH_OK) throw std::runtime_error("XFgrid: out of device memory");
+            side_cap = sb;
+        }
+        const void* dimg = nullptr;
+        if (depth && depth_type != XFH_DEPTH_NONE) {
+            if (cam.height <= 0 || depth_pitch == 0) throw std::runtime_error("XFgrid::buildFromRecord: depth image without a size");
+            const size_t ib = (size_t)cam.height * depth_pitch;
+            if (ib > img_cap) {
+                if (d_img) xfh_dev_free(d_img);
+                d_img = nullptr; img_cap = 0;
+                if (xfh_dev_alloc(&d_img, ib) != XFH_OK) throw std::runtime_error("XFgrid: out of device memory");
+                img_cap = ib;
+            }
+            // (the copy is synchronous: an earlier launch that read the buffer is ordered before it only after a host wait)
+            if (xfh_synchronize(ctx) != XFH_OK || xfh_memcpy_h2d(d_img, depth, ib) != XFH_OK) throw std::runtime_error("XFgrid::buildFromRecord: upload failed");
+            dimg = d_img;
+        }
+        side_n = nfeatures;
+        finish(xfh_frame_finish_records_device(ctx, d_record, 1, &cam, dimg, dimg ? depth_type : XFH_DEPTH_NONE, depth_pitch, depth_scale, &bounds, flags,
+                                               deviceKeysUn(), deviceURight(), deviceDepth(), d_grid),
+               nfeatures, bounds);
+        host_x.clear(); host_y.clear(); side_host = false;
     }
     const void* device() const { return d_grid; }
     int size() const { return n; }
+    // device arrays of the last buildFromRecord(.., cam, ..): xy_un[n][2], uright[n], depth[n] (nullptr before it)
+    float* deviceKeysUn() const { return (float*)d_side; }
+    float* deviceURight() const { return d_side ? (float*)d_side + 2 * (size_t)side_n : nullptr; }
+    float* deviceDepth() const { return d_side ? (float*)d_side + 3 * (size_t)side_n : nullptr; }
+    // host copies: mvKeysUn as (x, y) pairs, mvuRight, mvDepth
+    const std::vector<float>& keysUn() { fetch_side(); return h_xy; }
+    const std::vector<float>& uRight() { fetch_side(); return h_ur; }
+    const std::vector<float>& depth() { fetch_side(); return h_dz; }
 
     // Frame::GetFeaturesInArea on the host copy (downloaded and unpacked at the first call after a build): indices in the
     // reference's visiting order
@@ -134,7 +182,22 @@ private:
         }
         unpacked = true;
     }
+    void fetch_side() {
+        if (side_host) return;
+        if (!d_side || side_n != n) throw std::runtime_error("XFgrid: the grid was not built with a camera");
+        h_xy.assign(2 * (size_t)n, 0.f); h_ur.assign(n, 0.f); h_dz.assign(n, 0.f);
+        int rc = xfh_synchronize(ctx);
+        if (rc == XFH_OK && n > 0) rc = xfh_memcpy_d2h(h_xy.data(), deviceKeysUn(), (size_t)n * 8);
+        if (rc == XFH_OK && n > 0) rc = xfh_memcpy_d2h(h_ur.data(), deviceURight(), (size_t)n * 4);
+        if (rc == XFH_OK && n > 0) rc = xfh_memcpy_d2h(h_dz.data(), deviceDepth(), (size_t)n * 4);
+        if (rc != XFH_OK) throw std::runtime_error(std::string("XFgrid: ") + xfh_strerror(rc));
+        side_host = true;
+    }
     xfh_ctx* ctx;
+    void* d_side = nullptr; size_t side_cap = 0; int side_n = 0;      // xy_un, uright, depth of buildFromRecord(.., cam, ..)
+    void* d_img = nullptr; size_t img_cap = 0;                        // its depth image
+    bool side_host = false;
+    std::vector<float> h_xy, h_ur, h_dz;
     void* d_grid = nullptr; size_t grid_cap = 0;
     void* d_kps = nullptr; size_t kps_cap = 0;
     int n = 0;

@@ -1,6 +1,6 @@
 // image_io.h -- minimal image input for the replay harness (examples/frontend_replay.cpp) where OpenCV is absent:
 // binary PGM (P5) and non-interlaced 8-bit PNG (gray, gray+alpha, RGB, RGBA; zlib inflate + the five PNG filters),
-// converted to the CV_8UC1 image the extractor takes.
+// converted to the CV_8UC1 image the extractor takes; and 16-bit greyscale PNG (load_png16: TUM depth maps) as uint16.
 //
 // The reference reads frames with cv::imread(..., IMREAD_UNCHANGED) (examples/RGB-D/rgbd_tum.cc:78), which returns colour
 // images in B,G,R memory order, and Tracking::GrabImageRGBD converts with cv::COLOR_RGB2GRAY when Camera.RGB is 1 (TUM1.yaml:29,
@@ -82,6 +82,56 @@ inline bool load_png(const std::string& path, Image8& im) {
             cur[x] = (unsigned char)(in[1 + x] + pred);
         }
     }
+    return true;
+}
+
+// 16-bit greyscale PNG (TUM depth maps: colour type 0, bit depth 16, non-interlaced) -> uint16 in host byte order.  The reference
+// reads them with cv::imread(..., IMREAD_UNCHANGED) (examples/RGB-D/rgbd_tum.cc:79) and scales by 1 / DepthMapFactor later.
+// Everything else (8-bit, colour, palette, Adam7) is refused here; load_png above keeps refusing 16-bit files.
+struct Image16 { int rows = 0, cols = 0; std::vector<uint16_t> data; };
+
+inline bool load_png16(const std::string& path, Image16& im) {
+    std::ifstream f(path, std::ios::binary);
+    std::vector<unsigned char> buf((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
+    static const unsigned char sig[8] = {0x89, 'P', 'N', 'G', 0x0d, 0x0a, 0x1a, 0x0a};
+    if (buf.size() < 33 || memcmp(buf.data(), sig, 8) != 0) return false;
+    auto be32 = [&](size_t o) { return ((uint32_t)buf[o] << 24) | ((uint32_t)buf[o + 1] << 16) | ((uint32_t)buf[o + 2] << 8) | (uint32_t)buf[o + 3]; };
+    uint32_t w = 0, h = 0; int depth = 0, ctype = -1, interlace = 0;
+    std::vector<unsigned char> idat;
+    for (size_t o = 8; o + 12 <= buf.size();) {
+        const uint32_t len = be32(o);
+        if (o + 12 + (size_t)len > buf.size()) return false;
+        const char* ty = (const char*)&buf[o + 4];
+        if (!memcmp(ty, "IHDR", 4) && len >= 13 && ctype < 0) { w = be32(o + 8); h = be32(o + 12); depth = buf[o + 16]; ctype = buf[o + 17]; interlace = buf[o + 20]; }
+        else if (!memcmp(ty, "IDAT", 4)) idat.insert(idat.end(), buf.begin() + o + 8, buf.begin() + o + 8 + len);
+        else if (!memcmp(ty, "IEND", 4)) break;
+        o += 12 + (size_t)len;
+    }
+    if (!w || !h || depth != 16 || ctype != 0 || interlace) return false;
+    if (w > (uint32_t)kMaxSide || h > (uint32_t)kMaxSide) return false;    // bounded before any size is computed from them
+    const size_t bpp = 2, stride = (size_t)w * bpp;
+    std::vector<unsigned char> raw((stride + 1) * h), img(stride * h, 0);
+    uLongf rawlen = (uLongf)raw.size();
+    if (uncompress(raw.data(), &rawlen, idat.data(), (uLong)idat.size()) != Z_OK || rawlen != raw.size()) return false;
+    for (uint32_t y = 0; y < h; ++y) {                                     // the five filters work on BYTES, a pixel (bpp) apart
+        const unsigned char* in = &raw[(stride + 1) * y];
+        unsigned char* cur = &img[stride * y];
+        const unsigned char* up = y ? cur - stride : nullptr;
+        const int ft = in[0];
+        if (ft < 0 || ft > 4) return false;
+        for (size_t x = 0; x < stride; ++x) {
+            const int a = x >= bpp ? cur[x - bpp] : 0, b = up ? up[x] : 0, c = (up && x >= bpp) ? up[x - bpp] : 0;
+            int pred = 0;
+            if (ft == 1) pred = a;
+            else if (ft == 2) pred = b;
+            else if (ft == 3) pred = (a + b) >> 1;
+            else if (ft == 4) { const int p = a + b - c, pa = p > a ? p - a : a - p, pb = p > b ? p - b : b - p, pc = p > c ? p - c : c - p;
+                                pred = (pa <= pb && pa <= pc) ? a : (pb <= pc ? b : c); }
+            cur[x] = (unsigned char)(in[1 + x] + pred);
+        }
+    }
+    im.rows = (int)h; im.cols = (int)w; im.data.resize((size_t)w * h);
+    for (size_t p = 0; p < im.data.size(); ++p) im.data[p] = (uint16_t)((img[2 * p] << 8) | img[2 * p + 1]);     // samples are big-endian
     return true;
 }
 

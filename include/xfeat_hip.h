@@ -259,7 +259,8 @@ int xfh_best2_csr_device(xfh_ctx* ctx, const float* d_queries, int nq, const flo
  * straight from extraction records, and one fused kernel "window -> candidates -> best two" per batch of queries.
  *
  * Grid (Frame.cc:569-599, PosInGrid :918-929, bounds and inverse cell sizes :336-341, :985-1001): the caller gives the bounds
- * (0, 0, cols, rows for an undistorted camera; a caller with distortion passes undistorted keypoints and mnMinX .. mnMaxY);
+ * (0, 0, cols, rows for an undistorted camera; with distortion the grid is built from the UNDISTORTED keypoints with mnMinX .. mnMaxY:
+ * xfh_frame_finish_records_device and xfh_camera_bounds below);
  * inv_w = 64.0f / (max_x - min_x), inv_h = 48.0f / (max_y - min_y) in fp32.  Keypoint i goes to cell
  * (round((x - min_x) * inv_w), round((y - min_y) * inv_h)), round = roundf (half away from zero), and is NOT binned when a
  * coordinate is < 0, >= 64 resp. >= 48: the reference rounds (it does not floor), so the right-most / bottom half cell of the
@@ -313,6 +314,59 @@ int xfh_search_window_device(xfh_ctx* ctx, const float* d_queries, const float* 
 int xfh_search_window(xfh_ctx* ctx, const float* queries, const float* uvr, int nq, const xfh_keypoint* kps, const xfh_grid_bounds* bounds,
                       const float* targets, int nt, const uint8_t* skip_or_null, const float* uright_or_null, const float* ur_query_or_null,
                       int init_dist, int* best_idx, int* best_dist, int* second_idx, int* second_dist, int* n_candidates);
+
+/* ---- finishing an RGB-D frame on the device: undistort, depth, grid of mvKeysUn ------------------------------------------------
+ * Between ExtractXF and AssignFeaturesToGrid the reference's RGB-D constructor (src/Frame.cc:311-374) runs UndistortKeyPoints
+ * (:940-973), ComputeStereoFromRGBD (:1177-1198) and, once per calibration, ComputeImageBounds (:975-1002); the grid, GetFeaturesInArea
+ * and SearchByProjection then work on mvKeysUn and mvuRight.  These calls are that stage, so that extract -> finish -> grid -> search
+ * stays in device memory for a camera WITH distortion (the reference's examples/RGB-D/TUM1.yaml has five non-zero coefficients).
+ *
+ * Undistort: cv::undistortPoints(src, dst, K, dist, Mat(), P = K) restated from its documented algorithm (this library does not link
+ * OpenCV), per point in float64, in this operation order:
+ *     x0 = (u - cx) / fx; y0 = (v - cy) / fy; x = x0; y = y0
+ *     5 times (the default TermCriteria is COUNT 5, there is no epsilon exit):
+ *         r2 = x*x + y*y;  icdist = 1 / (1 + ((k3*r2 + k2)*r2 + k1)*r2);  if (icdist < 0) { x = x0; y = y0; stop }
+ *         dx = 2*p1*x*y + p2*(r2 + 2*x*x);  dy = p1*(r2 + 2*y*y) + 2*p2*x*y;  x = (x0 - dx)*icdist;  y = (y0 - dy)*icdist
+ *     u' = (float)(x*fx + cx); v' = (float)(y*fy + cy)
+ * k1 == 0 copies the points unchanged whatever the other coefficients are (Frame.cc:942), and the same test selects the bounds
+ * (0, 0, width, height) (:977).  Otherwise the bounds come from the undistorted corners p0 = (0, 0), p1 = (width, 0), p2 = (0, height),
+ * p3 = (width, height): min_x = min(p0.x, p2.x), max_x = max(p1.x, p3.x), min_y = min(p0.y, p1.y), max_y = max(p2.y, p3.y).
+ * All n slots are processed, padding slots at (0, 0) included, as the reference does (N = mvKeys.size()).
+ *
+ * Depth: the image is fp32 metres (XFH_DEPTH_F32) or raw uint16 (XFH_DEPTH_U16) with the multiplier depth_scale (the reference's
+ * 1.0f / DepthMapFactor, Tracking.cc:577-581): d = (float)raw * depth_scale, one fp32 rounding.  Rows are depth_pitch_bytes apart (a
+ * multiple of the element size).  It is sampled at ((int)v, (int)u) of the RAW keypoint; depth = d and uright = u' - bf / d (fp32) when
+ * d > 0, otherwise both are -1 (a NaN depth fails d > 0).  Where the reference would read outside the image the sample is 0 and nothing
+ * is read.  XFH_DEPTH_NONE writes -1 to both arrays: the monocular constructor.  A NULL image with XFH_DEPTH_F32 / XFH_DEPTH_U16 is accepted
+ * and treated as XFH_DEPTH_NONE; depth_pitch_bytes and depth_scale are ignored whenever there is no image.
+ *
+ *   xfh_undistort_points / xfh_camera_bounds   host, stateless, thread-safe: n (u, v) pairs -> n (u', v') pairs; mnMinX .. mnMaxY
+ *   xfh_frame_finish_records_device   B records of this ctx in ONE launch: per frame b xy_un[n][2] at d_xy_un + b * 2 * nfeatures floats,
+ *                                     the outputs d_uright / d_depth at + b * nfeatures floats (plain fp32 arrays: d_uright plugs into
+ *                                     xfh_search_window_device), INPUT depth image b at d_depth_or_null + b * height * depth_pitch_bytes, and -- unless
+ *                                     d_grids is NULL -- the grid blob of the UNDISTORTED coordinates with the caller's bounds at
+ *                                     d_grids + b * xfh_grid_bytes(nfeatures), in the format of xfh_grid_build_records_device (for k1 == 0
+ *                                     the same bytes).  XFH_GRID_SKIP_PADDING keeps padding slots out of the grid only; their side
+ *                                     arrays are written like everyone's.  Device pointers, asynchronous on the ctx stream, no allocation.
+ *   xfh_frame_finish                  host-pointer convenience form for one frame's n keypoints (side arrays only)
+ * XFH_ERR_INVALID_ARG before anything is launched: B outside 1 .. max_batch, nfeatures > XFH_GRID_MAX_N with a grid requested, a pitch
+ * smaller than a row or not a multiple of the element size, width or height <= 0, an unknown depth type, bounds as for
+ * xfh_grid_build_device, misaligned pointers (16 bytes for the grids, the element size otherwise).  Coefficients, keypoints and
+ * depth values may be anything, NaN and Inf included: a non-finite undistorted coordinate is not binned, and no load leaves the
+ * records, the depth images or the blob. */
+typedef struct {
+    float fx, fy, cx, cy, k1, k2, p1, p2, k3, bf;
+    int32_t width, height;
+    int32_t reserved[4];
+} xfh_camera;
+enum { XFH_DEPTH_NONE = 0, XFH_DEPTH_F32 = 1, XFH_DEPTH_U16 = 2 };
+int xfh_undistort_points(const xfh_camera* cam, const float* xy, int n, float* xy_un);
+int xfh_camera_bounds(const xfh_camera* cam, xfh_grid_bounds* out);
+int xfh_frame_finish_records_device(xfh_ctx* ctx, const void* d_records, int B, const xfh_camera* cam, const void* d_depth_or_null, int depth_type,
+                                    size_t depth_pitch_bytes, float depth_scale, const xfh_grid_bounds* bounds, int grid_flags,
+                                    float* d_xy_un, float* d_uright, float* d_depth, void* d_grids_or_null);
+int xfh_frame_finish(xfh_ctx* ctx, const xfh_keypoint* kps, int n, const xfh_camera* cam, const void* depth_or_null, int depth_type,
+                     size_t depth_pitch_bytes, float depth_scale, float* xy_un, float* uright, float* depth);
 
 /* MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:329-403), batched over map points: group g observes the
  * descriptor rows indices[offsets[g] .. offsets[g+1]) of `table` (n_rows x 64).  Pairwise DescriptorDistance inside

@@ -19,7 +19,8 @@ enum {
     XFH_K_NONE = 0, XFH_K_MNN_GEMM = 1, XFH_K_CONV_MFMA = 2, XFH_K_CONV_DIRECT = 3,
     XFH_K_NMS = 4, XFH_K_SELECT = 5, XFH_K_DESC = 6, XFH_K_HEADS = 7, XFH_K_DIST_I32 = 8,
     XFH_K_PREPROC = 9, XFH_K_BEST2 = 10, XFH_K_DISTINCTIVE = 11, XFH_K_MNN_GEMM_SEG = 12,
-    XFH_K_GRID_BUILD = 13, XFH_K_SEARCH_WINDOW = 14, XFH_K_COUNT = 15
+    XFH_K_GRID_BUILD = 13, XFH_K_SEARCH_WINDOW = 14,
+    XFH_K_FRAME_FINISH = 15, XFH_K_COUNT = 16
 };
 /* layer_mask selects conv layers for XFH_K_CONV_*: 0 = every layer, else bit i = BasicLayer i
  * (0..22 in XFeatModel order) and bit 23 = block_fusion.2 */

@@ -29,7 +29,7 @@ ERR_EMPTY_IMAGE = 2
 ERR_NO_DEVICE = 7
 ERR_COMM = 11
 
-K = dict(NONE=0, MNN_GEMM=1, CONV_MFMA=2, CONV_DIRECT=3, NMS=4, SELECT=5, DESC=6, HEADS=7, DIST_I32=8, PREPROC=9, BEST2=10, DISTINCTIVE=11, MNN_GEMM_SEG=12, GRID_BUILD=13, SEARCH_WINDOW=14)
+K = dict(NONE=0, MNN_GEMM=1, CONV_MFMA=2, CONV_DIRECT=3, NMS=4, SELECT=5, DESC=6, HEADS=7, DIST_I32=8, PREPROC=9, BEST2=10, DISTINCTIVE=11, MNN_GEMM_SEG=12, GRID_BUILD=13, SEARCH_WINDOW=14, FRAME_FINISH=15)
 T = dict(X=0, XSTAT=1, SKIP_POOL=2, FEATS=6, H1=8, K1H=9, RAW0=16, STAT0=48, SEL=80)
 
 
@@ -44,6 +44,14 @@ class GridBounds(C.Structure):
     _fields_ = [("min_x", C.c_float), ("min_y", C.c_float), ("max_x", C.c_float), ("max_y", C.c_float)]
 
 
+class Camera(C.Structure):
+    """xfh_camera: pinhole intrinsics, the radial-tangential coefficients (k1, k2, p1, p2, k3), mbf and the image size"""
+    _fields_ = [("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("k1", C.c_float), ("k2", C.c_float),
+                ("p1", C.c_float), ("p2", C.c_float), ("k3", C.c_float), ("bf", C.c_float), ("width", C.c_int32), ("height", C.c_int32),
+                ("reserved", C.c_int32 * 4)]
+
+
+DEPTH_NONE, DEPTH_F32, DEPTH_U16 = 0, 1, 2
 GRID_COLS, GRID_ROWS = 64, 48
 GRID_SKIP_PADDING = 1
 GRID_MAX_N = 16384
@@ -97,6 +105,10 @@ SYMBOLS = [
     ("xfh_grid_unpack", _i, [_vp, _sz, _i, _vp, _vp, _pi]),
     ("xfh_search_window_device", _i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
     ("xfh_search_window", _i, [_vp, _vp, _vp, _i, _vp, C.POINTER(GridBounds), _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    ("xfh_undistort_points", _i, [C.POINTER(Camera), _vp, _i, _vp]),
+    ("xfh_camera_bounds", _i, [C.POINTER(Camera), C.POINTER(GridBounds)]),
+    ("xfh_frame_finish_records_device", _i, [_vp, _vp, _i, C.POINTER(Camera), _vp, _i, _sz, _f, C.POINTER(GridBounds), _i, _vp, _vp, _vp, _vp]),
+    ("xfh_frame_finish", _i, [_vp, _vp, _i, C.POINTER(Camera), _vp, _i, _sz, _f, _vp, _vp, _vp]),
     ("xfh_distinctive_csr", _i, [_vp, _vp, _i, _vp, _vp, _i, _vp, _vp]),
     ("xfh_distinctive_csr_device", _i, [_vp, _vp, _i, _vp, _vp, _i, _i, _vp, _vp]),
     ("xfh_comm_unique_id", _i, [_vp]),

@@ -4,6 +4,7 @@
 #include "ctx.h"
 #include "mnn_seg_plan.h"
 #include "window_layout.h"
+#include "frame_math.h"
 
 #include <dlfcn.h>
 #include <math.h>
@@ -82,7 +83,7 @@ const char* xfh_strerror(int s) {
 const char* xfh_kernel_name(int id) {
     static const char* n[XFH_K_COUNT] = {"none", "k_mnn_gemm", "k_conv_mfma", "k_conv_direct", "k_nms_score", "k_select",
                                          "k_desc", "k_heads_kp", "k_dist_i32", "k_preproc", "k_best2_csr", "k_distinctive_csr", "k_mnn_gemm_seg",
-                                         "k_grid_build", "k_search_window"};
+                                         "k_grid_build", "k_search_window", "k_frame_finish"};
     return (id >= 0 && id < XFH_K_COUNT) ? n[id] : "?";
 }
 
@@ -908,6 +909,78 @@ int xfh_search_window(xfh_ctx* c, const float* q, const float* uvr, int nq, cons
                                   o[0], o[1], o[2], o[3], o[4]));
     int* out[5] = {best_idx, best_dist, second_idx, second_dist, n_candidates};
     for (int k = 0; k < 5; ++k) HIPCK(c, hipMemcpyAsync(out[k], o[k], (size_t)nq * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCK(c, hipStreamSynchronize(c->stream));
+    return XFH_OK;
+}
+
+// ---- finishing an RGB-D frame: undistort, depth / right coordinate, grid of the undistorted keypoints (frame_math.h, frame_finish.hip.h) ----
+int xfh_undistort_points(const xfh_camera* cam, const float* xy, int n, float* xy_un) {
+    if (!cam || n < 0 || (n > 0 && (!xy || !xy_un))) return XFH_ERR_INVALID_ARG;
+    for (int i = 0; i < n; ++i) xfh_undistort_point(*cam, xy[2 * i], xy[2 * i + 1], &xy_un[2 * i], &xy_un[2 * i + 1]);
+    return XFH_OK;
+}
+
+// Frame::ComputeImageBounds (Frame.cc:975-1002)
+int xfh_camera_bounds(const xfh_camera* cam, xfh_grid_bounds* out) {
+    if (!cam || !out || cam->width <= 0 || cam->height <= 0) return XFH_ERR_INVALID_ARG;
+    const float w = (float)cam->width, h = (float)cam->height;
+    if (cam->k1 == 0.0f) { out->min_x = 0.0f; out->min_y = 0.0f; out->max_x = w; out->max_y = h; return XFH_OK; }
+    const float in[8] = {0.0f, 0.0f, w, 0.0f, 0.0f, h, w, h};
+    float p[8];
+    for (int i = 0; i < 4; ++i) xfh_undistort_point(*cam, in[2 * i], in[2 * i + 1], &p[2 * i], &p[2 * i + 1]);
+    // std::min / std::max as the reference calls them (a NaN in the second operand is not taken)
+    out->min_x = p[4] < p[0] ? p[4] : p[0]; out->max_x = p[2] < p[6] ? p[6] : p[2];
+    out->min_y = p[3] < p[1] ? p[3] : p[1]; out->max_y = p[5] < p[7] ? p[7] : p[5];
+    return XFH_OK;
+}
+
+// the checks the two finish calls share: camera size, depth type / pitch / alignment
+static bool finish_depth_ok(const xfh_camera* cam, const void* depth, int depth_type, size_t pitch) {
+    if (!cam || cam->width <= 0 || cam->height <= 0) return false;
+    if (depth_type != XFH_DEPTH_NONE && depth_type != XFH_DEPTH_F32 && depth_type != XFH_DEPTH_U16) return false;
+    if (depth_type == XFH_DEPTH_NONE || !depth) return true;                               // no image: -1 everywhere, pitch unused
+    const size_t es = depth_type == XFH_DEPTH_F32 ? 4 : 2;
+    return pitch >= (size_t)cam->width * es && pitch % es == 0 && (((uintptr_t)depth) & (es - 1)) == 0;
+}
+
+int xfh_frame_finish_records_device(xfh_ctx* c, const void* d_records, int B, const xfh_camera* cam, const void* d_depth, int depth_type, size_t depth_pitch,
+                                    float depth_scale, const xfh_grid_bounds* bounds, int flags, float* d_xy_un, float* d_uright, float* d_depth_out, void* d_grids) {
+    if (!c || B < 1 || B > c->cfg.max_batch || (flags & ~XFH_GRID_SKIP_PADDING) || !finish_depth_ok(cam, d_depth, depth_type, depth_pitch)) return XFH_ERR_INVALID_ARG;
+    GridGeom g = {};
+    if (d_grids && !grid_geom(bounds, &g)) return XFH_ERR_INVALID_ARG;
+    const int nf = c->cfg.nfeatures;
+    if (!d_records || !d_xy_un || !d_uright || !d_depth_out || (d_grids && nf > XFH_GRID_MAX_N)) return XFH_ERR_INVALID_ARG;
+    if ((((uintptr_t)d_grids) & 15) || ((((uintptr_t)d_records) | ((uintptr_t)d_xy_un) | ((uintptr_t)d_uright) | ((uintptr_t)d_depth_out)) & 3)) return XFH_ERR_INVALID_ARG;
+    HIPCK(c, hipSetDevice(c->cfg.device));
+    const size_t rb = xfh_record_bytes(nf);
+    HIPCK(c, launch_frame_finish(c, (const char*)d_records + xfh_record_kps_offset(), rb, d_records, rb, *cam, d_depth, depth_type, depth_pitch, depth_scale,
+                                 d_xy_un, d_uright, d_depth_out, d_grids, xfh_grid_bytes(nf), nf, B, g, flags));
+    return XFH_OK;
+}
+
+int xfh_frame_finish(xfh_ctx* c, const xfh_keypoint* kps, int n, const xfh_camera* cam, const void* depth_img, int depth_type, size_t depth_pitch,
+                     float depth_scale, float* xy_un, float* uright, float* depth) {
+    if (!c || n < 0 || !finish_depth_ok(cam, depth_img, depth_type, depth_pitch)) return XFH_ERR_INVALID_ARG;
+    if (n == 0) return XFH_OK;
+    if (depth_type == XFH_DEPTH_NONE) depth_img = nullptr;
+    if (!kps || !xy_un || !uright || !depth) return XFH_ERR_INVALID_ARG;
+    HIPCK(c, hipSetDevice(c->cfg.device));
+    MatchWs& w = c->mws;
+    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    const size_t bk = al((size_t)n * sizeof(xfh_keypoint)), bo = al((size_t)n * 16), bd = depth_img ? al((size_t)cam->height * depth_pitch) : 0;
+    int rc = grow(c, &w.b2_buf, &w.cap_b2, bk + bo + bd);
+    if (rc != XFH_OK) return rc;
+    char* p = (char*)w.b2_buf;
+    xfh_keypoint* dk = (xfh_keypoint*)p; p += bk;
+    float* dxy = (float*)p; float* dur = dxy + 2 * (size_t)n; float* ddz = dur + n; p += bo;
+    void* dimg = depth_img ? p : nullptr;
+    HIPCK(c, hipMemcpyAsync(dk, kps, (size_t)n * sizeof(xfh_keypoint), hipMemcpyHostToDevice, c->stream));
+    if (depth_img) HIPCK(c, hipMemcpyAsync(dimg, depth_img, (size_t)cam->height * depth_pitch, hipMemcpyHostToDevice, c->stream));
+    GridGeom g = {};
+    HIPCK(c, launch_frame_finish(c, dk, 0, nullptr, 0, *cam, dimg, depth_type, depth_pitch, depth_scale, dxy, dur, ddz, nullptr, 0, n, 1, g, 0));
+    HIPCK(c, hipMemcpyAsync(xy_un, dxy, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCK(c, hipMemcpyAsync(uright, dur, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCK(c, hipMemcpyAsync(depth, ddz, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
     HIPCK(c, hipStreamSynchronize(c->stream));
     return XFH_OK;
 }

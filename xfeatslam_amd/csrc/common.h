@@ -180,7 +180,7 @@ struct MatchWs {
     int* o_buf = nullptr; size_t cap_out = 0;                          // device outputs of the host call: n, idx1[nm], idx2[nm], dist[nm]
     int* h_out = nullptr; size_t cap_hout = 0;                         // pinned mirror of o_buf
     int32_t* o_tab = nullptr; size_t cap_tab = 0;
-    void* b2_buf = nullptr; size_t cap_b2 = 0;                             // staging for the host-pointer best2 call
+    void* b2_buf = nullptr; size_t cap_b2 = 0;                             // staging of the host-pointer calls (xfh_best2_csr, xfh_search_window, xfh_frame_finish): each ends in a stream synchronise, so grow() may free it
     u64* bkeys = nullptr; size_t cap_bkeys = 0;                            // key planes + pairs of the many-pairs call (xfh_match_mnn_prepared_batch_device), grown on demand
 };
 
@@ -208,6 +208,9 @@ hipError_t launch_distinctive(xfh_ctx* c, const float* table, const int* offsets
 struct GridGeom;
 hipError_t launch_grid_build(xfh_ctx* c, const void* kps, size_t kps_stride, const void* hdr, size_t hdr_stride, void* grids, size_t grid_stride,
                              int n, int B, const GridGeom& g, int flags);                     // window_search.hip.h
+hipError_t launch_frame_finish(xfh_ctx* c, const void* kps, size_t kps_stride, const void* hdr, size_t hdr_stride, const xfh_camera& cam,
+                               const void* d_depth, int depth_type, size_t depth_pitch, float depth_scale, float* xy_un, float* uright, float* depth,
+                               void* grids, size_t grid_stride, int n, int B, const GridGeom& g, int flags);   // frame_finish.hip.h
 hipError_t launch_search_window(xfh_ctx* c, const float* q, const float* uvr, int nq, const void* grid, const float* tg, int nt,
                                 const uint8_t* skip, const float* uright, const float* ur_query, int init_dist,
                                 int* best_idx, int* best_dist, int* second_idx, int* second_dist, int* n_candidates);

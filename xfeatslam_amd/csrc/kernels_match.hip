@@ -11,6 +11,8 @@
 //   k_best2_csr   : best / second-best distance over candidate lists (the SearchBy* inner loop, :75-119).
 //   k_grid_build / k_search_window : the frame grid in device memory and the fused window -> candidates -> best two search
 //                   (Frame::AssignFeaturesToGrid / GetFeaturesInArea + the SearchByProjection loop; window_search.hip.h).
+//   k_frame_finish : undistort + depth / right coordinate + the grid of the undistorted keypoints for B records in one launch
+//                   (Frame::UndistortKeyPoints / ComputeStereoFromRGBD / AssignFeaturesToGrid of the RGB-D constructor; frame_finish.hip.h).
 //   k_distinctive_csr : MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:329-403), one wave per map point.
 //
 // Numerics: normalised rows and the 64-term dot products are bit-identical to the oracle
@@ -86,6 +88,7 @@ hipError_t launch_best2(xfh_ctx* c, const float* q, int nq, const float* tg, con
 }
 
 #include "window_search.hip.h"
+#include "frame_finish.hip.h"
 
 // ---- k_distinctive_csr: MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:329-403), batched -------
 // One wave per group (map point).  Rows are taken 64 at a time, lane = row: the lane keeps its descriptor in

@@ -21,36 +21,30 @@
 // of the input: two builds give identical bytes.
 #define XFH_GRID_DROPPED 0xFFFFFFFFu
 #define XFH_GRID_BUILD_THREADS 1024
-__global__ __launch_bounds__(XFH_GRID_BUILD_THREADS)
-void k_grid_build(const char* __restrict__ kps, size_t kps_stride, const char* __restrict__ hdr, size_t hdr_stride,
-                  char* __restrict__ grids, size_t grid_stride, int n, int P, GridGeom g, int flags) {
-    extern __shared__ unsigned gkeys[];                    // P keys, P = power of two >= max(n, 2)
-    const int f = blockIdx.x, tid = threadIdx.x;
-    const xfh_keypoint* kp = (const xfh_keypoint*)(kps + (size_t)f * kps_stride);
-    char* grid = grids + (size_t)f * grid_stride;
-    // valid slots of a record: [0, mono_index) and [n - (n_valid - mono_index), n) (xfh_match_records_device); all of them otherwise
-    int lo_end = n, hi_beg = n;
+// valid slots of a record: [0, mono_index) and [n - (n_valid - mono_index), n) (xfh_match_records_device); all of them otherwise
+__device__ __forceinline__ void grid_valid_slots(const char* hdr, size_t hdr_stride, int f, int n, int flags, int& lo_end, int& hi_beg) {
+    lo_end = n; hi_beg = n;
     if (hdr && (flags & XFH_GRID_SKIP_PADDING)) {
         const int* h = (const int*)(hdr + (size_t)f * hdr_stride);
         int nv = h[0], mono = h[1];
         nv = nv < 0 ? 0 : (nv > n ? n : nv); mono = mono < 0 ? 0 : (mono > nv ? nv : mono);
         lo_end = mono; hi_beg = n - (nv - mono);
     }
-    for (int i = tid; i < P; i += XFH_GRID_BUILD_THREADS) {
-        unsigned key = XFH_GRID_DROPPED;
-        if (i < n && (i < lo_end || i >= hi_beg)) {
-            const float fx = roundf((kp[i].x - g.min_x) * g.inv_w);        // posX = round((kp.pt.x - mnMinX) * mfGridElementWidthInv), :920
-            const float fy = roundf((kp[i].y - g.min_y) * g.inv_h);
-            // posX < 0 || posX >= FRAME_GRID_COLS || ... -> not binned (:925); decided on the float, so a non-finite or huge value never reaches the conversion
-            if (fx >= 0.0f && fx < (float)XFH_GRID_COLS && fy >= 0.0f && fy < (float)XFH_GRID_ROWS)
-                key = ((unsigned)((int)fx * XFH_GRID_ROWS + (int)fy) << 20) | (unsigned)i;
-        }
-        gkeys[i] = key;
-    }
-    __syncthreads();
-    // bitonic network.  Steps with a partner distance j >= 64 cross waves and end in a workgroup barrier; for j <= 32 the 64 pairs of a
-    // wave (t = 64 w .. 64 w + 63) touch exactly the keys [128 w, 128 w + 128) at every such j, so the steps j = 32 .. 1 of a stage run
-    // inside the wave, ordered by a wave-level fence only (27 workgroup barriers instead of 78 at 4096 slots).
+}
+// the key of slot i at (x, y): cell << 20 | slot, or XFH_GRID_DROPPED when PosInGrid drops it
+__device__ __forceinline__ unsigned grid_key(float x, float y, int i, const GridGeom& g) {
+    const float fx = roundf((x - g.min_x) * g.inv_w);                  // posX = round((kp.pt.x - mnMinX) * mfGridElementWidthInv), :920
+    const float fy = roundf((y - g.min_y) * g.inv_h);
+    // posX < 0 || posX >= FRAME_GRID_COLS || ... -> not binned (:925); decided on the float, so a non-finite or huge value never reaches the conversion
+    if (fx >= 0.0f && fx < (float)XFH_GRID_COLS && fy >= 0.0f && fy < (float)XFH_GRID_ROWS)
+        return ((unsigned)((int)fx * XFH_GRID_ROWS + (int)fy) << 20) | (unsigned)i;
+    return XFH_GRID_DROPPED;
+}
+// bitonic network over the P keys in LDS (all XFH_GRID_BUILD_THREADS threads; the caller has put a barrier behind the keys).
+// Steps with a partner distance j >= 64 cross waves and end in a workgroup barrier; for j <= 32 the 64 pairs of a
+// wave (t = 64 w .. 64 w + 63) touch exactly the keys [128 w, 128 w + 128) at every such j, so the steps j = 32 .. 1 of a stage run
+// inside the wave, ordered by a wave-level fence only (27 workgroup barriers instead of 78 at 4096 slots).
+__device__ __forceinline__ void grid_sort(unsigned* gkeys, int P, int tid) {
     auto exchange = [&](int t, int j, int k) {
         const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), l = i | j;
         const unsigned a = gkeys[i], b = gkeys[l];
@@ -70,6 +64,9 @@ void k_grid_build(const char* __restrict__ kps, size_t kps_stride, const char* _
             }
         __syncthreads();
     }
+}
+// the blob of one frame from its sorted keys; xy[2 * slot], xy[2 * slot + 1] (stride_floats apart per slot) are the coordinates the keys were made of
+__device__ __forceinline__ void grid_emit(char* grid, const unsigned* gkeys, const float* xy, int stride_floats, int n, int P, const GridGeom& g, int flags, int tid) {
     int* cs = (int*)(grid + XFH_GRID_CS_OFF);
     GridItem* items = (GridItem*)(grid + XFH_GRID_ITEMS_OFF);
     GridHeader* gh = (GridHeader*)grid;
@@ -81,7 +78,10 @@ void k_grid_build(const char* __restrict__ kps, size_t kps_stride, const char* _
         if (prev < XFH_GRID_CELLS && last == XFH_GRID_CELLS) gh->n_binned = p; // exactly one p: the first key past the binned ones
         if (p < n) {
             GridItem it = {-1, 0.0f, 0.0f, 0};
-            if (cell < XFH_GRID_CELLS) { const int idx = (int)(key & 0xFFFFFu); it.index = idx; it.x = kp[idx].x; it.y = kp[idx].y; }
+            if (cell < XFH_GRID_CELLS) {
+                const int idx = (int)(key & 0xFFFFFu);
+                it.index = idx; it.x = xy[(size_t)idx * stride_floats]; it.y = xy[(size_t)idx * stride_floats + 1];
+            }
             items[p] = it;
         }
     }
@@ -91,6 +91,24 @@ void k_grid_build(const char* __restrict__ kps, size_t kps_stride, const char* _
         for (int k = 0; k < 6; ++k) gh->pad[k] = 0;
     }
     for (int c = XFH_GRID_CELLS + 1 + tid; c < XFH_GRID_CS_SLOTS; c += XFH_GRID_BUILD_THREADS) cs[c] = 0;
+}
+
+__global__ __launch_bounds__(XFH_GRID_BUILD_THREADS)
+void k_grid_build(const char* __restrict__ kps, size_t kps_stride, const char* __restrict__ hdr, size_t hdr_stride,
+                  char* __restrict__ grids, size_t grid_stride, int n, int P, GridGeom g, int flags) {
+    extern __shared__ unsigned gkeys[];                    // P keys, P = power of two >= max(n, 2)
+    const int f = blockIdx.x, tid = threadIdx.x;
+    const xfh_keypoint* kp = (const xfh_keypoint*)(kps + (size_t)f * kps_stride);
+    int lo_end, hi_beg;
+    grid_valid_slots(hdr, hdr_stride, f, n, flags, lo_end, hi_beg);
+    for (int i = tid; i < P; i += XFH_GRID_BUILD_THREADS) {
+        unsigned key = XFH_GRID_DROPPED;
+        if (i < n && (i < lo_end || i >= hi_beg)) key = grid_key(kp[i].x, kp[i].y, i, g);
+        gkeys[i] = key;
+    }
+    __syncthreads();
+    grid_sort(gkeys, P, tid);
+    grid_emit(grids + (size_t)f * grid_stride, gkeys, (const float*)kp, (int)(sizeof(xfh_keypoint) / sizeof(float)), n, P, g, flags, tid);
 }
 
 hipError_t launch_grid_build(xfh_ctx* c, const void* kps, size_t kps_stride, const void* hdr, size_t hdr_stride, void* grids, size_t grid_stride,

@@ -241,6 +241,53 @@ class Context:
                                       None if uq is None else uq.ctypes.data, int(init_dist), *[o.ctypes.data for o in out]), self.h)
         return tuple(o[:nq] for o in out)
 
+    # -- finishing an RGB-D frame (xfh_undistort_points / xfh_camera_bounds / xfh_frame_finish*) ---------
+    @staticmethod
+    def undistort_points(cam, xy):
+        """xfh_undistort_points (host): [n][2] fp32 pixel coordinates -> mvKeysUn coordinates, cv::undistortPoints with P = K"""
+        a = np.ascontiguousarray(xy, np.float32).reshape(-1, 2)
+        out = np.empty_like(a)
+        check(lib().xfh_undistort_points(C.byref(cam), a.ctypes.data, len(a), out.ctypes.data))
+        return out
+
+    @staticmethod
+    def camera_bounds(cam):
+        """xfh_camera_bounds (host): Frame::ComputeImageBounds -> (mnMinX, mnMinY, mnMaxX, mnMaxY)"""
+        b = capi.GridBounds()
+        check(lib().xfh_camera_bounds(C.byref(cam), C.byref(b)))
+        return (b.min_x, b.min_y, b.max_x, b.max_y)
+
+    def frame_finish_records(self, d_records, B: int, cam, bounds=None, flags: int = 0, d_depth=None, depth_type: int = capi.DEPTH_NONE,
+                             depth_pitch: int = 0, depth_scale: float = 1.0, grid: bool = True, out=None):
+        """xfh_frame_finish_records_device: UndistortKeyPoints + ComputeStereoFromRGBD + AssignFeaturesToGrid of B extraction records
+        in device memory (pointer) in one launch; asynchronous.  d_depth: pointer to B depth images (fp32 metres or raw uint16 times
+        depth_scale), rows depth_pitch bytes apart.  -> (xy_un, uright, depth, grids) DeviceBuffers (grids None when grid=False): frame b
+        at 2 * b * nfeatures / b * nfeatures floats and b * grid_bytes(nfeatures) bytes.  out = the same tuple from an earlier call."""
+        nf = self.nfeatures
+        if out is None:
+            out = (capi.DeviceBuffer(max(B, 1) * nf * 8), capi.DeviceBuffer(max(B, 1) * nf * 4), capi.DeviceBuffer(max(B, 1) * nf * 4),
+                   capi.DeviceBuffer(max(B, 1) * self.grid_bytes(nf)) if grid else None)
+        xy, ur, dz, g = out
+        gb = C.byref(capi.GridBounds(*bounds)) if bounds is not None else None
+        check(lib().xfh_frame_finish_records_device(self.h, d_records, B, C.byref(cam), d_depth, depth_type, depth_pitch, float(depth_scale), gb, flags,
+                                                    xy.ptr, ur.ptr, dz.ptr, g.ptr if g else None), self.h)
+        return out
+
+    def frame_finish(self, kps, cam, depth=None, depth_scale: float = 1.0):
+        """xfh_frame_finish (host pointers): keypoints (KP_DTYPE) and an optional [height][width] depth image (float32 metres, or
+        uint16 times depth_scale) -> (xy_un[n][2], uright[n], depth[n])"""
+        k = np.ascontiguousarray(kps, KP_DTYPE)
+        n = len(k)
+        xy = np.zeros((max(n, 1), 2), np.float32); ur = np.zeros(max(n, 1), np.float32); dz = np.zeros(max(n, 1), np.float32)
+        img, dt, pitch = None, capi.DEPTH_NONE, 0
+        if depth is not None:
+            img = np.ascontiguousarray(depth)
+            dt = {np.dtype(np.float32): capi.DEPTH_F32, np.dtype(np.uint16): capi.DEPTH_U16}[img.dtype]
+            pitch = img.strides[0]
+        check(lib().xfh_frame_finish(self.h, k.ctypes.data, n, C.byref(cam), None if img is None else img.ctypes.data, dt, pitch, float(depth_scale),
+                                     xy.ctypes.data, ur.ctypes.data, dz.ctypes.data), self.h)
+        return xy[:n], ur[:n], dz[:n]
+
     def distinctive_csr(self, table, offsets, indices):
         """MapPoint::ComputeDistinctiveDescriptors over CSR groups of descriptor rows ->
         (position inside the group of the descriptor with the least median distance, that median)"""
