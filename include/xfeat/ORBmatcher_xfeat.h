@@ -10,6 +10,8 @@
  *        loop of SearchByProjection (ORBmatcher.cc:1925-1955) on the GPU: a frame grid in device memory and one fused
  *        window -> candidates -> best two call for all queries; XFgrid::buildFromRecord(record, n, camera, bounds, depth) is the rest
  *        of the RGB-D Frame constructor (UndistortKeyPoints, ComputeStereoFromRGBD, the grid on mvKeysUn; Frame.cc:311-374)
+ *   XFmatcher::searchByProjection: the whole of ORBmatcher::SearchByProjection(Frame&, const Frame&, th, bMono) (ORBmatcher.cc:1861-2047)
+ *        and of the SearchLocalPoints form (:42-141): projection, cull, windowed best two and the reference's claim order in one call
  *   best2 / distinctive: the batched inner loops of SearchBy* (ORBmatcher.cc:75-119) and of
  *        MapPoint::ComputeDistinctiveDescriptors (MapPoint.cc:329-403)
  *
@@ -303,7 +305,7 @@ public:
             for (int k = 0; k < n; ++k) _matches[p].emplace_back(DMatch(i1[k], i2[k], d[k]));
         }
     }
-    ~XFmatcher() { if (d_out) xfh_dev_free(d_out); }
+    ~XFmatcher() { if (d_out) xfh_dev_free(d_out); if (d_proj) xfh_dev_free(d_proj); }
     XFmatcher(const XFmatcher&) = delete;
     XFmatcher& operator=(const XFmatcher&) = delete;
 
@@ -365,6 +367,82 @@ public:
         if (rc != XFH_OK) throw std::runtime_error(std::string("XFmatcher::searchWindow: ") + xfh_strerror(rc));
     }
 
+    // ORBmatcher::SearchByProjection(Frame& CurrentFrame, const Frame& LastFrame, th, bMono) (ORBmatcher.cc:1861-2047) as ONE call
+    // (xfh_search_projection_device): query q is row q of `queries` (the map point's descriptor) with world position
+    // worldPoints[3q .. 3q + 2] and flags[q] (XFH_PROJ_FLAG_ACTIVE: pMP != NULL && !mvbOutlier; XFH_PROJ_FLAG_CLAIMS:
+    // pMP->Observations() > 0); Tcw is the row-major 3x4 [R|t] of CurrentFrame.GetPose(); `grid` / `targets` are the current frame's
+    // grid and descriptor rows; skip / uright as in searchWindow (skip: entries of mvpMapPoints that were set BEFORE the call).
+    // The queries are processed in index order with the reference's claim rule: matchOfQuery[q] = the keypoint query q wrote
+    // (mvpMapPoints[bestIdx2] = pMP, :1957) or -1, assignedQuery[k] = the query that holds mvpMapPoints[k] after the loop or -1 (the
+    // last writer wins), and the return value is nmatches.  nnRatio > 0 selects the SearchLocalPoints acceptance rule (:122-127).
+    // status / bestDist / secondDist / nCandidates of the last call stay readable in lastStatus() etc.  Blocks until the result is
+    // on the host.
+    int searchByProjection(const Mat& queries, const std::vector<float>& worldPoints, const std::vector<unsigned char>& flags, const float* Tcw,
+                           const xfh_camera& cam, const xfh_grid_bounds& bounds, float th, const XFgrid& grid, const Mat& targets,
+                           std::vector<int>& matchOfQuery, std::vector<int>& assignedQuery, const std::vector<unsigned char>* skip = nullptr,
+                           const std::vector<float>* uright = nullptr, int initDist = 256, float nnRatio = 0.f, int thHigh = TH_HIGH) {
+        const int nq = queries.rows, nt = targets.rows;
+        matchOfQuery.assign(nq, -1); assignedQuery.assign(nt, -1);
+        if (nq == 0 || nt == 0) return 0;
+        if ((int)worldPoints.size() != 3 * nq || (int)flags.size() != nq || nt != grid.size() || (skip && (int)skip->size() != nt) ||
+            (uright && (int)uright->size() != nt) || !Tcw)
+            throw std::runtime_error("XFmatcher::searchByProjection: sizes do not fit");
+        auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+        const size_t bq = al((size_t)nq * 256), bp = al((size_t)nq * 12), bfl = al((size_t)nq), bT = 256, bt = al((size_t)nt * 256), bs = al((size_t)nt), bf = al((size_t)nt * 4);
+        reserve(d_out, d_out_bytes, bq + bp + bfl + bT + bt + bs + bf, "XFmatcher::searchByProjection");
+        char* p = (char*)d_out;
+        float* dq = (float*)p; p += bq; float* dp = (float*)p; p += bp; unsigned char* dfl = (unsigned char*)p; p += bfl; float* dT = (float*)p; p += bT;
+        float* dt = (float*)p; p += bt; unsigned char* ds = (unsigned char*)p; p += bs; float* dr = (float*)p;
+        int rc = xfh_synchronize(ctx);                       // (the copies below are synchronous: nothing queued earlier may still read the buffer)
+        if (rc == XFH_OK) rc = xfh_memcpy_h2d(dq, queries.template ptr<float>(0), (size_t)nq * 256);
+        if (rc == XFH_OK) rc = xfh_memcpy_h2d(dp, worldPoints.data(), (size_t)nq * 12);
+        if (rc == XFH_OK) rc = xfh_memcpy_h2d(dfl, flags.data(), (size_t)nq);
+        if (rc == XFH_OK) rc = xfh_memcpy_h2d(dT, Tcw, 48);
+        if (rc == XFH_OK) rc = xfh_memcpy_h2d(dt, targets.template ptr<float>(0), (size_t)nt * 256);
+        if (rc == XFH_OK && skip) rc = xfh_memcpy_h2d(ds, skip->data(), (size_t)nt);
+        if (rc == XFH_OK && uright) rc = xfh_memcpy_h2d(dr, uright->data(), (size_t)nt * 4);
+        if (rc != XFH_OK) throw std::runtime_error(std::string("XFmatcher::searchByProjection: ") + xfh_strerror(rc));
+        return searchByProjection(XFH_PROJ_POINTS, nq, dp, nullptr, dT, &cam, &bounds, th, dq, dfl, grid, dt, skip ? ds : nullptr, uright ? dr : nullptr,
+                                  matchOfQuery, assignedQuery, initDist, nnRatio, thHigh);
+    }
+    // The same on DEVICE pointers and an XFgrid (a frame finished with XFgrid::buildFromRecord: d_targets = the record's descriptor block,
+    // d_uright = grid.deviceURight()).  mode XFH_PROJ_POINTS: d_points_or_uvr = world points [nq][3], d_Tcw = 12 floats in device memory;
+    // mode XFH_PROJ_GIVEN (the SearchLocalPoints form): d_points_or_uvr = (u, v, r) per query from the caller's isInFrustum, d_ur_query
+    // with d_uright or neither, nnRatio = mfNNratio.  Only the results travel to the host.
+    int searchByProjection(int mode, int nq, const float* d_points_or_uvr, const float* d_ur_query, const float* d_Tcw, const xfh_camera* cam,
+                           const xfh_grid_bounds* bounds, float radius, const float* d_queries, const unsigned char* d_flags, const XFgrid& grid,
+                           const float* d_targets, const unsigned char* d_skip, const float* d_uright, std::vector<int>& matchOfQuery,
+                           std::vector<int>& assignedQuery, int initDist = 256, float nnRatio = 0.f, int thHigh = TH_HIGH) {
+        const int nt = grid.size();
+        matchOfQuery.assign(nq > 0 ? nq : 0, -1); assignedQuery.assign(nt > 0 ? nt : 0, -1);
+        if (nq <= 0 || nt <= 0) return 0;
+        auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+        const size_t bw = al(xfh_search_projection_workspace_bytes(nq, nt, 1)), bn = al((size_t)nq * 4), ba = al((size_t)nt * 4), bs = al((size_t)nq);
+        reserve(d_proj, d_proj_bytes, bw + 4 * bn + ba + bs + 256, "XFmatcher::searchByProjection");
+        char* p = (char*)d_proj;
+        void* dws = p; p += bw;
+        int* o[4];
+        for (int k = 0; k < 4; ++k) { o[k] = (int*)p; p += bn; }
+        int* das = (int*)p; p += ba; unsigned char* dst = (unsigned char*)p; p += bs; int* dnm = (int*)p;
+        int rc = xfh_search_projection_device(ctx, mode, 1, nq, d_points_or_uvr, d_ur_query, d_Tcw, cam, bounds, radius, d_queries, d_flags, grid.device(),
+                                              d_targets, 0, nt, d_skip, d_uright, initDist, thHigh, nnRatio, dws, dst, o[0], o[1], o[2], o[3], nullptr, das, dnm);
+        if (rc == XFH_OK) rc = xfh_synchronize(ctx);
+        projStatus.assign(nq, 0); projBest.assign(nq, 0); projSecond.assign(nq, 0); projCandidates.assign(nq, 0);
+        int nmatches = 0;
+        int* out[4] = {matchOfQuery.data(), projBest.data(), projSecond.data(), projCandidates.data()};
+        for (int k = 0; k < 4 && rc == XFH_OK; ++k) rc = xfh_memcpy_d2h(out[k], o[k], (size_t)nq * 4);
+        if (rc == XFH_OK) rc = xfh_memcpy_d2h(projStatus.data(), dst, (size_t)nq);
+        if (rc == XFH_OK) rc = xfh_memcpy_d2h(assignedQuery.data(), das, (size_t)nt * 4);
+        if (rc == XFH_OK) rc = xfh_memcpy_d2h(&nmatches, dnm, 4);
+        if (rc != XFH_OK) throw std::runtime_error(std::string("XFmatcher::searchByProjection: ") + xfh_strerror(rc));
+        return nmatches;
+    }
+    // per query, of the last searchByProjection: XFH_PROJ_* status, best / second DescriptorDistance, survivors after the claim skip
+    const std::vector<unsigned char>& lastStatus() const { return projStatus; }
+    const std::vector<int>& lastBestDist() const { return projBest; }
+    const std::vector<int>& lastSecondDist() const { return projSecond; }
+    const std::vector<int>& lastCandidates() const { return projCandidates; }
+
     // MapPoint::ComputeDistinctiveDescriptors (MapPoint.cc:329-403), batched over map points: group g observes the
     // rows indices[offsets[g] .. offsets[g+1]) of `table`; bestPos[g] = position in the group of the descriptor with
     // the least median DescriptorDistance to the others (-1 for an empty group), bestMedian[g] = that median.
@@ -379,12 +457,22 @@ public:
     }
 
 protected:
+    static void reserve(void*& buf, size_t& cap, size_t bytes, const char* who) {
+        if (bytes <= cap) return;
+        if (buf) xfh_dev_free(buf);
+        buf = nullptr; cap = 0;
+        if (xfh_dev_alloc(&buf, bytes) != XFH_OK) throw std::runtime_error(std::string(who) + ": out of device memory");
+        cap = bytes;
+    }
     float mfNNratio;
     bool mbCheckOrientation;
     xfh_ctx* ctx;
     std::vector<int> i1, i2;
     std::vector<float> d;
     void* d_out = nullptr; size_t d_out_bytes = 0;          // device result buffer of matchPrepared
+    void* d_proj = nullptr; size_t d_proj_bytes = 0;        // workspace and results of searchByProjection
+    std::vector<unsigned char> projStatus;
+    std::vector<int> projBest, projSecond, projCandidates;
 };
 
 }  // namespace ORB_SLAM3

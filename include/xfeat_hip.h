@@ -285,8 +285,9 @@ int xfh_best2_csr_device(xfh_ctx* ctx, const float* d_queries, int nq, const flo
  *   c0x = max(0, (int)floorf((u - min_x - r) * inv_w)), no candidates if >= 64; c1x = min(63, (int)ceilf((u - min_x + r) * inv_w)),
  *   none if < 0; the same for y with 48 rows; cells ix = c0x .. c1x (outer), iy = c0y .. c1y (inner), a cell's keypoints in stored
  *   order; keypoint k is a candidate when fabsf(x_k - u) < r && fabsf(y_k - v) < r (strict);
- *   d_skip (optional, one byte per target, non-zero = skip): "already has a map point with observations" (:1931-1933), evaluated
- *   by the caller; d_uright + d_ur_query (optional, both or neither): a candidate with uright[k] > 0 is skipped when
+ *   d_skip (optional, one byte per target, non-zero = skip): "already has a map point with observations" (:1931-1933).  A static
+ *   mask is exact only for entries that were set BEFORE the loop: inside SearchByProjection the test also sees what earlier
+ *   iterations of the same loop wrote (:1957, :128) -- that order is xfh_search_projection_device below; d_uright + d_ur_query (optional, both or neither): a candidate with uright[k] > 0 is skipped when
  *   fabsf(ur_query[q] - uright[k]) > r (:1935-1941);
  *   over the survivors in visiting order the rule and the result contract of xfh_best2_csr (best = second = init_dist, strict '<',
  *   exact DescriptorDistance), indices = keypoint slot numbers.  A tie goes to the candidate visited FIRST, which is not the lowest
@@ -367,6 +368,97 @@ int xfh_frame_finish_records_device(xfh_ctx* ctx, const void* d_records, int B, 
                                     float* d_xy_un, float* d_uright, float* d_depth, void* d_grids_or_null);
 int xfh_frame_finish(xfh_ctx* ctx, const xfh_keypoint* kps, int n, const xfh_camera* cam, const void* depth_or_null, int depth_type,
                      size_t depth_pitch_bytes, float depth_scale, float* xy_un, float* uright, float* depth);
+
+/* ---- SearchByProjection with the reference's claim order, device resident ------------------------------------------------------
+ * ORBmatcher::SearchByProjection(Frame& CurrentFrame, const Frame& LastFrame, th, bMono) (src/ORBmatcher.cc:1861-2047, called from
+ * Tracking.cc:2914-2932) and the SearchLocalPoints form SearchByProjection(Frame&, vector<MapPoint*>&, ...) (:42-141) as one call: world
+ * points and a pose (or the caller's projections) in, the reference's mvpMapPoints assignment and nmatches out, everything in device
+ * memory.  The candidate test `CurrentFrame.mvpMapPoints[i2] && ->Observations() > 0` (:1932-1934, :87-89) cannot be evaluated
+ * beforehand: Tracking.cc:2914 fills mvpMapPoints with NULL just before the call, so every entry the test sees was written by an
+ * earlier iteration of the same loop (:1957, :128).  The loop is sequential and greedy; a query whose map point has observations
+ * claims its keypoint and later queries skip it; a query whose map point has none (the temporal points of UpdateLastFrame) does not
+ * claim and a later query may overwrite its assignment; nmatches counts both.  The contract is that sequential loop.  Each problem b
+ * has one current-frame grid with its nt target descriptors and nq queries:
+ *
+ *   claimed[k] = d_skip ? d_skip[k] != 0 : 0        for k in [0, nt)
+ *   assigned[k] = -1;  n_matches = 0
+ *   for q = 0 .. nq-1, in this order:
+ *     flags[q] bit0 clear                          -> status INACTIVE  (pMP == NULL or mvbOutlier, :1883-1885)
+ *     -- projection, mode XFH_PROJ_POINTS (fp32, no contraction, exactly this order)
+ *     xc = ((T[0]*X + T[1]*Y) + T[2]*Z) + T[3]     (T = row-major 3x4 [R|t] of Tcw; yc, zc likewise from rows 1, 2)
+ *     invz = (float)(1.0 / (double)zc);            invz < 0 -> status BEHIND           (:1893-1896)
+ *     u = fx*xc/zc + cx;  v = fy*yc/zc + cy        (multiply, divide, add: Pinhole.cpp:45-46)
+ *     u < min_x || u > max_x || v < min_y || v > max_y -> status OUT_OF_BOUNDS          (:1900-1903, a NaN passes as in the reference)
+ *     ur = u - bf*invz;  r = radius (one float per call: th * mvScaleFactors[0] = th)
+ *     -- mode XFH_PROJ_GIVEN: (u, v, r) = d_uvr[3q..], ur = d_ur_query[q]; no culls (the caller's isInFrustum did them)
+ *     window + candidate filters exactly as xfh_search_window_device documents them (strict |dx| < r, |dy| < r; the uright filter
+ *     only when d_uright is given; a non-finite u, v or r has no candidates), with ONE addition: a candidate k with claimed[k] is
+ *     skipped.                                      no survivors -> status NO_CANDIDATES (:1920 / :73)
+ *     best / second over the survivors in visiting order, the rule of xfh_best2_csr (init_dist, strict '<')
+ *     accept = best_idx >= 0 && best <= th_high && !(nn_ratio > 0 && second_idx >= 0 && (float)best > nn_ratio * (float)second)
+ *              (nn_ratio = 0: the Frame-Frame form :1955;  > 0: :122-127 with bestLevel == bestLevel2 == 0 whenever a second exists,
+ *               and bestLevel2 == -1 -- accepted without the ratio -- when it does not.  best_idx < 0, no survivor under init_dist:
+ *               the reference goes on to index mvpMapPoints with -1, which is undefined; here the query is rejected)
+ *     !accept -> status REJECTED;   accept -> status MATCHED, assigned[best_idx] = q, ++n_matches,
+ *                and if flags[q] bit1 ("the map point has Observations() > 0"): claimed[best_idx] = 1
+ *
+ * Outputs, all exact and all in device memory.  Per query: status (XFH_PROJ_*), match_idx (-1 unless MATCHED), best_dist,
+ * second_dist (init_dist where there is none), n_candidates (survivors AFTER the claim skip; 0 for a query that never reached the
+ * search), and optionally d_proj_out[q] = (u, v, ur) ((0, 0, 0) for INACTIVE and BEHIND; GIVEN: the caller's values, ur = 0 without
+ * d_ur_query).  Per keypoint: assigned[k] = the query that holds mvpMapPoints[k] after the loop, -1 for none: the last writer wins,
+ * as at :1957.  n_matches[b]: one int per problem, counting accepting queries, not distinct keypoints, as the reference does.
+ *
+ * What of the reference function does not appear, and why.  The level windows of bForward / bBackward (:1913-1918) admit every XFeat
+ * keypoint, because all have octave 0: Tlw is not an input.  The rotation histogram (:1960-1977, 2049 ff.) puts every match in bin 0,
+ * because every XFeat keypoint has angle = -1: it removes nothing.  The Nleft != -1 branch is fisheye stereo, which SURVEY.md puts out
+ * of scope.  The pose goes in as a 3x4 matrix with the stated operation order.  The reference applies Sophus::SE3f * Vector3f through
+ * Eigen's quaternion path, which cannot be compiled or run here: bit equality with the reference's own x3Dc is NOT claimed, and
+ * nobody has measured it.  Everything after x3Dc follows the reference's expressions.
+ *
+ *   xfh_project_points    host, stateless, thread-safe (like xfh_undistort_points): the projection arithmetic above for n points with
+ *                         ONE pose.  uvr[i] = (u, v, radius), ur[i], status[i] = XFH_PROJ_BEHIND (u = v = ur = 0),
+ *                         XFH_PROJ_OUT_OF_BOUNDS or XFH_PROJ_VISIBLE.  The same source line as the kernel (projection_math.h).
+ *   xfh_search_projection_workspace_bytes(nq, nt, B)   bytes of d_workspace (16-byte aligned, owned by the caller, contents
+ *                         irrelevant before the call), = B times the value for B = 1.  After the call the first two ints of problem
+ *                         b's slice say how many rounds the claim resolution took and how many queries it searched a second time.
+ *   xfh_search_projection_device   B problems with the same nq, nt, camera, bounds and thresholds.  Layouts: d_points_or_uvr [B][nq][3],
+ *                         d_ur_query [B][nq], d_Tcw [B][12] in DEVICE memory, d_query_desc [B][nq][64], d_query_flags [B][nq] bytes,
+ *                         grid b at d_grids + b * xfh_grid_bytes(nt), target rows of problem b at d_targets + b * target_stride_bytes
+ *                         (xfh_record_bytes(nfeatures) lets d_targets point at the desc block of record 0 of a batch), d_skip and
+ *                         d_uright [B][nt]; outputs d_status [B][nq] bytes, d_match_idx / d_best_dist / d_second_dist / d_n_candidates
+ *                         [B][nq] ints, d_proj_out [B][nq][3] or NULL, d_assigned [B][nt] ints, d_n_matches [B] ints.  All pointers are
+ *                         device pointers; asynchronous on the ctx stream, no host synchronisation, no allocation; the number of
+ *                         resolution rounds depends on the data and is decided on the device (at most nq: one workgroup per problem
+ *                         resolves the claims, so the cost grows with the depth of the claim chains -- measured figures in
+ *                         profiles/search_projection.md; thousands of queries on ONE spot take seconds).  cam (fx, fy, cx, cy, bf
+ *                         are read) and bounds are needed in POINTS mode only.  XFH_ERR_INVALID_ARG before any launch: B < 1, nq or
+ *                         nt outside 1 .. XFH_GRID_MAX_N, an unknown mode, GIVEN mode with d_ur_query but no d_uright or the reverse,
+ *                         POINTS mode without pose, camera or bounds, a NULL required pointer, misaligned pointers (16 bytes for
+ *                         descriptors, targets, the stride, grids and the workspace, the element size otherwise), a non-finite
+ *                         radius, nn_ratio < 0 or not finite.  Point coordinates, poses and descriptors may hold any value, NaN and
+ *                         Inf included: no load leaves the buffers the caller named.
+ *   xfh_search_projection host-pointer convenience form for ONE problem (like xfh_search_window): stages the inputs, builds the grid
+ *                         of the nt keypoints with flags 0, runs the call and copies the results back.  Tcw is a host array here and `bounds` (always
+ *                         needed) is also the grid's. */
+enum { XFH_PROJ_POINTS = 0, XFH_PROJ_GIVEN = 1 };
+enum { XFH_PROJ_INACTIVE = 0, XFH_PROJ_BEHIND = 1, XFH_PROJ_OUT_OF_BOUNDS = 2, XFH_PROJ_NO_CANDIDATES = 3, XFH_PROJ_REJECTED = 4, XFH_PROJ_MATCHED = 5,
+       XFH_PROJ_VISIBLE = 3 /* xfh_project_points: the point reaches the search */ };
+#define XFH_PROJ_FLAG_ACTIVE 1        /* d_query_flags bit0: pMP != NULL && !mvbOutlier */
+#define XFH_PROJ_FLAG_CLAIMS 2        /* d_query_flags bit1: pMP->Observations() > 0 */
+int xfh_project_points(const float* Tcw, const xfh_camera* cam, const xfh_grid_bounds* bounds, const float* xyz, int n, float radius,
+                       float* uvr, float* ur, uint8_t* status);
+size_t xfh_search_projection_workspace_bytes(int nq, int nt, int B);
+int xfh_search_projection_device(xfh_ctx* ctx, int mode, int B, int nq, const float* d_points_or_uvr, const float* d_ur_query_or_null, const float* d_Tcw,
+                                 const xfh_camera* cam, const xfh_grid_bounds* bounds, float radius, const float* d_query_desc,
+                                 const uint8_t* d_query_flags, const void* d_grids, const float* d_targets, size_t target_stride_bytes, int nt,
+                                 const uint8_t* d_skip_or_null, const float* d_uright_or_null, int init_dist, int th_high, float nn_ratio,
+                                 void* d_workspace, uint8_t* d_status, int* d_match_idx, int* d_best_dist, int* d_second_dist, int* d_n_candidates,
+                                 float* d_proj_out_or_null, int* d_assigned, int* d_n_matches);
+int xfh_search_projection(xfh_ctx* ctx, int mode, int nq, const float* points_or_uvr, const float* ur_query_or_null, const float* Tcw,
+                          const xfh_camera* cam, const xfh_grid_bounds* bounds, float radius, const float* query_desc, const uint8_t* query_flags,
+                          const xfh_keypoint* kps, const float* targets, int nt, const uint8_t* skip_or_null,
+                          const float* uright_or_null, int init_dist, int th_high, float nn_ratio, uint8_t* status, int* match_idx, int* best_dist,
+                          int* second_dist, int* n_candidates, float* proj_out_or_null, int* assigned, int* n_matches);
 
 /* MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:329-403), batched over map points: group g observes the
  * descriptor rows indices[offsets[g] .. offsets[g+1]) of `table` (n_rows x 64).  Pairwise DescriptorDistance inside

@@ -1,0 +1,118 @@
+"""The seeded scene of the projection-search tests in device memory (tests/test_gpu_projection.py, tools/time_projection.py):
+frames extracted and finished on the device, world points and poses from tests/ref_projection.py, and one guarded run of
+xfh_search_projection_device.  No test lives here, and nothing but numpy and the package is imported."""
+import numpy as np
+
+import ref_frame as RF
+import ref_projection as RP
+import ref_window as RW
+from xfeatslam_amd import capi, synth
+from xfeatslam_amd.extractor import Context
+
+F = np.float32
+H, W = 480, 640
+TUM1 = RF.camera()
+SCALE = F(1) / F(RF.TUM1_DEPTH_FACTOR)
+SHIFTS = [(2, 1), (1, 2), (3, 0), (0, 3)]                             # current frame p = the last frame moved by SHIFTS[p] pixels
+BIG = 1 << 30
+OUT_INT = ("match_idx", "best_dist", "second_dist", "n_candidates")
+GUARD = 256                                                           # sentinel bytes before and after every output array
+
+
+def cam_struct(c):
+    return capi.Camera(*[float(c[k]) for k in "fx fy cx cy k1 k2 p1 p2 k3 bf".split()], int(c["width"]), int(c["height"]))
+
+
+class Rig:
+    """frame 0 (the last frame) and four current frames in device memory: records, undistorted keypoints, uright, grids"""
+
+    def __init__(self, L, blob, nf, seed):
+        self.L, self.nf, self.seed = L, nf, seed
+        self.ctx = Context(nfeatures=nf, max_height=H, max_width=W, max_batch=5)
+        self.ctx.load_weights(blob)
+        img = synth.image(H, W, seed)
+        frames = np.stack([img] + [np.roll(img, (dy, dx), (0, 1)) for dx, dy in SHIFTS])
+        self.din = capi.DeviceBuffer(frames.nbytes).upload(frames)
+        self.rec = capi.DeviceBuffer(5 * self.ctx.rec_bytes)
+        capi.check(L.xfh_extract_batch_device(self.ctx.h, self.din.ptr, 5, H, W, 0, 0, self.rec.ptr), self.ctx.h)
+        rng = np.random.RandomState(seed + 7)
+        depth = rng.randint(1, 65536, (5, H, W)).astype(np.uint16)
+        depth[rng.rand(5, H, W) < 1 / 3] = 0
+        self.ddepth = capi.DeviceBuffer(depth.nbytes).upload(depth)
+        self.bounds = Context.camera_bounds(cam_struct(TUM1))
+        self.fin = self.ctx.frame_finish_records(self.rec.ptr, 5, cam_struct(TUM1), self.bounds, 0, self.ddepth.ptr, capi.DEPTH_U16, 2 * W, SCALE)
+        self.ctx.synchronize()
+        self.recs = self.ctx.parse_records(self.rec.download(np.uint8, 5 * self.ctx.rec_bytes), 5)
+        self.xy = self.fin[0].download(F, 5 * nf * 2).reshape(5, nf, 2)
+        self.ur = self.fin[1].download(F, 5 * nf).reshape(5, nf)
+        self.grids = [RW.build(self.xy[f][:, 0].copy(), self.xy[f][:, 1].copy(), self.bounds) for f in range(5)]
+        self.xyz, self.flags = RP.scene(seed, self.xy[0], TUM1)
+        self.poses = np.stack([RP.pose(seed + p, SHIFTS[p], cam=TUM1) for p in range(4)])
+        self.skip = (np.random.RandomState(seed + 3).rand(4, nf) < 0.2).astype(np.uint8) * 7
+        self.bufs = []
+
+    def dev(self, a):
+        b = capi.DeviceBuffer(max(np.ascontiguousarray(a).nbytes, 16)).upload(a)
+        self.bufs.append(b)
+        return b
+
+    def run(self, B, mode, pts, flags, radius=0.0, ur_query=None, skip=False, uright=False, init=BIG, th_high=1000, ratio=0.0, proj=True, fill=None):
+        """B problems: queries = frame 0's descriptors (replicated), problem p searches current frame p + 1.  -> (outputs per problem, raw
+        bytes of the output buffer, proj [B][nq][3], workspace header ints [B][2])"""
+        nf, ctx = self.nf, self.ctx
+        lay = Context.search_projection_layout(B, nf, nf, GUARD)
+        out = capi.DeviceBuffer(lay["bytes"]).upload(np.full(lay["bytes"], 0xA5, np.uint8))
+        dproj = capi.DeviceBuffer(B * nf * 12 + 2 * GUARD).upload(np.full(B * nf * 12 + 2 * GUARD, 0xA5, np.uint8)) if proj else None
+        wsb = Context.search_projection_workspace_bytes(nf, nf, B)
+        ws = capi.DeviceBuffer(wsb)
+        if fill is not None:
+            ws.upload(np.full(wsb, fill, np.uint8))
+        qd = self.dev(np.tile(self.recs[0][1], (B, 1)))
+        dp = self.dev(np.ascontiguousarray(pts, F)); dfl = self.dev(np.ascontiguousarray(flags, np.uint8)); dT = self.dev(self.poses[:B])
+        duq = self.dev(np.ascontiguousarray(ur_query, F)) if ur_query is not None else None
+        dsk = self.dev(self.skip[:B]) if skip else None
+        ctx.search_projection_device(mode, B, nf, dp.ptr, qd.ptr, dfl.ptr, self.fin[3].ptr + ctx.grid_bytes(nf), self.rec.ptr + ctx.rec_bytes + ctx.desc_off,
+                                     ctx.rec_bytes, nf, ws.ptr, out.ptr, radius=radius, d_Tcw=dT.ptr, cam=cam_struct(TUM1), bounds=self.bounds,
+                                     d_ur_query=duq.ptr if duq else None, d_skip=dsk.ptr if dsk else None,
+                                     d_uright=self.fin[1].ptr + 4 * nf if uright else None, init_dist=init, th_high=th_high, nn_ratio=ratio,
+                                     d_proj_out=dproj.ptr + GUARD if dproj else None, guard=GUARD)
+        ctx.synchronize()
+        raw = out.download(np.uint8, lay["bytes"])
+        res = []
+        for p in range(B):
+            r = {k: raw[lay[k] + 4 * p * nf: lay[k] + 4 * (p + 1) * nf].view(np.int32) for k in OUT_INT}
+            r["assigned"] = raw[lay["assigned"] + 4 * p * nf: lay["assigned"] + 4 * (p + 1) * nf].view(np.int32)
+            r["n_matches"] = int(raw[lay["n_matches"] + 4 * p: lay["n_matches"] + 4 * p + 4].view(np.int32)[0])
+            r["status"] = raw[lay["status"] + p * nf: lay["status"] + (p + 1) * nf]
+            res.append(r)
+        # guard words: at least GUARD bytes before and after every output array, and they still hold the fill
+        used = np.zeros(lay["bytes"], bool)
+        for k, n in (("match_idx", 4 * B * nf), ("best_dist", 4 * B * nf), ("second_dist", 4 * B * nf), ("n_candidates", 4 * B * nf),
+                     ("assigned", 4 * B * nf), ("n_matches", 4 * B), ("status", B * nf)):
+            used[lay[k]:lay[k] + n] = True
+            assert not used[lay[k] - GUARD:lay[k]].any() and not used[lay[k] + n:lay[k] + n + GUARD].any() and lay[k] + n + GUARD <= lay["bytes"]
+        assert np.all(raw[~used] == 0xA5), "a guard byte around the outputs was written"
+        pj = None
+        if dproj:
+            pr = dproj.download(np.uint8, B * nf * 12 + 2 * GUARD)
+            assert np.all(pr[:GUARD] == 0xA5) and np.all(pr[GUARD + B * nf * 12:] == 0xA5), "a guard byte around proj was written"
+            pj = pr[GUARD:GUARD + B * nf * 12].view(F).reshape(B, nf, 3)
+            dproj.free()
+        hdr = np.stack([ws.download(np.int32, 2, p * (wsb // B)) for p in range(B)])
+        out.free(); ws.free()
+        for b in self.bufs:
+            b.free()
+        self.bufs = []
+        return res, raw, pj, hdr
+
+    def model(self, O, p, status_in, u, v, r, ur, skip=False, uright=False, init=BIG, th_high=1000, ratio=0.0, claims=None):
+        f = p + 1
+        x, y = self.xy[f][:, 0].copy(), self.xy[f][:, 1].copy()
+        cl = (self.flags & 2) != 0 if claims is None else claims
+        return RP.search(O, status_in, cl, u, v, r, ur, self.recs[0][1], self.grids[f], x, y, self.bounds, self.recs[f][1],
+                         skip=self.skip[p] if skip else None, uright=self.ur[f] if uright else None, init_dist=init, th_high=th_high, nn_ratio=ratio)
+
+    def close(self):
+        for x in (self.din, self.rec, self.ddepth) + tuple(self.fin):
+            x.free()
+        self.ctx.close()

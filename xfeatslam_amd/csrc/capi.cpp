@@ -5,6 +5,7 @@
 #include "mnn_seg_plan.h"
 #include "window_layout.h"
 #include "frame_math.h"
+#include "projection_layout.h"
 
 #include <dlfcn.h>
 #include <math.h>
@@ -83,7 +84,7 @@ const char* xfh_strerror(int s) {
 const char* xfh_kernel_name(int id) {
     static const char* n[XFH_K_COUNT] = {"none", "k_mnn_gemm", "k_conv_mfma", "k_conv_direct", "k_nms_score", "k_select",
                                          "k_desc", "k_heads_kp", "k_dist_i32", "k_preproc", "k_best2_csr", "k_distinctive_csr", "k_mnn_gemm_seg",
-                                         "k_grid_build", "k_search_window", "k_frame_finish"};
+                                         "k_grid_build", "k_search_window", "k_frame_finish", "k_proj_candidates", "k_proj_resolve", "k_proj_count"};
     return (id >= 0 && id < XFH_K_COUNT) ? n[id] : "?";
 }
 
@@ -981,6 +982,106 @@ int xfh_frame_finish(xfh_ctx* c, const xfh_keypoint* kps, int n, const xfh_camer
     HIPCK(c, hipMemcpyAsync(xy_un, dxy, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
     HIPCK(c, hipMemcpyAsync(uright, dur, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
     HIPCK(c, hipMemcpyAsync(depth, ddz, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCK(c, hipStreamSynchronize(c->stream));
+    return XFH_OK;
+}
+
+// ---- SearchByProjection with the reference's claim order (projection_math.h, projection_search.hip.h) ---------------------------------
+int xfh_project_points(const float* Tcw, const xfh_camera* cam, const xfh_grid_bounds* bounds, const float* xyz, int n, float radius,
+                       float* uvr, float* ur, uint8_t* status) {
+    if (!Tcw || !cam || !bounds || n < 0 || (n > 0 && (!xyz || !uvr || !ur || !status))) return XFH_ERR_INVALID_ARG;
+    for (int i = 0; i < n; ++i) {
+        status[i] = (uint8_t)xfh_project_point(Tcw, *cam, *bounds, xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2], &uvr[3 * i], &uvr[3 * i + 1], &ur[i]);
+        uvr[3 * i + 2] = radius;
+    }
+    return XFH_OK;
+}
+
+size_t xfh_search_projection_workspace_bytes(int nq, int nt, int B) {
+    if (nq < 0 || nt < 0 || B < 0) return 0;
+    return proj_ws_layout(nq, nt).bytes * (size_t)B;
+}
+
+// the checks the two search calls share (everything that does not depend on where the pointers live)
+static bool proj_args_ok(int mode, int nq, int nt, const float* ur_query, const float* Tcw, const xfh_camera* cam, const xfh_grid_bounds* bounds,
+                         float radius, const float* uright, float nn_ratio) {
+    if (nq < 1 || nq > XFH_GRID_MAX_N || nt < 1 || nt > XFH_GRID_MAX_N) return false;
+    if (mode != XFH_PROJ_POINTS && mode != XFH_PROJ_GIVEN) return false;
+    if (mode == XFH_PROJ_GIVEN && (ur_query != nullptr) != (uright != nullptr)) return false;
+    if (mode == XFH_PROJ_POINTS && (!Tcw || !cam || !bounds)) return false;
+    return isfinite(radius) && isfinite(nn_ratio) && nn_ratio >= 0.0f;
+}
+
+int xfh_search_projection_device(xfh_ctx* c, int mode, int B, int nq, const float* d_pts, const float* d_ur_query, const float* d_Tcw,
+                                 const xfh_camera* cam, const xfh_grid_bounds* bounds, float radius, const float* d_qdesc, const uint8_t* d_qflags,
+                                 const void* d_grids, const float* d_targets, size_t target_stride, int nt, const uint8_t* d_skip, const float* d_uright,
+                                 int init_dist, int th_high, float nn_ratio, void* d_ws, uint8_t* d_status, int* d_match_idx, int* d_best_dist,
+                                 int* d_second_dist, int* d_n_candidates, float* d_proj_out, int* d_assigned, int* d_n_matches) {
+    if (!c || B < 1 || !proj_args_ok(mode, nq, nt, d_ur_query, d_Tcw, cam, bounds, radius, d_uright, nn_ratio)) return XFH_ERR_INVALID_ARG;
+    if (!d_pts || !d_qdesc || !d_qflags || !d_grids || !d_targets || !d_ws || !d_status || !d_match_idx || !d_best_dist || !d_second_dist ||
+        !d_n_candidates || !d_assigned || !d_n_matches) return XFH_ERR_INVALID_ARG;
+    if (((((uintptr_t)d_qdesc) | ((uintptr_t)d_targets) | ((uintptr_t)d_grids) | ((uintptr_t)d_ws) | (uintptr_t)target_stride) & 15) ||
+        ((((uintptr_t)d_pts) | ((uintptr_t)d_ur_query) | ((uintptr_t)d_Tcw) | ((uintptr_t)d_uright) | ((uintptr_t)d_match_idx) | ((uintptr_t)d_best_dist) |
+          ((uintptr_t)d_second_dist) | ((uintptr_t)d_n_candidates) | ((uintptr_t)d_proj_out) | ((uintptr_t)d_assigned) | ((uintptr_t)d_n_matches)) & 3))
+        return XFH_ERR_INVALID_ARG;
+    HIPCK(c, hipSetDevice(c->cfg.device));
+    ProjArgs a = {};
+    a.mode = mode; a.nq = nq; a.nt = nt; a.radius = radius;
+    a.pts = d_pts; a.ur_query = mode == XFH_PROJ_GIVEN ? d_ur_query : nullptr; a.Tcw = d_Tcw;
+    if (cam) a.cam = *cam;
+    if (bounds) a.bounds = *bounds;
+    a.qdesc = d_qdesc; a.qflags = d_qflags; a.grids = (const char*)d_grids; a.grid_stride = xfh_grid_bytes(nt);
+    a.targets = (const char*)d_targets; a.target_stride = target_stride; a.skip = d_skip; a.uright = d_uright;
+    a.init_dist = init_dist; a.th_high = th_high; a.nn_ratio = nn_ratio;
+    a.ws = (char*)d_ws; a.ws_stride = proj_ws_layout(nq, nt).bytes;
+    a.status = d_status; a.match_idx = d_match_idx; a.best_dist = d_best_dist; a.second_dist = d_second_dist; a.n_candidates = d_n_candidates;
+    a.proj_out = d_proj_out; a.assigned = d_assigned; a.n_matches = d_n_matches;
+    HIPCK(c, launch_search_projection(c, a, B));
+    return XFH_OK;
+}
+
+int xfh_search_projection(xfh_ctx* c, int mode, int nq, const float* pts, const float* ur_query, const float* Tcw, const xfh_camera* cam,
+                          const xfh_grid_bounds* bounds, float radius, const float* qdesc, const uint8_t* qflags, const xfh_keypoint* kps,
+                          const float* targets, int nt, const uint8_t* skip, const float* uright, int init_dist, int th_high, float nn_ratio,
+                          uint8_t* status, int* match_idx, int* best_dist, int* second_dist, int* n_candidates, float* proj_out, int* assigned, int* n_matches) {
+    GridGeom g;
+    if (!c || !grid_geom(bounds, &g) || !proj_args_ok(mode, nq, nt, ur_query, Tcw, cam, bounds, radius, uright, nn_ratio)) return XFH_ERR_INVALID_ARG;
+    if (!pts || !qdesc || !qflags || !kps || !targets || !status || !match_idx || !best_dist || !second_dist || !n_candidates || !assigned || !n_matches)
+        return XFH_ERR_INVALID_ARG;
+    HIPCK(c, hipSetDevice(c->cfg.device));
+    MatchWs& w = c->mws;
+    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    const size_t bq = al((size_t)nq * 256), bp = al((size_t)nq * 12), bn = al((size_t)nq * 4), bfl = al((size_t)nq), bT = 256, bt = al((size_t)nt * 256),
+                 bk = al((size_t)nt * sizeof(xfh_keypoint)), bg = al(xfh_grid_bytes(nt)), bs = al((size_t)nt), bf = al((size_t)nt * 4), bw = proj_ws_layout(nq, nt).bytes;
+    int rc = grow(c, &w.b2_buf, &w.cap_b2, bq + 2 * bp + 5 * bn + 2 * bfl + bT + bt + bk + bg + bs + 2 * bf + bw + 256);
+    if (rc != XFH_OK) return rc;
+    char* p = (char*)w.b2_buf;
+    auto take = [&](size_t n) { char* r = p; p += n; return r; };
+    float* dq = (float*)take(bq); float* dp = (float*)take(bp); float* dpo = (float*)take(bp); float* duq = (float*)take(bn);
+    int* o[4]; for (int k = 0; k < 4; ++k) o[k] = (int*)take(bn);
+    uint8_t* dfl = (uint8_t*)take(bfl); uint8_t* dst = (uint8_t*)take(bfl); float* dT = (float*)take(bT); float* dt = (float*)take(bt);
+    xfh_keypoint* dk = (xfh_keypoint*)take(bk); void* dg = take(bg); uint8_t* dsk = (uint8_t*)take(bs); float* dur = (float*)take(bf);
+    int* das = (int*)take(bf); void* dws = take(bw); int* dnm = (int*)take(256);
+    HIPCK(c, hipMemcpyAsync(dq, qdesc, (size_t)nq * 256, hipMemcpyHostToDevice, c->stream));
+    HIPCK(c, hipMemcpyAsync(dp, pts, (size_t)nq * 12, hipMemcpyHostToDevice, c->stream));
+    HIPCK(c, hipMemcpyAsync(dfl, qflags, (size_t)nq, hipMemcpyHostToDevice, c->stream));
+    HIPCK(c, hipMemcpyAsync(dt, targets, (size_t)nt * 256, hipMemcpyHostToDevice, c->stream));
+    HIPCK(c, hipMemcpyAsync(dk, kps, (size_t)nt * sizeof(xfh_keypoint), hipMemcpyHostToDevice, c->stream));
+    if (Tcw) HIPCK(c, hipMemcpyAsync(dT, Tcw, 48, hipMemcpyHostToDevice, c->stream));
+    if (ur_query) HIPCK(c, hipMemcpyAsync(duq, ur_query, (size_t)nq * 4, hipMemcpyHostToDevice, c->stream));
+    if (skip) HIPCK(c, hipMemcpyAsync(dsk, skip, (size_t)nt, hipMemcpyHostToDevice, c->stream));
+    if (uright) HIPCK(c, hipMemcpyAsync(dur, uright, (size_t)nt * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCK(c, launch_grid_build(c, dk, 0, nullptr, 0, dg, 0, nt, 1, g, 0));
+    rc = xfh_search_projection_device(c, mode, 1, nq, dp, ur_query ? duq : nullptr, Tcw ? dT : nullptr, cam, bounds, radius, dq, dfl, dg, dt, 0, nt,
+                                      skip ? dsk : nullptr, uright ? dur : nullptr, init_dist, th_high, nn_ratio, dws, dst, o[0], o[1], o[2], o[3],
+                                      proj_out ? dpo : nullptr, das, dnm);
+    if (rc != XFH_OK) return rc;
+    int* out[4] = {match_idx, best_dist, second_dist, n_candidates};
+    for (int k = 0; k < 4; ++k) HIPCK(c, hipMemcpyAsync(out[k], o[k], (size_t)nq * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCK(c, hipMemcpyAsync(status, dst, (size_t)nq, hipMemcpyDeviceToHost, c->stream));
+    if (proj_out) HIPCK(c, hipMemcpyAsync(proj_out, dpo, (size_t)nq * 12, hipMemcpyDeviceToHost, c->stream));
+    HIPCK(c, hipMemcpyAsync(assigned, das, (size_t)nt * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCK(c, hipMemcpyAsync(n_matches, dnm, 4, hipMemcpyDeviceToHost, c->stream));
     HIPCK(c, hipStreamSynchronize(c->stream));
     return XFH_OK;
 }

@@ -214,5 +214,7 @@ hipError_t launch_frame_finish(xfh_ctx* c, const void* kps, size_t kps_stride, c
 hipError_t launch_search_window(xfh_ctx* c, const float* q, const float* uvr, int nq, const void* grid, const float* tg, int nt,
                                 const uint8_t* skip, const float* uright, const float* ur_query, int init_dist,
                                 int* best_idx, int* best_dist, int* second_idx, int* second_dist, int* n_candidates);
+struct ProjArgs;
+hipError_t launch_search_projection(xfh_ctx* c, const ProjArgs& a, int B);            // projection_search.hip.h
 hipError_t launch_best2(xfh_ctx* c, const float* q, int nq, const float* tg, const int* offsets, const int* indices, int init_dist,
                         int* best_idx, int* best_dist, int* second_idx, int* second_dist);

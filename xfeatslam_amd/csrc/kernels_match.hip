@@ -13,6 +13,8 @@
 //                   (Frame::AssignFeaturesToGrid / GetFeaturesInArea + the SearchByProjection loop; window_search.hip.h).
 //   k_frame_finish : undistort + depth / right coordinate + the grid of the undistorted keypoints for B records in one launch
 //                   (Frame::UndistortKeyPoints / ComputeStereoFromRGBD / AssignFeaturesToGrid of the RGB-D constructor; frame_finish.hip.h).
+//   k_proj_candidates / k_proj_resolve / k_proj_count : ORBmatcher::SearchByProjection(Frame, Frame) and the SearchLocalPoints form as one
+//                   call: projection, cull, windowed best two and the reference's claim order (projection_search.hip.h).
 //   k_distinctive_csr : MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:329-403), one wave per map point.
 //
 // Numerics: normalised rows and the 64-term dot products are bit-identical to the oracle
@@ -89,6 +91,7 @@ hipError_t launch_best2(xfh_ctx* c, const float* q, int nq, const float* tg, con
 
 #include "window_search.hip.h"
 #include "frame_finish.hip.h"
+#include "projection_search.hip.h"
 
 // ---- k_distinctive_csr: MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:329-403), batched -------
 // One wave per group (map point).  Rows are taken 64 at a time, lane = row: the lane keeps its descriptor in

@@ -1,0 +1,239 @@
+// projection_search.hip.h -- ORBmatcher::SearchByProjection(Frame&, const Frame&, th, bMono) (src/ORBmatcher.cc:1861-2047) and the
+// SearchLocalPoints form (:42-141) as ONE device-resident call: projection, cull, windowed best / second best, and the reference's
+// claim order (xfh_search_projection_device; the contract is the sequential loop written out in include/xfeat_hip.h).
+//
+// The claim rule makes the loop sequential: CurrentFrame.mvpMapPoints is all NULL before the call (Tracking.cc:2914), so every entry
+// the candidate test (:1932-1934) sees was written by an earlier iteration (:1957).  It is a triangular system -- query q depends on
+// queries < q only.  With claim_min[k] = min{ j : match[j] == k and j claims } (a statically skipped k: -1), query q skips k iff
+// claim_min[k] < q.  All queries are re-evaluated against the previous round's claim_min until a round changes no match; the only
+// fixed point of that iteration is the sequential answer (induction over q), and when the smallest query a round changed is c, every
+// query <= c is final -- queries < c were evaluated against a final prefix and did not move, and c itself was evaluated against that
+// same prefix -- so round r + 1 starts at c + 1: at most nq rounds, whatever the data.
+//
+//   k_proj_candidates  many workgroups, one wave per query: flags, projection (projection_math.h) or the caller's (u, v, r), cull,
+//                      then the window walk of window_search.hip.h with the STATIC filters only.  Writes status and proj, and
+//                      into the workspace the query's XFH_PROJ_K best candidates ordered by (dist, visiting position) -- the
+//                      order in which the reference's strict '<' would pick them -- and the number of static candidates.
+//   k_proj_resolve     one workgroup per problem, claim_min of the nt keypoints in LDS (64 KB at 16384; LDS atomics, no global
+//                      atomics, no other workgroup to wait for).  A round: rebuild claim_min from the matches, then one THREAD per
+//                      query reads its K-list: best = first unclaimed entry, second = the next.  A query whose list was truncated
+//                      and holds fewer than two unclaimed entries goes on a list, and the WAVES of the workgroup then re-search
+//                      those in full with the claim test inside the walk.  The round count is data dependent and decided here: the
+//                      host reads nothing back.  At the end: match_idx, distances, status, assigned (largest matched q per
+//                      keypoint = last writer) and n_matches, and the final claim_min to the workspace.
+//   k_proj_count       many workgroups, one wave per query: n_candidates = survivors of the walk with the FINAL claim_min (no
+//                      descriptor is read).
+//
+// Bounds: slot numbers come from the blob and are checked against nt in the walk (window_walk) before anything is indexed with them;
+// list entries are such slot numbers; point coordinates and poses are only ever used as floats; a non-finite (u, v, r) opens no
+// window.  Nothing is read through a float.
+//
+// Cost of the worst case.  The lists and the round loop are sized for the usual scene, where a handful of rounds settle everything and
+// few lists run out.  When many queries sit on one spot, every round settles one query (lo advances by one) and every later query's
+// list is exhausted.  Searching all of those again each round would be about nq^2 / 2 full walks on one CU, every one of them stale
+// but the first; so a round walks only the queries below a cut T = lo + max(16, (nq - lo) * XFH_PROJ_REDO_BUDGET / nredo), which holds
+// about XFH_PROJ_REDO_BUDGET of them when they are spread evenly, and postpones the rest: their match stays as it was, the smallest
+// postponed query bounds the next round's lo from above, and the loop does not end while one is postponed (lo itself is always below
+// the cut, so every round still settles at least one query).  The worst case is then nq rounds of at most max(16, BUDGET) walks of up
+// to nt candidates each -- nq = nt = XFH_GRID_MAX_N on one spot is about 10^6 walks of 16384 distances on ONE CU, i.e. seconds, not
+// milliseconds: exact and terminating, as the contract asks, and nothing more.  A caller with such input should not expect frame rate.
+#pragma once
+#include "ctx.h"
+#include "projection_math.h"
+#include "projection_layout.h"
+#include "window_search.hip.h"
+
+#define XFH_PROJ_RESOLVE_THREADS 1024
+#define XFH_PROJ_REDO_BUDGET 64                                        // full walks k_proj_resolve aims at per round (four per wave)
+
+__device__ __forceinline__ u64 wave_min_u64(u64 x) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) { const u64 o = __shfl_xor(x, m); x = o < x ? o : x; }
+    return x;
+}
+
+__global__ __launch_bounds__(256)
+void k_proj_candidates(ProjArgs a) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int qi = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + wave), pb = blockIdx.y;
+    if (qi >= a.nq) return;
+    const size_t qg = (size_t)pb * a.nq + qi;                          // the query's place in the [B][nq] arrays
+    const ProjWs L = proj_ws_layout(a.nq, a.nt);
+    char* ws = a.ws + (size_t)pb * a.ws_stride;
+    int st = XFH_PROJ_INACTIVE;
+    float u = 0.0f, v = 0.0f, ur = 0.0f, r = a.radius;
+    if (a.qflags[qg] & 1) {
+        const float* p = a.pts + qg * 3;
+        if (a.mode == XFH_PROJ_POINTS) st = xfh_project_point(a.Tcw + (size_t)pb * 12, a.cam, a.bounds, p[0], p[1], p[2], &u, &v, &ur);
+        else { u = p[0]; v = p[1]; r = p[2]; ur = a.ur_query ? a.ur_query[qg] : 0.0f; st = XFH_PROJ_VISIBLE; }
+    }
+    if (lane == 0) {
+        a.status[qg] = (uint8_t)st;                                    // XFH_PROJ_VISIBLE is XFH_PROJ_NO_CANDIDATES until k_proj_resolve has found one
+        a.match_idx[qg] = -1; a.best_dist[qg] = a.init_dist; a.second_dist[qg] = a.init_dist; a.n_candidates[qg] = 0;
+        if (a.proj_out) { a.proj_out[qg * 3] = u; a.proj_out[qg * 3 + 1] = v; a.proj_out[qg * 3 + 2] = ur; }
+        float* pj = (float*)(ws + L.proj) + (size_t)qi * 4;
+        pj[0] = u; pj[1] = v; pj[2] = ur; pj[3] = r;
+    }
+    int* ntot = (int*)(ws + L.ntot);
+    if (st != XFH_PROJ_VISIBLE) { if (lane == 0) ntot[qi] = 0; return; }          // (uniform)
+    const char* grid = a.grids + (size_t)pb * a.grid_stride;
+    const float* tg = (const float*)(a.targets + (size_t)pb * a.target_stride);
+    const WindowWalk w = window_open(grid, u, v, r, a.nt, lane);
+    // the lane's K smallest keys, ascending, and their slots
+    const u64 NONE = ~0ull;
+    u64 k0 = NONE, k1 = NONE, k2 = NONE, k3 = NONE;
+    int i0 = -1, i1 = -1, i2 = -1, i3 = -1;
+    static_assert(XFH_PROJ_K == 4, "the per-lane insertion below is written for four entries");
+    const int nc = window_walk<true>(w, grid, a.qdesc + qg * 64, u, v, r, tg, a.nt, a.skip ? a.skip + (size_t)pb * a.nt : nullptr,
+                                     a.uright ? a.uright + (size_t)pb * a.nt : nullptr, ur, lane, [](int) { return true; },
+                                     [&](u64 key, int idx) {
+                                         if (key < k3) {
+                                             k3 = key; i3 = idx;
+                                             if (k3 < k2) { const u64 t = k2; k2 = k3; k3 = t; const int ti = i2; i2 = i3; i3 = ti; }
+                                             if (k2 < k1) { const u64 t = k1; k1 = k2; k2 = t; const int ti = i1; i1 = i2; i2 = ti; }
+                                             if (k1 < k0) { const u64 t = k0; k0 = k1; k1 = t; const int ti = i0; i0 = i1; i1 = ti; }
+                                         }
+                                     });
+    // the wave's K smallest: K times the minimum of the lanes' heads (keys are distinct: they carry the position); its owner writes and pops
+    int* ld = (int*)(ws + L.ldist) + (size_t)qi * XFH_PROJ_K;
+    int* li = (int*)(ws + L.lidx) + (size_t)qi * XFH_PROJ_K;
+    for (int j = 0; j < XFH_PROJ_K; ++j) {
+        const u64 m = wave_min_u64(k0);
+        if (m == NONE) break;                                          // (uniform)
+        if (k0 == m) {
+            ld[j] = (int)(m >> 32); li[j] = i0;
+            k0 = k1; i0 = i1; k1 = k2; i1 = i2; k2 = k3; i2 = i3; k3 = NONE;
+        }
+    }
+    if (lane == 0) ntot[qi] = nc;
+}
+
+// accept / reject of one query from its best two (include/xfeat_hip.h), the outputs, and the round's "smallest query that moved"
+__device__ __forceinline__ void proj_finish(const ProjArgs& a, size_t qg, int q, int bi, int bd, int si, int sd, bool survivors, int* changed_lo) {
+    const bool accept = bi >= 0 && bd <= a.th_high && !(a.nn_ratio > 0.0f && si >= 0 && (float)bd > a.nn_ratio * (float)sd);
+    const int m = accept ? bi : -1;
+    if (a.match_idx[qg] != m) { a.match_idx[qg] = m; atomicMin(changed_lo, q); }
+    a.best_dist[qg] = bd; a.second_dist[qg] = sd;
+    a.status[qg] = (uint8_t)(accept ? XFH_PROJ_MATCHED : (survivors ? XFH_PROJ_REJECTED : XFH_PROJ_NO_CANDIDATES));
+}
+
+__global__ __launch_bounds__(XFH_PROJ_RESOLVE_THREADS)
+void k_proj_resolve(ProjArgs a) {
+    extern __shared__ int claim[];                                     // nt entries: claim_min, at the end the assignment
+    __shared__ int s_changed_lo, s_defer_lo, s_nredo, s_nwalk, s_nmatch;
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, pb = blockIdx.x;
+    const int nq = a.nq, nt = a.nt;
+    const ProjWs L = proj_ws_layout(nq, nt);
+    char* ws = a.ws + (size_t)pb * a.ws_stride;
+    const float* proj = (const float*)(ws + L.proj);
+    const int* ld = (const int*)(ws + L.ldist);
+    const int* li = (const int*)(ws + L.lidx);
+    const int* ntot = (const int*)(ws + L.ntot);
+    int* redo = (int*)(ws + L.redo);
+    const size_t q0 = (size_t)pb * nq;
+    const uint8_t* skip = a.skip ? a.skip + (size_t)pb * nt : nullptr;
+    const uint8_t* qflags = a.qflags + q0;
+    const char* grid = a.grids + (size_t)pb * a.grid_stride;
+    const float* tg = (const float*)(a.targets + (size_t)pb * a.target_stride);
+    const float* uright = a.uright ? a.uright + (size_t)pb * nt : nullptr;
+    int lo = 0, rounds = 0;
+    if (tid == 0) s_nwalk = 0;                                         // (the first barrier of the loop publishes it)
+    for (;;) {
+        // claim_min of the matches so far (match_idx is global memory written by this workgroup only; the barriers order it)
+        for (int k = tid; k < nt; k += XFH_PROJ_RESOLVE_THREADS) claim[k] = (skip && skip[k]) ? -1 : 0x7fffffff;
+        if (tid == 0) { s_changed_lo = 0x7fffffff; s_defer_lo = 0x7fffffff; s_nredo = 0; }
+        __syncthreads();
+        for (int q = tid; q < nq; q += XFH_PROJ_RESOLVE_THREADS) {
+            const int m = a.match_idx[q0 + q];
+            if (m >= 0 && (qflags[q] & 2)) atomicMin(&claim[m], q);
+        }
+        __syncthreads();
+        // one thread per query: the K-list against claim_min
+        for (int q = lo + tid; q < nq; q += XFH_PROJ_RESOLVE_THREADS) {
+            if (a.status[q0 + q] < XFH_PROJ_NO_CANDIDATES) continue;
+            const int n = ntot[q], len = n < XFH_PROJ_K ? n : XFH_PROJ_K;
+            int found = 0, bi = -1, bd = a.init_dist, si = -1, sd = a.init_dist;
+            bool settled = false;                                      // nothing past the list can change best / second
+            for (int j = 0; j < len && !settled; ++j) {
+                const int idx = li[(size_t)q * XFH_PROJ_K + j];
+                if (claim[idx] < q) continue;
+                const int d = ld[(size_t)q * XFH_PROJ_K + j];
+                ++found;
+                if (d >= a.init_dist) settled = true;                  // ascending: every later survivor is >= init_dist too
+                else if (found == 1) { bi = idx; bd = d; }
+                else { si = idx; sd = d; settled = true; }
+            }
+            if (n > XFH_PROJ_K && !settled) redo[atomicAdd(&s_nredo, 1)] = q;
+            else proj_finish(a, q0 + q, q, bi, bd, si, sd, found > 0, &s_changed_lo);
+        }
+        __syncthreads();
+        // one wave per truncated query: the full walk with the claim test inside
+        const int nredo = s_nredo;
+        const int cut = nredo <= XFH_PROJ_REDO_BUDGET ? nq : lo + max(16, (int)((long long)(nq - lo) * XFH_PROJ_REDO_BUDGET / nredo));
+        for (int i = wave; i < nredo; i += XFH_PROJ_RESOLVE_THREADS / 64) {
+            const int q = __builtin_amdgcn_readfirstlane(redo[i]);
+            if (q >= cut) { if (lane == 0) atomicMin(&s_defer_lo, q); continue; }     // (uniform) postponed: see "Cost of the worst case"
+            if (lane == 0) atomicAdd(&s_nwalk, 1);
+            const float u = proj[(size_t)q * 4], v = proj[(size_t)q * 4 + 1], ur = proj[(size_t)q * 4 + 2], r = proj[(size_t)q * 4 + 3];
+            const WindowWalk w = window_open(grid, u, v, r, nt, lane);
+            u64 b = ~0ull, s2 = ~0ull;
+            const int nc = window_walk<true>(w, grid, a.qdesc + (q0 + q) * 64, u, v, r, tg, nt, skip, uright, ur, lane,
+                                             [&](int idx) { return claim[idx] >= q; },
+                                             [&](u64 key, int) { top2_insert(b, s2, key); });
+            int bi, bd, si, sd;
+            window_best2(w, grid, b, s2, a.init_dist, bi, bd, si, sd);
+            if (lane == 0) proj_finish(a, q0 + q, q, bi, bd, si, sd, nc > 0, &s_changed_lo);
+        }
+        __syncthreads();
+        const int c = s_changed_lo, d = s_defer_lo;
+        ++rounds;
+        __syncthreads();                                               // everyone has read the round's result before it is reset
+        if (c == 0x7fffffff && d == 0x7fffffff) break;
+        lo = c == 0x7fffffff ? d : min(c + 1, d);                      // queries < min(c, d) were evaluated against a final prefix and did not move
+    }
+    // claim_min is the one of the final matches: for k_proj_count
+    int* wclaim = (int*)(ws + L.claim);
+    for (int k = tid; k < nt; k += XFH_PROJ_RESOLVE_THREADS) wclaim[k] = claim[k];
+    if (tid == 0) { s_nmatch = 0; ((int*)ws)[0] = rounds; ((int*)ws)[1] = s_nwalk; ((int*)ws)[2] = 0; ((int*)ws)[3] = 0; }
+    __syncthreads();
+    // assigned[k] = the LAST query that wrote mvpMapPoints[k] (:1957) = the largest matched q; n_matches counts every accepting query
+    for (int k = tid; k < nt; k += XFH_PROJ_RESOLVE_THREADS) claim[k] = -1;
+    __syncthreads();
+    int mine = 0;
+    for (int q = tid; q < nq; q += XFH_PROJ_RESOLVE_THREADS) {
+        const int m = a.match_idx[q0 + q];
+        if (m >= 0) { atomicMax(&claim[m], q); ++mine; }
+    }
+    if (mine) atomicAdd(&s_nmatch, mine);
+    __syncthreads();
+    for (int k = tid; k < nt; k += XFH_PROJ_RESOLVE_THREADS) a.assigned[(size_t)pb * nt + k] = claim[k];
+    if (tid == 0) a.n_matches[pb] = s_nmatch;
+}
+
+__global__ __launch_bounds__(256)
+void k_proj_count(ProjArgs a) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int qi = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + wave), pb = blockIdx.y;
+    if (qi >= a.nq) return;
+    const size_t qg = (size_t)pb * a.nq + qi;
+    const ProjWs L = proj_ws_layout(a.nq, a.nt);
+    const char* ws = a.ws + (size_t)pb * a.ws_stride;
+    if (a.status[qg] < XFH_PROJ_NO_CANDIDATES || ((const int*)(ws + L.ntot))[qi] == 0) return;       // n_candidates is 0 already
+    const float* pj = (const float*)(ws + L.proj) + (size_t)qi * 4;
+    const int* wclaim = (const int*)(ws + L.claim);
+    const char* grid = a.grids + (size_t)pb * a.grid_stride;
+    const WindowWalk w = window_open(grid, pj[0], pj[1], pj[3], a.nt, lane);
+    const int nc = window_walk<false>(w, grid, nullptr, pj[0], pj[1], pj[3], nullptr, a.nt, a.skip ? a.skip + (size_t)pb * a.nt : nullptr,
+                                      a.uright ? a.uright + (size_t)pb * a.nt : nullptr, pj[2], lane,
+                                      [&](int idx) { return wclaim[idx] >= qi; }, [](u64, int) {});
+    if (lane == 0) a.n_candidates[qg] = nc;
+}
+
+hipError_t launch_search_projection(xfh_ctx* c, const ProjArgs& a, int B) {
+    XFH_SET_LDS_ATTR_ONCE(c, k_proj_resolve, XFH_GRID_MAX_N * sizeof(int));
+    const dim3 per_query((a.nq + 3) / 4, B);
+    launch_k(c, XFH_K_PROJ_CANDIDATES, -1, k_proj_candidates, per_query, dim3(256), 0, a);
+    launch_k(c, XFH_K_PROJ_RESOLVE, -1, k_proj_resolve, dim3(B), dim3(XFH_PROJ_RESOLVE_THREADS), (size_t)a.nt * sizeof(int), a);
+    launch_k(c, XFH_K_PROJ_COUNT, -1, k_proj_count, per_query, dim3(256), 0, a);
+    return hipGetLastError();
+}

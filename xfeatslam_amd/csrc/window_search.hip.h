@@ -135,21 +135,25 @@ hipError_t launch_grid_build(xfh_ctx* c, const void* kps, size_t kps_stride, con
 // Out-of-contract floats: a query with a non-finite u, v or r has no candidates; the cell bounds are clamped as floats before the
 // conversion to int; every range is clamped to [0, nt] and every slot number is checked against nt, so no load leaves the blob
 // or the target rows whatever the query holds.
-__global__ __launch_bounds__(256)
-void k_search_window(const float* __restrict__ q, const float* __restrict__ uvr, int nq, const char* __restrict__ grid,
-                     const float* __restrict__ tg, int nt, const uint8_t* __restrict__ skip, const float* __restrict__ uright,
-                     const float* __restrict__ ur_query, int init_dist, int* __restrict__ best_idx, int* __restrict__ best_dist,
-                     int* __restrict__ second_idx, int* __restrict__ second_dist, int* __restrict__ n_candidates) {
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int qi = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + wave);
-    if (qi >= nq) return;
+// The walk is written once, as device functions, for k_search_window and the kernels of projection_search.hip.h:
+//   window_open   the cell bounds of (u, v, r), lane = column: its range of items and its first position in the walk
+//   window_walk   deals the positions to the lanes, applies the window test and the static filters plus the caller's `extra(slot)`,
+//                 and calls visit(key, slot) for every survivor with key = dist << 32 | position (DIST = false: no descriptor is
+//                 read and the key's distance is 0); returns the number of survivors of the whole wave
+//   window_slot   the slot number at a position of the walk
+//   window_best2  butterfly merge of the lanes' two smallest keys and the reference's initial values (k_best2_csr's rule)
+// one key into a lane's two smallest: if (key < b) { s2 = b; b = key; } else if (key < s2) s2 = key; -- written as minima so that the pair
+// stays in registers when it is captured by reference
+__device__ __forceinline__ void top2_insert(u64& b, u64& s2, u64 key) {
+    const u64 hi = key < b ? b : key;
+    b = key < b ? key : b; s2 = hi < s2 ? hi : s2;
+}
+struct WindowWalk { int ncols, first, adj, T; };            // first / adj: of this lane's column; item = adj + position
+
+__device__ __forceinline__ WindowWalk window_open(const char* __restrict__ grid, float u, float v, float r, int nt, int lane) {
     const GridHeader* gh = (const GridHeader*)grid;
     const int* cs = (const int*)(grid + XFH_GRID_CS_OFF);
-    const GridItem* items = (const GridItem*)(grid + XFH_GRID_ITEMS_OFF);
-    const float* qr = q + (size_t)qi * 64;
-    const float u = uvr[(size_t)qi * 3], v = uvr[(size_t)qi * 3 + 1], r = uvr[(size_t)qi * 3 + 2];
     const float min_x = gh->min_x, min_y = gh->min_y, inv_w = gh->inv_w, inv_h = gh->inv_h;
-    const float urq = ur_query ? ur_query[qi] : 0.0f;
     int c0x = 0, c1x = -1, c0y = 0, c1y = -1;
     if (__builtin_isfinite(u) && __builtin_isfinite(v) && __builtin_isfinite(r)) {
         // nMinCellX = max(0, (int)floor((x - mnMinX - factorX) * mfGridElementWidthInv)) ... (:858-880); fminf / fmaxf also swallow a NaN
@@ -161,10 +165,11 @@ void k_search_window(const float* __restrict__ q, const float* __restrict__ uvr,
         const int b0 = (int)fy0 < 0 ? 0 : (int)fy0, b1 = (int)fy1 > XFH_GRID_ROWS - 1 ? XFH_GRID_ROWS - 1 : (int)fy1;
         if (a0 < XFH_GRID_COLS && a1 >= 0 && b0 < XFH_GRID_ROWS && b1 >= 0) { c0x = a0; c1x = a1; c0y = b0; c1y = b1; }   // else: the early returns
     }
-    const int ncols = (c1x >= c0x && c1y >= c0y) ? c1x - c0x + 1 : 0;
+    WindowWalk w;
+    w.ncols = (c1x >= c0x && c1y >= c0y) ? c1x - c0x + 1 : 0;
     // lane = column: its range of items, and an inclusive scan of the lengths
     int beg = 0, len = 0;
-    if (lane < ncols) {
+    if (lane < w.ncols) {
         const int col = (c0x + lane) * XFH_GRID_ROWS;
         int s = cs[col + c0y], e = cs[col + c1y + 1];
         s = s < 0 ? 0 : (s > nt ? nt : s); e = e < 0 ? 0 : (e > nt ? nt : e);
@@ -173,63 +178,105 @@ void k_search_window(const float* __restrict__ q, const float* __restrict__ uvr,
     int inc = len;
 #pragma unroll
     for (int d = 1; d < 64; d <<= 1) { const int t = __shfl_up(inc, d); if (lane >= d) inc += t; }
-    const int first = inc - len, adj = beg - first;        // column's first position in the walk; item = adj + position
-    const int T = __builtin_amdgcn_readlane(inc, 63);
-    const u64 NONE = ~0ull;
-    u64 b = NONE, s2 = NONE;
+    w.first = inc - len; w.adj = beg - w.first;            // column's first position in the walk; item = adj + position
+    w.T = __builtin_amdgcn_readlane(inc, 63);
+    return w;
+}
+
+// the last column whose first position is <= p holds p (empty columns repeat a value)
+__device__ __forceinline__ int window_base(const WindowWalk& w, int p) {
+    int a = 0;
+    for (int c = 0; c < w.ncols; ++c) {
+        const int fc = __builtin_amdgcn_readlane(w.first, c), ac = __builtin_amdgcn_readlane(w.adj, c);
+        a = p >= fc ? ac : a;
+    }
+    return a;
+}
+__device__ __forceinline__ int window_slot(const WindowWalk& w, const char* __restrict__ grid, int p) {
+    return ((const GridItem*)(grid + XFH_GRID_ITEMS_OFF))[window_base(w, p) + p].index;
+}
+
+template <bool DIST, typename Extra, typename Visit>
+__device__ __forceinline__ int window_walk(const WindowWalk& w, const char* __restrict__ grid, const float* __restrict__ qr, float u, float v, float r,
+                                           const float* __restrict__ tg, int nt, const uint8_t* __restrict__ skip, const float* __restrict__ uright,
+                                           float urq, int lane, Extra extra, Visit visit) {
+    const GridItem* items = (const GridItem*)(grid + XFH_GRID_ITEMS_OFF);
     int ncand = 0;
-    for (int p0 = 0; p0 < T; p0 += 64) {
+    for (int p0 = 0; p0 < w.T; p0 += 64) {
         const int p = p0 + lane;
-        int a = 0;
-        for (int c = 0; c < ncols; ++c) {                  // the last column whose first position is <= p holds p (empty columns repeat a value)
-            const int fc = __builtin_amdgcn_readlane(first, c), ac = __builtin_amdgcn_readlane(adj, c);
-            a = p >= fc ? ac : a;
-        }
+        const int a = window_base(w, p);
         bool pass = false;
         int idx = 0;
-        if (p < T) {
+        if (p < w.T) {
             const GridItem it = items[a + p];
             idx = it.index;
             pass = idx >= 0 && idx < nt && fabsf(it.x - u) < r && fabsf(it.y - v) < r;               // Frame.cc:904-908
             if (pass && skip) pass = skip[idx] == 0;                                                   // ORBmatcher.cc:1931-1933
             if (pass && uright) { const float ur = uright[idx]; if (ur > 0.0f && fabsf(urq - ur) > r) pass = false; }   // :1935-1941
+            if (pass) pass = extra(idx);
         }
         ncand += __popcll(__ballot(pass));
         if (pass) {
-            const f32x4* tr = (const f32x4*)(tg + (size_t)idx * 64);
-            double acc = 0.0;
+            int dist = 0;
+            if (DIST) {
+                const f32x4* tr = (const f32x4*)(tg + (size_t)idx * 64);
+                double acc = 0.0;
 #pragma unroll
-            for (int g = 0; g < 16; ++g) {
-                const f32x4 tv = tr[g];
+                for (int g = 0; g < 16; ++g) {
+                    const f32x4 tv = tr[g];
 #pragma unroll
-                for (int e = 0; e < 4; ++e) { const double df = (double)(qr[g * 4 + e] - tv[e]); acc = fma(df, df, acc); }
+                    for (int e = 0; e < 4; ++e) { const double df = (double)(qr[g * 4 + e] - tv[e]); acc = fma(df, df, acc); }
+                }
+                const float nd = (float)acc;
+                dist = (int)(nd * 512.0f);
             }
-            const float nd = (float)acc;
-            const int dist = (int)(nd * 512.0f);
-            const u64 key = ((u64)(unsigned)dist << 32) | (u64)(unsigned)p;
-            if (key < b) { s2 = b; b = key; } else if (key < s2) s2 = key;
+            visit(((u64)(unsigned)dist << 32) | (u64)(unsigned)p, idx);
         }
     }
+    return ncand;
+}
+
+// every lane gets the merged pair of the wave; the reference's initial values: a candidate only counts if dist < init_dist (k_best2_csr)
+__device__ __forceinline__ void window_best2(const WindowWalk& w, const char* __restrict__ grid, u64 b, u64 s2, int init_dist,
+                                             int& bi, int& bd, int& si, int& sd) {
+    const u64 NONE = ~0ull;
 #pragma unroll
     for (int m = 32; m >= 1; m >>= 1) {
         const u64 ob = __shfl_xor(b, m), os = __shfl_xor(s2, m);
         top2_merge(b, s2, ob, os);
     }
-    // every lane holds the merged pair; the slot numbers of the two winning positions
-    int pb = 0, ps = 0;
     const bool hb = b != NONE && (int)(b >> 32) < init_dist, hs = hb && s2 != NONE && (int)(s2 >> 32) < init_dist;
-    const int wb = (int)(b & 0xFFFFFFFFull), ws = (int)(s2 & 0xFFFFFFFFull);
-    for (int c = 0; c < ncols; ++c) {
-        const int fc = __builtin_amdgcn_readlane(first, c), ac = __builtin_amdgcn_readlane(adj, c);
-        pb = (hb && wb >= fc) ? ac : pb; ps = (hs && ws >= fc) ? ac : ps;
+    const int wb = hb ? (int)(b & 0xFFFFFFFFull) : 0, ws = hs ? (int)(s2 & 0xFFFFFFFFull) : 0;
+    // the items of the two winning positions (window_base for both in one pass over the columns)
+    int pb = 0, ps = 0;
+    for (int c = 0; c < w.ncols; ++c) {
+        const int fc = __builtin_amdgcn_readlane(w.first, c), ac = __builtin_amdgcn_readlane(w.adj, c);
+        pb = wb >= fc ? ac : pb; ps = ws >= fc ? ac : ps;
     }
-    if (lane == 0) {
-        // the reference's initial values: a candidate only counts if dist < init_dist (k_best2_csr)
-        int bd = init_dist, bi = -1, sd = init_dist, si = -1;
-        if (hb) { bd = (int)(b >> 32); bi = items[pb + wb].index; }
-        if (hs) { sd = (int)(s2 >> 32); si = items[ps + ws].index; }
-        best_idx[qi] = bi; best_dist[qi] = bd; second_idx[qi] = si; second_dist[qi] = sd; n_candidates[qi] = ncand;
-    }
+    const GridItem* items = (const GridItem*)(grid + XFH_GRID_ITEMS_OFF);
+    bd = init_dist; bi = -1; sd = init_dist; si = -1;
+    if (hb) { bd = (int)(b >> 32); bi = items[pb + wb].index; }
+    if (hs) { sd = (int)(s2 >> 32); si = items[ps + ws].index; }
+}
+
+__global__ __launch_bounds__(256)
+void k_search_window(const float* __restrict__ q, const float* __restrict__ uvr, int nq, const char* __restrict__ grid,
+                     const float* __restrict__ tg, int nt, const uint8_t* __restrict__ skip, const float* __restrict__ uright,
+                     const float* __restrict__ ur_query, int init_dist, int* __restrict__ best_idx, int* __restrict__ best_dist,
+                     int* __restrict__ second_idx, int* __restrict__ second_dist, int* __restrict__ n_candidates) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int qi = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + wave);
+    if (qi >= nq) return;
+    const float* qr = q + (size_t)qi * 64;
+    const float u = uvr[(size_t)qi * 3], v = uvr[(size_t)qi * 3 + 1], r = uvr[(size_t)qi * 3 + 2];
+    const float urq = ur_query ? ur_query[qi] : 0.0f;
+    const WindowWalk w = window_open(grid, u, v, r, nt, lane);
+    u64 b = ~0ull, s2 = ~0ull;
+    const int ncand = window_walk<true>(w, grid, qr, u, v, r, tg, nt, skip, uright, urq, lane, [](int) { return true; },
+                                        [&](u64 key, int) { top2_insert(b, s2, key); });
+    int bi, bd, si, sd;
+    window_best2(w, grid, b, s2, init_dist, bi, bd, si, sd);
+    if (lane == 0) { best_idx[qi] = bi; best_dist[qi] = bd; second_idx[qi] = si; second_dist[qi] = sd; n_candidates[qi] = ncand; }
 }
 
 hipError_t launch_search_window(xfh_ctx* c, const float* q, const float* uvr, int nq, const void* grid, const float* tg, int nt,

@@ -288,6 +288,65 @@ class Context:
                                      xy.ctypes.data, ur.ctypes.data, dz.ctypes.data), self.h)
         return xy[:n], ur[:n], dz[:n]
 
+    # -- SearchByProjection with the reference's claim order (xfh_project_points / xfh_search_projection*) -------
+    @staticmethod
+    def project_points(Tcw, cam, bounds, xyz, radius: float):
+        """xfh_project_points (host): world points [n][3] through the row-major 3x4 pose -> (uvr[n][3], ur[n], status[n])"""
+        T = np.ascontiguousarray(Tcw, np.float32).reshape(12); p = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+        n = len(p)
+        uvr = np.zeros((max(n, 1), 3), np.float32); ur = np.zeros(max(n, 1), np.float32); st = np.zeros(max(n, 1), np.uint8)
+        check(lib().xfh_project_points(T.ctypes.data, C.byref(cam), C.byref(capi.GridBounds(*bounds)), p.ctypes.data, n, float(radius),
+                                       uvr.ctypes.data, ur.ctypes.data, st.ctypes.data))
+        return uvr[:n], ur[:n], st[:n]
+
+    @staticmethod
+    def search_projection_workspace_bytes(nq: int, nt: int, B: int = 1) -> int:
+        return int(lib().xfh_search_projection_workspace_bytes(nq, nt, B))
+
+    def search_projection_device(self, mode: int, B: int, nq: int, d_points, d_query_desc, d_query_flags, d_grids, d_targets, target_stride: int, nt: int,
+                                 d_workspace, d_out, radius: float = 0.0, d_Tcw=None, cam=None, bounds=None, d_ur_query=None, d_skip=None, d_uright=None,
+                                 init_dist: int = 256, th_high: int = 1000, nn_ratio: float = 0.0, d_proj_out=None, guard: int = 0):
+        """xfh_search_projection_device on device pointers; asynchronous.  d_out: pointer to the outputs laid out as
+        search_projection_layout(B, nq, nt, guard) says"""
+        o = self.search_projection_layout(B, nq, nt, guard)
+        check(lib().xfh_search_projection_device(self.h, mode, B, nq, d_points, d_ur_query, d_Tcw, C.byref(cam) if cam is not None else None,
+                                                 C.byref(capi.GridBounds(*bounds)) if bounds is not None else None, float(radius), d_query_desc, d_query_flags,
+                                                 d_grids, d_targets, target_stride, nt, d_skip, d_uright, int(init_dist), int(th_high), float(nn_ratio),
+                                                 d_workspace, d_out + o["status"], d_out + o["match_idx"], d_out + o["best_dist"], d_out + o["second_dist"],
+                                                 d_out + o["n_candidates"], d_proj_out, d_out + o["assigned"], d_out + o["n_matches"]), self.h)
+
+    @staticmethod
+    def search_projection_layout(B: int, nq: int, nt: int, guard: int = 0):
+        """byte offsets of the outputs of search_projection_device inside one buffer (and its size under "bytes"); guard > 0 leaves
+        at least that many bytes the call never writes before the first array and after every array (for tests that fill them)"""
+        al = lambda x: (x + 255) & ~255
+        o, off = {}, al(guard)
+        for name, nbytes in (("match_idx", 4 * B * nq), ("best_dist", 4 * B * nq), ("second_dist", 4 * B * nq), ("n_candidates", 4 * B * nq),
+                             ("assigned", 4 * B * nt), ("n_matches", 4 * B), ("status", B * nq)):
+            o[name] = off; off += al(nbytes) + al(guard)
+        o["bytes"] = off
+        return o
+
+    def search_projection(self, mode: int, points, query_desc, query_flags, kps, bounds, targets, radius: float = 0.0, Tcw=None, cam=None,
+                          ur_query=None, skip=None, uright=None, init_dist: int = 256, th_high: int = 1000, nn_ratio: float = 0.0):
+        """xfh_search_projection (host pointers, one problem) -> dict(status, match_idx, best_dist, second_dist, n_candidates, proj, assigned, n_matches)"""
+        p = np.ascontiguousarray(points, np.float32).reshape(-1, 3); q = np.ascontiguousarray(query_desc, np.float32)
+        fl = np.ascontiguousarray(query_flags, np.uint8); k = np.ascontiguousarray(kps, KP_DTYPE); tg = np.ascontiguousarray(targets, np.float32)
+        nq, nt = len(p), len(k)
+        assert len(q) == nq and len(fl) == nq and len(tg) == nt
+        T = None if Tcw is None else np.ascontiguousarray(Tcw, np.float32).reshape(12)
+        uq = None if ur_query is None else np.ascontiguousarray(ur_query, np.float32)
+        sk = None if skip is None else np.ascontiguousarray(skip, np.uint8)
+        ur = None if uright is None else np.ascontiguousarray(uright, np.float32)
+        ptr = lambda a: None if a is None else a.ctypes.data
+        st = np.zeros(nq, np.uint8); oi = [np.zeros(nq, np.int32) for _ in range(4)]; proj = np.zeros((nq, 3), np.float32)
+        asg = np.zeros(nt, np.int32); nm = np.zeros(1, np.int32)
+        check(lib().xfh_search_projection(self.h, mode, nq, p.ctypes.data, ptr(uq), ptr(T), C.byref(cam) if cam is not None else None,
+                                          C.byref(capi.GridBounds(*bounds)), float(radius), q.ctypes.data, fl.ctypes.data, k.ctypes.data, tg.ctypes.data, nt,
+                                          ptr(sk), ptr(ur), int(init_dist), int(th_high), float(nn_ratio), st.ctypes.data, *[o.ctypes.data for o in oi],
+                                          proj.ctypes.data, asg.ctypes.data, nm.ctypes.data), self.h)
+        return dict(status=st, match_idx=oi[0], best_dist=oi[1], second_dist=oi[2], n_candidates=oi[3], proj=proj, assigned=asg, n_matches=int(nm[0]))
+
     def distinctive_csr(self, table, offsets, indices):
         """MapPoint::ComputeDistinctiveDescriptors over CSR groups of descriptor rows ->
         (position inside the group of the descriptor with the least median distance, that median)"""
