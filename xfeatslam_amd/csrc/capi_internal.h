@@ -1,0 +1,14 @@
+// capi_internal.h -- what the entry-point files (capi.cpp, capi_search.cpp, capi_bench.cpp) share.
+#pragma once
+#include "ctx.h"
+#include <vector>
+#define HIPCK(c, x) do { hipError_t _e = (x); if (_e != hipSuccess) { (c)->hip_err = std::string(#x) + ": " + hipGetErrorString(_e); return XFH_ERR_HIP; } } while (0)
+
+// true when any of the pointers (or strides) has a bit of `mask` set: misaligned(15, a, b) = a or b is not 16-byte aligned; null passes
+template <typename... P>
+inline bool misaligned(uintptr_t mask, P... p) { return ((... | (uintptr_t)p) & mask) != 0; }
+// the argument checks of the many-pairs calls -> the launcher's pair list (capi_search.cpp)
+int gather_pairs(xfh_ctx* c, int n_pairs, const void* const* image1, const int* n1, const void* const* image2, const int* n2,
+                 int* const* idx1, int* const* idx2, float* const* dist, int* n_matches, bool need_out, std::vector<XfhMatchPair>& v);
+// bytes of the staging arena xfh_match_mnn needs for n1 x n2 rows: xfh_create reserves that for nfeatures x nfeatures (capi_search.cpp)
+size_t match_mnn_stage_bytes(int n1, int n2);

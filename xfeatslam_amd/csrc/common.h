@@ -176,11 +176,8 @@ struct KTimer {
 struct MatchWs {
     float* img1 = nullptr; float* img2 = nullptr; size_t cap_p1 = 0, cap_p2 = 0;   // panel images of the two sets (capacity in panels of 256 rows)
     u64* keys = nullptr; u64* partR = nullptr; u64* partC = nullptr; u64* pairs = nullptr;   // one allocation: arg-max key planes (one per GEMM block column / row), (column, value) pairs
-    float* h_d1 = nullptr; float* h_d2 = nullptr; size_t cap_in = 0;   // device staging of host inputs
-    int* o_buf = nullptr; size_t cap_out = 0;                          // device outputs of the host call: n, idx1[nm], idx2[nm], dist[nm]
-    int* h_out = nullptr; size_t cap_hout = 0;                         // pinned mirror of o_buf
-    int32_t* o_tab = nullptr; size_t cap_tab = 0;
-    void* b2_buf = nullptr; size_t cap_b2 = 0;                             // staging of the host-pointer calls (xfh_best2_csr, xfh_search_window, xfh_frame_finish): each ends in a stream synchronise, so grow() may free it
+    void* stage = nullptr; size_t cap_stage = 0;                           // staging arena of every host-pointer call (host_stage.h): inputs, outputs and scratch of ONE call at a time
+    int* h_out = nullptr; size_t cap_hout = 0;                             // pinned mirror of xfh_match_mnn's output block: n, idx1[nm], idx2[nm], dist[nm]
     u64* bkeys = nullptr; size_t cap_bkeys = 0;                            // key planes + pairs of the many-pairs call (xfh_match_mnn_prepared_batch_device), grown on demand
 };
 

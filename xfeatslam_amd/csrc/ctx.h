@@ -126,13 +126,13 @@ void xfh_trace_pop();
 bool xfh_verbose();
 struct XfhRange { explicit XfhRange(const char* n) { xfh_trace_push(n); } ~XfhRange() { xfh_trace_pop(); } };
 
-// helpers shared by capi.cpp / pipeline.cpp
+// helpers shared by capi.cpp / pipeline.cpp (ctx_share_weights: capi.cpp, the others: pipeline.cpp)
 int ctx_share_weights(xfh_ctx* parent, xfh_ctx* child);      // child borrows the parent's packed weights (and its eval()-mode statistics)
 void pipe_destroy(xfh_ctx* c);
 int pipe_reshare_weights(xfh_ctx* c);
 void pipe_wait_idle(xfh_ctx* c);
 
-// helpers implemented in capi.cpp
+// implemented in capi_bench.cpp, beside xfh_timing_enable / _read
 // kernel timing: when the timer is armed for (kernel_id, layer) the launch goes through
 // hipExtLaunchKernelGGL with a start/stop event pair attached to the dispatch itself, so the
 // measured time is the kernel's own begin..end (what rocprofv3 --kernel-trace reports), not the

@@ -1,5 +1,5 @@
 // frame_math.h -- the per-keypoint arithmetic of the reference's RGB-D Frame constructor (src/Frame.cc:311-374), written ONCE for the
-// host entry points (xfh_undistort_points, xfh_camera_bounds; capi.cpp) and the kernel (frame_finish.hip.h).
+// host entry points (xfh_undistort_points, xfh_camera_bounds; capi_search.cpp) and the kernel (frame_finish.hip.h).
 //
 //   Frame::UndistortKeyPoints     :940-973   cv::undistortPoints(src, dst, K, dist, Mat(), P = K), restated from OpenCV's documented
 //                                            algorithm (the library does not link OpenCV): five fixed-point iterations of the inverse

@@ -1,5 +1,5 @@
 // projection_layout.h -- the workspace layout and the kernel arguments of xfh_search_projection_device (plain C++: the kernels in
-// projection_search.hip.h and the entry points in capi.cpp share it).
+// projection_search.hip.h and the entry points in capi_search.cpp share it).
 #pragma once
 #include <stddef.h>
 #include <stdint.h>

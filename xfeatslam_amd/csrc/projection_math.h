@@ -1,6 +1,6 @@
 // projection_math.h -- the per-point arithmetic of ORBmatcher::SearchByProjection(Frame&, const Frame&, th, bMono) before the window
 // search (src/ORBmatcher.cc:1888-1909, :1938 with Pinhole::project, src/CameraModels/Pinhole.cpp:43-49), written ONCE for the host
-// entry point (xfh_project_points; capi.cpp) and the kernel (projection_search.hip.h).
+// entry point (xfh_project_points; capi_search.cpp) and the kernel (projection_search.hip.h).
 //
 //   x3Dc = Tcw * x3Dw     here: row-major 3x4 [R|t], xc = ((T[0]*X + T[1]*Y) + T[2]*Z) + T[3], yc / zc from rows 1 / 2.  The reference
 //                         multiplies through Sophus::SE3f (Eigen's quaternion path); bit equality with its x3Dc is not claimed.

@@ -1,5 +1,5 @@
 // window_layout.h -- the frame-grid blob of xfh_grid_build_device / xfh_search_window_device (plain C++: the kernels in
-// window_search.hip.h and the host reader xfh_grid_unpack in capi.cpp share it).
+// window_search.hip.h and the host reader xfh_grid_unpack in capi_search.cpp share it).
 //
 // One blob per frame, xfh_grid_bytes(n) bytes, self-contained (the search kernel needs no pointer into the record):
 //   GridHeader          64 bytes: magic, n, n_binned, flags, the bounds and the inverse cell sizes (Frame.cc:336-341)
