@@ -443,6 +443,84 @@ public:
     const std::vector<int>& lastSecondDist() const { return projSecond; }
     const std::vector<int>& lastCandidates() const { return projCandidates; }
 
+    // The search of ORBmatcher::Fuse(KeyFrame*, const vector<MapPoint*>&, th) (ORBmatcher.cc:1333-1523; sim3 = true: the form of :1525-1640
+    // with Tcw = [R | t/s] and Ow from the caller's decomposition of Scw, :1534-1535 -- no chi-square gates, bestDist starts at INT_MAX) as
+    // ONE call (xfh_fuse_search_device).  Query q is map point q: row q of `queries`, world position worldPoints[3q ..], normal
+    // normals[3q ..], distances[3q ..] = (GetMinDistanceInvariance(), GetMaxDistanceInvariance(), mfMaxDistance) and flags[q] bit0 =
+    // `pMP && !pMP->isBad() && !pMP->IsInKeyFrame(pKF)`.  `grid` / `targets` / uright are the keyframe's (mvKeysUn grid, mDescriptors,
+    // mvuRight; uright = nullptr: a monocular keyframe); scaleFactors = mvScaleFactors.  bestIdx[q] is the keypoint the reference's loop
+    // would look at when lastFuseStatus()[q] == XFH_FUSE_FUSED; the return value is nFused.  The bookkeeping (:1497-1516 resp.
+    // :1622-1636) is the caller's, over q in order.  Blocks until the result is on the host.
+    int fuse(const Mat& queries, const std::vector<float>& worldPoints, const std::vector<float>& normals, const std::vector<float>& distances,
+             const std::vector<unsigned char>& flags, const float* Tcw, const float* Ow, const xfh_camera& cam, const xfh_grid_bounds& bounds, float th,
+             const std::vector<float>& scaleFactors, const XFgrid& grid, const Mat& targets, std::vector<int>& bestIdx,
+             const std::vector<float>* uright = nullptr, bool sim3 = false) {
+        const int nq = queries.rows, nt = targets.rows;
+        bestIdx.assign(nq, -1);
+        if (nq == 0 || nt == 0) return 0;
+        if ((int)worldPoints.size() != 3 * nq || (int)normals.size() != 3 * nq || (int)distances.size() != 3 * nq || (int)flags.size() != nq || nt != grid.size() ||
+            (uright && (int)uright->size() != nt) || !Tcw || !Ow)
+            throw std::runtime_error("XFmatcher::fuse: sizes do not fit");
+        auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+        const size_t bq = al((size_t)nq * 256), bp = al((size_t)nq * 12), bfl = al((size_t)nq), bT = 256, bt = al((size_t)nt * 256), bf = al((size_t)nt * 4);
+        reserve(d_out, d_out_bytes, bq + 3 * bp + bfl + 2 * bT + bt + bf, "XFmatcher::fuse");
+        char* p = (char*)d_out;
+        float* dq = (float*)p; p += bq; float* dp = (float*)p; p += bp; float* dn = (float*)p; p += bp; float* dd = (float*)p; p += bp;
+        unsigned char* dfl = (unsigned char*)p; p += bfl; float* dT = (float*)p; p += bT; float* dO = (float*)p; p += bT; float* dt = (float*)p; p += bt; float* dr = (float*)p;
+        int rc = xfh_synchronize(ctx);                       // (the copies below are synchronous: nothing queued earlier may still read the buffer)
+        if (rc == XFH_OK) rc = xfh_memcpy_h2d(dq, queries.template ptr<float>(0), (size_t)nq * 256);
+        if (rc == XFH_OK) rc = xfh_memcpy_h2d(dp, worldPoints.data(), (size_t)nq * 12);
+        if (rc == XFH_OK) rc = xfh_memcpy_h2d(dn, normals.data(), (size_t)nq * 12);
+        if (rc == XFH_OK) rc = xfh_memcpy_h2d(dd, distances.data(), (size_t)nq * 12);
+        if (rc == XFH_OK) rc = xfh_memcpy_h2d(dfl, flags.data(), (size_t)nq);
+        if (rc == XFH_OK) rc = xfh_memcpy_h2d(dT, Tcw, 48);
+        if (rc == XFH_OK) rc = xfh_memcpy_h2d(dO, Ow, 12);
+        if (rc == XFH_OK) rc = xfh_memcpy_h2d(dt, targets.template ptr<float>(0), (size_t)nt * 256);
+        if (rc == XFH_OK && uright) rc = xfh_memcpy_h2d(dr, uright->data(), (size_t)nt * 4);
+        if (rc != XFH_OK) throw std::runtime_error(std::string("XFmatcher::fuse: ") + xfh_strerror(rc));
+        return fuse(nq, dp, dn, dd, dq, dfl, dT, dO, cam, bounds, th, scaleFactors, grid, dt, uright ? dr : nullptr, bestIdx, sim3);
+    }
+    // The same on DEVICE pointers and an XFgrid (a keyframe finished with XFgrid::buildFromRecord: d_targets = the record's descriptor
+    // block, d_uright = grid.deviceURight()).  Only the results travel to the host.
+    int fuse(int nq, const float* d_points, const float* d_normals, const float* d_distances, const float* d_queries, const unsigned char* d_flags,
+             const float* d_Tcw, const float* d_Ow, const xfh_camera& cam, const xfh_grid_bounds& bounds, float th, const std::vector<float>& scaleFactors,
+             const XFgrid& grid, const float* d_targets, const float* d_uright, std::vector<int>& bestIdx, bool sim3 = false) {
+        const int nt = grid.size(), nl = (int)scaleFactors.size();
+        bestIdx.assign(nq > 0 ? nq : 0, -1);
+        if (nq <= 0 || nt <= 0) return 0;
+        if (nl < 1 || nl > XFH_FUSE_MAX_LEVELS) throw std::runtime_error("XFmatcher::fuse: 1 .. XFH_FUSE_MAX_LEVELS scale factors");
+        if (fuseRatioMax.size() + 1 != (size_t)nl || fuseScale != (nl > 1 ? scaleFactors[1] : 0.f)) {           // the table of this pyramid, once
+            fuseRatioMax.assign(nl - 1, 0.f);
+            if (nl > 1 && xfh_scale_level_thresholds(scaleFactors[1], nl, fuseRatioMax.data()) != XFH_OK) throw std::runtime_error("XFmatcher::fuse: scale factor must be > 1");
+            fuseScale = nl > 1 ? scaleFactors[1] : 0.f;
+        }
+        auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+        const size_t bn = al((size_t)nq * 4), bs = al((size_t)nq);
+        reserve(d_proj, d_proj_bytes, 5 * bn + bs + 256, "XFmatcher::fuse");
+        char* p = (char*)d_proj;
+        int* o[5];
+        for (int k = 0; k < 5; ++k) { o[k] = (int*)p; p += bn; }
+        unsigned char* dst = (unsigned char*)p; p += bs; int* dnf = (int*)p;
+        int rc = xfh_fuse_search_device(ctx, 1, nq, 0, d_points, d_normals, d_distances, d_queries, d_flags, d_Tcw, d_Ow, &cam, &bounds, th, scaleFactors.data(),
+                                        fuseRatioMax.data(), nl, grid.device(), d_targets, 0, nt, d_uright, sim3 ? 0 : XFH_FUSE_CHI2, sim3 ? 0x7fffffff : 256, TH_LOW,
+                                        dst, o[0], o[1], o[2], o[3], o[4], nullptr, dnf);
+        if (rc == XFH_OK) rc = xfh_synchronize(ctx);
+        fuseStatus.assign(nq, 0); fuseBest.assign(nq, 0); fuseWindow.assign(nq, 0); fuseTested.assign(nq, 0); fuseLevel.assign(nq, 0);
+        int nfused = 0;
+        int* out[5] = {bestIdx.data(), fuseBest.data(), fuseWindow.data(), fuseTested.data(), fuseLevel.data()};
+        for (int k = 0; k < 5 && rc == XFH_OK; ++k) rc = xfh_memcpy_d2h(out[k], o[k], (size_t)nq * 4);
+        if (rc == XFH_OK) rc = xfh_memcpy_d2h(fuseStatus.data(), dst, (size_t)nq);
+        if (rc == XFH_OK) rc = xfh_memcpy_d2h(&nfused, dnf, 4);
+        if (rc != XFH_OK) throw std::runtime_error(std::string("XFmatcher::fuse: ") + xfh_strerror(rc));
+        return nfused;
+    }
+    // per query, of the last fuse: XFH_FUSE_* status, best DescriptorDistance, window members, candidates compared, predicted level
+    const std::vector<unsigned char>& lastFuseStatus() const { return fuseStatus; }
+    const std::vector<int>& lastFuseBestDist() const { return fuseBest; }
+    const std::vector<int>& lastFuseWindow() const { return fuseWindow; }
+    const std::vector<int>& lastFuseTested() const { return fuseTested; }
+    const std::vector<int>& lastFuseLevel() const { return fuseLevel; }
+
     // MapPoint::ComputeDistinctiveDescriptors (MapPoint.cc:329-403), batched over map points: group g observes the
     // rows indices[offsets[g] .. offsets[g+1]) of `table`; bestPos[g] = position in the group of the descriptor with
     // the least median DescriptorDistance to the others (-1 for an empty group), bestMedian[g] = that median.
@@ -473,6 +551,9 @@ protected:
     void* d_proj = nullptr; size_t d_proj_bytes = 0;        // workspace and results of searchByProjection
     std::vector<unsigned char> projStatus;
     std::vector<int> projBest, projSecond, projCandidates;
+    std::vector<unsigned char> fuseStatus;                  // results of fuse, and the level thresholds of the pyramid it was last called with
+    std::vector<int> fuseBest, fuseWindow, fuseTested, fuseLevel;
+    std::vector<float> fuseRatioMax; float fuseScale = 0.f;
 };
 
 }  // namespace ORB_SLAM3

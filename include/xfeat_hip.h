@@ -460,6 +460,111 @@ int xfh_search_projection(xfh_ctx* ctx, int mode, int nq, const float* points_or
                           const float* uright_or_null, int init_dist, int th_high, float nn_ratio, uint8_t* status, int* match_idx, int* best_dist,
                           int* second_dist, int* n_candidates, float* proj_out_or_null, int* assigned, int* n_matches);
 
+/* ---- Fuse: map points projected into keyframes and searched, device resident -------------------------------------------------------
+ * ORBmatcher::Fuse(KeyFrame* pKF, const vector<MapPoint*>& vpMapPoints, th, bRight = false) (src/ORBmatcher.cc:1333-1523, the SE3 form,
+ * called from LocalMapping::SearchInNeighbors, src/LocalMapping.cc:714 ff.) and Fuse(KeyFrame*, Sim3f& Scw, vpPoints, th, vpReplacePoint)
+ * (:1525-1640, the Sim3 form of LoopClosing; the caller decomposes Scw into Tcw = [R | t/s] and Ow as :1534-1535 do) as one call for B
+ * keyframes.  The search reads no map state: everything up to `bestDist <= TH_LOW` is a function of the query and the keyframe, and two
+ * queries do not see each other.  Only the bookkeeping behind it (:1497-1516, :1622-1636: Replace / AddObservation / AddMapPoint /
+ * vpReplacePoint) is sequential; it stays with the caller, who consumes best_idx[q] in query order.  There is no claim order and no
+ * assigned[]: two queries may name the same keypoint, and the caller's loop resolves that as the reference's does.
+ *
+ * Problem b is one keyframe: pose Tcw[12] (row-major 3x4), camera centre Ow[3], its grid blob (built from mvKeysUn: the blob carries
+ * every item's x, y, which is where the chi-square test reads the candidate's coordinates -- xy_un itself is not an input of the
+ * device call), nt descriptor rows and uright[nt] (mvuRight; NULL = a monocular keyframe, every entry -1).  Query q is a map point:
+ * world position X, normal Pn, dist = (min_distance, max_distance, predict_distance), a 64-D descriptor and a flag byte whose bit0
+ * (XFH_FUSE_FLAG_ACTIVE) is `pMP && !pMP->isBad() && !pMP->IsInKeyFrame(pKF)` (:1366-1381) resp. `!pMP->isBad() &&
+ * !spAlreadyFound.count(pMP)` (:1550).  min_distance / max_distance are GetMinDistanceInvariance() / GetMaxDistanceInvariance() (0.8f *
+ * mfMinDistance, 1.2f * mfMaxDistance, MapPoint.cc:502-512); predict_distance is the UNSCALED mfMaxDistance that PredictScale divides
+ * (MapPoint.cc:519).  They are separate inputs because 1.2f * x cannot be undone exactly; a caller without access to mfMaxDistance
+ * passes max_distance twice and gets a ratio 1.2 times the reference's.
+ * All arithmetic is fp32 in the order written unless stated otherwise (the library is built with -ffp-contract=off):
+ *
+ *   flags bit0 clear                                      -> INACTIVE
+ *   xc = ((T[0]*X + T[1]*Y) + T[2]*Z) + T[3], yc / zc from rows 1 / 2          (as xfh_search_projection_device)
+ *   zc < 0.0f                                             -> BEHIND          (:1387; zc == 0 and NaN go on)
+ *   invz = 1.0f / zc                                      (a FLOAT division, :1393 -- not the double one of :1893)
+ *   u = fx*xc/zc + cx;  v = fy*yc/zc + cy                 (Pinhole.cpp:45-46)
+ *   !(u >= min_x && u < max_x && v >= min_y && v < max_y) -> OUT_OF_IMAGE    (KeyFrame::IsInImage, KeyFrame.cc:750-753: half-open, NaN is out)
+ *   ur = u - bf*invz                                      (:1404)
+ *   PO = X - Ow;  dist3D = sqrtf((PO.x*PO.x + PO.y*PO.y) + PO.z*PO.z)
+ *   dist3D < min_distance || dist3D > max_distance        -> OUT_OF_RANGE    (:1412)
+ *   dot = (PO.x*Pn.x + PO.y*Pn.y) + PO.z*Pn.z;  (double)dot < 0.5 * (double)dist3D -> BAD_ANGLE (:1420: more than 60 degrees)
+ *   ratio = predict_distance / dist3D;  level = PredictScale(ratio), see below;  r = th * scale_factors[level]     (:1426-1429)
+ *   window: exactly xfh_search_window_device's (KeyFrame::GetFeaturesInArea, KeyFrame.cc:704-748, is the expression sequence of
+ *           Frame::GetFeaturesInArea), no skip mask and no uright filter;  n_window = its size;  n_window == 0 -> NO_CANDIDATES (:1433)
+ *   per candidate k in visiting order (kpLevel = 0 for every XFeat keypoint, mvInvLevelSigma2[0] = 1.0f):
+ *       level > 1                                         -> skipped         (:1454: kpLevel < nPredictedLevel - 1)
+ *       with XFH_FUSE_CHI2 (the SE3 form):  ex = u - x_k;  ey = v - y_k
+ *           uright[k] >= 0:  er = ur - uright[k];  e2 = (ex*ex + ey*ey) + er*er;  (double)e2 > 7.8  -> skipped   (:1457-1470)
+ *           else          :                         e2 =  ex*ex + ey*ey;           (double)e2 > 5.99 -> skipped   (:1471-1481)
+ *           (a NaN e2 is not skipped; a NaN uright[k] takes the monocular branch)
+ *       dist = DescriptorDistance;  dist < best -> best = dist, best_idx = k   (strict: the candidate visited first wins a tie)
+ *   best starts at init_dist (256 in the SE3 form, INT_MAX in the Sim3 form);  n_tested = candidates that reached DescriptorDistance
+ *   best_idx >= 0 && best <= th_low -> FUSED, else REJECTED   (TH_LOW = 100, :1497 / :1622)
+ *
+ * PredictScale (MapPoint.cc:514-529) is ceil(log(ratio) / mfLogScaleFactor) through the float overloads of the host's libm
+ * (mfLogScaleFactor = log(mfScaleFactor) in float, Frame.cc:113), clamped to [0, nlevels - 1].  A device logf is not that function to
+ * the bit, and the level decides the radius (th or 1.2f * th) and whether there are candidates at all (level <= 1) -- so the device
+ * computes no logarithm: xfh_scale_level_thresholds (host, stateless) finds, per level l < nlevels - 1, ratio_max[l] = the largest finite
+ * float for which the HOST expression ceilf(logf(ratio) / logf(scale_factor)) is <= l, by bisection over the float's bit pattern, which
+ * relies on the host's logf being monotone (glibc's is).  The kernel gets ratio_max and scale_factors (mvScaleFactors, the caller's) by
+ * value and computes level = #{ l : ratio > ratio_max[l] }.  That also settles the inputs for which the reference's (int) conversion is
+ * undefined: a NaN ratio gives level 0, +Inf gives nlevels - 1, a ratio <= 0 gives level 0.  nlevels <= XFH_FUSE_MAX_LEVELS.
+ *
+ * Outputs, all exact, all in device memory.  Per query: status (XFH_FUSE_*), best_idx (-1 unless a candidate got under init_dist),
+ * best_dist (init_dist where there is none), n_window, n_tested (both 0 for a culled query), level (-1 for a query culled before
+ * PredictScale), and optionally proj[q] = (u, v, ur): zeros for INACTIVE and BEHIND, the computed values otherwise.  Per problem: n_fused.
+ *
+ *   xfh_scale_level_thresholds   host, stateless: ratio_max[nlevels - 1].  XFH_ERR_INVALID_ARG: nlevels outside 1 .. XFH_FUSE_MAX_LEVELS, a
+ *                         scale_factor that is not finite or not > 1.
+ *   xfh_fuse_project      host, stateless, thread-safe: the per-point arithmetic above for n points and ONE pose down to status
+ *                         (BEHIND .. BAD_ANGLE or XFH_FUSE_VISIBLE), level and radius: uvr[i] = (u, v, r), r = 0 for a culled point.  The same
+ *                         source lines as the kernel (fuse_math.h).
+ *   xfh_fuse_search_device   B problems of nq queries with the same camera, bounds, th and thresholds.  Query arrays: d_points, d_normals,
+ *                         d_distances [.][nq][3], d_query_desc [.][nq][64], d_query_flags [.][nq] bytes, problem b's block starting
+ *                         query_problem_stride * b queries into each: the stride is nq (own queries per problem) or 0 (all B problems read
+ *                         the SAME block: SearchInNeighbors, the current keyframe's points against every neighbour).  d_Tcw [B][12],
+ *                         d_Ow [B][3]; grid b at d_grids + b * xfh_grid_bytes(nt), target rows of problem b at d_targets + b *
+ *                         target_stride_bytes (as xfh_search_projection_device), d_uright [B][nt] or NULL: the grids and uright of
+ *                         xfh_frame_finish_records_device plug in unchanged.  Outputs d_status [B][nq] bytes, d_best_idx / d_best_dist /
+ *                         d_n_window / d_n_tested / d_level [B][nq] ints, d_proj_out [B][nq][3] or NULL, d_n_fused [B] ints.  flags:
+ *                         XFH_FUSE_CHI2 or 0.  All pointers but cam, bounds, scale_factors and ratio_max are device pointers;
+ *                         asynchronous on the ctx stream, no allocation, no workspace, ONE kernel launch (behind a 4 * B byte memset of
+ *                         d_n_fused on the same stream).  nt in 1 .. XFH_GRID_MAX_N, nq in 1 .. 2^20 (nothing here sorts queries in LDS),
+ *                         B in 1 .. 65535.  XFH_ERR_INVALID_ARG before anything is queued: those ranges, nlevels outside 1 ..
+ *                         XFH_FUSE_MAX_LEVELS, a stride other than 0 or nq, a non-finite th, unknown flag bits, a NULL required pointer,
+ *                         misaligned pointers (16 bytes for descriptors, targets, the target stride and grids, the element size
+ *                         otherwise).  Points, normals, distances, poses, scale tables and descriptors may hold anything, NaN and Inf
+ *                         included: no load leaves the buffers the caller named.
+ *   xfh_fuse_search       host-pointer convenience form for ONE problem: stages the inputs, builds the grid of the nt keypoints (x, y =
+ *                         the undistorted coordinates) with flags 0 and `bounds`, runs the call and copies the results back.
+ *                         XFH_ERR_INVALID_ARG for the device form's classes of error (and bounds no grid can be built from) before
+ *                         anything is staged or queued.
+ * Out of scope: bRight / NLeft != -1 (fisheye stereo), the Sim3 SearchByProjection forms and SearchBySim3, and the functions
+ * that walk DBoW2 feature vectors (SearchByBoW, SearchForTriangulation). */
+#define XFH_FUSE_MAX_LEVELS 16
+#define XFH_FUSE_FLAG_ACTIVE 1        /* d_query_flags bit0 */
+#define XFH_FUSE_CHI2 1               /* flags: the chi-square reprojection gates of the SE3 form */
+enum { XFH_FUSE_INACTIVE = 0, XFH_FUSE_BEHIND = 1, XFH_FUSE_OUT_OF_IMAGE = 2, XFH_FUSE_OUT_OF_RANGE = 3, XFH_FUSE_BAD_ANGLE = 4,
+       XFH_FUSE_NO_CANDIDATES = 5, XFH_FUSE_REJECTED = 6, XFH_FUSE_FUSED = 7,
+       XFH_FUSE_VISIBLE = 5 /* xfh_fuse_project: the point reaches the search */ };
+int xfh_scale_level_thresholds(float scale_factor, int nlevels, float* ratio_max /* [nlevels - 1] */);
+int xfh_fuse_project(const float* Tcw, const float* Ow, const xfh_camera* cam, const xfh_grid_bounds* bounds, float th, const float* scale_factors,
+                     const float* ratio_max, int nlevels, const float* xyz, const float* normals, const float* distances, int n,
+                     float* uvr, float* ur, int* level, uint8_t* status);
+int xfh_fuse_search_device(xfh_ctx* ctx, int B, int nq, size_t query_problem_stride, const float* d_points, const float* d_normals,
+                           const float* d_distances, const float* d_query_desc, const uint8_t* d_query_flags, const float* d_Tcw, const float* d_Ow,
+                           const xfh_camera* cam, const xfh_grid_bounds* bounds, float th, const float* scale_factors, const float* ratio_max, int nlevels,
+                           const void* d_grids, const float* d_targets, size_t target_stride_bytes, int nt, const float* d_uright_or_null,
+                           int flags, int init_dist, int th_low, uint8_t* d_status, int* d_best_idx, int* d_best_dist, int* d_n_window, int* d_n_tested,
+                           int* d_level, float* d_proj_out_or_null, int* d_n_fused);
+int xfh_fuse_search(xfh_ctx* ctx, int nq, const float* points, const float* normals, const float* distances, const float* query_desc,
+                    const uint8_t* query_flags, const float* Tcw, const float* Ow, const xfh_camera* cam, const xfh_grid_bounds* bounds, float th,
+                    const float* scale_factors, const float* ratio_max, int nlevels, const xfh_keypoint* kps, const float* targets, int nt,
+                    const float* uright_or_null, int flags, int init_dist, int th_low, uint8_t* status, int* best_idx, int* best_dist, int* n_window,
+                    int* n_tested, int* level, float* proj_out_or_null, int* n_fused);
+
 /* MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:329-403), batched over map points: group g observes the
  * descriptor rows indices[offsets[g] .. offsets[g+1]) of `table` (n_rows x 64).  Pairwise DescriptorDistance inside
  * the group (diagonal 0), per row the median sorted[(N-1)/2], and the FIRST row with the least median wins:

@@ -29,7 +29,7 @@ ERR_EMPTY_IMAGE = 2
 ERR_NO_DEVICE = 7
 ERR_COMM = 11
 
-K = dict(NONE=0, MNN_GEMM=1, CONV_MFMA=2, CONV_DIRECT=3, NMS=4, SELECT=5, DESC=6, HEADS=7, DIST_I32=8, PREPROC=9, BEST2=10, DISTINCTIVE=11, MNN_GEMM_SEG=12, GRID_BUILD=13, SEARCH_WINDOW=14, FRAME_FINISH=15, PROJ_CANDIDATES=16, PROJ_RESOLVE=17, PROJ_COUNT=18)
+K = dict(NONE=0, MNN_GEMM=1, CONV_MFMA=2, CONV_DIRECT=3, NMS=4, SELECT=5, DESC=6, HEADS=7, DIST_I32=8, PREPROC=9, BEST2=10, DISTINCTIVE=11, MNN_GEMM_SEG=12, GRID_BUILD=13, SEARCH_WINDOW=14, FRAME_FINISH=15, PROJ_CANDIDATES=16, PROJ_RESOLVE=17, PROJ_COUNT=18, FUSE_SEARCH=19)
 T = dict(X=0, XSTAT=1, SKIP_POOL=2, FEATS=6, H1=8, K1H=9, RAW0=16, STAT0=48, SEL=80)
 
 
@@ -59,6 +59,11 @@ PROJ_POINTS, PROJ_GIVEN = 0, 1
 PROJ_INACTIVE, PROJ_BEHIND, PROJ_OUT_OF_BOUNDS, PROJ_NO_CANDIDATES, PROJ_REJECTED, PROJ_MATCHED = range(6)
 PROJ_VISIBLE = 3
 PROJ_FLAG_ACTIVE, PROJ_FLAG_CLAIMS = 1, 2
+FUSE_INACTIVE, FUSE_BEHIND, FUSE_OUT_OF_IMAGE, FUSE_OUT_OF_RANGE, FUSE_BAD_ANGLE, FUSE_NO_CANDIDATES, FUSE_REJECTED, FUSE_FUSED = range(8)
+FUSE_VISIBLE = 5
+FUSE_FLAG_ACTIVE = 1
+FUSE_CHI2 = 1
+FUSE_MAX_LEVELS = 16
 
 FLAG_RESCALE_KEYPOINTS = 1
 FLAG_SERIAL_BRANCH = 2
@@ -119,6 +124,12 @@ SYMBOLS = [
                                           _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("xfh_search_projection", _i, [_vp, _i, _i, _vp, _vp, _vp, C.POINTER(Camera), C.POINTER(GridBounds), _f, _vp, _vp, _vp, _vp, _i, _vp, _vp,
                                    _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("xfh_scale_level_thresholds", _i, [_f, _i, _vp]),
+    ("xfh_fuse_project", _i, [_vp, _vp, C.POINTER(Camera), C.POINTER(GridBounds), _f, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
+    ("xfh_fuse_search_device", _i, [_vp, _i, _i, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(Camera), C.POINTER(GridBounds), _f, _vp, _vp, _i,
+                                    _vp, _vp, _sz, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("xfh_fuse_search", _i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(Camera), C.POINTER(GridBounds), _f, _vp, _vp, _i, _vp, _vp, _i,
+                             _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("xfh_distinctive_csr", _i, [_vp, _vp, _i, _vp, _vp, _i, _vp, _vp]),
     ("xfh_distinctive_csr_device", _i, [_vp, _vp, _i, _vp, _vp, _i, _i, _vp, _vp]),
     ("xfh_comm_unique_id", _i, [_vp]),

@@ -197,16 +197,6 @@ int xfh_best2_csr(xfh_ctx* c, const float* q, int nq, const float* tg, int nt, c
 // ---- frame grid + windowed search (window_search.hip.h, window_layout.h) -----------------------------------
 size_t xfh_grid_bytes(int n) { return n < 0 ? 0 : (size_t)XFH_GRID_ITEMS_OFF + (size_t)n * sizeof(GridItem); }
 
-// mfGridElementWidthInv = FRAME_GRID_COLS / (mnMaxX - mnMinX), mfGridElementHeightInv likewise, in fp32 (Frame.cc:336-341)
-static bool grid_geom(const xfh_grid_bounds* b, GridGeom* g) {
-    if (!b || !isfinite(b->min_x) || !isfinite(b->min_y) || !isfinite(b->max_x) || !isfinite(b->max_y)) return false;
-    if (!(b->max_x > b->min_x) || !(b->max_y > b->min_y)) return false;
-    g->min_x = b->min_x; g->min_y = b->min_y; g->max_x = b->max_x; g->max_y = b->max_y;
-    g->inv_w = (float)XFH_GRID_COLS / (b->max_x - b->min_x);
-    g->inv_h = (float)XFH_GRID_ROWS / (b->max_y - b->min_y);
-    return isfinite(g->inv_w) && isfinite(g->inv_h) && g->inv_w > 0.0f && g->inv_h > 0.0f;
-}
-
 int xfh_grid_build_device(xfh_ctx* c, const xfh_keypoint* d_kps, int n, const void* d_record, const xfh_grid_bounds* bounds, int flags, void* d_grid) {
     GridGeom g;
     if (!c || n < 0 || n > XFH_GRID_MAX_N || !d_grid || (n > 0 && !d_kps) || (flags & ~XFH_GRID_SKIP_PADDING)) return XFH_ERR_INVALID_ARG;

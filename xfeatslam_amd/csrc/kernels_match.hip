@@ -15,6 +15,8 @@
 //                   (Frame::UndistortKeyPoints / ComputeStereoFromRGBD / AssignFeaturesToGrid of the RGB-D constructor; frame_finish.hip.h).
 //   k_proj_candidates / k_proj_resolve / k_proj_count : ORBmatcher::SearchByProjection(Frame, Frame) and the SearchLocalPoints form as one
 //                   call: projection, cull, windowed best two and the reference's claim order (projection_search.hip.h).
+//   k_fuse_search : both ORBmatcher::Fuse overloads up to the map bookkeeping, B keyframes per launch: projection, the distance, angle and
+//                   level culls, the window walk with the chi-square gate, best candidate (fuse_search.hip.h).
 //   k_distinctive_csr : MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:329-403), one wave per map point.
 //
 // Numerics: normalised rows and the 64-term dot products are bit-identical to the oracle
@@ -92,6 +94,7 @@ hipError_t launch_best2(xfh_ctx* c, const float* q, int nq, const float* tg, con
 #include "window_search.hip.h"
 #include "frame_finish.hip.h"
 #include "projection_search.hip.h"
+#include "fuse_search.hip.h"
 
 // ---- k_distinctive_csr: MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:329-403), batched -------
 // One wave per group (map point).  Rows are taken 64 at a time, lane = row: the lane keeps its descriptor in

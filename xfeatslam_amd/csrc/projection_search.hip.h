@@ -85,7 +85,7 @@ void k_proj_candidates(ProjArgs a) {
     int i0 = -1, i1 = -1, i2 = -1, i3 = -1;
     static_assert(XFH_PROJ_K == 4, "the per-lane insertion below is written for four entries");
     const int nc = window_walk<true>(w, grid, a.qdesc + qg * 64, u, v, r, tg, a.nt, a.skip ? a.skip + (size_t)pb * a.nt : nullptr,
-                                     a.uright ? a.uright + (size_t)pb * a.nt : nullptr, ur, lane, [](int) { return true; },
+                                     a.uright ? a.uright + (size_t)pb * a.nt : nullptr, ur, lane, [](int, float, float) { return true; },
                                      [&](u64 key, int idx) {
                                          if (key < k3) {
                                              k3 = key; i3 = idx;
@@ -178,7 +178,7 @@ void k_proj_resolve(ProjArgs a) {
             const WindowWalk w = window_open(grid, u, v, r, nt, lane);
             u64 b = ~0ull, s2 = ~0ull;
             const int nc = window_walk<true>(w, grid, a.qdesc + (q0 + q) * 64, u, v, r, tg, nt, skip, uright, ur, lane,
-                                             [&](int idx) { return claim[idx] >= q; },
+                                             [&](int idx, float, float) { return claim[idx] >= q; },
                                              [&](u64 key, int) { top2_insert(b, s2, key); });
             int bi, bd, si, sd;
             window_best2(w, grid, b, s2, a.init_dist, bi, bd, si, sd);
@@ -225,7 +225,7 @@ void k_proj_count(ProjArgs a) {
     const WindowWalk w = window_open(grid, pj[0], pj[1], pj[3], a.nt, lane);
     const int nc = window_walk<false>(w, grid, nullptr, pj[0], pj[1], pj[3], nullptr, a.nt, a.skip ? a.skip + (size_t)pb * a.nt : nullptr,
                                       a.uright ? a.uright + (size_t)pb * a.nt : nullptr, pj[2], lane,
-                                      [&](int idx) { return wclaim[idx] >= qi; }, [](u64, int) {});
+                                      [&](int idx, float, float) { return wclaim[idx] >= qi; }, [](u64, int) {});
     if (lane == 0) a.n_candidates[qg] = nc;
 }
 

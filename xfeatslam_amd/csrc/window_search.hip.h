@@ -137,7 +137,8 @@ hipError_t launch_grid_build(xfh_ctx* c, const void* kps, size_t kps_stride, con
 // or the target rows whatever the query holds.
 // The walk is written once, as device functions, for k_search_window and the kernels of projection_search.hip.h:
 //   window_open   the cell bounds of (u, v, r), lane = column: its range of items and its first position in the walk
-//   window_walk   deals the positions to the lanes, applies the window test and the static filters plus the caller's `extra(slot)`,
+//   window_walk   deals the positions to the lanes, applies the window test and the static filters plus the caller's `extra(slot, x, y)`
+//                 (x, y: the item's coordinates),
 //                 and calls visit(key, slot) for every survivor with key = dist << 32 | position (DIST = false: no descriptor is
 //                 read and the key's distance is 0); returns the number of survivors of the whole wave
 //   window_slot   the slot number at a position of the walk
@@ -213,7 +214,7 @@ __device__ __forceinline__ int window_walk(const WindowWalk& w, const char* __re
             pass = idx >= 0 && idx < nt && fabsf(it.x - u) < r && fabsf(it.y - v) < r;               // Frame.cc:904-908
             if (pass && skip) pass = skip[idx] == 0;                                                   // ORBmatcher.cc:1931-1933
             if (pass && uright) { const float ur = uright[idx]; if (ur > 0.0f && fabsf(urq - ur) > r) pass = false; }   // :1935-1941
-            if (pass) pass = extra(idx);
+            if (pass) pass = extra(idx, it.x, it.y);
         }
         ncand += __popcll(__ballot(pass));
         if (pass) {
@@ -272,7 +273,7 @@ void k_search_window(const float* __restrict__ q, const float* __restrict__ uvr,
     const float urq = ur_query ? ur_query[qi] : 0.0f;
     const WindowWalk w = window_open(grid, u, v, r, nt, lane);
     u64 b = ~0ull, s2 = ~0ull;
-    const int ncand = window_walk<true>(w, grid, qr, u, v, r, tg, nt, skip, uright, urq, lane, [](int) { return true; },
+    const int ncand = window_walk<true>(w, grid, qr, u, v, r, tg, nt, skip, uright, urq, lane, [](int, float, float) { return true; },
                                         [&](u64 key, int) { top2_insert(b, s2, key); });
     int bi, bd, si, sd;
     window_best2(w, grid, b, s2, init_dist, bi, bd, si, sd);

@@ -357,6 +357,74 @@ class Context:
         check(lib().xfh_distinctive_csr(self.h, tb.ctypes.data, len(tb), off.ctypes.data, ind.ctypes.data, ng, pos.ctypes.data, med.ctypes.data), self.h)
         return pos[:ng], med[:ng]
 
+    # -- Fuse: map points into keyframes (xfh_scale_level_thresholds / xfh_fuse_project / xfh_fuse_search*) -------
+    @staticmethod
+    def scale_level_thresholds(scale_factor: float, nlevels: int) -> np.ndarray:
+        """xfh_scale_level_thresholds (host): ratio_max[nlevels - 1], the table that stands for MapPoint::PredictScale on the device"""
+        r = np.zeros(max(nlevels - 1, 1), np.float32)
+        check(lib().xfh_scale_level_thresholds(float(scale_factor), int(nlevels), r.ctypes.data))
+        return r[:max(nlevels - 1, 0)]
+
+    @staticmethod
+    def fuse_project(Tcw, Ow, cam, bounds, th: float, scale_factors, ratio_max, xyz, normals, distances):
+        """xfh_fuse_project (host): the per-point arithmetic of ORBmatcher::Fuse for one pose -> (uvr[n][3], ur[n], level[n], status[n])"""
+        T = np.ascontiguousarray(Tcw, np.float32).reshape(12); O = np.ascontiguousarray(Ow, np.float32).reshape(3)
+        sf = np.ascontiguousarray(scale_factors, np.float32); rm = np.ascontiguousarray(ratio_max, np.float32)
+        p = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3); nr = np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
+        d = np.ascontiguousarray(distances, np.float32).reshape(-1, 3)
+        n = len(p)
+        assert len(nr) == n and len(d) == n and len(rm) >= len(sf) - 1
+        uvr = np.zeros((max(n, 1), 3), np.float32); ur = np.zeros(max(n, 1), np.float32); lv = np.zeros(max(n, 1), np.int32); st = np.zeros(max(n, 1), np.uint8)
+        check(lib().xfh_fuse_project(T.ctypes.data, O.ctypes.data, C.byref(cam), C.byref(capi.GridBounds(*bounds)), float(th), sf.ctypes.data, rm.ctypes.data,
+                                     len(sf), p.ctypes.data, nr.ctypes.data, d.ctypes.data, n, uvr.ctypes.data, ur.ctypes.data, lv.ctypes.data, st.ctypes.data))
+        return uvr[:n], ur[:n], lv[:n], st[:n]
+
+    FUSE_OUT_INT = ("best_idx", "best_dist", "n_window", "n_tested", "level")
+
+    @staticmethod
+    def fuse_search_layout(B: int, nq: int, guard: int = 0):
+        """byte offsets of the outputs of fuse_search_device inside one buffer (and its size under "bytes"); guard > 0 leaves at least
+        that many bytes the call never writes before the first array and after every array (for tests that fill them)"""
+        al = lambda x: (x + 255) & ~255
+        o, off = {}, al(guard)
+        for name, nbytes in (("best_idx", 4 * B * nq), ("best_dist", 4 * B * nq), ("n_window", 4 * B * nq), ("n_tested", 4 * B * nq), ("level", 4 * B * nq),
+                             ("proj", 12 * B * nq), ("n_fused", 4 * B), ("status", B * nq)):
+            o[name] = off; off += al(nbytes) + al(guard)
+        o["bytes"] = off
+        return o
+
+    def fuse_search_device(self, B: int, nq: int, query_stride: int, d_points, d_normals, d_distances, d_query_desc, d_query_flags, d_Tcw, d_Ow, cam, bounds,
+                           th: float, scale_factors, ratio_max, d_grids, d_targets, target_stride: int, nt: int, d_out, d_uright=None, chi2: bool = True,
+                           init_dist: int = 256, th_low: int = 100, proj: bool = True, guard: int = 0):
+        """xfh_fuse_search_device on device pointers; asynchronous.  d_out: pointer to the outputs laid out as fuse_search_layout(B, nq,
+        guard) says (proj = False: the proj block is left alone)"""
+        o = self.fuse_search_layout(B, nq, guard)
+        sf = np.ascontiguousarray(scale_factors, np.float32); rm = np.ascontiguousarray(ratio_max, np.float32)
+        check(lib().xfh_fuse_search_device(self.h, B, nq, query_stride, d_points, d_normals, d_distances, d_query_desc, d_query_flags, d_Tcw, d_Ow, C.byref(cam),
+                                           C.byref(capi.GridBounds(*bounds)), float(th), sf.ctypes.data, rm.ctypes.data, len(sf), d_grids, d_targets,
+                                           target_stride, nt, d_uright, capi.FUSE_CHI2 if chi2 else 0, int(init_dist), int(th_low), d_out + o["status"],
+                                           *[d_out + o[k] for k in self.FUSE_OUT_INT], d_out + o["proj"] if proj else None, d_out + o["n_fused"]), self.h)
+
+    def fuse_search(self, points, normals, distances, query_desc, query_flags, Tcw, Ow, cam, bounds, th: float, scale_factors, ratio_max, kps, targets,
+                    uright=None, chi2: bool = True, init_dist: int = 256, th_low: int = 100):
+        """xfh_fuse_search (host pointers, one keyframe) -> dict(status, best_idx, best_dist, n_window, n_tested, level, proj, n_fused)"""
+        p = np.ascontiguousarray(points, np.float32).reshape(-1, 3); nr = np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
+        d = np.ascontiguousarray(distances, np.float32).reshape(-1, 3); q = np.ascontiguousarray(query_desc, np.float32)
+        fl = np.ascontiguousarray(query_flags, np.uint8); k = np.ascontiguousarray(kps, KP_DTYPE); tg = np.ascontiguousarray(targets, np.float32)
+        T = np.ascontiguousarray(Tcw, np.float32).reshape(12); O = np.ascontiguousarray(Ow, np.float32).reshape(3)
+        sf = np.ascontiguousarray(scale_factors, np.float32); rm = np.ascontiguousarray(ratio_max, np.float32)
+        nq, nt = len(p), len(k)
+        assert len(nr) == nq and len(d) == nq and len(q) == nq and len(fl) == nq and len(tg) == nt and len(rm) >= len(sf) - 1
+        ur = None if uright is None else np.ascontiguousarray(uright, np.float32)
+        st = np.zeros(nq, np.uint8); oi = [np.zeros(nq, np.int32) for _ in range(5)]; proj = np.zeros((nq, 3), np.float32); nf = np.zeros(1, np.int32)
+        check(lib().xfh_fuse_search(self.h, nq, p.ctypes.data, nr.ctypes.data, d.ctypes.data, q.ctypes.data, fl.ctypes.data, T.ctypes.data, O.ctypes.data,
+                                    C.byref(cam), C.byref(capi.GridBounds(*bounds)), float(th), sf.ctypes.data, rm.ctypes.data, len(sf), k.ctypes.data,
+                                    tg.ctypes.data, nt, None if ur is None else ur.ctypes.data, capi.FUSE_CHI2 if chi2 else 0, int(init_dist), int(th_low),
+                                    st.ctypes.data, *[o.ctypes.data for o in oi], proj.ctypes.data, nf.ctypes.data), self.h)
+        r = dict(zip(self.FUSE_OUT_INT, oi))
+        r.update(status=st, proj=proj, n_fused=int(nf[0]))
+        return r
+
     # -- timing ---------------------------------------------------------------------------
     def timing_enable(self, kernel_id: int, layer_mask: int = 0):
         check(lib().xfh_timing_enable(self.h, kernel_id, layer_mask), self.h)
@@ -433,6 +501,18 @@ class ORBmatcher:
     def DescriptorDistance(a: np.ndarray, b: np.ndarray) -> int:
         a = np.ascontiguousarray(a, np.float32).ravel(); b = np.ascontiguousarray(b, np.float32).ravel()
         return int(lib().xfh_descriptor_distance(a.ctypes.data, b.ctypes.data))
+
+    def fuse(self, points, normals, distances, query_desc, query_flags, Tcw, Ow, cam, bounds, th: float, scale_factors, kps, targets, uright=None,
+             sim3: bool = False, ratio_max=None):
+        """The search of `ORBmatcher::Fuse` for one keyframe (ORBmatcher.cc:1333-1523; sim3 = True: the form of :1525-1640 with Tcw = [R | t/s]
+        and Ow from the caller's decomposition: no chi-square gates, bestDist starts at INT_MAX).  -> (nFused, result dict of
+        Context.fuse_search); the caller runs :1497-1516 resp. :1622-1636 over best_idx in query order."""
+        sf = np.ascontiguousarray(scale_factors, np.float32)
+        if ratio_max is None:
+            ratio_max = Context.scale_level_thresholds(float(sf[1]) if len(sf) > 1 else 1.2, len(sf))
+        r = self.ctx.fuse_search(points, normals, distances, query_desc, query_flags, Tcw, Ow, cam, bounds, th, sf, ratio_max, kps, targets, uright=uright,
+                                 chi2=not sim3, init_dist=0x7fffffff if sim3 else 256, th_low=self.TH_LOW)
+        return r["n_fused"], r
 
     def match(self, desc1: np.ndarray, desc2: np.ndarray, min_cossim: float = -1.0):
         """-> list of (queryIdx, trainIdx, distance) like std::vector<cv::DMatch>"""
