@@ -12,6 +12,8 @@
  *        of the RGB-D Frame constructor (UndistortKeyPoints, ComputeStereoFromRGBD, the grid on mvKeysUn; Frame.cc:311-374)
  *   XFmatcher::searchByProjection: the whole of ORBmatcher::SearchByProjection(Frame&, const Frame&, th, bMono) (ORBmatcher.cc:1861-2047)
  *        and of the SearchLocalPoints form (:42-141): projection, cull, windowed best two and the reference's claim order in one call
+ *   XFmatcher::fuse / searchForTriangulation: the two matchers of LocalMapping, ORBmatcher::Fuse (ORBmatcher.cc:1333-1640) up to the map
+ *        bookkeeping and ORBmatcher::SearchForTriangulation (:1092-1331) over the nodes of the DBoW2 feature vectors, each as one call
  *   best2 / distinctive: the batched inner loops of SearchBy* (ORBmatcher.cc:75-119) and of
  *        MapPoint::ComputeDistinctiveDescriptors (MapPoint.cc:329-403)
  *
@@ -25,7 +27,9 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstdint>
 #include <cstring>
+#include <utility>
 
 namespace xfeat {
 #if !XFEAT_HAVE_OPENCV
@@ -521,6 +525,78 @@ public:
     const std::vector<int>& lastFuseTested() const { return fuseTested; }
     const std::vector<int>& lastFuseLevel() const { return fuseLevel; }
 
+    // ORBmatcher::SearchForTriangulation(pKF1, pKF2, vMatchedPairs, bOnlyStereo, bCoarse) (ORBmatcher.cc:1092-1331; mbCheckOrientation = false as
+    // LocalMapping builds the matcher, no second camera) as ONE call (xfh_triangulation_search): every keypoint of KF1 without a map point
+    // against the keypoints of KF2 without one that share its vocabulary node, under the epipole radius and the epipolar test.  Per keyframe:
+    // desc = mDescriptors, keysUn = mvKeysUn as (x, y) pairs, uright = mvuRight (nullptr: monocular), has[i] != 0 where GetMapPoint(i) is set,
+    // nodeOf[i] = the NodeId of keypoint i in mFeatVec (XFH_NODE_NONE: in none).  F12 (row-major, the matrix of Pinhole.cpp:112) and ep (the
+    // epipole of :1105) are the caller's, computed once per pair.  scaleFactor0 / levelSigma2_0 = mvScaleFactors[0] / mvLevelSigma2[0] of KF2.
+    // vMatchedPairs comes back in ascending idx1 (:1320-1328); the return value is nmatches.  Blocks until the result is on the host.
+    int searchForTriangulation(const Mat& desc1, const std::vector<float>& keysUn1, const std::vector<float>* uright1, const std::vector<unsigned char>& has1,
+                               const std::vector<uint32_t>& nodeOf1, const Mat& desc2, const std::vector<float>& keysUn2, const std::vector<float>* uright2,
+                               const std::vector<unsigned char>& has2, const std::vector<uint32_t>& nodeOf2, const float* F12, const float* ep,
+                               std::vector<std::pair<size_t, size_t>>& vMatchedPairs, bool bOnlyStereo = false, bool bCoarse = false, float scaleFactor0 = 1.f,
+                               float levelSigma2_0 = 1.f) {
+        const int n1 = desc1.rows, n2 = desc2.rows;
+        vMatchedPairs.clear();
+        triStatus.assign(n1, 0); triMatch.assign(n1, -1); triBest.assign(n1, TH_LOW); triCandidates.assign(n1, 0); triGeom.assign(n1, 0);
+        if (n1 == 0 || n2 == 0) return 0;
+        if ((int)keysUn1.size() != 2 * n1 || (int)has1.size() != n1 || (int)nodeOf1.size() != n1 || (uright1 && (int)uright1->size() != n1) ||
+            (int)keysUn2.size() != 2 * n2 || (int)has2.size() != n2 || (int)nodeOf2.size() != n2 || (uright2 && (int)uright2->size() != n2) || !F12 || !ep)
+            throw std::runtime_error("XFmatcher::searchForTriangulation: sizes do not fit");
+        int nmatches = 0;
+        const int rc = xfh_triangulation_search(ctx, n1, n2, (bOnlyStereo ? XFH_TRI_ONLY_STEREO : 0) | (bCoarse ? XFH_TRI_COARSE : 0), TH_LOW, 100 * scaleFactor0,
+                                                levelSigma2_0, nodeOf1.data(), keysUn1.data(), uright1 ? uright1->data() : nullptr, has1.data(),
+                                                desc1.template ptr<float>(0), nodeOf2.data(), keysUn2.data(), uright2 ? uright2->data() : nullptr, has2.data(),
+                                                desc2.template ptr<float>(0), F12, ep, triStatus.data(), triMatch.data(), triBest.data(), triCandidates.data(),
+                                                triGeom.data(), &nmatches);
+        if (rc != XFH_OK) throw std::runtime_error(std::string("XFmatcher::searchForTriangulation: ") + xfh_strerror(rc));
+        return triPairs(vMatchedPairs, nmatches);
+    }
+    // The same on two keyframes that live in device memory: XFgrids finished with XFgrid::buildFromRecord(record, n, camera, ..) (their
+    // deviceKeysUn() / deviceURight() are mvKeysUn / mvuRight), the records' descriptor blocks, and per keyframe a node blob (xfh_nodes_pack,
+    // uploaded by the caller) and the has-a-map-point bytes in device memory.  F12 and ep are host arrays.  Only the results travel back.
+    int searchForTriangulation(const XFgrid& grid1, const float* d_desc1, const void* d_nodes1, const unsigned char* d_has1, const XFgrid& grid2,
+                               const float* d_desc2, const void* d_nodes2, const unsigned char* d_has2, const float* F12, const float* ep,
+                               std::vector<std::pair<size_t, size_t>>& vMatchedPairs, bool bOnlyStereo = false, bool bCoarse = false, float scaleFactor0 = 1.f,
+                               float levelSigma2_0 = 1.f) {
+        const int n1 = grid1.size(), n2 = grid2.size();
+        vMatchedPairs.clear();
+        triStatus.assign(n1 > 0 ? n1 : 0, 0); triMatch.assign(triStatus.size(), -1); triBest.assign(triStatus.size(), TH_LOW);
+        triCandidates.assign(triStatus.size(), 0); triGeom.assign(triStatus.size(), 0);
+        if (n1 <= 0 || n2 <= 0) return 0;
+        if (!grid1.deviceKeysUn() || !grid2.deviceKeysUn() || !F12 || !ep) throw std::runtime_error("XFmatcher::searchForTriangulation: the grids were not built with a camera");
+        auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+        const size_t bn = al((size_t)n1 * 4), bs = al((size_t)n1);
+        reserve(d_proj, d_proj_bytes, 4 * bn + bs + 3 * 256, "XFmatcher::searchForTriangulation");
+        char* p = (char*)d_proj;
+        int* o[4];
+        for (int k = 0; k < 4; ++k) { o[k] = (int*)p; p += bn; }
+        unsigned char* dst = (unsigned char*)p; p += bs; int* dnm = (int*)p; p += 256; float* dF = (float*)p; p += 256; float* de = (float*)p;
+        int rc = xfh_synchronize(ctx);                       // (the copies below are synchronous: nothing queued earlier may still read the buffer)
+        if (rc == XFH_OK) rc = xfh_memcpy_h2d(dF, F12, 36);
+        if (rc == XFH_OK) rc = xfh_memcpy_h2d(de, ep, 8);
+        if (rc == XFH_OK)
+            rc = xfh_triangulation_search_device(ctx, 1, n1, n2, 1, (bOnlyStereo ? XFH_TRI_ONLY_STEREO : 0) | (bCoarse ? XFH_TRI_COARSE : 0), TH_LOW, 100 * scaleFactor0,
+                                                 levelSigma2_0, d_nodes1, grid1.deviceKeysUn(), grid1.deviceURight(), d_has1, d_desc1, 0, d_nodes2, grid2.deviceKeysUn(),
+                                                 grid2.deviceURight(), d_has2, d_desc2, 0, dF, de, dst, o[0], o[1], o[2], o[3], dnm);
+        if (rc == XFH_OK) rc = xfh_synchronize(ctx);
+        int nmatches = 0;
+        int* out[4] = {triMatch.data(), triBest.data(), triCandidates.data(), triGeom.data()};
+        for (int k = 0; k < 4 && rc == XFH_OK; ++k) rc = xfh_memcpy_d2h(out[k], o[k], (size_t)n1 * 4);
+        if (rc == XFH_OK) rc = xfh_memcpy_d2h(triStatus.data(), dst, (size_t)n1);
+        if (rc == XFH_OK) rc = xfh_memcpy_d2h(&nmatches, dnm, 4);
+        if (rc != XFH_OK) throw std::runtime_error(std::string("XFmatcher::searchForTriangulation: ") + xfh_strerror(rc));
+        return triPairs(vMatchedPairs, nmatches);
+    }
+    // per keypoint of KF1, of the last searchForTriangulation: XFH_TRI_* status, vMatches12, best DescriptorDistance, the members of KF2's node that
+    // were candidates, and those of them that passed the geometry
+    const std::vector<unsigned char>& lastTriangulationStatus() const { return triStatus; }
+    const std::vector<int>& lastTriangulationMatches() const { return triMatch; }
+    const std::vector<int>& lastTriangulationBestDist() const { return triBest; }
+    const std::vector<int>& lastTriangulationCandidates() const { return triCandidates; }
+    const std::vector<int>& lastTriangulationGeom() const { return triGeom; }
+
     // MapPoint::ComputeDistinctiveDescriptors (MapPoint.cc:329-403), batched over map points: group g observes the
     // rows indices[offsets[g] .. offsets[g+1]) of `table`; bestPos[g] = position in the group of the descriptor with
     // the least median DescriptorDistance to the others (-1 for an empty group), bestMedian[g] = that median.
@@ -535,6 +611,11 @@ public:
     }
 
 protected:
+    int triPairs(std::vector<std::pair<size_t, size_t>>& vMatchedPairs, int nmatches) const {          // :1320-1328
+        vMatchedPairs.reserve(nmatches > 0 ? nmatches : 0);
+        for (size_t i = 0; i < triMatch.size(); ++i) if (triMatch[i] >= 0) vMatchedPairs.push_back(std::make_pair(i, (size_t)triMatch[i]));
+        return nmatches;
+    }
     static void reserve(void*& buf, size_t& cap, size_t bytes, const char* who) {
         if (bytes <= cap) return;
         if (buf) xfh_dev_free(buf);
@@ -554,6 +635,8 @@ protected:
     std::vector<unsigned char> fuseStatus;                  // results of fuse, and the level thresholds of the pyramid it was last called with
     std::vector<int> fuseBest, fuseWindow, fuseTested, fuseLevel;
     std::vector<float> fuseRatioMax; float fuseScale = 0.f;
+    std::vector<unsigned char> triStatus;                   // results of searchForTriangulation
+    std::vector<int> triMatch, triBest, triCandidates, triGeom;
 };
 
 }  // namespace ORB_SLAM3

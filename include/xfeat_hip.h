@@ -541,8 +541,8 @@ int xfh_search_projection(xfh_ctx* ctx, int mode, int nq, const float* points_or
  *                         the undistorted coordinates) with flags 0 and `bounds`, runs the call and copies the results back.
  *                         XFH_ERR_INVALID_ARG for the device form's classes of error (and bounds no grid can be built from) before
  *                         anything is staged or queued.
- * Out of scope: bRight / NLeft != -1 (fisheye stereo), the Sim3 SearchByProjection forms and SearchBySim3, and the functions
- * that walk DBoW2 feature vectors (SearchByBoW, SearchForTriangulation). */
+ * Out of scope: bRight / NLeft != -1 (fisheye stereo), the Sim3 SearchByProjection forms and SearchBySim3, and SearchByBoW
+ * (SearchForTriangulation, the other function that walks DBoW2 feature vectors, is xfh_triangulation_search_device below). */
 #define XFH_FUSE_MAX_LEVELS 16
 #define XFH_FUSE_FLAG_ACTIVE 1        /* d_query_flags bit0 */
 #define XFH_FUSE_CHI2 1               /* flags: the chi-square reprojection gates of the SE3 form */
@@ -564,6 +564,101 @@ int xfh_fuse_search(xfh_ctx* ctx, int nq, const float* points, const float* norm
                     const float* scale_factors, const float* ratio_max, int nlevels, const xfh_keypoint* kps, const float* targets, int nt,
                     const float* uright_or_null, int flags, int init_dist, int th_low, uint8_t* status, int* best_idx, int* best_dist, int* n_window,
                     int* n_tested, int* level, float* proj_out_or_null, int* n_fused);
+
+/* ---- SearchForTriangulation over feature-vector nodes, device resident ---------------------------------------------------------------
+ * ORBmatcher::SearchForTriangulation(KeyFrame* pKF1, KeyFrame* pKF2, vMatchedPairs, bOnlyStereo, bCoarse) (src/ORBmatcher.cc:1092-1331,
+ * called once per covisible neighbour from LocalMapping::CreateNewMapPoints, src/LocalMapping.cc:434-466) up to vMatches12, as one call
+ * for B keyframe pairs.  Every keypoint of KF1 without a map point is compared with the keypoints of KF2 without a map point that share
+ * its vocabulary node, under an epipolar test.  vbMatched2 is created at :1134 and read at :1189 but never written in this function
+ * (the write exists only in SearchByBoW, :1038): two keypoints of KF1 never see each other, there is no claim order, two of them may
+ * name the same keypoint of KF2 as in the reference, and the call needs no workspace.
+ *
+ * Node index.  TemplatedVocabulary::transform visits the features in ascending index and FeatureVector::addFeature push_backs, so
+ * mFeatVec is "node id ascending, keypoint index ascending inside a node": a function of node_of[i], the NodeId of keypoint i
+ * (XFH_NODE_NONE: keypoint i is in no node; every other uint32 is a valid id).  DBoW2 itself stays with the caller, who
+ * flattens mFeatVec into node_of on the host, where it was computed.
+ *   xfh_nodes_bytes / xfh_nodes_pack   host, stateless: node_of[n] -> an opaque, self-contained blob of xfh_nodes_bytes(n) bytes (a multiple
+ *                         of 16): a header, the distinct node ids ascending, node_start, the items (keypoint indices, nodes in id order,
+ *                         ascending inside a node) and a copy of node_of.  The caller uploads it with xfh_memcpy_h2d (16-byte aligned); one
+ *                         blob serves a keyframe on either side.  Packing the same input twice gives identical bytes; padding is zeroed.
+ *                         n in 1 .. XFH_GRID_MAX_N.
+ *   xfh_nodes_unpack      the test and debug inverse: node_ids[n] (the first *n_nodes meaningful), node_start[n + 1], items[n] (-1 past the
+ *                         item count).  A truncated or inconsistent blob is XFH_ERR_INVALID_ARG, never an out-of-bounds access.
+ *
+ * Problem b is the pair (KF1, KF2_b).  With side1_shared = 1 all B problems read the SAME side-1 arrays (CreateNewMapPoints: the new
+ * keyframe against every neighbour; its rows are then served from L2, and desc1_stride_bytes is ignored); with 0 problem b reads its own.
+ * Per side and problem: the node blob (b * xfh_nodes_bytes(n) bytes in), xy[n][2] (mvKeysUn, the layout of xfh_frame_finish_records_device's
+ * xy_un), uright[n] (mvuRight; NULL = a monocular keyframe, every entry -1), has[n] bytes (non-zero: GetMapPoint(idx) != NULL) -- these
+ * three b * n elements in -- and descriptor rows b * desc_stride_bytes in (xfh_record_bytes(nfeatures) lets d_desc point at the desc block
+ * of record 0 of a batch).  Per problem: F12[9] row-major, the matrix of Pinhole.cpp:112 (K1^-T [t12]x R12 K2^-1), and ep[2], the epipole
+ * of :1105 -- both computed once per pair by the caller with its own Eigen (the reference recomputes the identical F12 per candidate).
+ * Scalars: th_low (TH_LOW = 100), epipole_r2 = 100 * mvScaleFactors[0] (:1215), unc = mvLevelSigma2[0] (:1257): every XFeat keypoint has
+ * octave 0.  flags: XFH_TRI_ONLY_STEREO = bOnlyStereo, XFH_TRI_COARSE = bCoarse.
+ * All arithmetic is fp32 in the order written unless stated otherwise (the library is built with -ffp-contract=off).  For keypoint i of KF1:
+ *
+ *   has1[i] != 0                                          -> INACTIVE        (:1159)
+ *   stereo1 = uright1[i] >= 0 (NULL or NaN: false);  ONLY_STEREO && !stereo1 -> INACTIVE   (:1164-1168)
+ *   node = node_of1[i];  node == XFH_NODE_NONE or absent from KF2's node ids -> NO_NODE
+ *   a = (x1*F[0] + y1*F[3]) + F[6];  b = (x1*F[1] + y1*F[4]) + F[7];  c = (x1*F[2] + y1*F[5]) + F[8];  den = a*a + b*b   (Pinhole.cpp:115-121)
+ *   per member k of KF2's node, in stored (ascending index) order:
+ *       has2[k] != 0                                      -> skipped         (:1189)
+ *       stereo2 = uright2[k] >= 0;  ONLY_STEREO && !stereo2 -> skipped       (:1192-1196)
+ *       -- n_candidates counts the members that got here
+ *       !stereo1 && !stereo2:  dx = ep[0] - x2;  dy = ep[1] - y2;  dx*dx + dy*dy < epipole_r2 -> skipped   (:1211-1219)
+ *       without XFH_TRI_COARSE:  num = (a*x2 + b*y2) + c;  den == 0 -> skipped;  dsqr = (num*num) / den;
+ *                                !((double)dsqr < 3.84 * (double)unc) -> skipped   (a NaN dsqr is skipped; Pinhole.cpp:119-128)
+ *       -- n_geom counts the members that got here
+ *       dist = DescriptorDistance(row i of KF1, row k of KF2);  dist <= th_low && dist <= best -> best = dist, best_idx = k
+ *   best starts at th_low;  best_idx >= 0 -> MATCHED, else n_candidates == 0 -> NO_CANDIDATES, else REJECTED
+ *
+ * The reference tests `dist>TH_LOW || dist>bestDist` (:1202, continue on strictly greater) BEFORE the geometry and lowers bestDist only for
+ * a candidate that passes everything: the result is the least dist over the members that pass every gate with dist <= th_low, and among
+ * equal distances the member visited LAST wins -- the opposite of xfh_best2_csr's rule.  The gates are pure, so their order changes
+ * neither the result nor the two counts; the kernel applies the geometry first and computes distances only for the n_geom survivors.
+ * Outputs, all exact, all in device memory.  Per (problem, i): status (XFH_TRI_*), match12 (vMatches12: idx2 or -1), best_dist (th_low
+ * where there is none), n_candidates, n_geom (both 0 for a query that never reached a node).  Per problem: n_matches (nmatches).  The
+ * caller builds vMatchedPairs from match12 in ascending i (:1320-1328).
+ *
+ *   xfh_epipolar_gate     host, stateless, thread-safe: the gates above for ONE keypoint (x1, y1, stereo1) of KF1 against n keypoints of KF2
+ *                         that have no map point: pass[k] = XFH_TRI_GATE_SKIPPED (the stereo-only gate; every k when ONLY_STEREO && !stereo1),
+ *                         XFH_TRI_GATE_REJECTED (a candidate the epipole or epipolar test drops) or XFH_TRI_GATE_PASSED (it reaches
+ *                         DescriptorDistance).  The same source lines as the kernel (tri_math.h).
+ *   xfh_triangulation_search_device   B problems with the same n1, n2, flags and scalars.  d_F12 [B][9], d_ep [B][2]; outputs d_status [B][n1]
+ *                         bytes, d_match12 / d_best_dist / d_n_candidates / d_n_geom [B][n1] ints, d_n_matches [B] ints.  All pointers are
+ *                         device pointers; asynchronous on the ctx stream, no allocation, no workspace, ONE kernel launch (behind a 4 * B
+ *                         byte memset of d_n_matches on the same stream).  XFH_ERR_INVALID_ARG before anything is queued: n1 or n2
+ *                         outside 1 .. XFH_GRID_MAX_N, B outside 1 .. 65535, side1_shared other than 0 or 1, unknown flag bits, a non-finite
+ *                         epipole_r2 or unc, a NULL required pointer, misaligned pointers (16 bytes for descriptor rows, their strides and
+ *                         the blobs, the element size otherwise).  Blobs, F12, ep, coordinates and uright may hold anything, NaN and Inf
+ *                         included: every count and range read from a blob is clamped and every item is checked against n2 before it
+ *                         indexes anything, so no load leaves the buffers the caller named.  The distance of a row that holds a NaN is
+ *                         not defined.
+ *   xfh_triangulation_search   host-pointer convenience form for ONE problem: packs both node blobs, stages the inputs, runs the call and
+ *                         copies the results back.  XFH_ERR_INVALID_ARG for the device form's classes of error before anything is staged
+ *                         or queued.
+ * Out of scope: mbCheckOrientation and the rotation histogram (:1272-1318; the only caller builds ORBmatcher(0.6f, false),
+ * LocalMapping.cc:412); fisheye stereo (mpCamera2, NLeft != -1, the four T12 variants of :1221-1255); KannalaBrandt8::epipolarConstrain;
+ * computing F12 or the epipole; computing the feature vector (DBoW2); SearchByBoW, which has a real claim order and a ratio test; and the
+ * triangulation itself. */
+#define XFH_NODE_NONE 0xFFFFFFFFu     /* node_of: the keypoint is in no node of the feature vector */
+#define XFH_TRI_ONLY_STEREO 1         /* flags: bOnlyStereo */
+#define XFH_TRI_COARSE 2              /* flags: bCoarse */
+enum { XFH_TRI_INACTIVE = 0, XFH_TRI_NO_NODE = 1, XFH_TRI_NO_CANDIDATES = 2, XFH_TRI_REJECTED = 3, XFH_TRI_MATCHED = 4 };
+enum { XFH_TRI_GATE_SKIPPED = 0, XFH_TRI_GATE_REJECTED = 1, XFH_TRI_GATE_PASSED = 2 };
+size_t xfh_nodes_bytes(int n);
+int xfh_nodes_pack(const uint32_t* node_of, int n, void* blob /* xfh_nodes_bytes(n) */, int* n_nodes_or_null);
+int xfh_nodes_unpack(const void* blob, size_t nbytes, int n, uint32_t* node_ids /* [n] */, int* node_start /* [n + 1] */, int* items /* [n] */, int* n_nodes);
+int xfh_epipolar_gate(const float* F12, const float* ep, float epipole_r2, float unc, int flags, float x1, float y1, int stereo1, const float* xy2,
+                      const float* uright2_or_null, int n, uint8_t* pass);
+int xfh_triangulation_search_device(xfh_ctx* ctx, int B, int n1, int n2, int side1_shared, int flags, int th_low, float epipole_r2, float unc,
+                                    const void* d_nodes1, const float* d_xy1, const float* d_uright1_or_null, const uint8_t* d_has1, const float* d_desc1,
+                                    size_t desc1_stride_bytes, const void* d_nodes2, const float* d_xy2, const float* d_uright2_or_null,
+                                    const uint8_t* d_has2, const float* d_desc2, size_t desc2_stride_bytes, const float* d_F12, const float* d_ep,
+                                    uint8_t* d_status, int* d_match12, int* d_best_dist, int* d_n_candidates, int* d_n_geom, int* d_n_matches);
+int xfh_triangulation_search(xfh_ctx* ctx, int n1, int n2, int flags, int th_low, float epipole_r2, float unc, const uint32_t* node_of1, const float* xy1,
+                             const float* uright1_or_null, const uint8_t* has1, const float* desc1, const uint32_t* node_of2, const float* xy2,
+                             const float* uright2_or_null, const uint8_t* has2, const float* desc2, const float* F12, const float* ep, uint8_t* status,
+                             int* match12, int* best_dist, int* n_candidates, int* n_geom, int* n_matches);
 
 /* MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:329-403), batched over map points: group g observes the
  * descriptor rows indices[offsets[g] .. offsets[g+1]) of `table` (n_rows x 64).  Pairwise DescriptorDistance inside

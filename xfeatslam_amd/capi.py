@@ -29,7 +29,7 @@ ERR_EMPTY_IMAGE = 2
 ERR_NO_DEVICE = 7
 ERR_COMM = 11
 
-K = dict(NONE=0, MNN_GEMM=1, CONV_MFMA=2, CONV_DIRECT=3, NMS=4, SELECT=5, DESC=6, HEADS=7, DIST_I32=8, PREPROC=9, BEST2=10, DISTINCTIVE=11, MNN_GEMM_SEG=12, GRID_BUILD=13, SEARCH_WINDOW=14, FRAME_FINISH=15, PROJ_CANDIDATES=16, PROJ_RESOLVE=17, PROJ_COUNT=18, FUSE_SEARCH=19)
+K = dict(NONE=0, MNN_GEMM=1, CONV_MFMA=2, CONV_DIRECT=3, NMS=4, SELECT=5, DESC=6, HEADS=7, DIST_I32=8, PREPROC=9, BEST2=10, DISTINCTIVE=11, MNN_GEMM_SEG=12, GRID_BUILD=13, SEARCH_WINDOW=14, FRAME_FINISH=15, PROJ_CANDIDATES=16, PROJ_RESOLVE=17, PROJ_COUNT=18, FUSE_SEARCH=19, TRIANGULATION_SEARCH=20)
 T = dict(X=0, XSTAT=1, SKIP_POOL=2, FEATS=6, H1=8, K1H=9, RAW0=16, STAT0=48, SEL=80)
 
 
@@ -64,6 +64,10 @@ FUSE_VISIBLE = 5
 FUSE_FLAG_ACTIVE = 1
 FUSE_CHI2 = 1
 FUSE_MAX_LEVELS = 16
+NODE_NONE = 0xFFFFFFFF
+TRI_ONLY_STEREO, TRI_COARSE = 1, 2
+TRI_INACTIVE, TRI_NO_NODE, TRI_NO_CANDIDATES, TRI_REJECTED, TRI_MATCHED = range(5)
+TRI_GATE_SKIPPED, TRI_GATE_REJECTED, TRI_GATE_PASSED = range(3)
 
 FLAG_RESCALE_KEYPOINTS = 1
 FLAG_SERIAL_BRANCH = 2
@@ -130,6 +134,13 @@ SYMBOLS = [
                                     _vp, _vp, _sz, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("xfh_fuse_search", _i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(Camera), C.POINTER(GridBounds), _f, _vp, _vp, _i, _vp, _vp, _i,
                              _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("xfh_nodes_bytes", _sz, [_i]),
+    ("xfh_nodes_pack", _i, [_vp, _i, _vp, _pi]),
+    ("xfh_nodes_unpack", _i, [_vp, _sz, _i, _vp, _vp, _vp, _pi]),
+    ("xfh_epipolar_gate", _i, [_vp, _vp, _f, _f, _i, _f, _f, _i, _vp, _vp, _i, _vp]),
+    ("xfh_triangulation_search_device", _i, [_vp, _i, _i, _i, _i, _i, _i, _f, _f, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp,
+                                             _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("xfh_triangulation_search", _i, [_vp, _i, _i, _i, _i, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("xfh_distinctive_csr", _i, [_vp, _vp, _i, _vp, _vp, _i, _vp, _vp]),
     ("xfh_distinctive_csr_device", _i, [_vp, _vp, _i, _vp, _vp, _i, _i, _vp, _vp]),
     ("xfh_comm_unique_id", _i, [_vp]),

@@ -17,6 +17,9 @@
 //                   call: projection, cull, windowed best two and the reference's claim order (projection_search.hip.h).
 //   k_fuse_search : both ORBmatcher::Fuse overloads up to the map bookkeeping, B keyframes per launch: projection, the distance, angle and
 //                   level culls, the window walk with the chi-square gate, best candidate (fuse_search.hip.h).
+//   k_triangulation_search : ORBmatcher::SearchForTriangulation up to vMatches12, B keyframe pairs per launch: the node of every unmatched
+//                   keypoint looked up in the neighbour's feature vector, the stereo, epipole and epipolar gates, best candidate with the
+//                   reference's last-wins tie (triangulation_search.hip.h).
 //   k_distinctive_csr : MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:329-403), one wave per map point.
 //
 // Numerics: normalised rows and the 64-term dot products are bit-identical to the oracle
@@ -95,6 +98,7 @@ hipError_t launch_best2(xfh_ctx* c, const float* q, int nq, const float* tg, con
 #include "frame_finish.hip.h"
 #include "projection_search.hip.h"
 #include "fuse_search.hip.h"
+#include "triangulation_search.hip.h"
 
 // ---- k_distinctive_csr: MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:329-403), batched -------
 // One wave per group (map point).  Rows are taken 64 at a time, lane = row: the lane keeps its descriptor in

@@ -425,6 +425,88 @@ class Context:
         r.update(status=st, proj=proj, n_fused=int(nf[0]))
         return r
 
+    # -- SearchForTriangulation over feature-vector nodes (xfh_nodes_* / xfh_epipolar_gate / xfh_triangulation_search*) -------
+    @staticmethod
+    def nodes_bytes(n: int) -> int:
+        return int(lib().xfh_nodes_bytes(n))
+
+    @staticmethod
+    def nodes_pack(node_of) -> np.ndarray:
+        """xfh_nodes_pack (host): node_of[n] (uint32, capi.NODE_NONE = in no node) -> the node blob as bytes, ready for upload"""
+        no = np.ascontiguousarray(node_of, np.uint32)
+        n = len(no)
+        blob = np.full(max(Context.nodes_bytes(n), 16), 0xA5, np.uint8)
+        check(lib().xfh_nodes_pack(no.ctypes.data, n, blob.ctypes.data, None))
+        return blob
+
+    @staticmethod
+    def nodes_unpack(blob: np.ndarray, n: int):
+        """xfh_nodes_unpack (host): a node blob -> (node_ids[n_nodes], node_start[n_nodes + 1], items[n_items])"""
+        b = np.ascontiguousarray(blob, np.uint8)
+        ids = np.zeros(max(n, 1), np.uint32); ns = np.zeros(max(n, 1) + 1, np.int32); items = np.zeros(max(n, 1), np.int32); nn = C.c_int(0)
+        check(lib().xfh_nodes_unpack(b.ctypes.data, b.nbytes, n, ids.ctypes.data, ns.ctypes.data, items.ctypes.data, C.byref(nn)))
+        return ids[:nn.value].copy(), ns[:nn.value + 1].copy(), items[:ns[nn.value]].copy()
+
+    @staticmethod
+    def epipolar_gate(F12, ep, epipole_r2: float, unc: float, flags: int, x1: float, y1: float, stereo1: bool, xy2, uright2=None) -> np.ndarray:
+        """xfh_epipolar_gate (host): the gates of SearchForTriangulation for one keypoint of KF1 against n of KF2 -> capi.TRI_GATE_* per keypoint"""
+        Fm = np.ascontiguousarray(F12, np.float32).reshape(9); e = np.ascontiguousarray(ep, np.float32).reshape(2)
+        xy = np.ascontiguousarray(xy2, np.float32).reshape(-1, 2)
+        ur = None if uright2 is None else np.ascontiguousarray(uright2, np.float32)
+        n = len(xy)
+        assert ur is None or len(ur) == n
+        out = np.zeros(max(n, 1), np.uint8)
+        check(lib().xfh_epipolar_gate(Fm.ctypes.data, e.ctypes.data, float(epipole_r2), float(unc), int(flags), float(x1), float(y1), int(bool(stereo1)),
+                                      xy.ctypes.data, None if ur is None else ur.ctypes.data, n, out.ctypes.data))
+        return out[:n]
+
+    TRI_OUT_INT = ("match12", "best_dist", "n_candidates", "n_geom")
+
+    @staticmethod
+    def triangulation_search_layout(B: int, n1: int, guard: int = 0):
+        """byte offsets of the outputs of triangulation_search_device inside one buffer (and its size under "bytes"); guard as in
+        fuse_search_layout"""
+        al = lambda x: (x + 255) & ~255
+        o, off = {}, al(guard)
+        for name, nbytes in (("match12", 4 * B * n1), ("best_dist", 4 * B * n1), ("n_candidates", 4 * B * n1), ("n_geom", 4 * B * n1), ("n_matches", 4 * B),
+                             ("status", B * n1)):
+            o[name] = off; off += al(nbytes) + al(guard)
+        o["bytes"] = off
+        return o
+
+    def triangulation_search_device(self, B: int, n1: int, n2: int, side1_shared: bool, d_nodes1, d_xy1, d_uright1, d_has1, d_desc1, desc1_stride: int,
+                                    d_nodes2, d_xy2, d_uright2, d_has2, d_desc2, desc2_stride: int, d_F12, d_ep, d_out, only_stereo: bool = False,
+                                    coarse: bool = False, th_low: int = 100, epipole_r2: float = 100.0, unc: float = 1.0, guard: int = 0):
+        """xfh_triangulation_search_device on device pointers; asynchronous.  d_out: pointer to the outputs laid out as
+        triangulation_search_layout(B, n1, guard) says"""
+        o = self.triangulation_search_layout(B, n1, guard)
+        flags = (capi.TRI_ONLY_STEREO if only_stereo else 0) | (capi.TRI_COARSE if coarse else 0)
+        check(lib().xfh_triangulation_search_device(self.h, B, n1, n2, 1 if side1_shared else 0, flags, int(th_low), float(epipole_r2), float(unc),
+                                                    d_nodes1, d_xy1, d_uright1, d_has1, d_desc1, desc1_stride, d_nodes2, d_xy2, d_uright2, d_has2, d_desc2,
+                                                    desc2_stride, d_F12, d_ep, d_out + o["status"], *[d_out + o[k] for k in self.TRI_OUT_INT],
+                                                    d_out + o["n_matches"]), self.h)
+
+    def triangulation_search(self, node_of1, xy1, has1, desc1, node_of2, xy2, has2, desc2, F12, ep, uright1=None, uright2=None, only_stereo: bool = False,
+                             coarse: bool = False, th_low: int = 100, epipole_r2: float = 100.0, unc: float = 1.0):
+        """xfh_triangulation_search (host pointers, one keyframe pair) -> dict(status, match12, best_dist, n_candidates, n_geom, n_matches)"""
+        f32 = lambda a: np.ascontiguousarray(a, np.float32)
+        no1, no2 = np.ascontiguousarray(node_of1, np.uint32), np.ascontiguousarray(node_of2, np.uint32)
+        x1, x2, d1, d2 = f32(xy1).reshape(-1, 2), f32(xy2).reshape(-1, 2), f32(desc1), f32(desc2)
+        h1, h2 = np.ascontiguousarray(has1, np.uint8), np.ascontiguousarray(has2, np.uint8)
+        Fm, e = f32(F12).reshape(9), f32(ep).reshape(2)
+        n1, n2 = len(no1), len(no2)
+        assert len(x1) == n1 and len(h1) == n1 and len(d1) == n1 and len(x2) == n2 and len(h2) == n2 and len(d2) == n2
+        u1 = None if uright1 is None else f32(uright1); u2 = None if uright2 is None else f32(uright2)
+        st = np.zeros(n1, np.uint8); oi = [np.zeros(n1, np.int32) for _ in range(4)]; nm = np.zeros(1, np.int32)
+        flags = (capi.TRI_ONLY_STEREO if only_stereo else 0) | (capi.TRI_COARSE if coarse else 0)
+        check(lib().xfh_triangulation_search(self.h, n1, n2, flags, int(th_low), float(epipole_r2), float(unc), no1.ctypes.data, x1.ctypes.data,
+                                             None if u1 is None else u1.ctypes.data, h1.ctypes.data, d1.ctypes.data, no2.ctypes.data, x2.ctypes.data,
+                                             None if u2 is None else u2.ctypes.data, h2.ctypes.data, d2.ctypes.data, Fm.ctypes.data, e.ctypes.data,
+                                             st.ctypes.data, *[o.ctypes.data for o in oi], nm.ctypes.data), self.h)
+        r = dict(zip(self.TRI_OUT_INT, oi))
+        r.update(status=st, n_matches=int(nm[0]))
+        return r
+
     # -- timing ---------------------------------------------------------------------------
     def timing_enable(self, kernel_id: int, layer_mask: int = 0):
         check(lib().xfh_timing_enable(self.h, kernel_id, layer_mask), self.h)
@@ -513,6 +595,16 @@ class ORBmatcher:
         r = self.ctx.fuse_search(points, normals, distances, query_desc, query_flags, Tcw, Ow, cam, bounds, th, sf, ratio_max, kps, targets, uright=uright,
                                  chi2=not sim3, init_dist=0x7fffffff if sim3 else 256, th_low=self.TH_LOW)
         return r["n_fused"], r
+
+    def search_for_triangulation(self, node_of1, xy1, has1, desc1, node_of2, xy2, has2, desc2, F12, ep, uright1=None, uright2=None,
+                                 only_stereo: bool = False, coarse: bool = False, scale_factor0: float = 1.0, level_sigma2_0: float = 1.0):
+        """`ORBmatcher::SearchForTriangulation` for one keyframe pair (ORBmatcher.cc:1092-1331) without the rotation histogram
+        -> (nmatches, vMatchedPairs in ascending idx1, result dict of Context.triangulation_search)"""
+        r = self.ctx.triangulation_search(node_of1, xy1, has1, desc1, node_of2, xy2, has2, desc2, F12, ep, uright1=uright1, uright2=uright2,
+                                          only_stereo=only_stereo, coarse=coarse, th_low=self.TH_LOW,
+                                          epipole_r2=float(np.float32(100) * np.float32(scale_factor0)), unc=level_sigma2_0)
+        m = r["match12"]
+        return r["n_matches"], [(int(i), int(m[i])) for i in np.nonzero(m >= 0)[0]], r
 
     def match(self, desc1: np.ndarray, desc2: np.ndarray, min_cossim: float = -1.0):
         """-> list of (queryIdx, trainIdx, distance) like std::vector<cv::DMatch>"""
