@@ -597,6 +597,63 @@ public:
     const std::vector<int>& lastTriangulationCandidates() const { return triCandidates; }
     const std::vector<int>& lastTriangulationGeom() const { return triGeom; }
 
+    // ORBmatcher::SearchByBoW, both overloads (ORBmatcher.cc:408-610 and :950-1090; no second camera; the rotation histogram removes nothing
+    // because every XFeat angle is -1, so mbCheckOrientation stays without effect) as ONE call (xfh_bow_search).  Side 1 is the keyframe whose
+    // map points are matched: desc1 = mDescriptors, nodeOf1[i] = the NodeId of keypoint i in mFeatVec (XFH_NODE_NONE: in none), active1[i] != 0
+    // where its map point i exists and is not bad.  Side 2 is the frame (keyframeForm = false: eligible2 is not read and may be empty,
+    // `bestDist1 <= TH_LOW`) or the second keyframe (keyframeForm = true: eligible2[k] != 0 where ITS map point k exists and is not bad,
+    // `bestDist1 < TH_LOW`).  mfNNratio is the matcher's.  matchOfQuery[i] = the keypoint of side 2 matched to keypoint i of side 1 or -1
+    // (vpMatches12 by index), assignedQuery[k] = the keypoint of side 1 that claimed keypoint k of side 2 or -1 (vpMapPointMatches[k] =
+    // vpMapPointsKF[assignedQuery[k]]); the return value is nmatches.  Blocks until the result is on the host.
+    int searchByBoW(const Mat& desc1, const std::vector<uint32_t>& nodeOf1, const std::vector<unsigned char>& active1, const Mat& desc2,
+                    const std::vector<uint32_t>& nodeOf2, const std::vector<unsigned char>& eligible2, bool keyframeForm, std::vector<int>& matchOfQuery,
+                    std::vector<int>& assignedQuery) {
+        const int n1 = desc1.rows, n2 = desc2.rows;
+        bowReset(n1, n2, matchOfQuery, assignedQuery);
+        if (n1 == 0 || n2 == 0) return 0;
+        if ((int)nodeOf1.size() != n1 || (int)active1.size() != n1 || (int)nodeOf2.size() != n2 || (keyframeForm && (int)eligible2.size() != n2))
+            throw std::runtime_error("XFmatcher::searchByBoW: sizes do not fit");
+        int nmatches = 0;
+        const int rc = xfh_bow_search(ctx, n1, n2, keyframeForm ? XFH_BOW_STRICT_LOW : 0, 256, TH_LOW, mfNNratio, nodeOf1.data(), active1.data(),
+                                      desc1.template ptr<float>(0), nodeOf2.data(), keyframeForm ? eligible2.data() : nullptr, desc2.template ptr<float>(0),
+                                      bowStatus.data(), matchOfQuery.data(), bowBest.data(), bowSecond.data(), bowCandidates.data(), assignedQuery.data(), &nmatches);
+        if (rc != XFH_OK) throw std::runtime_error(std::string("XFmatcher::searchByBoW: ") + xfh_strerror(rc));
+        return nmatches;
+    }
+    // The same on two sides that live in device memory: the descriptor blocks of two records, per side a node blob (xfh_nodes_pack, uploaded by
+    // the caller) and the flag bytes (d_eligible2 is not read when keyframeForm is false).  Only the results travel back.
+    int searchByBoW(int n1, const float* d_desc1, const void* d_nodes1, const unsigned char* d_active1, int n2, const float* d_desc2, const void* d_nodes2,
+                    const unsigned char* d_eligible2, bool keyframeForm, std::vector<int>& matchOfQuery, std::vector<int>& assignedQuery) {
+        bowReset(n1 > 0 ? n1 : 0, n2 > 0 ? n2 : 0, matchOfQuery, assignedQuery);
+        if (n1 <= 0 || n2 <= 0) return 0;
+        auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+        const size_t b1 = al((size_t)n1 * 4), b2 = al((size_t)n2 * 4), bs = al((size_t)n1), wsb = al(xfh_bow_search_workspace_bytes(n1, n2, 1));
+        if (wsb == 0) throw std::runtime_error("XFmatcher::searchByBoW: sizes out of range");
+        reserve(d_proj, d_proj_bytes, wsb + 4 * b1 + b2 + bs + 256, "XFmatcher::searchByBoW");
+        char* p = (char*)d_proj;
+        void* ws = p; p += wsb;
+        int* o[4];
+        for (int k = 0; k < 4; ++k) { o[k] = (int*)p; p += b1; }
+        int* das = (int*)p; p += b2; unsigned char* dst = (unsigned char*)p; p += bs; int* dnm = (int*)p;
+        int rc = xfh_bow_search_device(ctx, 1, n1, n2, 0, keyframeForm ? XFH_BOW_STRICT_LOW : 0, 256, TH_LOW, mfNNratio, d_nodes1, d_active1, d_desc1, 0, d_nodes2,
+                                       keyframeForm ? d_eligible2 : nullptr, d_desc2, 0, ws, dst, o[0], o[1], o[2], o[3], das, dnm);
+        if (rc == XFH_OK) rc = xfh_synchronize(ctx);
+        int nmatches = 0;
+        int* out[4] = {matchOfQuery.data(), bowBest.data(), bowSecond.data(), bowCandidates.data()};
+        for (int k = 0; k < 4 && rc == XFH_OK; ++k) rc = xfh_memcpy_d2h(out[k], o[k], (size_t)n1 * 4);
+        if (rc == XFH_OK) rc = xfh_memcpy_d2h(assignedQuery.data(), das, (size_t)n2 * 4);
+        if (rc == XFH_OK) rc = xfh_memcpy_d2h(bowStatus.data(), dst, (size_t)n1);
+        if (rc == XFH_OK) rc = xfh_memcpy_d2h(&nmatches, dnm, 4);
+        if (rc != XFH_OK) throw std::runtime_error(std::string("XFmatcher::searchByBoW: ") + xfh_strerror(rc));
+        return nmatches;
+    }
+    // per keypoint of side 1, of the last searchByBoW: XFH_BOW_* status, best and second-best DescriptorDistance (256 where there is none) and
+    // the members of side 2's node that were candidates when the query's turn came
+    const std::vector<unsigned char>& lastBoWStatus() const { return bowStatus; }
+    const std::vector<int>& lastBoWBestDist() const { return bowBest; }
+    const std::vector<int>& lastBoWSecondDist() const { return bowSecond; }
+    const std::vector<int>& lastBoWCandidates() const { return bowCandidates; }
+
     // MapPoint::ComputeDistinctiveDescriptors (MapPoint.cc:329-403), batched over map points: group g observes the
     // rows indices[offsets[g] .. offsets[g+1]) of `table`; bestPos[g] = position in the group of the descriptor with
     // the least median DescriptorDistance to the others (-1 for an empty group), bestMedian[g] = that median.
@@ -615,6 +672,10 @@ protected:
         vMatchedPairs.reserve(nmatches > 0 ? nmatches : 0);
         for (size_t i = 0; i < triMatch.size(); ++i) if (triMatch[i] >= 0) vMatchedPairs.push_back(std::make_pair(i, (size_t)triMatch[i]));
         return nmatches;
+    }
+    void bowReset(int n1, int n2, std::vector<int>& matchOfQuery, std::vector<int>& assignedQuery) {
+        matchOfQuery.assign(n1, -1); assignedQuery.assign(n2, -1);
+        bowStatus.assign(n1, 0); bowBest.assign(n1, 256); bowSecond.assign(n1, 256); bowCandidates.assign(n1, 0);
     }
     static void reserve(void*& buf, size_t& cap, size_t bytes, const char* who) {
         if (bytes <= cap) return;
@@ -637,6 +698,8 @@ protected:
     std::vector<float> fuseRatioMax; float fuseScale = 0.f;
     std::vector<unsigned char> triStatus;                   // results of searchForTriangulation
     std::vector<int> triMatch, triBest, triCandidates, triGeom;
+    std::vector<unsigned char> bowStatus;                   // results of searchByBoW
+    std::vector<int> bowBest, bowSecond, bowCandidates;
 };
 
 }  // namespace ORB_SLAM3

@@ -541,8 +541,8 @@ int xfh_search_projection(xfh_ctx* ctx, int mode, int nq, const float* points_or
  *                         the undistorted coordinates) with flags 0 and `bounds`, runs the call and copies the results back.
  *                         XFH_ERR_INVALID_ARG for the device form's classes of error (and bounds no grid can be built from) before
  *                         anything is staged or queued.
- * Out of scope: bRight / NLeft != -1 (fisheye stereo), the Sim3 SearchByProjection forms and SearchBySim3, and SearchByBoW
- * (SearchForTriangulation, the other function that walks DBoW2 feature vectors, is xfh_triangulation_search_device below). */
+ * Out of scope: bRight / NLeft != -1 (fisheye stereo), the Sim3 SearchByProjection forms and SearchBySim3 (the two functions
+ * that walk DBoW2 feature vectors are xfh_triangulation_search_device and xfh_bow_search_device below). */
 #define XFH_FUSE_MAX_LEVELS 16
 #define XFH_FUSE_FLAG_ACTIVE 1        /* d_query_flags bit0 */
 #define XFH_FUSE_CHI2 1               /* flags: the chi-square reprojection gates of the SE3 form */
@@ -638,8 +638,8 @@ int xfh_fuse_search(xfh_ctx* ctx, int nq, const float* points, const float* norm
  *                         or queued.
  * Out of scope: mbCheckOrientation and the rotation histogram (:1272-1318; the only caller builds ORBmatcher(0.6f, false),
  * LocalMapping.cc:412); fisheye stereo (mpCamera2, NLeft != -1, the four T12 variants of :1221-1255); KannalaBrandt8::epipolarConstrain;
- * computing F12 or the epipole; computing the feature vector (DBoW2); SearchByBoW, which has a real claim order and a ratio test; and the
- * triangulation itself. */
+ * computing F12 or the epipole; computing the feature vector (DBoW2); and the triangulation itself.  (SearchByBoW, which has a real claim
+ * order and a ratio test, is xfh_bow_search_device below.) */
 #define XFH_NODE_NONE 0xFFFFFFFFu     /* node_of: the keypoint is in no node of the feature vector */
 #define XFH_TRI_ONLY_STEREO 1         /* flags: bOnlyStereo */
 #define XFH_TRI_COARSE 2              /* flags: bCoarse */
@@ -659,6 +659,80 @@ int xfh_triangulation_search(xfh_ctx* ctx, int n1, int n2, int flags, int th_low
                              const float* uright1_or_null, const uint8_t* has1, const float* desc1, const uint32_t* node_of2, const float* xy2,
                              const float* uright2_or_null, const uint8_t* has2, const float* desc2, const float* F12, const float* ep, uint8_t* status,
                              int* match12, int* best_dist, int* n_candidates, int* n_geom, int* n_matches);
+
+/* ---- SearchByBoW over feature-vector nodes, device resident ------------------------------------------------------------------------------
+ * ORBmatcher::SearchByBoW, both overloads (src/ORBmatcher.cc): the frame form SearchByBoW(KeyFrame*, Frame&, vpMapPointMatches) (:408-610;
+ * Tracking::TrackReferenceKeyFrame, Tracking.cc:2759, and once per candidate keyframe from Tracking::Relocalization, Tracking.cc:3697) and
+ * the keyframe form SearchByBoW(KeyFrame*, KeyFrame*, vpMatches12) (:950-1090; LoopClosing.cc:662, the current keyframe against each
+ * covisible keyframe of a candidate), as one call for B problems.  Side 1 holds the queries (the keyframe whose map points are matched),
+ * side 2 the targets.  Both overloads walk the two feature vectors with the two-iterator / lower_bound loop, keep best and second best
+ * with the strict `<` / `else if <` update from 256, and let an accepted query CLAIM its target (vpMapPointMatches[realIdxF] is tested at
+ * :463 and written at :516 -- the vector is all NULL at :412, so only an earlier iteration of this call can have set it; vbMatched2 at :1011
+ * and :1038).  The claim makes the loop sequential, but only inside a node: a keypoint is in exactly one node (node_of[i] is a function of
+ * i), so a claim made while node A is walked is seen by later queries of node A only; nodes are independent, in any order, and inside a
+ * node the queries are resolved in stored (ascending index) order.  Node blobs: xfh_nodes_pack above.
+ *
+ * Per problem, the contract is this loop.  All integer comparisons are exact; the one float expression is fp32 in the order written (the
+ * library is built with -ffp-contract=off):
+ *
+ *   claimed[k] = 0 for all k
+ *   for every node id present on both sides; for the members i of side 1's node in stored order:
+ *       active1[i] == 0                              -> INACTIVE
+ *       best = second = init_dist; best_idx = -1; n_candidates = 0
+ *       for the members k of side 2's node in stored order:
+ *           eligible2 && eligible2[k] == 0 -> skip;  claimed[k] -> skip;  ++n_candidates
+ *           d = DescriptorDistance(row i, row k)
+ *           d < best ? (second = best, best = d, best_idx = k) : (d < second ? second = d : nothing)
+ *       accept = best_idx >= 0 && (STRICT_LOW ? best < th_low : best <= th_low) && (float)best < nn_ratio * (float)second
+ *       accept -> MATCHED, match12[i] = best_idx, assigned2[best_idx] = i, claimed[best_idx] = 1, ++n_matches
+ *       else   -> n_candidates == 0 ? NO_CANDIDATES : REJECTED
+ *
+ * An active query whose node is XFH_NODE_NONE or absent from side 2 is NO_NODE; an inactive query is INACTIVE whatever its node.  Among
+ * equal distances the member visited FIRST wins -- the opposite of the triangulation rule.  match12 is -1 unless MATCHED, best_dist and
+ * second_dist are init_dist where there is none, assigned2[k] is -1 for an unclaimed keypoint.
+ * The frame form is flags = 0, eligible2 = NULL, active1[i] = "pKF's map point i exists and is not bad" (:445), th_low = TH_LOW = 100
+ * (`bestDist1 <= TH_LOW`, :512), init_dist = 256, nn_ratio = mfNNratio; match12 / assigned2 are vpMapPointMatches seen from either side.
+ * The keyframe form is XFH_BOW_STRICT_LOW (`bestDist1 < TH_LOW`, :1033) with eligible2[k] = the same predicate on side 2 (:1009-1015);
+ * match12 is vpMatches12 by index.  The rotation histogram (:523-538 and :589-607, and its counterpart in the keyframe form) puts every match in bin 0, because every
+ * XFeat keypoint has angle -1 (the argument of the projection contract above): it removes nothing, and mbCheckOrientation stays without
+ * effect.
+ *
+ *   xfh_bow_accept        host, stateless, thread-safe: the `accept` line, 1 or 0.  The same source line as the kernel (bow_math.h).
+ *   xfh_bow_search_workspace_bytes   bytes of d_workspace for B problems (0 for sizes the call would refuse); n2 does not enter today.
+ *   xfh_bow_search_device   B problems with the same n1, n2, flags and scalars.  shared = 0: problem b reads its own two sides; 1: all
+ *                         problems read side 1 (blob, active1, rows) of problem 0 (LoopClosing: the current keyframe against its
+ *                         covisibles); 2: the same for side 2 (Relocalization: the candidates against one frame); the stride of the
+ *                         shared side's rows is ignored.  Per side and problem: the node blob (b * xfh_nodes_bytes(n) bytes in), the flag
+ *                         bytes (b * n in; d_eligible2 may be NULL) and descriptor rows b * desc_stride_bytes in.  Outputs are always
+ *                         d_status [B][n1] bytes, d_match12 / d_best_dist / d_second_dist / d_n_candidates [B][n1] ints, d_assigned2
+ *                         [B][n2] ints, d_n_matches [B] ints.  All pointers are device pointers; asynchronous on the ctx stream, no
+ *                         allocation, no host synchronisation: three memsets (n_matches, assigned2, the workspace counters) and two
+ *                         kernel launches; every data-dependent iteration count is decided on the device.  The first int[4] per problem
+ *                         of the workspace are counters (queries that needed a full re-search, queries resolved, nodes resolved, 0).
+ *                         XFH_ERR_INVALID_ARG before anything is queued: n1 or n2 outside 1 .. XFH_GRID_MAX_N, B outside 1 .. 65535,
+ *                         shared outside 0 .. 2, unknown flag bits, nn_ratio negative or not finite, th_low < 0, init_dist < 0, a NULL
+ *                         required pointer, misaligned pointers (16 bytes for descriptor rows, their strides, the blobs and the
+ *                         workspace, 4 for the int outputs).  Blobs may hold anything: every count, range and item read from one is
+ *                         clamped or checked before it indexes anything, so no access leaves the buffers the caller named; the results
+ *                         of the nodes such a blob misdescribes are unspecified, those of the others are the loop's.  The distance of a
+ *                         row that holds a NaN is not defined.
+ *   xfh_bow_search        host-pointer convenience form for ONE problem: packs both node blobs, stages the inputs and the workspace, runs
+ *                         the call and copies the results back.  XFH_ERR_INVALID_ARG for the device form's classes of error before
+ *                         anything is staged or queued.
+ * Out of scope: the Nleft != -1 branches (fisheye stereo); computing the BoW or feature vector (DBoW2 stays with the caller);
+ * the relocalisation and Sim3 SearchByProjection forms, SearchBySim3 and SearchForInitialization; the PnP and Sim3 solvers that consume
+ * the matches. */
+#define XFH_BOW_STRICT_LOW 1          /* flags: accept on best < th_low (the keyframe form) instead of best <= th_low */
+enum { XFH_BOW_INACTIVE = 0, XFH_BOW_NO_NODE = 1, XFH_BOW_NO_CANDIDATES = 2, XFH_BOW_REJECTED = 3, XFH_BOW_MATCHED = 4 };
+int xfh_bow_accept(int best_idx, int best, int second, int th_low, float nn_ratio, int flags);
+size_t xfh_bow_search_workspace_bytes(int n1, int n2, int B);
+int xfh_bow_search_device(xfh_ctx* ctx, int B, int n1, int n2, int shared, int flags, int init_dist, int th_low, float nn_ratio, const void* d_nodes1,
+                          const uint8_t* d_active1, const float* d_desc1, size_t desc1_stride_bytes, const void* d_nodes2,
+                          const uint8_t* d_eligible2_or_null, const float* d_desc2, size_t desc2_stride_bytes, void* d_workspace, uint8_t* d_status,
+                          int* d_match12, int* d_best_dist, int* d_second_dist, int* d_n_candidates, int* d_assigned2, int* d_n_matches);
+int xfh_bow_search(xfh_ctx* ctx, int n1, int n2, int flags, int init_dist, int th_low, float nn_ratio, const uint32_t* node_of1, const uint8_t* active1,
+                   const float* desc1, const uint32_t* node_of2, const uint8_t* eligible2_or_null, const float* desc2, uint8_t* status, int* match12,
+                   int* best_dist, int* second_dist, int* n_candidates, int* assigned2, int* n_matches);
 
 /* MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:329-403), batched over map points: group g observes the
  * descriptor rows indices[offsets[g] .. offsets[g+1]) of `table` (n_rows x 64).  Pairwise DescriptorDistance inside

@@ -29,7 +29,7 @@ ERR_EMPTY_IMAGE = 2
 ERR_NO_DEVICE = 7
 ERR_COMM = 11
 
-K = dict(NONE=0, MNN_GEMM=1, CONV_MFMA=2, CONV_DIRECT=3, NMS=4, SELECT=5, DESC=6, HEADS=7, DIST_I32=8, PREPROC=9, BEST2=10, DISTINCTIVE=11, MNN_GEMM_SEG=12, GRID_BUILD=13, SEARCH_WINDOW=14, FRAME_FINISH=15, PROJ_CANDIDATES=16, PROJ_RESOLVE=17, PROJ_COUNT=18, FUSE_SEARCH=19, TRIANGULATION_SEARCH=20)
+K = dict(NONE=0, MNN_GEMM=1, CONV_MFMA=2, CONV_DIRECT=3, NMS=4, SELECT=5, DESC=6, HEADS=7, DIST_I32=8, PREPROC=9, BEST2=10, DISTINCTIVE=11, MNN_GEMM_SEG=12, GRID_BUILD=13, SEARCH_WINDOW=14, FRAME_FINISH=15, PROJ_CANDIDATES=16, PROJ_RESOLVE=17, PROJ_COUNT=18, FUSE_SEARCH=19, TRIANGULATION_SEARCH=20, BOW_CANDIDATES=21, BOW_RESOLVE=22)
 T = dict(X=0, XSTAT=1, SKIP_POOL=2, FEATS=6, H1=8, K1H=9, RAW0=16, STAT0=48, SEL=80)
 
 
@@ -68,6 +68,8 @@ NODE_NONE = 0xFFFFFFFF
 TRI_ONLY_STEREO, TRI_COARSE = 1, 2
 TRI_INACTIVE, TRI_NO_NODE, TRI_NO_CANDIDATES, TRI_REJECTED, TRI_MATCHED = range(5)
 TRI_GATE_SKIPPED, TRI_GATE_REJECTED, TRI_GATE_PASSED = range(3)
+BOW_STRICT_LOW = 1
+BOW_INACTIVE, BOW_NO_NODE, BOW_NO_CANDIDATES, BOW_REJECTED, BOW_MATCHED = range(5)
 
 FLAG_RESCALE_KEYPOINTS = 1
 FLAG_SERIAL_BRANCH = 2
@@ -141,6 +143,10 @@ SYMBOLS = [
     ("xfh_triangulation_search_device", _i, [_vp, _i, _i, _i, _i, _i, _i, _f, _f, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp,
                                              _vp, _vp, _vp, _vp, _vp, _vp]),
     ("xfh_triangulation_search", _i, [_vp, _i, _i, _i, _i, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("xfh_bow_accept", _i, [_i, _i, _i, _i, _f, _i]),
+    ("xfh_bow_search_workspace_bytes", _sz, [_i, _i, _i]),
+    ("xfh_bow_search_device", _i, [_vp, _i, _i, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("xfh_bow_search", _i, [_vp, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("xfh_distinctive_csr", _i, [_vp, _vp, _i, _vp, _vp, _i, _vp, _vp]),
     ("xfh_distinctive_csr_device", _i, [_vp, _vp, _i, _vp, _vp, _i, _i, _vp, _vp]),
     ("xfh_comm_unique_id", _i, [_vp]),

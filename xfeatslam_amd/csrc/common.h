@@ -217,5 +217,7 @@ struct FuseArgs;
 hipError_t launch_fuse_search(xfh_ctx* c, const FuseArgs& a, int B);                  // fuse_search.hip.h
 struct TriArgs;
 hipError_t launch_triangulation_search(xfh_ctx* c, const TriArgs& a, int B);          // triangulation_search.hip.h
+struct BowArgs;
+hipError_t launch_bow_search(xfh_ctx* c, const BowArgs& a, int B);                    // bow_search.hip.h
 hipError_t launch_best2(xfh_ctx* c, const float* q, int nq, const float* tg, const int* offsets, const int* indices, int init_dist,
                         int* best_idx, int* best_dist, int* second_idx, int* second_dist);

@@ -20,6 +20,8 @@
 //   k_triangulation_search : ORBmatcher::SearchForTriangulation up to vMatches12, B keyframe pairs per launch: the node of every unmatched
 //                   keypoint looked up in the neighbour's feature vector, the stereo, epipole and epipolar gates, best candidate with the
 //                   reference's last-wins tie (triangulation_search.hip.h).
+//   k_bow_candidates / k_bow_resolve : both ORBmatcher::SearchByBoW overloads, B problems per call: per query the least members of its node, then
+//                   the reference's claim order resolved per node, one wave each, the claimed set in LDS (bow_search.hip.h).
 //   k_distinctive_csr : MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:329-403), one wave per map point.
 //
 // Numerics: normalised rows and the 64-term dot products are bit-identical to the oracle
@@ -99,6 +101,7 @@ hipError_t launch_best2(xfh_ctx* c, const float* q, int nq, const float* tg, con
 #include "projection_search.hip.h"
 #include "fuse_search.hip.h"
 #include "triangulation_search.hip.h"
+#include "bow_search.hip.h"
 
 // ---- k_distinctive_csr: MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:329-403), batched -------
 // One wave per group (map point).  Rows are taken 64 at a time, lane = row: the lane keeps its descriptor in

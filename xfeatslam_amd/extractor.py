@@ -507,6 +507,58 @@ class Context:
         r.update(status=st, n_matches=int(nm[0]))
         return r
 
+    # -- SearchByBoW over feature-vector nodes (xfh_bow_accept / xfh_bow_search*) ---------------------------------------------
+    BOW_OUT_INT = ("match12", "best_dist", "second_dist", "n_candidates")
+
+    @staticmethod
+    def bow_accept(best_idx: int, best: int, second: int, th_low: int, nn_ratio: float, flags: int = 0) -> bool:
+        """xfh_bow_accept (host): the acceptance line of SearchByBoW"""
+        return bool(lib().xfh_bow_accept(int(best_idx), int(best), int(second), int(th_low), float(nn_ratio), int(flags)))
+
+    @staticmethod
+    def bow_search_workspace_bytes(n1: int, n2: int, B: int = 1) -> int:
+        return int(lib().xfh_bow_search_workspace_bytes(n1, n2, B))
+
+    @staticmethod
+    def bow_search_layout(B: int, n1: int, n2: int, guard: int = 0):
+        """byte offsets of the outputs of bow_search_device inside one buffer (and its size under "bytes"); guard as in fuse_search_layout.
+        The workspace is a buffer of its own (bow_search_workspace_bytes)."""
+        al = lambda x: (x + 255) & ~255
+        o, off = {}, al(guard)
+        for name, nbytes in (("match12", 4 * B * n1), ("best_dist", 4 * B * n1), ("second_dist", 4 * B * n1), ("n_candidates", 4 * B * n1),
+                             ("assigned2", 4 * B * n2), ("n_matches", 4 * B), ("status", B * n1)):
+            o[name] = off; off += al(nbytes) + al(guard)
+        o["bytes"] = off
+        return o
+
+    def bow_search_device(self, B: int, n1: int, n2: int, shared: int, d_nodes1, d_active1, d_desc1, desc1_stride: int, d_nodes2, d_eligible2, d_desc2,
+                          desc2_stride: int, d_workspace, d_out, strict_low: bool = False, init_dist: int = 256, th_low: int = 100, nn_ratio: float = 0.6,
+                          guard: int = 0):
+        """xfh_bow_search_device on device pointers; asynchronous.  shared: 0 none, 1 side 1, 2 side 2.  d_out: pointer to the outputs laid
+        out as bow_search_layout(B, n1, n2, guard) says"""
+        o = self.bow_search_layout(B, n1, n2, guard)
+        check(lib().xfh_bow_search_device(self.h, B, n1, n2, int(shared), capi.BOW_STRICT_LOW if strict_low else 0, int(init_dist), int(th_low), float(nn_ratio),
+                                          d_nodes1, d_active1, d_desc1, desc1_stride, d_nodes2, d_eligible2, d_desc2, desc2_stride, d_workspace,
+                                          d_out + o["status"], *[d_out + o[k] for k in self.BOW_OUT_INT], d_out + o["assigned2"], d_out + o["n_matches"]), self.h)
+
+    def bow_search(self, node_of1, active1, desc1, node_of2, desc2, eligible2=None, strict_low: bool = False, init_dist: int = 256, th_low: int = 100,
+                   nn_ratio: float = 0.6):
+        """xfh_bow_search (host pointers, one problem) -> dict(status, match12, best_dist, second_dist, n_candidates, assigned2, n_matches)"""
+        f32 = lambda a: np.ascontiguousarray(a, np.float32)
+        no1, no2 = np.ascontiguousarray(node_of1, np.uint32), np.ascontiguousarray(node_of2, np.uint32)
+        d1, d2 = f32(desc1), f32(desc2)
+        a1 = np.ascontiguousarray(active1, np.uint8)
+        e2 = None if eligible2 is None else np.ascontiguousarray(eligible2, np.uint8)
+        n1, n2 = len(no1), len(no2)
+        assert len(a1) == n1 and len(d1) == n1 and len(d2) == n2 and (e2 is None or len(e2) == n2)
+        st = np.zeros(n1, np.uint8); oi = [np.zeros(n1, np.int32) for _ in range(4)]; as2 = np.zeros(n2, np.int32); nm = np.zeros(1, np.int32)
+        check(lib().xfh_bow_search(self.h, n1, n2, capi.BOW_STRICT_LOW if strict_low else 0, int(init_dist), int(th_low), float(nn_ratio), no1.ctypes.data,
+                                   a1.ctypes.data, d1.ctypes.data, no2.ctypes.data, None if e2 is None else e2.ctypes.data, d2.ctypes.data, st.ctypes.data,
+                                   *[o.ctypes.data for o in oi], as2.ctypes.data, nm.ctypes.data), self.h)
+        r = dict(zip(self.BOW_OUT_INT, oi))
+        r.update(status=st, assigned2=as2, n_matches=int(nm[0]))
+        return r
+
     # -- timing ---------------------------------------------------------------------------
     def timing_enable(self, kernel_id: int, layer_mask: int = 0):
         check(lib().xfh_timing_enable(self.h, kernel_id, layer_mask), self.h)
@@ -605,6 +657,22 @@ class ORBmatcher:
                                           epipole_r2=float(np.float32(100) * np.float32(scale_factor0)), unc=level_sigma2_0)
         m = r["match12"]
         return r["n_matches"], [(int(i), int(m[i])) for i in np.nonzero(m >= 0)[0]], r
+
+    def search_by_bow(self, node_of1, has1, desc1, node_of2, desc2):
+        """`ORBmatcher::SearchByBoW(KeyFrame*, Frame&, vpMapPointMatches)` (ORBmatcher.cc:408-610): side 1 = the keyframe (has1[i] != 0 where
+        its map point i exists and is not bad), side 2 = the frame.  The rotation histogram removes nothing (every XFeat angle is -1).
+        -> (nmatches, match12 = per keyframe keypoint the frame keypoint or -1, result dict of Context.bow_search; its assigned2 is
+        vpMapPointMatches by frame keypoint)"""
+        r = self.ctx.bow_search(node_of1, has1, desc1, node_of2, desc2, eligible2=None, strict_low=False, init_dist=256, th_low=self.TH_LOW,
+                                nn_ratio=self.mfNNratio)
+        return r["n_matches"], r["match12"], r
+
+    def search_by_bow_keyframes(self, node_of1, has1, desc1, node_of2, has2, desc2):
+        """`ORBmatcher::SearchByBoW(KeyFrame*, KeyFrame*, vpMatches12)` (ORBmatcher.cc:950-1090): both sides need a good map point and the
+        threshold is strict.  -> (nmatches, match12 = vpMatches12 by index, result dict of Context.bow_search)"""
+        r = self.ctx.bow_search(node_of1, has1, desc1, node_of2, desc2, eligible2=has2, strict_low=True, init_dist=256, th_low=self.TH_LOW,
+                                nn_ratio=self.mfNNratio)
+        return r["n_matches"], r["match12"], r
 
     def match(self, desc1: np.ndarray, desc2: np.ndarray, min_cossim: float = -1.0):
         """-> list of (queryIdx, trainIdx, distance) like std::vector<cv::DMatch>"""
