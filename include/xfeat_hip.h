@@ -10,6 +10,21 @@
  * per GPU for multi-GPU use.  xfh_descriptor_distance is stateless and thread-safe like
  * the static ORBmatcher::DescriptorDistance.
  *
+ * Threads (each of the three points is tested; INTEGRATION.md section 4 names the tests):
+ *   - several ctx may be driven from several host threads at the same time, one thread per
+ *     ctx -- the way Tracking, LocalMapping and LoopClosing run beside each other
+ *     (System.cc:197,214,233) -- also when all of them are inside the SAME entry point;
+ *   - a ctx may be handed from one thread to another (System constructs the extractor on
+ *     one thread, Tracking calls it from another): one caller at a time, not always the
+ *     same thread.  Two threads inside ONE ctx at the same time are outside the contract;
+ *   - pure host code, stateless, callable from any thread at any time, the first call of
+ *     the process included: xfh_version, xfh_strerror, xfh_kernel_name, xfh_config_default,
+ *     xfh_descriptor_distance, xfh_undistort_points, xfh_camera_bounds, xfh_project_points,
+ *     xfh_scale_level_thresholds, xfh_fuse_project, xfh_epipolar_gate, xfh_bow_accept,
+ *     xfh_nodes_pack, xfh_nodes_unpack, xfh_grid_unpack and the size / layout helpers
+ *     (xfh_record_*, xfh_*_bytes, xfh_compact_bytes_max); xfh_create itself may run on
+ *     several threads at once (without a device each call returns XFH_ERR_NO_DEVICE).
+ *
  * The C++ wrappers that restore the reference's class surface on top of this ABI are
  * include/xfeat/XFextractor.h and include/xfeat/ORBmatcher_xfeat.h; INTEGRATION.md shows
  * the edits a maintainer makes in the reference tree.

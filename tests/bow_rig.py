@@ -12,6 +12,8 @@ side-1 sizes are 1, 64, 65 and 135 among others.  Planted on purpose, with the q
               claimed entries ahead (with nn_ratio = 1.5, where every one of them is accepted)
   duplicates  pairs of identical target rows at about 10 from their query
 The problems of a batch: side-1 block p is block 0 rotated by p * ROLL places with its own active bytes.  No test lives here."""
+import struct
+
 import numpy as np
 
 import ref_bow as RB
@@ -139,6 +141,16 @@ class Scene:
         a, k = self.want(O, 0, 0, False), self.want(O, 0, 0, True)
         both = np.nonzero((a["status"] == RB.MATCHED) & (k["status"] == RB.MATCHED) & (a["best_dist"] == k["best_dist"]) & (a["best_dist"] >= 40))[0]
         return int(a["best_dist"][both].max())
+
+
+def write_in(path, s1, s2, keyframe, ratio):
+    """the in.bin of tests/cpp/bow_test.cpp (and of tests/cpp/threads_test.cpp) for one problem: side 1 with its active bytes, side 2 with its
+    has-a-map-point bytes"""
+    with open(path, "wb") as f:
+        f.write(struct.pack("<4if", len(s1["node_of"]), len(s2["node_of"]), int(keyframe), 0, ratio))
+        for k, flag in ((s1, "active"), (s2, "has")):
+            for a in (k["desc"].astype(F), k["node_of"].astype(np.uint32), k[flag].astype(np.uint8)):
+                f.write(np.ascontiguousarray(a).tobytes())
 
 
 class BowRig:

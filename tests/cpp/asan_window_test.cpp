@@ -7,23 +7,20 @@
 #include <vector>
 #include "xfeat_hip.h"
 #include "xfeat_hip_bench.h"
+#include "grid_blob.h"
 
 #define CHECK(x) do { if (!(x)) { fprintf(stderr, "asan_window_test: %s failed (line %d)\n", #x, __LINE__); return 1; } } while (0)
 
 static const int CELLS = XFH_GRID_COLS * XFH_GRID_ROWS;
-static const size_t CS_OFF = 64, ITEMS_OFF = 12416;
+static const size_t CS_OFF = XFH_GRID_CS_OFF, ITEMS_OFF = XFH_GRID_ITEMS_OFF;
 
 int main() {
     CHECK(xfh_grid_bytes(0) == ITEMS_OFF && xfh_grid_bytes(-1) == 0 && xfh_grid_bytes(XFH_GRID_MAX_N) == ITEMS_OFF + 16 * (size_t)XFH_GRID_MAX_N);
     CHECK(strcmp(xfh_kernel_name(XFH_K_GRID_BUILD), "k_grid_build") == 0 && strcmp(xfh_kernel_name(XFH_K_SEARCH_WINDOW), "k_search_window") == 0);
     // a well-formed blob of n = 8 slots: slots 5, 2 in cell 0, slot 7 in cell 49, slot 0 in the last cell; 4 slots not binned
-    const int n = 8;
-    std::vector<unsigned char> blob(xfh_grid_bytes(n), 0);
-    int* h = (int*)blob.data(); int* cs = (int*)(blob.data() + CS_OFF); int* it = (int*)(blob.data() + ITEMS_OFF);
-    h[0] = 0x31474658; h[1] = n; h[2] = 4;
-    for (int c = 1; c <= CELLS; ++c) cs[c] = c <= 49 ? 2 : (c < CELLS ? 3 : 4);
-    const int slots[8] = {2, 5, 7, 0, -1, -1, -1, -1};
-    for (int k = 0; k < n; ++k) it[4 * k] = slots[k];
+    const int n = GRID_BLOB_N;
+    std::vector<unsigned char> blob = example_grid_blob();
+    CHECK(blob.size() == xfh_grid_bytes(n));
     std::vector<int> ocs(CELLS + 1), oit(n);
     int nb = -1;
     CHECK(xfh_grid_unpack(blob.data(), blob.size(), n, ocs.data(), oit.data(), &nb) == XFH_OK && nb == 4);

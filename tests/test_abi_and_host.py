@@ -161,6 +161,24 @@ def test_host_code_under_sanitizers(tmp_path):
     assert r.returncode == 0 and "asan_host_test ok" in r.stdout, r.stderr[-3000:]
 
 
+def test_host_entry_points_under_thread_sanitizer(tmp_path):
+    """the entry points the headers call "host, stateless, thread-safe" (include/xfeat_hip.h), entered by eight threads
+    at the same moment, the first call of the process included: libxfeat_hip's HOST code built with ThreadSanitizer (make -C xfeatslam_amd/csrc
+    tsan; device code is not instrumented) and tests/cpp/tsan_host_test.cpp, a stand-alone program compiled the same way.  Every pass of every
+    thread equals a serial pass byte for byte, xfh_create without a device returns XFH_ERR_NO_DEVICE on every thread, and halt_on_error turns any
+    ThreadSanitizer report into a non-zero exit.  No suppressions.  Host code on a machine without a GPU only: the program expects to find no device."""
+    if capi.lib().xfh_device_count() > 0:
+        pytest.skip("a GPU is present: the sanitizer build never runs next to a device")
+    subprocess.check_call(["make", "-C", os.path.join(ROOT, "xfeatslam_amd", "csrc"), "tsan", "-s", "-j8"])
+    exe = str(tmp_path / "tsan_host_test")
+    subprocess.check_call(["/opt/rocm/lib/llvm/bin/clang++", "-std=c++17", "-O1", "-g", "-fsanitize=thread", "-pthread", "-I" + os.path.join(ROOT, "include"),
+                           os.path.join(ROOT, "tests", "cpp", "tsan_host_test.cpp"), "-L" + os.path.join(ROOT, "xfeatslam_amd"), "-lxfeat_hip_tsan",
+                           "-Wl,-rpath," + os.path.join(ROOT, "xfeatslam_amd"), "-Wl,-rpath,/opt/rocm/lib", "-o", exe])
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=600, env=dict(os.environ, TSAN_OPTIONS="halt_on_error=1"))
+    print(r.stdout.strip())
+    assert r.returncode == 0 and "tsan_host_test ok" in r.stdout and "ThreadSanitizer" not in r.stderr, (r.returncode, r.stderr[-3000:])
+
+
 def test_convert_weights_tool(tmp_path):
     import torch
     w = WT.make_synthetic(99)

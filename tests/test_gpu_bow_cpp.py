@@ -3,7 +3,6 @@ device-resident sides (the descriptor blocks of records, uploaded node blobs and
 with g++ like the other drop-in classes: both produce the dump of the C ABI (xfh_bow_search) for the rig's scene written to a file, and
 that dump is the restatement's answer (tests/ref_bow.py): matchOfQuery, assignedQuery, the return value and the last...() arrays."""
 import os
-import struct
 import subprocess
 
 import numpy as np
@@ -40,11 +39,8 @@ def exe(tmp_path_factory):
 def test_cpp_search_by_bow(scene, oracle_mod, tmp_path, exe, b, keyframe, ratio):
     s1, s2 = scene.s1, scene.s2[b]
     n1, n2 = BR.N1, BR.N2
-    with open(tmp_path / "in.bin", "wb") as f:
-        f.write(struct.pack("<4if", n1, n2, int(keyframe), 0, ratio))
-        for k, flag in ((s1, "active"), (s2, "has")):
-            for a in (k["desc"].astype(F), k["node_of"].astype(np.uint32), k[flag].astype(np.uint8)):
-                f.write(np.ascontiguousarray(a).tobytes())
+    assert (len(s1["node_of"]), len(s2["node_of"])) == (n1, n2)
+    BR.write_in(tmp_path / "in.bin", s1, s2, keyframe, ratio)
     r = subprocess.run([exe, str(tmp_path / "in.bin"), str(tmp_path / "out.bin")], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, (r.returncode, r.stderr)
     raw = np.fromfile(tmp_path / "out.bin", np.int32)

@@ -3,7 +3,6 @@ the form on device-resident keyframes (records finished by XFgrid::buildFromReco
 drop-in classes: both produce the dump of the C ABI (xfh_triangulation_search) for the rig's scene written to a file, and that dump is the
 restatement's answer (tests/ref_triangulation.py): vMatchedPairs in ascending idx1, the return value and the last...() arrays."""
 import os
-import struct
 import subprocess
 
 import numpy as np
@@ -26,14 +25,7 @@ def gxx(src, exe, *libs):
                            "-Wl,-rpath,/opt/rocm/lib", "-o", exe])
 
 
-def rgbd(cam, k):
-    """the keyframe as the RGB-D constructor sees it: a depth image that holds the scene's depth under every stereo keypoint, and mvuRight
-    recomputed FROM that image (ComputeStereoFromRGBD), so that the host arrays and the device's own are the same numbers"""
-    img = np.zeros((int(cam["height"]), int(cam["width"])), F)
-    for (x, y), ur in zip(k["xy"], k["ur"]):
-        if ur >= 0 and 0 <= int(x) < img.shape[1] and 0 <= int(y) < img.shape[0] and x > ur:
-            img[int(y), int(x)] = F(cam["bf"]) / (F(x) - F(ur))
-    return dict(k, ur=RF.stereo(cam, k["xy"], k["xy"], img)[1]), img
+rgbd = TR.rgbd
 
 
 @pytest.fixture(scope="module")
@@ -49,14 +41,8 @@ def test_cpp_search_for_triangulation(scene, oracle_mod, tmp_path, b, flags):
     (k1, img1), (k2, img2) = rgbd(cam, scene.k1), rgbd(cam, scene.k2[b])
     assert (k1["ur"] >= 0).sum() >= 60 and (k2["ur"] >= 0).sum() >= 100
     n1, n2 = TR.N1, TR.N2
-    with open(tmp_path / "in.bin", "wb") as f:
-        f.write(struct.pack("<4i", n1, n2, flags, 0))
-        f.write(struct.pack("<10f6i", *[float(cam[c]) for c in "fx fy cx cy k1 k2 p1 p2 k3 bf".split()], int(cam["width"]), int(cam["height"]), 0, 0, 0, 0))
-        f.write(scene.F12[b].astype(F).tobytes()); f.write(scene.ep[b].astype(F).tobytes())
-        for k, img in ((k1, img1), (k2, img2)):
-            kp = np.zeros(len(k["xy"]), capi.KP_DTYPE); kp["x"] = k["xy"][:, 0]; kp["y"] = k["xy"][:, 1]; kp["size"] = 1; kp["angle"] = -1
-            for a in (kp, k["desc"].astype(F), k["ur"].astype(F), k["has"].astype(np.uint8), k["node_of"].astype(np.uint32), img):
-                f.write(np.ascontiguousarray(a).tobytes())
+    assert (len(k1["xy"]), len(k2["xy"])) == (n1, n2)
+    TR.write_in(tmp_path / "in.bin", cam, k1, img1, k2, img2, scene.F12[b], scene.ep[b], flags)
     r = subprocess.run([exe, str(tmp_path / "in.bin"), str(tmp_path / "out.bin")], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, (r.returncode, r.stderr)
     raw = np.fromfile(tmp_path / "out.bin", np.int32)

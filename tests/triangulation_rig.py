@@ -6,8 +6,11 @@ vocabulary nodes with the sizes the kernel can go wrong at (1, 63, 64, 65, 150 m
 keypoints in no node.  Planted on purpose: duplicate rows (a tie the LATER member must win), exact copies of the query row far off the
 epipolar line (the nearest candidate fails the gate), monocular and stereo keypoints within the epipole radius.  F12 and the epipole
 are computed in float64 and rounded once.  No test lives here."""
+import struct
+
 import numpy as np
 
+import ref_frame as RF
 import ref_triangulation as RT
 from xfeatslam_amd import capi
 from xfeatslam_amd.extractor import Context
@@ -135,6 +138,28 @@ class Scene:
 
 def mono(k):
     return dict(k, ur=None)
+
+
+def rgbd(cam, k):
+    """the keyframe as the RGB-D constructor sees it: a depth image that holds the scene's depth under every stereo keypoint, and mvuRight
+    recomputed FROM that image (ComputeStereoFromRGBD), so that the host arrays and the device's own are the same numbers"""
+    img = np.zeros((int(cam["height"]), int(cam["width"])), F)
+    for (x, y), ur in zip(k["xy"], k["ur"]):
+        if ur >= 0 and 0 <= int(x) < img.shape[1] and 0 <= int(y) < img.shape[0] and x > ur:
+            img[int(y), int(x)] = F(cam["bf"]) / (F(x) - F(ur))
+    return dict(k, ur=RF.stereo(cam, k["xy"], k["xy"], img)[1]), img
+
+
+def write_in(path, cam, k1, img1, k2, img2, F12, ep, flags):
+    """the in.bin of tests/cpp/triangulation_test.cpp (and of tests/cpp/threads_test.cpp) for one keyframe pair from rgbd()"""
+    with open(path, "wb") as f:
+        f.write(struct.pack("<4i", len(k1["xy"]), len(k2["xy"]), flags, 0))
+        f.write(struct.pack("<10f6i", *[float(cam[c]) for c in "fx fy cx cy k1 k2 p1 p2 k3 bf".split()], int(cam["width"]), int(cam["height"]), 0, 0, 0, 0))
+        f.write(np.asarray(F12).astype(F).tobytes()); f.write(np.asarray(ep).astype(F).tobytes())
+        for k, img in ((k1, img1), (k2, img2)):
+            kp = np.zeros(len(k["xy"]), capi.KP_DTYPE); kp["x"] = k["xy"][:, 0]; kp["y"] = k["xy"][:, 1]; kp["size"] = 1; kp["angle"] = -1
+            for a in (kp, k["desc"].astype(F), k["ur"].astype(F), k["has"].astype(np.uint8), k["node_of"].astype(np.uint32), img):
+                f.write(np.ascontiguousarray(a).tobytes())
 
 
 class TriRig:
