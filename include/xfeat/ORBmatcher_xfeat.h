@@ -14,6 +14,10 @@
  *        and of the SearchLocalPoints form (:42-141): projection, cull, windowed best two and the reference's claim order in one call
  *   XFmatcher::fuse / searchForTriangulation: the two matchers of LocalMapping, ORBmatcher::Fuse (ORBmatcher.cc:1333-1640) up to the map
  *        bookkeeping and ORBmatcher::SearchForTriangulation (:1092-1331) over the nodes of the DBoW2 feature vectors, each as one call
+ *   XFmatcher::searchByProjection(Sim3Form / RelocForm, ...) / searchBySim3: the matchers of LoopClosing and Tracking::Relocalization, the Sim3
+ *        forms of SearchByProjection (ORBmatcher.cc:612-717, :719-831), the relocalisation form (:2074-2195) and SearchBySim3 (:1642-1859), each
+ *        as one call.  The caller keeps what needs Sophus or the map: the decomposition of Scw into Tcw = [R | t/s] and Ow (:621-622), S12 and its
+ *        inverse as 3x4 [s*R | t], vbAlreadyMatched (:1662-1675, folded into the flag bytes) and the pointer writes behind the matches
  *   best2 / distinctive: the batched inner loops of SearchBy* (ORBmatcher.cc:75-119) and of
  *        MapPoint::ComputeDistinctiveDescriptors (MapPoint.cc:329-403)
  *
@@ -492,12 +496,7 @@ public:
         const int nt = grid.size(), nl = (int)scaleFactors.size();
         bestIdx.assign(nq > 0 ? nq : 0, -1);
         if (nq <= 0 || nt <= 0) return 0;
-        if (nl < 1 || nl > XFH_FUSE_MAX_LEVELS) throw std::runtime_error("XFmatcher::fuse: 1 .. XFH_FUSE_MAX_LEVELS scale factors");
-        if (fuseRatioMax.size() + 1 != (size_t)nl || fuseScale != (nl > 1 ? scaleFactors[1] : 0.f)) {           // the table of this pyramid, once
-            fuseRatioMax.assign(nl - 1, 0.f);
-            if (nl > 1 && xfh_scale_level_thresholds(scaleFactors[1], nl, fuseRatioMax.data()) != XFH_OK) throw std::runtime_error("XFmatcher::fuse: scale factor must be > 1");
-            fuseScale = nl > 1 ? scaleFactors[1] : 0.f;
-        }
+        levelTable(scaleFactors, "XFmatcher::fuse");
         auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
         const size_t bn = al((size_t)nq * 4), bs = al((size_t)nq);
         reserve(d_proj, d_proj_bytes, 5 * bn + bs + 256, "XFmatcher::fuse");
@@ -524,6 +523,152 @@ public:
     const std::vector<int>& lastFuseWindow() const { return fuseWindow; }
     const std::vector<int>& lastFuseTested() const { return fuseTested; }
     const std::vector<int>& lastFuseLevel() const { return fuseLevel; }
+
+    // The map-point forms of SearchByProjection, which claim keypoints in query order (xfh_map_projection_search_device), each as ONE call.
+    //   Sim3Form{ratioHamming, withKeyFrames}: ORBmatcher::SearchByProjection(KeyFrame*, Sim3f& Scw, vpPoints, vpMatched, th, ratioHamming)
+    //       (ORBmatcher.cc:612-717; withKeyFrames: the form of :719-831 with vpPointsKFs / vpMatchedKF), called from LoopClosing.  Tcw = [R | t/s]
+    //       and Ow come from the caller's decomposition of Scw (:621-622).
+    //   RelocForm{ORBdist}: ORBmatcher::SearchByProjection(Frame& CurrentFrame, KeyFrame*, sAlreadyFound, th, ORBdist) (:2074-2195), called from
+    //       Tracking::Relocalization: the candidate keyframe's map points in keypoint order; Tcw / Ow are the frame's pose and camera centre
+    //       (:2078-2079).  normals are not read by this form.  mbCheckOrientation stays without effect: every XFeat angle is -1.
+    // Query q is map point q of the reference's loop: row q of `queries` (pMP->GetDescriptor()), worldPoints / normals / distances as in fuse(),
+    // flags[q] bit0 = `!pMP->isBad() && !spAlreadyFound.count(pMP)` (with `pMP &&` in the relocalisation form).  `grid` / `targets` are the
+    // keyframe's resp. the current frame's; taken[k] != 0 where vpMatched[k] resp. mvpMapPoints[k] is set before the call (nullptr: none).
+    // matchOfQuery[q] = the keypoint query q claimed or -1; assignedQuery[k] = the query that claimed keypoint k or -1 -- the caller writes
+    // vpMatched[k] = vpPoints[assignedQuery[k]] (and vpMatchedKF[k] = vpPointsKFs[assignedQuery[k]]) resp. mvpMapPoints[k]; the return value is
+    // nmatches.  Blocks until the result is on the host.
+    struct Sim3Form { float ratioHamming = 1.0f; bool withKeyFrames = false; };
+    struct RelocForm { int ORBdist = TH_LOW; };
+    int searchByProjection(const Sim3Form& form, const Mat& queries, const std::vector<float>& worldPoints, const std::vector<float>& normals,
+                           const std::vector<float>& distances, const std::vector<unsigned char>& flags, const float* Tcw, const float* Ow, const xfh_camera& cam,
+                           const xfh_grid_bounds& bounds, float th, const std::vector<float>& scaleFactors, const XFgrid& grid, const Mat& targets,
+                           std::vector<int>& matchOfQuery, std::vector<int>& assignedQuery, const std::vector<unsigned char>* taken = nullptr) {
+        return mapProjectionHost(form.withKeyFrames ? XFH_MAPPROJ_FORM_SIM3_KF : XFH_MAPPROJ_FORM_SIM3, (float)TH_LOW * form.ratioHamming, queries, worldPoints, normals,
+                                 distances, flags, Tcw, Ow, cam, bounds, th, scaleFactors, grid, targets, matchOfQuery, assignedQuery, taken);
+    }
+    int searchByProjection(const RelocForm& form, const Mat& queries, const std::vector<float>& worldPoints, const std::vector<float>& normals,
+                           const std::vector<float>& distances, const std::vector<unsigned char>& flags, const float* Tcw, const float* Ow, const xfh_camera& cam,
+                           const xfh_grid_bounds& bounds, float th, const std::vector<float>& scaleFactors, const XFgrid& grid, const Mat& targets,
+                           std::vector<int>& matchOfQuery, std::vector<int>& assignedQuery, const std::vector<unsigned char>* taken = nullptr) {
+        return mapProjectionHost(XFH_MAPPROJ_FORM_RELOC, (float)form.ORBdist, queries, worldPoints, normals, distances, flags, Tcw, Ow, cam, bounds, th, scaleFactors,
+                                 grid, targets, matchOfQuery, assignedQuery, taken);
+    }
+    // The same on DEVICE pointers and an XFgrid (a frame or keyframe finished with XFgrid::buildFromRecord: d_targets = the record's descriptor
+    // block).  Only the results travel to the host.
+    int searchByProjection(const Sim3Form& form, int nq, const float* d_points, const float* d_normals, const float* d_distances, const float* d_queries,
+                           const unsigned char* d_flags, const float* d_Tcw, const float* d_Ow, const xfh_camera& cam, const xfh_grid_bounds& bounds, float th,
+                           const std::vector<float>& scaleFactors, const XFgrid& grid, const float* d_targets, const unsigned char* d_taken,
+                           std::vector<int>& matchOfQuery, std::vector<int>& assignedQuery) {
+        return mapProjection(form.withKeyFrames ? XFH_MAPPROJ_FORM_SIM3_KF : XFH_MAPPROJ_FORM_SIM3, (float)TH_LOW * form.ratioHamming, nq, d_points, d_normals, d_distances,
+                             d_queries, d_flags, d_Tcw, d_Ow, cam, bounds, th, scaleFactors, grid, d_targets, d_taken, matchOfQuery, assignedQuery);
+    }
+    int searchByProjection(const RelocForm& form, int nq, const float* d_points, const float* d_normals, const float* d_distances, const float* d_queries,
+                           const unsigned char* d_flags, const float* d_Tcw, const float* d_Ow, const xfh_camera& cam, const xfh_grid_bounds& bounds, float th,
+                           const std::vector<float>& scaleFactors, const XFgrid& grid, const float* d_targets, const unsigned char* d_taken,
+                           std::vector<int>& matchOfQuery, std::vector<int>& assignedQuery) {
+        return mapProjection(XFH_MAPPROJ_FORM_RELOC, (float)form.ORBdist, nq, d_points, d_normals, d_distances, d_queries, d_flags, d_Tcw, d_Ow, cam, bounds, th,
+                             scaleFactors, grid, d_targets, d_taken, matchOfQuery, assignedQuery);
+    }
+    // per query, of the last map-point searchByProjection: XFH_MAPPROJ_* status, best DescriptorDistance, window members, candidates compared
+    // when the query's turn came, predicted level
+    const std::vector<unsigned char>& lastMapProjectionStatus() const { return mapStatus; }
+    const std::vector<int>& lastMapProjectionBestDist() const { return mapBest; }
+    const std::vector<int>& lastMapProjectionWindow() const { return mapWindow; }
+    const std::vector<int>& lastMapProjectionTested() const { return mapTested; }
+    const std::vector<int>& lastMapProjectionLevel() const { return mapLevel; }
+
+    // ORBmatcher::SearchBySim3(pKF1, pKF2, vpMatches12, S12, th) (ORBmatcher.cc:1642-1859; no call site in the reference's LoopClosing.cc) as ONE call
+    // (xfh_sim3_search): the map points of
+    // each keyframe projected into the other through S21 / S12 and searched, then the agreement step.  Per keyframe: keysUn = mvKeysUn, desc =
+    // mDescriptors, and per keypoint i the map point it holds: points[3i ..] = GetWorldPos(), distances[3i ..] = (GetMinDistanceInvariance(),
+    // GetMaxDistanceInvariance(), mfMaxDistance), row i of mpDesc = pMP->GetDescriptor(), flags[i] bit0 = `pMP && !vbAlreadyMatched[i] &&
+    // !pMP->isBad()` with vbAlreadyMatched as :1662-1675 compute it; Tw = the keyframe's pose (row-major 3x4).  M21 / M12 = the row-major 3x4
+    // [s*R | t] of S12.inverse() and S12 (the caller's Sophus).  cam: pKF1's intrinsics serve both directions (:1644-1647).
+    // match12[i1] = the keypoint of keyframe 2 or -1: the caller writes vpMatches12[i1] = vpMapPoints2[match12[i1]] (:1852); the return value is
+    // nFound.  Blocks until the result is on the host.
+    struct Sim3KeyFrame {
+        const std::vector<XFgrid::KeyPoint>* keysUn; const Mat* desc; const std::vector<float>* points; const std::vector<float>* distances; const Mat* mpDesc;
+        const std::vector<unsigned char>* flags; const float* Tw;
+    };
+    int searchBySim3(const Sim3KeyFrame& kf1, const Sim3KeyFrame& kf2, const float* M21, const float* M12, const xfh_camera& cam, const xfh_grid_bounds& bounds,
+                     float th, const std::vector<float>& scaleFactors, std::vector<int>& match12) {
+        const Sim3KeyFrame* kf[2] = {&kf1, &kf2};
+        xfh_sim3_side side[2];
+        int n[2];
+        for (int s = 0; s < 2; ++s) {
+            const Sim3KeyFrame& k = *kf[s];
+            if (!k.keysUn || !k.desc || !k.points || !k.distances || !k.mpDesc || !k.flags || !k.Tw) throw std::runtime_error("XFmatcher::searchBySim3: a keyframe is incomplete");
+            n[s] = (int)k.keysUn->size();
+            if (k.desc->rows != n[s] || k.mpDesc->rows != n[s] || (int)k.points->size() != 3 * n[s] || (int)k.distances->size() != 3 * n[s] || (int)k.flags->size() != n[s])
+                throw std::runtime_error("XFmatcher::searchBySim3: sizes do not fit");
+            sim3Reset(s, n[s]);
+        }
+        match12.assign(n[0], -1);
+        if (n[0] == 0 || n[1] == 0) return 0;
+        if (!M21 || !M12) throw std::runtime_error("XFmatcher::searchBySim3: sizes do not fit");
+        levelTable(scaleFactors, "XFmatcher::searchBySim3");
+        for (int s = 0; s < 2; ++s) {
+            const Sim3KeyFrame& k = *kf[s];
+            side[s] = xfh_sim3_side{n[s], nullptr, (const xfh_keypoint*)k.keysUn->data(), k.desc->template ptr<float>(0), 0, k.points->data(), k.distances->data(),
+                                    k.mpDesc->template ptr<float>(0), k.flags->data(), k.Tw, sim3Status[s].data(), sim3Match[s].data(), sim3Best[s].data(),
+                                    sim3Window[s].data(), sim3Tested[s].data(), sim3Level[s].data(), nullptr};
+        }
+        int nfound = 0;
+        const int rc = xfh_sim3_search(ctx, &side[0], &side[1], M21, M12, &cam, &bounds, th, scaleFactors.data(), fuseRatioMax.data(), (int)scaleFactors.size(), TH_HIGH,
+                                       match12.data(), &nfound);
+        if (rc != XFH_OK) throw std::runtime_error(std::string("XFmatcher::searchBySim3: ") + xfh_strerror(rc));
+        return nfound;
+    }
+    // The same on two keyframes that live in device memory: their XFgrids (built from mvKeysUn), the records' descriptor blocks and the map-point
+    // arrays, poses and M21 / M12 as device pointers.  Only the results travel back.
+    struct Sim3KeyFrameDevice {
+        const XFgrid* grid; const float* d_desc; const float* d_points; const float* d_distances; const float* d_mpDesc; const unsigned char* d_flags; const float* d_Tw;
+    };
+    int searchBySim3(const Sim3KeyFrameDevice& kf1, const Sim3KeyFrameDevice& kf2, const float* d_M21, const float* d_M12, const xfh_camera& cam,
+                     const xfh_grid_bounds& bounds, float th, const std::vector<float>& scaleFactors, std::vector<int>& match12) {
+        const Sim3KeyFrameDevice* kf[2] = {&kf1, &kf2};
+        if (!kf1.grid || !kf2.grid) throw std::runtime_error("XFmatcher::searchBySim3: a keyframe is incomplete");
+        const int n[2] = {kf1.grid->size(), kf2.grid->size()};
+        for (int s = 0; s < 2; ++s) sim3Reset(s, n[s] > 0 ? n[s] : 0);
+        match12.assign(n[0] > 0 ? n[0] : 0, -1);
+        if (n[0] <= 0 || n[1] <= 0) return 0;
+        levelTable(scaleFactors, "XFmatcher::searchBySim3");
+        auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+        size_t total = al((size_t)n[0] * 4) + 256;
+        for (int s = 0; s < 2; ++s) total += 5 * al((size_t)n[s] * 4) + al((size_t)n[s]);
+        reserve(d_proj, d_proj_bytes, total, "XFmatcher::searchBySim3");
+        char* p = (char*)d_proj;
+        int* o[2][5]; unsigned char* dst[2];
+        xfh_sim3_side side[2];
+        for (int s = 0; s < 2; ++s) {
+            for (int k = 0; k < 5; ++k) { o[s][k] = (int*)p; p += al((size_t)n[s] * 4); }
+            dst[s] = (unsigned char*)p; p += al((size_t)n[s]);
+            side[s] = xfh_sim3_side{n[s], kf[s]->grid->device(), nullptr, kf[s]->d_desc, 0, kf[s]->d_points, kf[s]->d_distances, kf[s]->d_mpDesc, kf[s]->d_flags, kf[s]->d_Tw,
+                                    dst[s], o[s][0], o[s][1], o[s][2], o[s][3], o[s][4], nullptr};
+        }
+        int* dm12 = (int*)p; p += al((size_t)n[0] * 4); int* dnf = (int*)p;
+        int rc = xfh_sim3_search_device(ctx, 1, 0, &side[0], &side[1], d_M21, d_M12, &cam, &bounds, th, scaleFactors.data(), fuseRatioMax.data(), (int)scaleFactors.size(),
+                                        TH_HIGH, dm12, dnf);
+        if (rc == XFH_OK) rc = xfh_synchronize(ctx);
+        int nfound = 0;
+        for (int s = 0; s < 2; ++s) {
+            int* out[5] = {sim3Match[s].data(), sim3Best[s].data(), sim3Window[s].data(), sim3Tested[s].data(), sim3Level[s].data()};
+            for (int k = 0; k < 5 && rc == XFH_OK; ++k) rc = xfh_memcpy_d2h(out[k], o[s][k], (size_t)n[s] * 4);
+            if (rc == XFH_OK) rc = xfh_memcpy_d2h(sim3Status[s].data(), dst[s], (size_t)n[s]);
+        }
+        if (rc == XFH_OK) rc = xfh_memcpy_d2h(match12.data(), dm12, (size_t)n[0] * 4);
+        if (rc == XFH_OK) rc = xfh_memcpy_d2h(&nfound, dnf, 4);
+        if (rc != XFH_OK) throw std::runtime_error(std::string("XFmatcher::searchBySim3: ") + xfh_strerror(rc));
+        return nfound;
+    }
+    // per keypoint of keyframe `side` (1 or 2), of the last searchBySim3: XFH_SIM3_* status, vnMatch1 / vnMatch2, best DescriptorDistance, window
+    // members, candidates compared, predicted level
+    const std::vector<unsigned char>& lastSim3Status(int side) const { return sim3Status[side == 2]; }
+    const std::vector<int>& lastSim3Matches(int side) const { return sim3Match[side == 2]; }
+    const std::vector<int>& lastSim3BestDist(int side) const { return sim3Best[side == 2]; }
+    const std::vector<int>& lastSim3Window(int side) const { return sim3Window[side == 2]; }
+    const std::vector<int>& lastSim3Tested(int side) const { return sim3Tested[side == 2]; }
+    const std::vector<int>& lastSim3Level(int side) const { return sim3Level[side == 2]; }
 
     // ORBmatcher::SearchForTriangulation(pKF1, pKF2, vMatchedPairs, bOnlyStereo, bCoarse) (ORBmatcher.cc:1092-1331; mbCheckOrientation = false as
     // LocalMapping builds the matcher, no second camera) as ONE call (xfh_triangulation_search): every keypoint of KF1 without a map point
@@ -668,9 +813,85 @@ public:
     }
 
 protected:
+    // the level thresholds of this pyramid (xfh_scale_level_thresholds), computed once per pyramid
+    void levelTable(const std::vector<float>& scaleFactors, const char* who) {
+        const int nl = (int)scaleFactors.size();
+        if (nl < 1 || nl > XFH_FUSE_MAX_LEVELS) throw std::runtime_error(std::string(who) + ": 1 .. XFH_FUSE_MAX_LEVELS scale factors");
+        if (fuseRatioMax.size() + 1 != (size_t)nl || fuseScale != (nl > 1 ? scaleFactors[1] : 0.f)) {
+            fuseRatioMax.assign(nl - 1, 0.f);
+            if (nl > 1 && xfh_scale_level_thresholds(scaleFactors[1], nl, fuseRatioMax.data()) != XFH_OK) throw std::runtime_error(std::string(who) + ": scale factor must be > 1");
+            fuseScale = nl > 1 ? scaleFactors[1] : 0.f;
+        }
+    }
     int triPairs(std::vector<std::pair<size_t, size_t>>& vMatchedPairs, int nmatches) const {          // :1320-1328
         vMatchedPairs.reserve(nmatches > 0 ? nmatches : 0);
         for (size_t i = 0; i < triMatch.size(); ++i) if (triMatch[i] >= 0) vMatchedPairs.push_back(std::make_pair(i, (size_t)triMatch[i]));
+        return nmatches;
+    }
+    void sim3Reset(int s, int n) {
+        sim3Status[s].assign(n, 0); sim3Match[s].assign(n, -1); sim3Best[s].assign(n, 0x7fffffff); sim3Window[s].assign(n, 0); sim3Tested[s].assign(n, 0);
+        sim3Level[s].assign(n, -1);
+    }
+    int mapProjectionHost(int form, float acceptMax, const Mat& queries, const std::vector<float>& worldPoints, const std::vector<float>& normals,
+                          const std::vector<float>& distances, const std::vector<unsigned char>& flags, const float* Tcw, const float* Ow, const xfh_camera& cam,
+                          const xfh_grid_bounds& bounds, float th, const std::vector<float>& scaleFactors, const XFgrid& grid, const Mat& targets,
+                          std::vector<int>& matchOfQuery, std::vector<int>& assignedQuery, const std::vector<unsigned char>* taken) {
+        const int nq = queries.rows, nt = targets.rows;
+        matchOfQuery.assign(nq, -1); assignedQuery.assign(nt, -1);
+        if (nq == 0 || nt == 0) return 0;
+        if ((int)worldPoints.size() != 3 * nq || (int)normals.size() != 3 * nq || (int)distances.size() != 3 * nq || (int)flags.size() != nq || nt != grid.size() ||
+            (taken && (int)taken->size() != nt) || !Tcw || !Ow)
+            throw std::runtime_error("XFmatcher::searchByProjection: sizes do not fit");
+        auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+        const size_t bq = al((size_t)nq * 256), bp = al((size_t)nq * 12), bfl = al((size_t)nq), bT = 256, bt = al((size_t)nt * 256), bk = al((size_t)nt);
+        reserve(d_out, d_out_bytes, bq + 3 * bp + bfl + 2 * bT + bt + bk, "XFmatcher::searchByProjection");
+        char* p = (char*)d_out;
+        float* dq = (float*)p; p += bq; float* dp = (float*)p; p += bp; float* dn = (float*)p; p += bp; float* dd = (float*)p; p += bp;
+        unsigned char* dfl = (unsigned char*)p; p += bfl; float* dT = (float*)p; p += bT; float* dO = (float*)p; p += bT; float* dt = (float*)p; p += bt;
+        unsigned char* dk = (unsigned char*)p;
+        int rc = xfh_synchronize(ctx);                       // (the copies below are synchronous: nothing queued earlier may still read the buffer)
+        if (rc == XFH_OK) rc = xfh_memcpy_h2d(dq, queries.template ptr<float>(0), (size_t)nq * 256);
+        if (rc == XFH_OK) rc = xfh_memcpy_h2d(dp, worldPoints.data(), (size_t)nq * 12);
+        if (rc == XFH_OK) rc = xfh_memcpy_h2d(dn, normals.data(), (size_t)nq * 12);
+        if (rc == XFH_OK) rc = xfh_memcpy_h2d(dd, distances.data(), (size_t)nq * 12);
+        if (rc == XFH_OK) rc = xfh_memcpy_h2d(dfl, flags.data(), (size_t)nq);
+        if (rc == XFH_OK) rc = xfh_memcpy_h2d(dT, Tcw, 48);
+        if (rc == XFH_OK) rc = xfh_memcpy_h2d(dO, Ow, 12);
+        if (rc == XFH_OK) rc = xfh_memcpy_h2d(dt, targets.template ptr<float>(0), (size_t)nt * 256);
+        if (rc == XFH_OK && taken) rc = xfh_memcpy_h2d(dk, taken->data(), (size_t)nt);
+        if (rc != XFH_OK) throw std::runtime_error(std::string("XFmatcher::searchByProjection: ") + xfh_strerror(rc));
+        return mapProjection(form, acceptMax, nq, dp, dn, dd, dq, dfl, dT, dO, cam, bounds, th, scaleFactors, grid, dt, taken ? dk : nullptr, matchOfQuery, assignedQuery);
+    }
+    int mapProjection(int form, float acceptMax, int nq, const float* d_points, const float* d_normals, const float* d_distances, const float* d_queries,
+                      const unsigned char* d_flags, const float* d_Tcw, const float* d_Ow, const xfh_camera& cam, const xfh_grid_bounds& bounds, float th,
+                      const std::vector<float>& scaleFactors, const XFgrid& grid, const float* d_targets, const unsigned char* d_taken, std::vector<int>& matchOfQuery,
+                      std::vector<int>& assignedQuery) {
+        const int nt = grid.size();
+        matchOfQuery.assign(nq > 0 ? nq : 0, -1); assignedQuery.assign(nt > 0 ? nt : 0, -1);
+        mapStatus.assign(matchOfQuery.size(), 0); mapBest.assign(matchOfQuery.size(), 256); mapWindow.assign(matchOfQuery.size(), 0);
+        mapTested.assign(matchOfQuery.size(), 0); mapLevel.assign(matchOfQuery.size(), -1);
+        if (nq <= 0 || nt <= 0) return 0;
+        levelTable(scaleFactors, "XFmatcher::searchByProjection");
+        auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+        const size_t bw = al(xfh_map_projection_search_workspace_bytes(nq, nt, 1)), bn = al((size_t)nq * 4), ba = al((size_t)nt * 4), bs = al((size_t)nq);
+        if (bw == 0) throw std::runtime_error("XFmatcher::searchByProjection: sizes out of range");
+        reserve(d_proj, d_proj_bytes, bw + 5 * bn + ba + bs + 256, "XFmatcher::searchByProjection");
+        char* p = (char*)d_proj;
+        void* dws = p; p += bw;
+        int* o[5];
+        for (int k = 0; k < 5; ++k) { o[k] = (int*)p; p += bn; }
+        int* das = (int*)p; p += ba; unsigned char* dst = (unsigned char*)p; p += bs; int* dnm = (int*)p;
+        int rc = xfh_map_projection_search_device(ctx, form, 1, nq, d_points, d_normals, d_distances, d_queries, d_flags, d_Tcw, d_Ow, &cam, &bounds, th,
+                                                  scaleFactors.data(), fuseRatioMax.data(), (int)scaleFactors.size(), grid.device(), d_targets, 0, 0, nt, d_taken, 256,
+                                                  acceptMax, dws, dst, o[0], o[1], o[2], o[3], o[4], nullptr, das, dnm);
+        if (rc == XFH_OK) rc = xfh_synchronize(ctx);
+        int nmatches = 0;
+        int* out[5] = {matchOfQuery.data(), mapBest.data(), mapWindow.data(), mapTested.data(), mapLevel.data()};
+        for (int k = 0; k < 5 && rc == XFH_OK; ++k) rc = xfh_memcpy_d2h(out[k], o[k], (size_t)nq * 4);
+        if (rc == XFH_OK) rc = xfh_memcpy_d2h(mapStatus.data(), dst, (size_t)nq);
+        if (rc == XFH_OK) rc = xfh_memcpy_d2h(assignedQuery.data(), das, (size_t)nt * 4);
+        if (rc == XFH_OK) rc = xfh_memcpy_d2h(&nmatches, dnm, 4);
+        if (rc != XFH_OK) throw std::runtime_error(std::string("XFmatcher::searchByProjection: ") + xfh_strerror(rc));
         return nmatches;
     }
     void bowReset(int n1, int n2, std::vector<int>& matchOfQuery, std::vector<int>& assignedQuery) {
@@ -696,6 +917,10 @@ protected:
     std::vector<unsigned char> fuseStatus;                  // results of fuse, and the level thresholds of the pyramid it was last called with
     std::vector<int> fuseBest, fuseWindow, fuseTested, fuseLevel;
     std::vector<float> fuseRatioMax; float fuseScale = 0.f;
+    std::vector<unsigned char> mapStatus;                   // results of the map-point searchByProjection forms
+    std::vector<int> mapBest, mapWindow, mapTested, mapLevel;
+    std::vector<unsigned char> sim3Status[2];               // results of searchBySim3, per side
+    std::vector<int> sim3Match[2], sim3Best[2], sim3Window[2], sim3Tested[2], sim3Level[2];
     std::vector<unsigned char> triStatus;                   // results of searchForTriangulation
     std::vector<int> triMatch, triBest, triCandidates, triGeom;
     std::vector<unsigned char> bowStatus;                   // results of searchByBoW

@@ -24,6 +24,8 @@
  *     xfh_nodes_pack, xfh_nodes_unpack, xfh_grid_unpack and the size / layout helpers
  *     (xfh_record_*, xfh_*_bytes, xfh_compact_bytes_max); xfh_create itself may run on
  *     several threads at once (without a device each call returns XFH_ERR_NO_DEVICE).
+ *     xfh_map_project, xfh_sim3_project and xfh_map_projection_search_workspace_bytes are stateless in the same way (a loop over
+ *     one pure function, no static data); they are not part of the ThreadSanitizer run.
  *
  * The C++ wrappers that restore the reference's class surface on top of this ABI are
  * include/xfeat/XFextractor.h and include/xfeat/ORBmatcher_xfeat.h; INTEGRATION.md shows
@@ -556,8 +558,9 @@ int xfh_search_projection(xfh_ctx* ctx, int mode, int nq, const float* points_or
  *                         the undistorted coordinates) with flags 0 and `bounds`, runs the call and copies the results back.
  *                         XFH_ERR_INVALID_ARG for the device form's classes of error (and bounds no grid can be built from) before
  *                         anything is staged or queued.
- * Out of scope: bRight / NLeft != -1 (fisheye stereo), the Sim3 SearchByProjection forms and SearchBySim3 (the two functions
- * that walk DBoW2 feature vectors are xfh_triangulation_search_device and xfh_bow_search_device below). */
+ * Out of scope: bRight / NLeft != -1 (fisheye stereo).  (The Sim3 SearchByProjection forms are
+ * xfh_map_projection_search_device and SearchBySim3 is xfh_sim3_search_device, both below; the two functions that walk DBoW2 feature
+ * vectors are xfh_triangulation_search_device and xfh_bow_search_device.) */
 #define XFH_FUSE_MAX_LEVELS 16
 #define XFH_FUSE_FLAG_ACTIVE 1        /* d_query_flags bit0 */
 #define XFH_FUSE_CHI2 1               /* flags: the chi-square reprojection gates of the SE3 form */
@@ -735,8 +738,8 @@ int xfh_triangulation_search(xfh_ctx* ctx, int n1, int n2, int flags, int th_low
  *                         the call and copies the results back.  XFH_ERR_INVALID_ARG for the device form's classes of error before
  *                         anything is staged or queued.
  * Out of scope: the Nleft != -1 branches (fisheye stereo); computing the BoW or feature vector (DBoW2 stays with the caller);
- * the relocalisation and Sim3 SearchByProjection forms, SearchBySim3 and SearchForInitialization; the PnP and Sim3 solvers that consume
- * the matches. */
+ * SearchForInitialization (the relocalisation and Sim3 SearchByProjection forms are xfh_map_projection_search_device, SearchBySim3 is
+ * xfh_sim3_search_device, both below); the PnP and Sim3 solvers that consume the matches. */
 #define XFH_BOW_STRICT_LOW 1          /* flags: accept on best < th_low (the keyframe form) instead of best <= th_low */
 enum { XFH_BOW_INACTIVE = 0, XFH_BOW_NO_NODE = 1, XFH_BOW_NO_CANDIDATES = 2, XFH_BOW_REJECTED = 3, XFH_BOW_MATCHED = 4 };
 int xfh_bow_accept(int best_idx, int best, int second, int th_low, float nn_ratio, int flags);
@@ -748,6 +751,206 @@ int xfh_bow_search_device(xfh_ctx* ctx, int B, int n1, int n2, int shared, int f
 int xfh_bow_search(xfh_ctx* ctx, int n1, int n2, int flags, int init_dist, int th_low, float nn_ratio, const uint32_t* node_of1, const uint8_t* active1,
                    const float* desc1, const uint32_t* node_of2, const uint8_t* eligible2_or_null, const float* desc2, uint8_t* status, int* match12,
                    int* best_dist, int* second_dist, int* n_candidates, int* assigned2, int* n_matches);
+
+/* ---- SearchByProjection of map points with a claim: the Sim3 forms and the relocalisation form, device resident -----------------------
+ * Three reference functions as one call (src/ORBmatcher.cc):
+ *   SearchByProjection(KeyFrame*, Sim3f& Scw, vpPoints, vpMatched, th, ratioHamming)                              :612-717    LoopClosing.cc:777, :964
+ *   SearchByProjection(KeyFrame*, Sim3f& Scw, vpPoints, vpPointsKFs, vpMatched, vpMatchedKF, th, ratioHamming)    :719-831    LoopClosing.cc:755
+ *   SearchByProjection(Frame& CurrentFrame, KeyFrame*, sAlreadyFound, th, ORBdist)                                :2074-2195  Tracking.cc:3785, :3799 (Relocalization)
+ * Unlike Fuse they CLAIM: an accepted query writes vpMatched[idx] (:710, :823) resp. CurrentFrame.mvpMapPoints[i2] (:2153), and a later
+ * query skips that keypoint (:689, :802, :2137).  The loop is therefore sequential in the query order; the library resolves it on the
+ * device with the resolver of xfh_search_projection_device and gives the sequential answer.
+ *
+ * Problem b is one target frame / keyframe: nt keypoints, their grid blob, their descriptor rows, pose Tcw[12] (row-major 3x4) and camera
+ * centre Ow[3] -- the caller decomposes Scw into Tcw = [R | t/s] and Ow as :621-622 do, resp. takes both from the frame pose
+ * (:2078-2079) -- and taken[nt], nonzero where vpMatched[idx] != NULL resp. mvpMapPoints[i2] != NULL at entry (NULL: none).  Query q is a
+ * map point in the reference's iteration order: world position X, normal Pn, dist = (min_distance, max_distance, predict_distance), a
+ * 64-D descriptor and a flag byte -- exactly the query arrays of xfh_fuse_search_device; bit0 (XFH_MAPPROJ_FLAG_ACTIVE) is `!pMP->isBad()
+ * && !spAlreadyFound.count(pMP)` (:636, :744) resp. `pMP && !pMP->isBad() && !sAlreadyFound.count(pMP)` (:2093-2095).  The loop, fp32 in
+ * the order written (the library is built with -ffp-contract=off):
+ *
+ *   taken[k] = d_taken ? d_taken[k] != 0 : 0;  assigned[k] = -1;  n_matches = 0
+ *   for q = 0 .. nq-1, in this order:
+ *     flags[q] bit0 clear                                 -> INACTIVE
+ *     xc, yc, zc = Tcw * X                                (each row as ((m0*x + m1*y) + m2*z) + m3, as Fuse)
+ *     form & XFH_MAPPROJ_CULL_BEHIND and zc < 0.0f        -> BEHIND          (:646 / :754; the relocalisation form has no such test)
+ *     form & XFH_MAPPROJ_PROJECT_INVZ:  invz = 1.0f / zc;  x = xc*invz;  y = yc*invz;  u = fx*x + cx;  v = fy*y + cy      (:758-763)
+ *     otherwise (Pinhole::project):     u = fx*xc/zc + cx;  v = fy*yc/zc + cy                                             (:650, :2101)
+ *     form & XFH_MAPPROJ_BOUNDS_CLOSED: u < min_x || u > max_x || v < min_y || v > max_y -> OUT_OF_IMAGE   (a NaN passes, :2103-2106)
+ *     otherwise (IsInImage): !(u >= min_x && u < max_x && v >= min_y && v < max_y)       -> OUT_OF_IMAGE   (half-open, a NaN is out)
+ *     PO = X - Ow;  dist3D = sqrtf((PO.x*PO.x + PO.y*PO.y) + PO.z*PO.z);  dist3D < min || dist3D > max     -> OUT_OF_RANGE
+ *     form & XFH_MAPPROJ_CHECK_ANGLE and (double)((PO.x*Pn.x + PO.y*Pn.y) + PO.z*Pn.z) < 0.5 * (double)dist3D -> BAD_ANGLE  (:668 / :781)
+ *     level = #{ l : predict_distance / dist3D > ratio_max[l] } (xfh_scale_level_thresholds, as Fuse);  r = th * scale_factors[level]
+ *     n_window = members of the window (exactly xfh_search_window_device's window, before any filter)
+ *     per member k in visiting order:  taken[k] -> skipped;  level > 1 -> skipped (every XFeat keypoint has octave 0: :694, :807, and the
+ *         level window of Frame::GetFeaturesInArea at :2124);  ++n_tested;
+ *         d = DescriptorDistance;  d < best -> best = d, best_idx = k              (best starts at init_dist, 256 in all three forms)
+ *     accept = best_idx >= 0 && (float)best <= accept_max
+ *     accept -> MATCHED, match_idx[q] = best_idx, assigned[best_idx] = q, taken[best_idx] = 1, ++n_matches
+ *     else   -> n_tested == 0 ? NO_CANDIDATES : REJECTED
+ *
+ * accept_max is ONE float the caller computes as the reference does: (float)TH_LOW * ratioHamming (int times float, :708 / :821) for the
+ * Sim3 forms, (float)ORBdist (:2151) for the relocalisation form.  The forms are flag sets: XFH_MAPPROJ_FORM_SIM3 (:612),
+ * XFH_MAPPROJ_FORM_SIM3_KF (:719) and XFH_MAPPROJ_FORM_RELOC (:2074); any combination of the four bits is valid.
+ * Where the reference's observable result does not depend on a distinction it is not modelled: the reference leaves a query whose window
+ * is empty (:678) before the loop and one whose members are all skipped after it, with the same outcome, and here both are NO_CANDIDATES;
+ * in the relocalisation form at level > 1 the reference's vIndices2 is empty already, here n_window still counts the members, and the
+ * outcome (no match) is the same.  vpMatchedKF of :824 is vpPointsKFs[assigned[k]]: caller bookkeeping, as are the pointer writes.  The
+ * rotation histogram of :2156-2192 removes nothing: every XFeat keypoint has angle -1, so rot = 0 for every match and all land in one bin.
+ *
+ * Outputs, all exact, all in device memory.  Per query: status (XFH_MAPPROJ_*, numbered like XFH_FUSE_*), match_idx (-1 unless MATCHED),
+ * best_dist (init_dist where no candidate got under it), n_window, n_tested (counted when the query's turn came, i.e. after the claims of
+ * the queries before it), level (-1 for a query culled before PredictScale), optionally proj[q] = (u, v, r): zeros for INACTIVE and
+ * BEHIND, r = 0 for every culled query.  Per keypoint: assigned[k] = the query that claimed it or -1; every match claims, so a keypoint
+ * is assigned at most once.  Per problem: n_matches.
+ *
+ *   xfh_map_project       host, stateless, thread-safe: the per-point arithmetic above for n points and ONE pose down to status (BEHIND ..
+ *                         BAD_ANGLE or XFH_MAPPROJ_VISIBLE), level and radius: uvr[i] = (u, v, r).  The same source lines as the kernel
+ *                         (mapproj_math.h).
+ *   xfh_map_projection_search_workspace_bytes   bytes of d_workspace for B problems (0 for sizes the call would refuse).
+ *   xfh_map_projection_search_device   B problems with the same nq, nt, camera, bounds, th, form and thresholds.  d_points, d_normals,
+ *                         d_distances [B][nq][3], d_query_desc [B][nq][64], d_query_flags [B][nq] bytes, d_Tcw [B][12], d_Ow [B][3],
+ *                         d_taken [B][nt] bytes or NULL: all per problem.  target_shared = 0: grid b at d_grids + b * xfh_grid_bytes(nt),
+ *                         target rows of problem b at d_targets + b * target_stride_bytes, as xfh_fuse_search_device.  target_shared = 1:
+ *                         every problem reads the grid and the rows of problem 0 and the stride is ignored -- LoopClosing's shape (several
+ *                         hypotheses Scw with their own vpPoints against the one current keyframe) and Relocalization's (several candidate
+ *                         keyframes against the one current frame); taken stays per problem.  Outputs d_status [B][nq] bytes, d_match_idx /
+ *                         d_best_dist / d_n_window / d_n_tested / d_level [B][nq] ints, d_proj_out [B][nq][3] or NULL, d_assigned [B][nt]
+ *                         ints, d_n_matches [B] ints.  The first four ints of problem b's part of the workspace (which starts b *
+ *                         xfh_search_projection_workspace_bytes(nq, nt, 1) bytes in) hold afterwards: rounds of the resolver, queries it searched again in full, 0, 0.  All pointers but cam, bounds,
+ *                         scale_factors and ratio_max are device pointers; asynchronous on the ctx stream, no allocation, no host
+ *                         synchronisation, THREE kernel launches; the data-dependent round count is decided on the device.  nq, nt in 1 ..
+ *                         XFH_GRID_MAX_N, B in 1 .. 65535.  XFH_ERR_INVALID_ARG before anything is queued: those ranges, nlevels outside 1 ..
+ *                         XFH_FUSE_MAX_LEVELS, unknown form bits, target_shared outside 0 .. 1, a non-finite th or accept_max, accept_max <
+ *                         0, a NULL required pointer, misaligned pointers (16 bytes for descriptors, targets, the target stride, grids and the
+ *                         workspace, the element size otherwise).  Points, normals, distances, poses, camera centres and descriptors may
+ *                         hold anything, NaN and Inf included: no load leaves the buffers the caller named.  Many queries piled on one spot
+ *                         cost what xfh_search_projection_device says of that case: exact and terminating, but seconds.
+ *   xfh_map_projection_search   host-pointer convenience form for ONE problem: stages the inputs and the workspace, builds the grid of the
+ *                         nt keypoints (x, y = the undistorted coordinates) with flags 0 and `bounds`, runs the call and copies the results
+ *                         back.  XFH_ERR_INVALID_ARG for the device form's classes of error (and bounds no grid can be built from) before
+ *                         anything is staged or queued.
+ * Out of scope: SearchForInitialization (monocular initialisation only; its retraction rule needs another resolution scheme); fisheye
+ * stereo; the PnP and Sim3 solvers that consume the matches. */
+#define XFH_MAPPROJ_FLAG_ACTIVE 1     /* d_query_flags bit0 */
+#define XFH_MAPPROJ_CULL_BEHIND 1     /* form bits */
+#define XFH_MAPPROJ_CHECK_ANGLE 2
+#define XFH_MAPPROJ_PROJECT_INVZ 4
+#define XFH_MAPPROJ_BOUNDS_CLOSED 8
+#define XFH_MAPPROJ_FORM_SIM3 (XFH_MAPPROJ_CULL_BEHIND | XFH_MAPPROJ_CHECK_ANGLE)
+#define XFH_MAPPROJ_FORM_SIM3_KF (XFH_MAPPROJ_CULL_BEHIND | XFH_MAPPROJ_CHECK_ANGLE | XFH_MAPPROJ_PROJECT_INVZ)
+#define XFH_MAPPROJ_FORM_RELOC XFH_MAPPROJ_BOUNDS_CLOSED
+enum { XFH_MAPPROJ_INACTIVE = 0, XFH_MAPPROJ_BEHIND = 1, XFH_MAPPROJ_OUT_OF_IMAGE = 2, XFH_MAPPROJ_OUT_OF_RANGE = 3, XFH_MAPPROJ_BAD_ANGLE = 4,
+       XFH_MAPPROJ_NO_CANDIDATES = 5, XFH_MAPPROJ_REJECTED = 6, XFH_MAPPROJ_MATCHED = 7,
+       XFH_MAPPROJ_VISIBLE = 5 /* xfh_map_project: the point reaches the search */ };
+int xfh_map_project(const float* Tcw, const float* Ow, const xfh_camera* cam, const xfh_grid_bounds* bounds, float th, const float* scale_factors,
+                    const float* ratio_max, int nlevels, int form, const float* xyz, const float* normals, const float* distances, int n,
+                    float* uvr, int* level, uint8_t* status);
+size_t xfh_map_projection_search_workspace_bytes(int nq, int nt, int B);
+int xfh_map_projection_search_device(xfh_ctx* ctx, int form, int B, int nq, const float* d_points, const float* d_normals, const float* d_distances,
+                                     const float* d_query_desc, const uint8_t* d_query_flags, const float* d_Tcw, const float* d_Ow,
+                                     const xfh_camera* cam, const xfh_grid_bounds* bounds, float th, const float* scale_factors, const float* ratio_max,
+                                     int nlevels, const void* d_grids, const float* d_targets, size_t target_stride_bytes, int target_shared, int nt,
+                                     const uint8_t* d_taken_or_null, int init_dist, float accept_max, void* d_workspace, uint8_t* d_status,
+                                     int* d_match_idx, int* d_best_dist, int* d_n_window, int* d_n_tested, int* d_level, float* d_proj_out_or_null,
+                                     int* d_assigned, int* d_n_matches);
+int xfh_map_projection_search(xfh_ctx* ctx, int form, int nq, const float* points, const float* normals, const float* distances,
+                              const float* query_desc, const uint8_t* query_flags, const float* Tcw, const float* Ow, const xfh_camera* cam,
+                              const xfh_grid_bounds* bounds, float th, const float* scale_factors, const float* ratio_max, int nlevels,
+                              const xfh_keypoint* kps, const float* targets, int nt, const uint8_t* taken_or_null, int init_dist, float accept_max,
+                              uint8_t* status, int* match_idx, int* best_dist, int* n_window, int* n_tested, int* level, float* proj_out_or_null,
+                              int* assigned, int* n_matches);
+
+/* ---- SearchBySim3: two keyframes' map points projected into each other and searched, device resident ---------------------------------
+ * ORBmatcher::SearchBySim3(KeyFrame* pKF1, KeyFrame* pKF2, vpMatches12, const Sim3f& S12, th) (src/ORBmatcher.cc:1642-1859; the reference's own
+ * LoopClosing.cc no longer calls it, a caller that refines S12 against a candidate keyframe does) up to vpMatches12, as one call for B keyframe pairs.  Both directions
+ * read no map state and no query sees another -- there is no claim -- so the whole function is two independent searches and the
+ * agreement step behind them (:1840-1856).  What stays with the caller: S12 and its inverse (its own Sophus), vbAlreadyMatched1 / 2 as
+ * :1662-1675 compute them (folded into the flag bytes), and the pointer write vpMatches12[i1] = vpMapPoints2[match12[i1]] (:1852).
+ *
+ * Problem b is a keyframe pair.  Side s (1 or 2) is xfh_sim3_side: n keypoints, their grid blob (built from mvKeysUn), the keyframe's
+ * descriptor rows desc[n][64] (mDescriptors), and per keypoint i the map point it holds (vpMapPoints_s[i]): world position points[i],
+ * dist[i] = (min_distance, max_distance, predict_distance) as in Fuse above, the map point's OWN descriptor mp_desc[i][64]
+ * (pMP->GetDescriptor(), :1730 -- not the keyframe's row i) and a flag byte whose bit0 (XFH_SIM3_FLAG_ACTIVE) is `pMP &&
+ * !vbAlreadyMatched_s[i] && !pMP->isBad()` (:1685-1689, :1765-1769); the arrays of a keypoint without a map point may hold anything.
+ * Tw[12] is the side's pose (row-major 3x4).  Per problem: M21[12] and M12[12], the row-major 3x4 [s*R | t] of S12.inverse() and S12,
+ * so that M * p is the Sim3 applied to p.  Bit equality with Sophus' Sim3 * Vector3 is not claimed, as for every pose product in this
+ * header.  ONE camera and ONE bounds struct serve both directions: the reference uses pKF1's intrinsics for both (:1644-1647).
+ * All arithmetic is fp32 in the order written unless stated otherwise (the library is built with -ffp-contract=off).
+ * Direction 1->2, for i1 in any order (2->1 is the mirror image with T2w, M12 and side 1's grid and rows):
+ *
+ *   flags1[i1] bit0 clear                                 -> INACTIVE
+ *   p1 = T1w * X;  p2 = M21 * p1                          (each row as ((m0*x + m1*y) + m2*z) + m3, as Fuse)
+ *   p2.z < 0.0f                                           -> BEHIND          (:1696; +-0 and NaN go on)
+ *   invz = (float)(1.0 / (double)p2.z)                    (a DOUBLE division rounded once, :1699)
+ *   x = p2.x*invz;  y = p2.y*invz;  u = fx*x + cx;  v = fy*y + cy            (:1700-1704)
+ *   !(u >= min_x && u < max_x && v >= min_y && v < max_y) -> OUT_OF_IMAGE    (KeyFrame::IsInImage: half-open, NaN is out)
+ *   dist3D = sqrtf((p2.x*p2.x + p2.y*p2.y) + p2.z*p2.z)   (the norm of the CAMERA-frame point, :1712 -- not |X - Ow| as in Fuse)
+ *   dist3D < min_distance || dist3D > max_distance        -> OUT_OF_RANGE    (:1715)
+ *   level = #{ l : predict_distance / dist3D > ratio_max[l] } (xfh_scale_level_thresholds, as Fuse);  r = th * scale_factors[level]
+ *   window: exactly xfh_search_window_device's, no skip mask and no uright filter;  n_window = its size;  0 -> NO_CANDIDATES (:1726)
+ *   per member k in visiting order:  level > 1 -> skipped (every XFeat keypoint has octave 0, :1740);  ++n_tested;
+ *       dist = DescriptorDistance(mp_desc1[i1], desc2[k]);  dist < best -> best = dist, best_idx = k     (best starts at INT_MAX)
+ *   best_idx >= 0 && best <= th_high -> FOUND, match1[i1] = best_idx;  else REJECTED, match1[i1] = -1   (TH_HIGH, :1754)
+ *
+ * Agreement (:1840-1856): match12[i1] = idx2 iff match1[i1] == idx2 >= 0 && match2[idx2] == i1, else -1; n_found[b] counts them.  There
+ * is no viewing-angle test and no rotation histogram in SearchBySim3.
+ *
+ * Outputs, all exact, all in device memory.  Per side and keypoint: status (XFH_SIM3_*, numbered like XFH_FUSE_* without BAD_ANGLE),
+ * match, best_dist (INT_MAX where no candidate was tested; the best of a REJECTED query otherwise), n_window, n_tested (both 0 for a
+ * culled query), level (-1 for a query culled before PredictScale) and optionally proj[i] = (u, v, r): zeros for INACTIVE and BEHIND,
+ * r = 0 for every culled query.  Per problem: match12[n1] and n_found.
+ *
+ *   xfh_sim3_project      host, stateless, thread-safe: the per-point arithmetic above for n points, ONE pose Tqw and ONE M down to
+ *                         status (BEHIND .. OUT_OF_RANGE or XFH_SIM3_VISIBLE), level and radius: uvr[i] = (u, v, r).  The same source
+ *                         lines as the kernel (sim3_math.h).
+ *   xfh_sim3_search_device   B pairs with the same n1, n2, camera, bounds, th, th_high and scale tables.  Of a side it reads n, grid
+ *                         (problem b's blob at grid + b * xfh_grid_bytes(n)), desc (problem b's rows desc_stride_bytes * b in), points /
+ *                         dist [B][n][3], mp_desc [B][n][64], flags [B][n] bytes, Tw [B][12], and writes status [B][n] bytes, match /
+ *                         best_dist / n_window / n_tested / level [B][n] ints and proj_out [B][n][3] (or NULL); kps is not read.
+ *                         d_M21 / d_M12 [B][12], d_match12 [B][n1], d_n_found [B].  side1_shared = 1: every problem reads the INPUTS of
+ *                         side 1 (grid, desc, points, dist, mp_desc, flags, Tw) of problem 0 and side1->desc_stride_bytes is ignored --
+ *                         LoopClosing's shape, the current keyframe against several candidates; the outputs stay [B][n1].  All pointers
+ *                         inside the sides and d_M21, d_M12, d_match12, d_n_found are device pointers; the side structs themselves, cam,
+ *                         bounds and the scale tables are host memory, read before the call returns.  Asynchronous on the ctx stream, no
+ *                         allocation, no workspace, TWO kernel launches (behind a 4 * B byte memset of d_n_found on the same stream).
+ *                         n1, n2 in 1 .. XFH_GRID_MAX_N, B in 1 .. 65535.  XFH_ERR_INVALID_ARG before anything is queued: those ranges,
+ *                         nlevels outside 1 .. XFH_FUSE_MAX_LEVELS, a non-finite th, side1_shared outside 0 .. 1, a NULL required pointer,
+ *                         misaligned pointers (16 bytes for desc, mp_desc, the desc strides and grids, the element size otherwise).
+ *                         Points, distances, poses, M21 / M12, scale tables and descriptors may hold anything, NaN and Inf included: no
+ *                         load leaves the buffers the caller named.
+ *   xfh_sim3_search       host-pointer convenience form for ONE pair: every pointer of the sides is host memory, kps holds the side's n
+ *                         keypoints (x, y = the undistorted coordinates) instead of a grid, and desc_stride_bytes is ignored.  It stages the
+ *                         inputs, builds both grids with flags 0 and `bounds`, runs the call and copies the results back.
+ *                         XFH_ERR_INVALID_ARG for the device form's classes of error (and bounds no grid can be built from) before
+ *                         anything is staged or queued.
+ * Out of scope: SearchForInitialization; fisheye stereo; the Sim3 solver that produces S12 and consumes the matches. */
+#define XFH_SIM3_FLAG_ACTIVE 1        /* flags bit0 */
+enum { XFH_SIM3_INACTIVE = 0, XFH_SIM3_BEHIND = 1, XFH_SIM3_OUT_OF_IMAGE = 2, XFH_SIM3_OUT_OF_RANGE = 3,
+       XFH_SIM3_NO_CANDIDATES = 5, XFH_SIM3_REJECTED = 6, XFH_SIM3_FOUND = 7,
+       XFH_SIM3_VISIBLE = 5 /* xfh_sim3_project: the point reaches the search */ };
+typedef struct xfh_sim3_side {
+    int n;                            /* keypoints of the keyframe */
+    const void* grid;                 /* device form: the grid blobs */
+    const xfh_keypoint* kps;          /* host form: the n keypoints the grid is built from */
+    const float* desc;                /* keyframe descriptor rows */
+    size_t desc_stride_bytes;         /* device form: from one problem's rows to the next one's */
+    const float* points;              /* world position of the map point of keypoint i */
+    const float* dist;                /* (min_distance, max_distance, predict_distance) */
+    const float* mp_desc;             /* the map point's own descriptor */
+    const uint8_t* flags;
+    const float* Tw;
+    uint8_t* status; int* match; int* best_dist; int* n_window; int* n_tested; int* level;
+    float* proj_out_or_null;
+} xfh_sim3_side;
+int xfh_sim3_project(const float* Tqw, const float* M, const xfh_camera* cam, const xfh_grid_bounds* bounds, float th, const float* scale_factors,
+                     const float* ratio_max, int nlevels, const float* xyz, const float* distances, int n, float* uvr, int* level, uint8_t* status);
+int xfh_sim3_search_device(xfh_ctx* ctx, int B, int side1_shared, const xfh_sim3_side* side1, const xfh_sim3_side* side2, const float* d_M21,
+                           const float* d_M12, const xfh_camera* cam, const xfh_grid_bounds* bounds, float th, const float* scale_factors,
+                           const float* ratio_max, int nlevels, int th_high, int* d_match12, int* d_n_found);
+int xfh_sim3_search(xfh_ctx* ctx, const xfh_sim3_side* side1, const xfh_sim3_side* side2, const float* M21, const float* M12, const xfh_camera* cam,
+                    const xfh_grid_bounds* bounds, float th, const float* scale_factors, const float* ratio_max, int nlevels, int th_high,
+                    int* match12, int* n_found);
 
 /* MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:329-403), batched over map points: group g observes the
  * descriptor rows indices[offsets[g] .. offsets[g+1]) of `table` (n_rows x 64).  Pairwise DescriptorDistance inside

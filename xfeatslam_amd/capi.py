@@ -29,7 +29,7 @@ ERR_EMPTY_IMAGE = 2
 ERR_NO_DEVICE = 7
 ERR_COMM = 11
 
-K = dict(NONE=0, MNN_GEMM=1, CONV_MFMA=2, CONV_DIRECT=3, NMS=4, SELECT=5, DESC=6, HEADS=7, DIST_I32=8, PREPROC=9, BEST2=10, DISTINCTIVE=11, MNN_GEMM_SEG=12, GRID_BUILD=13, SEARCH_WINDOW=14, FRAME_FINISH=15, PROJ_CANDIDATES=16, PROJ_RESOLVE=17, PROJ_COUNT=18, FUSE_SEARCH=19, TRIANGULATION_SEARCH=20, BOW_CANDIDATES=21, BOW_RESOLVE=22)
+K = dict(NONE=0, MNN_GEMM=1, CONV_MFMA=2, CONV_DIRECT=3, NMS=4, SELECT=5, DESC=6, HEADS=7, DIST_I32=8, PREPROC=9, BEST2=10, DISTINCTIVE=11, MNN_GEMM_SEG=12, GRID_BUILD=13, SEARCH_WINDOW=14, FRAME_FINISH=15, PROJ_CANDIDATES=16, PROJ_RESOLVE=17, PROJ_COUNT=18, FUSE_SEARCH=19, TRIANGULATION_SEARCH=20, BOW_CANDIDATES=21, BOW_RESOLVE=22, MAPPROJ_CANDIDATES=23, SIM3_SEARCH=24, SIM3_AGREE=25)
 T = dict(X=0, XSTAT=1, SKIP_POOL=2, FEATS=6, H1=8, K1H=9, RAW0=16, STAT0=48, SEL=80)
 
 
@@ -51,6 +51,14 @@ class Camera(C.Structure):
                 ("reserved", C.c_int32 * 4)]
 
 
+class Sim3Side(C.Structure):
+    """xfh_sim3_side: one keyframe of a SearchBySim3 pair (device pointers for xfh_sim3_search_device, host pointers for xfh_sim3_search)"""
+    _fields_ = [("n", C.c_int), ("grid", C.c_void_p), ("kps", C.c_void_p), ("desc", C.c_void_p), ("desc_stride_bytes", C.c_size_t),
+                ("points", C.c_void_p), ("dist", C.c_void_p), ("mp_desc", C.c_void_p), ("flags", C.c_void_p), ("Tw", C.c_void_p),
+                ("status", C.c_void_p), ("match", C.c_void_p), ("best_dist", C.c_void_p), ("n_window", C.c_void_p), ("n_tested", C.c_void_p),
+                ("level", C.c_void_p), ("proj_out", C.c_void_p)]
+
+
 DEPTH_NONE, DEPTH_F32, DEPTH_U16 = 0, 1, 2
 GRID_COLS, GRID_ROWS = 64, 48
 GRID_SKIP_PADDING = 1
@@ -70,6 +78,15 @@ TRI_INACTIVE, TRI_NO_NODE, TRI_NO_CANDIDATES, TRI_REJECTED, TRI_MATCHED = range(
 TRI_GATE_SKIPPED, TRI_GATE_REJECTED, TRI_GATE_PASSED = range(3)
 BOW_STRICT_LOW = 1
 BOW_INACTIVE, BOW_NO_NODE, BOW_NO_CANDIDATES, BOW_REJECTED, BOW_MATCHED = range(5)
+MAPPROJ_INACTIVE, MAPPROJ_BEHIND, MAPPROJ_OUT_OF_IMAGE, MAPPROJ_OUT_OF_RANGE, MAPPROJ_BAD_ANGLE, MAPPROJ_NO_CANDIDATES, MAPPROJ_REJECTED, MAPPROJ_MATCHED = range(8)
+MAPPROJ_VISIBLE = 5
+MAPPROJ_FLAG_ACTIVE = 1
+MAPPROJ_CULL_BEHIND, MAPPROJ_CHECK_ANGLE, MAPPROJ_PROJECT_INVZ, MAPPROJ_BOUNDS_CLOSED = 1, 2, 4, 8
+MAPPROJ_FORM_SIM3, MAPPROJ_FORM_SIM3_KF, MAPPROJ_FORM_RELOC = 3, 7, 8
+SIM3_INACTIVE, SIM3_BEHIND, SIM3_OUT_OF_IMAGE, SIM3_OUT_OF_RANGE = range(4)
+SIM3_NO_CANDIDATES, SIM3_REJECTED, SIM3_FOUND = 5, 6, 7
+SIM3_VISIBLE = 5
+SIM3_FLAG_ACTIVE = 1
 
 FLAG_RESCALE_KEYPOINTS = 1
 FLAG_SERIAL_BRANCH = 2
@@ -147,6 +164,16 @@ SYMBOLS = [
     ("xfh_bow_search_workspace_bytes", _sz, [_i, _i, _i]),
     ("xfh_bow_search_device", _i, [_vp, _i, _i, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("xfh_bow_search", _i, [_vp, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("xfh_map_project", _i, [_vp, _vp, C.POINTER(Camera), C.POINTER(GridBounds), _f, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
+    ("xfh_map_projection_search_workspace_bytes", _sz, [_i, _i, _i]),
+    ("xfh_map_projection_search_device", _i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(Camera), C.POINTER(GridBounds), _f, _vp, _vp, _i,
+                                              _vp, _vp, _sz, _i, _i, _vp, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("xfh_map_projection_search", _i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(Camera), C.POINTER(GridBounds), _f, _vp, _vp, _i, _vp, _vp, _i,
+                                       _vp, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("xfh_sim3_project", _i, [_vp, _vp, C.POINTER(Camera), C.POINTER(GridBounds), _f, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp]),
+    ("xfh_sim3_search_device", _i, [_vp, _i, _i, C.POINTER(Sim3Side), C.POINTER(Sim3Side), _vp, _vp, C.POINTER(Camera), C.POINTER(GridBounds), _f, _vp, _vp, _i,
+                                    _i, _vp, _vp]),
+    ("xfh_sim3_search", _i, [_vp, C.POINTER(Sim3Side), C.POINTER(Sim3Side), _vp, _vp, C.POINTER(Camera), C.POINTER(GridBounds), _f, _vp, _vp, _i, _i, _vp, _vp]),
     ("xfh_distinctive_csr", _i, [_vp, _vp, _i, _vp, _vp, _i, _vp, _vp]),
     ("xfh_distinctive_csr_device", _i, [_vp, _vp, _i, _vp, _vp, _i, _i, _vp, _vp]),
     ("xfh_comm_unique_id", _i, [_vp]),

@@ -9,8 +9,8 @@
 // MapPoint::PredictScale before the clamp (MapPoint.cc:522), float overloads: what the thresholds are bisected against
 static float scale_level_expr(float ratio, float log_sf) { return ceilf(logf(ratio) / log_sf); }
 
-// the checks every Fuse entry shares, and the tables as the kernel takes them
-static bool fuse_levels(const float* scale_factors, const float* ratio_max, int nlevels, FuseLevels* L) {
+// the checks every entry with a scale table shares, and the tables as the kernels take them (also capi_loop.cpp)
+bool fuse_levels(const float* scale_factors, const float* ratio_max, int nlevels, FuseLevels* L) {
     if (nlevels < 1 || nlevels > XFH_FUSE_MAX_LEVELS || !scale_factors || (nlevels > 1 && !ratio_max)) return false;
     memset(L, 0, sizeof *L);
     L->nlevels = nlevels;

@@ -1,4 +1,4 @@
-// capi_internal.h -- what the entry-point files (capi.cpp, capi_search.cpp, capi_fuse.cpp, capi_triangulation.cpp, capi_bow.cpp, capi_bench.cpp) share.
+// capi_internal.h -- what the entry-point files (capi.cpp, capi_search.cpp, capi_fuse.cpp, capi_triangulation.cpp, capi_bow.cpp, capi_loop.cpp, capi_bench.cpp) share.
 #pragma once
 #include "ctx.h"
 #include "window_layout.h"
@@ -14,6 +14,9 @@ int gather_pairs(xfh_ctx* c, int n_pairs, const void* const* image1, const int* 
                  int* const* idx1, int* const* idx2, float* const* dist, int* n_matches, bool need_out, std::vector<XfhMatchPair>& v);
 // bytes of the staging arena xfh_match_mnn needs for n1 x n2 rows: xfh_create reserves that for nfeatures x nfeatures (capi_search.cpp)
 size_t match_mnn_stage_bytes(int n1, int n2);
+// the caller's scale tables checked and copied into the kernels' argument form (capi_fuse.cpp)
+struct FuseLevels;
+bool fuse_levels(const float* scale_factors, const float* ratio_max, int nlevels, FuseLevels* L);
 // the caller's grid bounds -> the kernels' geometry; false for bounds that are not finite or not ordered.
 // mfGridElementWidthInv = FRAME_GRID_COLS / (mnMaxX - mnMinX), mfGridElementHeightInv likewise, in fp32 (Frame.cc:336-341)
 inline bool grid_geom(const xfh_grid_bounds* b, GridGeom* g) {

@@ -217,6 +217,10 @@ struct FuseArgs;
 hipError_t launch_fuse_search(xfh_ctx* c, const FuseArgs& a, int B);                  // fuse_search.hip.h
 struct TriArgs;
 hipError_t launch_triangulation_search(xfh_ctx* c, const TriArgs& a, int B);          // triangulation_search.hip.h
+struct MapProjArgs;
+hipError_t launch_map_projection_search(xfh_ctx* c, const MapProjArgs& m, int B);   // mapproj_search.hip.h
+struct Sim3Args;
+hipError_t launch_sim3_search(xfh_ctx* c, const Sim3Args& a, int B);                  // sim3_search.hip.h
 struct BowArgs;
 hipError_t launch_bow_search(xfh_ctx* c, const BowArgs& a, int B);                    // bow_search.hip.h
 hipError_t launch_best2(xfh_ctx* c, const float* q, int nq, const float* tg, const int* offsets, const int* indices, int init_dist,

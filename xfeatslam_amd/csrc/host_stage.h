@@ -16,7 +16,7 @@
 #include <stdlib.h>
 
 struct HostStage {
-    static const int MAXP = 24; static const size_t SLACK = 16;
+    static const int MAXP = 40; static const size_t SLACK = 16;
     struct Piece { size_t bytes, off; const void* src; void* dst; bool absent; };
     template <typename T> struct Dev { const HostStage* s; int i; operator T*() const { return (T*)s->ptr(i); } };
     xfh_ctx* c; Piece pc[MAXP]; int n = 0;                                   // an aggregate: HostStage s{c};

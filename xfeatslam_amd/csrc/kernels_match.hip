@@ -22,6 +22,10 @@
 //                   reference's last-wins tie (triangulation_search.hip.h).
 //   k_bow_candidates / k_bow_resolve : both ORBmatcher::SearchByBoW overloads, B problems per call: per query the least members of its node, then
 //                   the reference's claim order resolved per node, one wave each, the claimed set in LDS (bow_search.hip.h).
+//   k_mapproj_candidates : the front kernel of the Sim3 and relocalisation forms of SearchByProjection: per map point the projection, the culls, the level and
+//                   the window walk with the K best candidates; k_proj_resolve / k_proj_count settle the claims behind it (mapproj_search.hip.h).
+//   k_sim3_search / k_sim3_agree : ORBmatcher::SearchBySim3 up to vpMatches12, B keyframe pairs per call: both directions of the projection through
+//                   S21 / S12 with the range and level culls and the window walk in one launch, then the agreement step (sim3_search.hip.h).
 //   k_distinctive_csr : MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:329-403), one wave per map point.
 //
 // Numerics: normalised rows and the 64-term dot products are bit-identical to the oracle
@@ -102,6 +106,8 @@ hipError_t launch_best2(xfh_ctx* c, const float* q, int nq, const float* tg, con
 #include "fuse_search.hip.h"
 #include "triangulation_search.hip.h"
 #include "bow_search.hip.h"
+#include "mapproj_search.hip.h"
+#include "sim3_search.hip.h"
 
 // ---- k_distinctive_csr: MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:329-403), batched -------
 // One wave per group (map point).  Rows are taken 64 at a time, lane = row: the lane keeps its descriptor in

@@ -42,5 +42,8 @@ struct ProjArgs {
     float* proj_out;                 // [B][nq][3] or NULL
     int* assigned;                   // [B][nt]
     int* n_matches;                  // [B]
+    // what xfh_map_projection_search_device sets (mapproj_search.hip.h); zero in xfh_search_projection_device, whose kernel instances do not read them
+    int status_base;                 // added to XFH_PROJ_NO_CANDIDATES / REJECTED / MATCHED: 2 = the numbering of XFH_MAPPROJ_* (and of XFH_FUSE_*)
+    int flags_or;                    // or-ed into every query's flag byte: 2 = every query claims
 };
 

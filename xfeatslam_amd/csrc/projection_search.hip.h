@@ -23,6 +23,9 @@
 //                      keypoint = last writer) and n_matches, and the final claim_min to the workspace.
 //   k_proj_count       many workgroups, one wave per query: n_candidates = survivors of the walk with the FINAL claim_min (no
 //                      descriptor is read).
+// k_proj_resolve and k_proj_count also serve xfh_map_projection_search_device behind its own front kernel (mapproj_search.hip.h), which
+// fills the same workspace; ProjArgs::status_base and ::flags_or are what differs.  Both are 0 here, and the kernels are templates on
+// whether they read the two fields at all: the <false> instances this file launches are the code they were before the fields existed.
 //
 // Bounds: slot numbers come from the blob and are checked against nt in the walk (window_walk) before anything is indexed with them;
 // list entries are such slot numbers; point coordinates and poses are only ever used as floats; a non-finite (u, v, r) opens no
@@ -109,16 +112,18 @@ void k_proj_candidates(ProjArgs a) {
 }
 
 // accept / reject of one query from its best two (include/xfeat_hip.h), the outputs, and the round's "smallest query that moved"
-__device__ __forceinline__ void proj_finish(const ProjArgs& a, size_t qg, int q, int bi, int bd, int si, int sd, bool survivors, int* changed_lo) {
+__device__ __forceinline__ void proj_finish(const ProjArgs& a, int sbase, size_t qg, int q, int bi, int bd, int si, int sd, bool survivors, int* changed_lo) {
     const bool accept = bi >= 0 && bd <= a.th_high && !(a.nn_ratio > 0.0f && si >= 0 && (float)bd > a.nn_ratio * (float)sd);
     const int m = accept ? bi : -1;
     if (a.match_idx[qg] != m) { a.match_idx[qg] = m; atomicMin(changed_lo, q); }
     a.best_dist[qg] = bd; a.second_dist[qg] = sd;
-    a.status[qg] = (uint8_t)(accept ? XFH_PROJ_MATCHED : (survivors ? XFH_PROJ_REJECTED : XFH_PROJ_NO_CANDIDATES));
+    a.status[qg] = (uint8_t)((accept ? XFH_PROJ_MATCHED : (survivors ? XFH_PROJ_REJECTED : XFH_PROJ_NO_CANDIDATES)) + sbase);
 }
 
+template <bool MAPPROJ>
 __global__ __launch_bounds__(XFH_PROJ_RESOLVE_THREADS)
 void k_proj_resolve(ProjArgs a) {
+    const int sbase = MAPPROJ ? a.status_base : 0, flags_or = MAPPROJ ? a.flags_or : 0;
     extern __shared__ int claim[];                                     // nt entries: claim_min, at the end the assignment
     __shared__ int s_changed_lo, s_defer_lo, s_nredo, s_nwalk, s_nmatch;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, pb = blockIdx.x;
@@ -145,12 +150,12 @@ void k_proj_resolve(ProjArgs a) {
         __syncthreads();
         for (int q = tid; q < nq; q += XFH_PROJ_RESOLVE_THREADS) {
             const int m = a.match_idx[q0 + q];
-            if (m >= 0 && (qflags[q] & 2)) atomicMin(&claim[m], q);
+            if (m >= 0 && ((qflags[q] | flags_or) & 2)) atomicMin(&claim[m], q);
         }
         __syncthreads();
         // one thread per query: the K-list against claim_min
         for (int q = lo + tid; q < nq; q += XFH_PROJ_RESOLVE_THREADS) {
-            if (a.status[q0 + q] < XFH_PROJ_NO_CANDIDATES) continue;
+            if (a.status[q0 + q] < XFH_PROJ_NO_CANDIDATES + sbase) continue;
             const int n = ntot[q], len = n < XFH_PROJ_K ? n : XFH_PROJ_K;
             int found = 0, bi = -1, bd = a.init_dist, si = -1, sd = a.init_dist;
             bool settled = false;                                      // nothing past the list can change best / second
@@ -164,7 +169,7 @@ void k_proj_resolve(ProjArgs a) {
                 else { si = idx; sd = d; settled = true; }
             }
             if (n > XFH_PROJ_K && !settled) redo[atomicAdd(&s_nredo, 1)] = q;
-            else proj_finish(a, q0 + q, q, bi, bd, si, sd, found > 0, &s_changed_lo);
+            else proj_finish(a, sbase, q0 + q, q, bi, bd, si, sd, found > 0, &s_changed_lo);
         }
         __syncthreads();
         // one wave per truncated query: the full walk with the claim test inside
@@ -182,7 +187,7 @@ void k_proj_resolve(ProjArgs a) {
                                              [&](u64 key, int) { top2_insert(b, s2, key); });
             int bi, bd, si, sd;
             window_best2(w, grid, b, s2, a.init_dist, bi, bd, si, sd);
-            if (lane == 0) proj_finish(a, q0 + q, q, bi, bd, si, sd, nc > 0, &s_changed_lo);
+            if (lane == 0) proj_finish(a, sbase, q0 + q, q, bi, bd, si, sd, nc > 0, &s_changed_lo);
         }
         __syncthreads();
         const int c = s_changed_lo, d = s_defer_lo;
@@ -210,15 +215,17 @@ void k_proj_resolve(ProjArgs a) {
     if (tid == 0) a.n_matches[pb] = s_nmatch;
 }
 
+template <bool MAPPROJ>
 __global__ __launch_bounds__(256)
 void k_proj_count(ProjArgs a) {
+    const int sbase = MAPPROJ ? a.status_base : 0;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int qi = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + wave), pb = blockIdx.y;
     if (qi >= a.nq) return;
     const size_t qg = (size_t)pb * a.nq + qi;
     const ProjWs L = proj_ws_layout(a.nq, a.nt);
     const char* ws = a.ws + (size_t)pb * a.ws_stride;
-    if (a.status[qg] < XFH_PROJ_NO_CANDIDATES || ((const int*)(ws + L.ntot))[qi] == 0) return;       // n_candidates is 0 already
+    if (a.status[qg] < XFH_PROJ_NO_CANDIDATES + sbase || ((const int*)(ws + L.ntot))[qi] == 0) return;       // n_candidates is 0 already
     const float* pj = (const float*)(ws + L.proj) + (size_t)qi * 4;
     const int* wclaim = (const int*)(ws + L.claim);
     const char* grid = a.grids + (size_t)pb * a.grid_stride;
@@ -230,10 +237,10 @@ void k_proj_count(ProjArgs a) {
 }
 
 hipError_t launch_search_projection(xfh_ctx* c, const ProjArgs& a, int B) {
-    XFH_SET_LDS_ATTR_ONCE(c, k_proj_resolve, XFH_GRID_MAX_N * sizeof(int));
+    XFH_SET_LDS_ATTR_ONCE(c, k_proj_resolve<false>, XFH_GRID_MAX_N * sizeof(int));
     const dim3 per_query((a.nq + 3) / 4, B);
     launch_k(c, XFH_K_PROJ_CANDIDATES, -1, k_proj_candidates, per_query, dim3(256), 0, a);
-    launch_k(c, XFH_K_PROJ_RESOLVE, -1, k_proj_resolve, dim3(B), dim3(XFH_PROJ_RESOLVE_THREADS), (size_t)a.nt * sizeof(int), a);
-    launch_k(c, XFH_K_PROJ_COUNT, -1, k_proj_count, per_query, dim3(256), 0, a);
+    launch_k(c, XFH_K_PROJ_RESOLVE, -1, k_proj_resolve<false>, dim3(B), dim3(XFH_PROJ_RESOLVE_THREADS), (size_t)a.nt * sizeof(int), a);
+    launch_k(c, XFH_K_PROJ_COUNT, -1, k_proj_count<false>, per_query, dim3(256), 0, a);
     return hipGetLastError();
 }

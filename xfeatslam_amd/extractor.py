@@ -559,6 +559,142 @@ class Context:
         r.update(status=st, assigned2=as2, n_matches=int(nm[0]))
         return r
 
+    # -- SearchByProjection of map points with a claim: the Sim3 and relocalisation forms (xfh_map_project / xfh_map_projection_search*) ----
+    MAPPROJ_OUT_INT = ("match_idx", "best_dist", "n_window", "n_tested", "level")
+
+    @staticmethod
+    def map_project(Tcw, Ow, cam, bounds, th: float, scale_factors, ratio_max, form: int, xyz, normals, distances):
+        """xfh_map_project (host): the per-point arithmetic of the map-point SearchByProjection forms for one pose -> (uvr[n][3], level[n], status[n])"""
+        T = np.ascontiguousarray(Tcw, np.float32).reshape(12); O = np.ascontiguousarray(Ow, np.float32).reshape(3)
+        sf = np.ascontiguousarray(scale_factors, np.float32); rm = np.ascontiguousarray(ratio_max, np.float32)
+        p = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3); nr = np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
+        d = np.ascontiguousarray(distances, np.float32).reshape(-1, 3)
+        n = len(p)
+        assert len(nr) == n and len(d) == n and len(rm) >= len(sf) - 1
+        uvr = np.zeros((max(n, 1), 3), np.float32); lv = np.zeros(max(n, 1), np.int32); st = np.zeros(max(n, 1), np.uint8)
+        check(lib().xfh_map_project(T.ctypes.data, O.ctypes.data, C.byref(cam), C.byref(capi.GridBounds(*bounds)), float(th), sf.ctypes.data, rm.ctypes.data,
+                                    len(sf), int(form), p.ctypes.data, nr.ctypes.data, d.ctypes.data, n, uvr.ctypes.data, lv.ctypes.data, st.ctypes.data))
+        return uvr[:n], lv[:n], st[:n]
+
+    @staticmethod
+    def map_projection_search_workspace_bytes(nq: int, nt: int, B: int = 1) -> int:
+        return int(lib().xfh_map_projection_search_workspace_bytes(nq, nt, B))
+
+    @staticmethod
+    def map_projection_search_layout(B: int, nq: int, nt: int, guard: int = 0):
+        """byte offsets of the outputs of map_projection_search_device inside one buffer (and its size under "bytes"); guard as in
+        fuse_search_layout.  The workspace is a buffer of its own (map_projection_search_workspace_bytes)."""
+        al = lambda x: (x + 255) & ~255
+        o, off = {}, al(guard)
+        for name, nbytes in (("match_idx", 4 * B * nq), ("best_dist", 4 * B * nq), ("n_window", 4 * B * nq), ("n_tested", 4 * B * nq), ("level", 4 * B * nq),
+                             ("proj", 12 * B * nq), ("assigned", 4 * B * nt), ("n_matches", 4 * B), ("status", B * nq)):
+            o[name] = off; off += al(nbytes) + al(guard)
+        o["bytes"] = off
+        return o
+
+    def map_projection_search_device(self, form: int, B: int, nq: int, d_points, d_normals, d_distances, d_query_desc, d_query_flags, d_Tcw, d_Ow, cam, bounds,
+                                     th: float, scale_factors, ratio_max, d_grids, d_targets, target_stride: int, target_shared: int, nt: int, d_workspace,
+                                     d_out, d_taken=None, init_dist: int = 256, accept_max: float = 100.0, proj: bool = True, guard: int = 0):
+        """xfh_map_projection_search_device on device pointers; asynchronous.  d_out: pointer to the outputs laid out as
+        map_projection_search_layout(B, nq, nt, guard) says (proj = False: the proj block is left alone)"""
+        o = self.map_projection_search_layout(B, nq, nt, guard)
+        sf = np.ascontiguousarray(scale_factors, np.float32); rm = np.ascontiguousarray(ratio_max, np.float32)
+        check(lib().xfh_map_projection_search_device(self.h, int(form), B, nq, d_points, d_normals, d_distances, d_query_desc, d_query_flags, d_Tcw, d_Ow,
+                                                     C.byref(cam), C.byref(capi.GridBounds(*bounds)), float(th), sf.ctypes.data, rm.ctypes.data, len(sf), d_grids,
+                                                     d_targets, target_stride, int(target_shared), nt, d_taken, int(init_dist), float(accept_max), d_workspace,
+                                                     d_out + o["status"], *[d_out + o[k] for k in self.MAPPROJ_OUT_INT], d_out + o["proj"] if proj else None,
+                                                     d_out + o["assigned"], d_out + o["n_matches"]), self.h)
+
+    def map_projection_search(self, form: int, points, normals, distances, query_desc, query_flags, Tcw, Ow, cam, bounds, th: float, scale_factors, ratio_max,
+                              kps, targets, taken=None, init_dist: int = 256, accept_max: float = 100.0):
+        """xfh_map_projection_search (host pointers, one problem) -> dict(status, match_idx, best_dist, n_window, n_tested, level, proj, assigned, n_matches)"""
+        p = np.ascontiguousarray(points, np.float32).reshape(-1, 3); nr = np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
+        d = np.ascontiguousarray(distances, np.float32).reshape(-1, 3); q = np.ascontiguousarray(query_desc, np.float32)
+        fl = np.ascontiguousarray(query_flags, np.uint8); k = np.ascontiguousarray(kps, KP_DTYPE); tg = np.ascontiguousarray(targets, np.float32)
+        T = np.ascontiguousarray(Tcw, np.float32).reshape(12); O = np.ascontiguousarray(Ow, np.float32).reshape(3)
+        sf = np.ascontiguousarray(scale_factors, np.float32); rm = np.ascontiguousarray(ratio_max, np.float32)
+        nq, nt = len(p), len(k)
+        tk = None if taken is None else np.ascontiguousarray(taken, np.uint8)
+        assert len(nr) == nq and len(d) == nq and len(q) == nq and len(fl) == nq and len(tg) == nt and len(rm) >= len(sf) - 1 and (tk is None or len(tk) == nt)
+        st = np.zeros(nq, np.uint8); oi = [np.zeros(nq, np.int32) for _ in range(5)]; proj = np.zeros((nq, 3), np.float32)
+        asg = np.zeros(nt, np.int32); nm = np.zeros(1, np.int32)
+        check(lib().xfh_map_projection_search(self.h, int(form), nq, p.ctypes.data, nr.ctypes.data, d.ctypes.data, q.ctypes.data, fl.ctypes.data, T.ctypes.data,
+                                              O.ctypes.data, C.byref(cam), C.byref(capi.GridBounds(*bounds)), float(th), sf.ctypes.data, rm.ctypes.data, len(sf),
+                                              k.ctypes.data, tg.ctypes.data, nt, None if tk is None else tk.ctypes.data, int(init_dist), float(accept_max),
+                                              st.ctypes.data, *[o.ctypes.data for o in oi], proj.ctypes.data, asg.ctypes.data, nm.ctypes.data), self.h)
+        r = dict(zip(self.MAPPROJ_OUT_INT, oi))
+        r.update(status=st, proj=proj, assigned=asg, n_matches=int(nm[0]))
+        return r
+
+    # -- SearchBySim3: two keyframes' map points into each other (xfh_sim3_project / xfh_sim3_search*) ---------------------------
+    SIM3_OUT_INT = ("match", "best_dist", "n_window", "n_tested", "level")
+
+    @staticmethod
+    def sim3_project(Tqw, M, cam, bounds, th: float, scale_factors, ratio_max, xyz, distances):
+        """xfh_sim3_project (host): the per-point arithmetic of ORBmatcher::SearchBySim3 for one pose and one Sim3 -> (uvr[n][3], level[n], status[n])"""
+        T = np.ascontiguousarray(Tqw, np.float32).reshape(12); Mm = np.ascontiguousarray(M, np.float32).reshape(12)
+        sf = np.ascontiguousarray(scale_factors, np.float32); rm = np.ascontiguousarray(ratio_max, np.float32)
+        p = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3); d = np.ascontiguousarray(distances, np.float32).reshape(-1, 3)
+        n = len(p)
+        assert len(d) == n and len(rm) >= len(sf) - 1
+        uvr = np.zeros((max(n, 1), 3), np.float32); lv = np.zeros(max(n, 1), np.int32); st = np.zeros(max(n, 1), np.uint8)
+        check(lib().xfh_sim3_project(T.ctypes.data, Mm.ctypes.data, C.byref(cam), C.byref(capi.GridBounds(*bounds)), float(th), sf.ctypes.data, rm.ctypes.data,
+                                     len(sf), p.ctypes.data, d.ctypes.data, n, uvr.ctypes.data, lv.ctypes.data, st.ctypes.data))
+        return uvr[:n], lv[:n], st[:n]
+
+    @staticmethod
+    def sim3_search_layout(B: int, n1: int, n2: int, guard: int = 0):
+        """byte offsets of the outputs of sim3_search_device inside one buffer (and its size under "bytes"): the per-side arrays under
+        "match1", "status2", ..., then "match12" and "n_found"; guard as in fuse_search_layout"""
+        al = lambda x: (x + 255) & ~255
+        o, off = {}, al(guard)
+        for s, n in (("1", n1), ("2", n2)):
+            for name, nbytes in (("match", 4 * B * n), ("best_dist", 4 * B * n), ("n_window", 4 * B * n), ("n_tested", 4 * B * n), ("level", 4 * B * n),
+                                 ("proj", 12 * B * n), ("status", B * n)):
+                o[name + s] = off; off += al(nbytes) + al(guard)
+        for name, nbytes in (("match12", 4 * B * n1), ("n_found", 4 * B)):
+            o[name] = off; off += al(nbytes) + al(guard)
+        o["bytes"] = off
+        return o
+
+    @staticmethod
+    def sim3_side(n: int, grid, desc, desc_stride: int, points, dist, mp_desc, flags, Tw, out, lay, s: str, proj: bool = True, kps=None):
+        """one xfh_sim3_side from pointers (ints); its outputs lie at out + lay[name + s] (sim3_search_layout)"""
+        return capi.Sim3Side(n, grid, kps, desc, desc_stride, points, dist, mp_desc, flags, Tw, out + lay["status" + s],
+                             *[out + lay[k + s] for k in Context.SIM3_OUT_INT], out + lay["proj" + s] if proj else None)
+
+    def sim3_search_device(self, B: int, side1_shared: int, side1, side2, d_M21, d_M12, cam, bounds, th: float, scale_factors, ratio_max, d_match12,
+                           d_n_found, th_high: int = 1000):
+        """xfh_sim3_search_device on device pointers; asynchronous.  side1 / side2: capi.Sim3Side (Context.sim3_side)"""
+        sf = np.ascontiguousarray(scale_factors, np.float32); rm = np.ascontiguousarray(ratio_max, np.float32)
+        check(lib().xfh_sim3_search_device(self.h, B, int(side1_shared), C.byref(side1), C.byref(side2), d_M21, d_M12, C.byref(cam),
+                                           C.byref(capi.GridBounds(*bounds)), float(th), sf.ctypes.data, rm.ctypes.data, len(sf), int(th_high), d_match12,
+                                           d_n_found), self.h)
+
+    def sim3_search(self, side1, side2, M21, M12, cam, bounds, th: float, scale_factors, ratio_max, th_high: int = 1000):
+        """xfh_sim3_search (host pointers, one pair).  side = dict(kps, desc, points, dist, mp_desc, flags, Tw) -> dict(match12, n_found, and per
+        side s in "12": status, match, best_dist, n_window, n_tested, level, proj under name + s)"""
+        sf = np.ascontiguousarray(scale_factors, np.float32); rm = np.ascontiguousarray(ratio_max, np.float32)
+        f32 = lambda a: np.ascontiguousarray(a, np.float32)
+        keep, sides, r = [], [], {}
+        for s, sd in (("1", side1), ("2", side2)):
+            k = np.ascontiguousarray(sd["kps"], KP_DTYPE); n = len(k)
+            a = [f32(sd["desc"]), f32(sd["points"]).reshape(-1, 3), f32(sd["dist"]).reshape(-1, 3), f32(sd["mp_desc"]), np.ascontiguousarray(sd["flags"], np.uint8),
+                 f32(sd["Tw"]).reshape(12)]
+            assert all(len(x) == n for x in a[:5]) and len(rm) >= len(sf) - 1
+            st = np.zeros(n, np.uint8); oi = [np.zeros(n, np.int32) for _ in range(5)]; proj = np.zeros((n, 3), np.float32)
+            keep += [k, a, st, oi, proj]
+            sides.append(capi.Sim3Side(n, None, k.ctypes.data, a[0].ctypes.data, 0, *[x.ctypes.data for x in a[1:]], st.ctypes.data,
+                                       *[o.ctypes.data for o in oi], proj.ctypes.data))
+            r.update({name + s: o for name, o in zip(self.SIM3_OUT_INT, oi)})
+            r["status" + s] = st; r["proj" + s] = proj
+        m21, m12 = f32(M21).reshape(12), f32(M12).reshape(12)
+        match12 = np.zeros(sides[0].n, np.int32); nf = np.zeros(1, np.int32)
+        check(lib().xfh_sim3_search(self.h, C.byref(sides[0]), C.byref(sides[1]), m21.ctypes.data, m12.ctypes.data, C.byref(cam), C.byref(capi.GridBounds(*bounds)),
+                                    float(th), sf.ctypes.data, rm.ctypes.data, len(sf), int(th_high), match12.ctypes.data, nf.ctypes.data), self.h)
+        r.update(match12=match12, n_found=int(nf[0]))
+        return r
+
     # -- timing ---------------------------------------------------------------------------
     def timing_enable(self, kernel_id: int, layer_mask: int = 0):
         check(lib().xfh_timing_enable(self.h, kernel_id, layer_mask), self.h)
@@ -673,6 +809,44 @@ class ORBmatcher:
         r = self.ctx.bow_search(node_of1, has1, desc1, node_of2, desc2, eligible2=has2, strict_low=True, init_dist=256, th_low=self.TH_LOW,
                                 nn_ratio=self.mfNNratio)
         return r["n_matches"], r["match12"], r
+
+    def _map_projection(self, form, accept_max, points, normals, distances, query_desc, query_flags, Tcw, Ow, cam, bounds, th, scale_factors, kps, targets, taken,
+                        ratio_max):
+        sf = np.ascontiguousarray(scale_factors, np.float32)
+        if ratio_max is None:
+            ratio_max = Context.scale_level_thresholds(float(sf[1]) if len(sf) > 1 else 1.2, len(sf))
+        r = self.ctx.map_projection_search(form, points, normals, distances, query_desc, query_flags, Tcw, Ow, cam, bounds, th, sf, ratio_max, kps, targets,
+                                           taken=taken, init_dist=256, accept_max=accept_max)
+        return r["n_matches"], r
+
+    def searchByProjectionSim3(self, points, normals, distances, query_desc, query_flags, Tcw, Ow, cam, bounds, th: float, ratioHamming: float, scale_factors,
+                               kps, targets, taken=None, with_keyframes: bool = False, ratio_max=None):
+        """`ORBmatcher::SearchByProjection(KeyFrame*, Sim3f& Scw, vpPoints, vpMatched, th, ratioHamming)` (ORBmatcher.cc:612-717; with_keyframes: the
+        form of :719-831 with vpPointsKFs / vpMatchedKF, which projects with invz) for one keyframe.  Tcw = [R | t/s] and Ow from the caller's
+        decomposition of Scw; taken[k] != 0 where vpMatched[k] is set at entry.  -> (nmatches, result dict of Context.map_projection_search);
+        the caller writes vpMatched[k] = vpPoints[assigned[k]] (and vpMatchedKF[k] = vpPointsKFs[assigned[k]]) where assigned[k] >= 0."""
+        accept = float(np.float32(self.TH_LOW) * np.float32(ratioHamming))                       # TH_LOW*ratioHamming: int times float (:708)
+        return self._map_projection(capi.MAPPROJ_FORM_SIM3_KF if with_keyframes else capi.MAPPROJ_FORM_SIM3, accept, points, normals, distances, query_desc,
+                                    query_flags, Tcw, Ow, cam, bounds, th, scale_factors, kps, targets, taken, ratio_max)
+
+    def searchByProjectionReloc(self, points, normals, distances, query_desc, query_flags, Tcw, Ow, cam, bounds, th: float, ORBdist: int, scale_factors,
+                                kps, targets, taken=None, ratio_max=None):
+        """`ORBmatcher::SearchByProjection(Frame& CurrentFrame, KeyFrame*, sAlreadyFound, th, ORBdist)` (ORBmatcher.cc:2074-2195) for one candidate
+        keyframe: its map points (in keypoint order) into the current frame.  taken[k] != 0 where CurrentFrame.mvpMapPoints[k] is set at entry;
+        normals are not read by this form.  -> (nmatches, result dict); the caller writes mvpMapPoints[k] where assigned[k] >= 0."""
+        return self._map_projection(capi.MAPPROJ_FORM_RELOC, float(np.float32(int(ORBdist))), points, normals, distances, query_desc, query_flags, Tcw, Ow, cam,
+                                    bounds, th, scale_factors, kps, targets, taken, ratio_max)
+
+    def searchBySim3(self, side1, side2, M21, M12, cam, bounds, th: float, scale_factors, ratio_max=None):
+        """`ORBmatcher::SearchBySim3` for one keyframe pair (ORBmatcher.cc:1642-1859).  side = dict(kps, desc, points, dist, mp_desc, flags, Tw) as
+        Context.sim3_search takes it (flags bit0 = `pMP && !vbAlreadyMatched[i] && !pMP->isBad()`); M21 / M12 = the 3x4 [s*R | t] of S12.inverse() and
+        S12.  -> (nFound, match12 = per keypoint of keyframe 1 the keypoint of keyframe 2 or -1, result dict of Context.sim3_search); the
+        caller writes vpMatches12[i1] = vpMapPoints2[match12[i1]] (:1852)."""
+        sf = np.ascontiguousarray(scale_factors, np.float32)
+        if ratio_max is None:
+            ratio_max = Context.scale_level_thresholds(float(sf[1]) if len(sf) > 1 else 1.2, len(sf))
+        r = self.ctx.sim3_search(side1, side2, M21, M12, cam, bounds, th, sf, ratio_max, th_high=self.TH_HIGH)
+        return r["n_found"], r["match12"], r
 
     def match(self, desc1: np.ndarray, desc2: np.ndarray, min_cossim: float = -1.0):
         """-> list of (queryIdx, trainIdx, distance) like std::vector<cv::DMatch>"""
