@@ -18,6 +18,9 @@
  *        forms of SearchByProjection (ORBmatcher.cc:612-717, :719-831), the relocalisation form (:2074-2195) and SearchBySim3 (:1642-1859), each
  *        as one call.  The caller keeps what needs Sophus or the map: the decomposition of Scw into Tcw = [R | t/s] and Ow (:621-622), S12 and its
  *        inverse as 3x4 [s*R | t], vbAlreadyMatched (:1662-1675, folded into the flag bytes) and the pointer writes behind the matches
+ *   XFmatcher::searchForInitialization: ORBmatcher::SearchForInitialization (ORBmatcher.cc:833-948), the matcher of
+ *        Tracking::MonocularInitialization, with the reference's retraction order as one call; vbPrevMatched travels as (x, y) floats and is
+ *        updated in place
  *   best2 / distinctive: the batched inner loops of SearchBy* (ORBmatcher.cc:75-119) and of
  *        MapPoint::ComputeDistinctiveDescriptors (MapPoint.cc:329-403)
  *
@@ -118,6 +121,12 @@ public:
         host_x.clear(); host_y.clear(); side_host = false;
     }
     const void* device() const { return d_grid; }
+    // the coordinates the grid was built from as (x, y) pairs, on the host (a keypoint the grid dropped reads 0, 0 when the grid came from a record)
+    void keysXY(std::vector<float>& xy) {
+        unpack();
+        xy.resize(2 * (size_t)(n > 0 ? n : 0));
+        for (int i = 0; i < n; ++i) { xy[2 * (size_t)i] = host_x[i]; xy[2 * (size_t)i + 1] = host_y[i]; }
+    }
     int size() const { return n; }
     // device arrays of the last buildFromRecord(.., cam, ..): xy_un[n][2], uright[n], depth[n] (nullptr before it)
     float* deviceKeysUn() const { return (float*)d_side; }
@@ -670,6 +679,79 @@ public:
     const std::vector<int>& lastSim3Tested(int side) const { return sim3Tested[side == 2]; }
     const std::vector<int>& lastSim3Level(int side) const { return sim3Level[side == 2]; }
 
+    // ORBmatcher::SearchForInitialization(F1, F2, vbPrevMatched, vnMatches12, windowSize) (ORBmatcher.cc:833-948) as ONE call (xfh_init_search_device)
+    // with the reference's retraction order: a later query that is strictly closer takes a keypoint away from an earlier one, whose match is
+    // then gone for good.  `queries` = F1.mDescriptors, vbPrevMatched = the window centres as (x, y) pairs, updated in place as :943-945 do;
+    // `grid` / `targets` = F2's grid (on mvKeysUn) and F2.mDescriptors; flags: bit0 clear leaves a query out (nullptr: all take part, the
+    // reference).  mfNNratio and TH_LOW are the matcher's; the level test and the rotation histogram remove nothing (every XFeat keypoint has
+    // octave 0 and angle -1).  The return value is nmatches.  Blocks until the result is on the host.
+    int searchForInitialization(const Mat& queries, std::vector<float>& vbPrevMatched, XFgrid& grid, const Mat& targets, std::vector<int>& vnMatches12,
+                                int windowSize = 10, const std::vector<unsigned char>* flags = nullptr) {
+        const int nq = queries.rows, nt = targets.rows;
+        if (nq == 0 || nt == 0) { initReset(nq, nt, vnMatches12); return 0; }
+        if ((int)vbPrevMatched.size() != 2 * nq || nt != grid.size() || (flags && (int)flags->size() != nq))
+            throw std::runtime_error("XFmatcher::searchForInitialization: sizes do not fit");
+        std::vector<float> xy;
+        grid.keysXY(xy);
+        auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+        const size_t bq = al((size_t)nq * 256), bp = al((size_t)nq * 8), bfl = al((size_t)nq), bt = al((size_t)nt * 256), bx = al((size_t)nt * 8);
+        reserve(d_out, d_out_bytes, bq + bp + bfl + bt + bx, "XFmatcher::searchForInitialization");
+        char* p = (char*)d_out;
+        float* dq = (float*)p; p += bq; float* dp = (float*)p; p += bp; unsigned char* dfl = (unsigned char*)p; p += bfl; float* dt = (float*)p; p += bt;
+        float* dx = (float*)p;
+        int rc = xfh_synchronize(ctx);                       // (the copies below are synchronous: nothing queued earlier may still read the buffer)
+        if (rc == XFH_OK) rc = xfh_memcpy_h2d(dq, queries.template ptr<float>(0), (size_t)nq * 256);
+        if (rc == XFH_OK) rc = xfh_memcpy_h2d(dp, vbPrevMatched.data(), (size_t)nq * 8);
+        if (rc == XFH_OK && flags) rc = xfh_memcpy_h2d(dfl, flags->data(), (size_t)nq);
+        if (rc == XFH_OK) rc = xfh_memcpy_h2d(dt, targets.template ptr<float>(0), (size_t)nt * 256);
+        if (rc == XFH_OK) rc = xfh_memcpy_h2d(dx, xy.data(), (size_t)nt * 8);
+        if (rc != XFH_OK) throw std::runtime_error(std::string("XFmatcher::searchForInitialization: ") + xfh_strerror(rc));
+        const int nmatches = searchForInitialization(nq, dq, dp, flags ? dfl : nullptr, grid, dt, dx, vnMatches12, windowSize);
+        if (xfh_memcpy_d2h(vbPrevMatched.data(), dp, (size_t)nq * 8) != XFH_OK) throw std::runtime_error("XFmatcher::searchForInitialization: download failed");
+        return nmatches;
+    }
+    // The same on DEVICE pointers and an XFgrid (F2 finished with XFgrid::buildFromRecord(record, n, camera, ..): d_targets = the record's
+    // descriptor block, d_targetXY = grid.deviceKeysUn()).  d_prevMatched [nq][2] is updated in place; with d_targetXY = nullptr it is left
+    // as it is.  Only the results travel to the host.
+    int searchForInitialization(int nq, const float* d_queries, float* d_prevMatched, const unsigned char* d_flags, const XFgrid& grid, const float* d_targets,
+                                const float* d_targetXY, std::vector<int>& vnMatches12, int windowSize = 10) {
+        const int nt = grid.size();
+        initReset(nq > 0 ? nq : 0, nt > 0 ? nt : 0, vnMatches12);
+        if (nq <= 0 || nt <= 0) return 0;
+        auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+        const size_t bw = al(xfh_init_search_workspace_bytes(nq, nt, 1)), bn = al((size_t)nq * 4), ba = al((size_t)nt * 4), bs = al((size_t)nq);
+        if (bw == 0) throw std::runtime_error("XFmatcher::searchForInitialization: sizes out of range");
+        reserve(d_proj, d_proj_bytes, bw + 6 * bn + 2 * ba + bs + 256, "XFmatcher::searchForInitialization");
+        char* p = (char*)d_proj;
+        void* dws = p; p += bw;
+        int* o[6];
+        for (int k = 0; k < 6; ++k) { o[k] = (int*)p; p += bn; }
+        int* d21 = (int*)p; p += ba; int* dmd = (int*)p; p += ba; unsigned char* dst = (unsigned char*)p; p += bs; int* dnm = (int*)p;
+        int rc = xfh_init_search_device(ctx, 1, nq, d_queries, d_prevMatched, d_flags, (float)windowSize, grid.device(), d_targets, 0, d_targetXY, nt, TH_LOW,
+                                        mfNNratio, dws, dst, o[0], o[1], o[2], o[3], o[4], o[5], d21, dmd, dnm, d_targetXY ? d_prevMatched : nullptr);
+        if (rc == XFH_OK) rc = xfh_synchronize(ctx);
+        int nmatches = 0;
+        int* out[6] = {initClaim.data(), vnMatches12.data(), initBest.data(), initSecond.data(), initWindow.data(), initTested.data()};
+        for (int k = 0; k < 6 && rc == XFH_OK; ++k) rc = xfh_memcpy_d2h(out[k], o[k], (size_t)nq * 4);
+        if (rc == XFH_OK) rc = xfh_memcpy_d2h(initStatus.data(), dst, (size_t)nq);
+        if (rc == XFH_OK) rc = xfh_memcpy_d2h(initMatches21.data(), d21, (size_t)nt * 4);
+        if (rc == XFH_OK) rc = xfh_memcpy_d2h(initMatchedDistance.data(), dmd, (size_t)nt * 4);
+        if (rc == XFH_OK) rc = xfh_memcpy_d2h(&nmatches, dnm, 4);
+        if (rc != XFH_OK) throw std::runtime_error(std::string("XFmatcher::searchForInitialization: ") + xfh_strerror(rc));
+        return nmatches;
+    }
+    // of the last searchForInitialization.  Per query of F1: XFH_INIT_* status, the keypoint it wrote when its turn came (-1: none; a retracted
+    // query keeps it), best / second DescriptorDistance (INT_MAX: none), window members, members compared when its turn came.  Per keypoint of
+    // F2: vnMatches21 and vMatchedDistance
+    const std::vector<unsigned char>& lastInitStatus() const { return initStatus; }
+    const std::vector<int>& lastInitClaim() const { return initClaim; }
+    const std::vector<int>& lastInitBestDist() const { return initBest; }
+    const std::vector<int>& lastInitSecondDist() const { return initSecond; }
+    const std::vector<int>& lastInitWindow() const { return initWindow; }
+    const std::vector<int>& lastInitTested() const { return initTested; }
+    const std::vector<int>& lastInitMatches21() const { return initMatches21; }
+    const std::vector<int>& lastInitMatchedDistance() const { return initMatchedDistance; }
+
     // ORBmatcher::SearchForTriangulation(pKF1, pKF2, vMatchedPairs, bOnlyStereo, bCoarse) (ORBmatcher.cc:1092-1331; mbCheckOrientation = false as
     // LocalMapping builds the matcher, no second camera) as ONE call (xfh_triangulation_search): every keypoint of KF1 without a map point
     // against the keypoints of KF2 without one that share its vocabulary node, under the epipole radius and the epipolar test.  Per keyframe:
@@ -894,6 +976,11 @@ protected:
         if (rc != XFH_OK) throw std::runtime_error(std::string("XFmatcher::searchByProjection: ") + xfh_strerror(rc));
         return nmatches;
     }
+    void initReset(int nq, int nt, std::vector<int>& vnMatches12) {
+        vnMatches12.assign(nq, -1);
+        initStatus.assign(nq, 0); initClaim.assign(nq, -1); initBest.assign(nq, 0x7fffffff); initSecond.assign(nq, 0x7fffffff); initWindow.assign(nq, 0);
+        initTested.assign(nq, 0); initMatches21.assign(nt, -1); initMatchedDistance.assign(nt, 0x7fffffff);
+    }
     void bowReset(int n1, int n2, std::vector<int>& matchOfQuery, std::vector<int>& assignedQuery) {
         matchOfQuery.assign(n1, -1); assignedQuery.assign(n2, -1);
         bowStatus.assign(n1, 0); bowBest.assign(n1, 256); bowSecond.assign(n1, 256); bowCandidates.assign(n1, 0);
@@ -925,6 +1012,8 @@ protected:
     std::vector<int> triMatch, triBest, triCandidates, triGeom;
     std::vector<unsigned char> bowStatus;                   // results of searchByBoW
     std::vector<int> bowBest, bowSecond, bowCandidates;
+    std::vector<unsigned char> initStatus;                  // results of searchForInitialization
+    std::vector<int> initClaim, initBest, initSecond, initWindow, initTested, initMatches21, initMatchedDistance;
 };
 
 }  // namespace ORB_SLAM3

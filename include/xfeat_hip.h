@@ -25,7 +25,8 @@
  *     (xfh_record_*, xfh_*_bytes, xfh_compact_bytes_max); xfh_create itself may run on
  *     several threads at once (without a device each call returns XFH_ERR_NO_DEVICE).
  *     xfh_map_project, xfh_sim3_project and xfh_map_projection_search_workspace_bytes are stateless in the same way (a loop over
- *     one pure function, no static data); they are not part of the ThreadSanitizer run.
+ *     one pure function, no static data); they are not part of the ThreadSanitizer run.  So are xfh_init_accept,
+ *     xfh_init_list_entries and xfh_init_search_workspace_bytes.
  *
  * The C++ wrappers that restore the reference's class surface on top of this ABI are
  * include/xfeat/XFextractor.h and include/xfeat/ORBmatcher_xfeat.h; INTEGRATION.md shows
@@ -738,8 +739,8 @@ int xfh_triangulation_search(xfh_ctx* ctx, int n1, int n2, int flags, int th_low
  *                         the call and copies the results back.  XFH_ERR_INVALID_ARG for the device form's classes of error before
  *                         anything is staged or queued.
  * Out of scope: the Nleft != -1 branches (fisheye stereo); computing the BoW or feature vector (DBoW2 stays with the caller);
- * SearchForInitialization (the relocalisation and Sim3 SearchByProjection forms are xfh_map_projection_search_device, SearchBySim3 is
- * xfh_sim3_search_device, both below); the PnP and Sim3 solvers that consume the matches. */
+ * (SearchForInitialization is xfh_init_search_device, the relocalisation and Sim3 SearchByProjection forms are
+ * xfh_map_projection_search_device, SearchBySim3 is xfh_sim3_search_device, all below); the PnP and Sim3 solvers that consume the matches. */
 #define XFH_BOW_STRICT_LOW 1          /* flags: accept on best < th_low (the keyframe form) instead of best <= th_low */
 enum { XFH_BOW_INACTIVE = 0, XFH_BOW_NO_NODE = 1, XFH_BOW_NO_CANDIDATES = 2, XFH_BOW_REJECTED = 3, XFH_BOW_MATCHED = 4 };
 int xfh_bow_accept(int best_idx, int best, int second, int th_low, float nn_ratio, int flags);
@@ -830,7 +831,7 @@ int xfh_bow_search(xfh_ctx* ctx, int n1, int n2, int flags, int init_dist, int t
  *                         nt keypoints (x, y = the undistorted coordinates) with flags 0 and `bounds`, runs the call and copies the results
  *                         back.  XFH_ERR_INVALID_ARG for the device form's classes of error (and bounds no grid can be built from) before
  *                         anything is staged or queued.
- * Out of scope: SearchForInitialization (monocular initialisation only; its retraction rule needs another resolution scheme); fisheye
+ * Out of scope: fisheye
  * stereo; the PnP and Sim3 solvers that consume the matches. */
 #define XFH_MAPPROJ_FLAG_ACTIVE 1     /* d_query_flags bit0 */
 #define XFH_MAPPROJ_CULL_BEHIND 1     /* form bits */
@@ -924,7 +925,7 @@ int xfh_map_projection_search(xfh_ctx* ctx, int form, int nq, const float* point
  *                         inputs, builds both grids with flags 0 and `bounds`, runs the call and copies the results back.
  *                         XFH_ERR_INVALID_ARG for the device form's classes of error (and bounds no grid can be built from) before
  *                         anything is staged or queued.
- * Out of scope: SearchForInitialization; fisheye stereo; the Sim3 solver that produces S12 and consumes the matches. */
+ * Out of scope: fisheye stereo; the Sim3 solver that produces S12 and consumes the matches. */
 #define XFH_SIM3_FLAG_ACTIVE 1        /* flags bit0 */
 enum { XFH_SIM3_INACTIVE = 0, XFH_SIM3_BEHIND = 1, XFH_SIM3_OUT_OF_IMAGE = 2, XFH_SIM3_OUT_OF_RANGE = 3,
        XFH_SIM3_NO_CANDIDATES = 5, XFH_SIM3_REJECTED = 6, XFH_SIM3_FOUND = 7,
@@ -951,6 +952,99 @@ int xfh_sim3_search_device(xfh_ctx* ctx, int B, int side1_shared, const xfh_sim3
 int xfh_sim3_search(xfh_ctx* ctx, const xfh_sim3_side* side1, const xfh_sim3_side* side2, const float* M21, const float* M12, const xfh_camera* cam,
                     const xfh_grid_bounds* bounds, float th, const float* scale_factors, const float* ratio_max, int nlevels, int th_high,
                     int* match12, int* n_found);
+
+/* ---- SearchForInitialization with the reference's retraction order, device resident ----------------------------------------------------
+ * ORBmatcher::SearchForInitialization(F1, F2, vbPrevMatched, vnMatches12, windowSize) (src/ORBmatcher.cc:833-948), the first matcher of a
+ * monocular session: Tracking::MonocularInitialization calls it on every frame until the map initialises (Tracking.cc:2518-2519:
+ * ORBmatcher(0.9, true), windowSize = 100) and carries mvbPrevMatched from call to call.  Unlike every other matcher here a keypoint of
+ * F2 is never "taken": a later query may take it away from an earlier one if it is strictly closer (vMatchedDistance, :872), and the
+ * earlier query's match is then RETRACTED (:891-895) without a second try.  The loop is sequential in the query order; the library
+ * resolves it on the device and gives the sequential answer.
+ *
+ * Problem b is one pair (initial frame F1, current frame F2): nq query keypoints of F1 with their descriptor rows and prev_matched[nq][2]
+ * (the window centres, vbPrevMatched); F2's grid blob, its nt descriptor rows and optionally its undistorted coordinates target_xy[nt][2]
+ * (mvKeysUn[k].pt).  The loop; all integer comparisons are exact, the one float expression is fp32 in the order written (the library is
+ * built with -ffp-contract=off):
+ *
+ *   matched_distance[k] = INT_MAX; matches21[k] = -1 for k in [0, nt); matches12[q] = -1; n_matches = 0
+ *   for q = 0 .. nq-1, in this order:
+ *     query_flags given and bit0 clear                    -> INACTIVE   (the caller's `level1 > 0`, :850, or slots it wants left out; NULL =
+ *                                                                        all active, which is the reference: padding slots included)
+ *     (u, v) = prev_matched[q];  r = window (one float per call, (float)windowSize)
+ *     n_window = members of the window, exactly xfh_search_window_device's window; a non-finite u or v has none
+ *     n_window == 0                                       -> NO_CANDIDATES  (:855)
+ *     best = second = INT_MAX; best_idx = -1; n_tested = 0
+ *     per member k in visiting order:  d = DescriptorDistance(q, k)
+ *         matched_distance[k] <= d -> skipped             (:872, '<=': an equal distance is blocked)
+ *         ++n_tested;  d < best ? (second = best, best = d, best_idx = k) : (d < second ? second = d : nothing)     (xfh_best2_csr's rule:
+ *                                                          strict '<', the first visited wins a tie)
+ *     accept = best_idx >= 0 && best <= th_low && (float)best < (float)second * nn_ratio      (:887-889; second == INT_MAX when there is none)
+ *     !accept -> REJECTED
+ *     accept  -> MATCHED: if matches21[best_idx] >= 0 { matches12[matches21[best_idx]] = -1; --n_matches }           (:891-895, the retraction)
+ *                claim_idx[q] = matches12[q] = best_idx;  matches21[best_idx] = q;  matched_distance[best_idx] = best;  ++n_matches
+ *   after the loop:  prev_out[q] = matches12[q] >= 0 ? target_xy[matches12[q]] : prev_matched[q]                      (:943-945)
+ *
+ * DescriptorDistance here is xfh_descriptor_distance where the fp32 squared norm is below 2^31 / 512, and INT_MAX otherwise (Inf, NaN):
+ * such a member is always skipped (INT_MAX <= INT_MAX), so rows may hold anything.  The level window (level1, level1) = (0, 0) of :853
+ * admits every XFeat keypoint, and the rotation histogram (:901-940) removes nothing: every XFeat keypoint has octave 0 and angle -1 (the
+ * argument of the projection contract above), so rot = 0 for every match, all land in bin 0, and mbCheckOrientation stays without effect.
+ * A retracted query keeps status MATCHED and its claim_idx: both say what the query did when its turn came; matches12 is the final
+ * vnMatches12.
+ *
+ * Outputs, all exact, all in device memory.  Per query: status (XFH_INIT_*), claim_idx (what q wrote when its turn came, -1 otherwise),
+ * matches12 (the final vnMatches12, i.e. after retractions), best_dist, second_dist (INT_MAX where there is none), n_window (0 for an
+ * inactive query) and n_tested (counted when q's turn came).  Per keypoint: matches21 and matched_distance (INT_MAX where unmatched).
+ * Per problem: n_matches.  prev_out and target_xy are given together or both NULL; prev_out may be the same pointer as prev_matched (the
+ * reference's in-place update): the window centres are copied into the workspace before anything is written.
+ *
+ * How it is made parallel.  A retracted query never searches again and matched_distance[k] only ever decreases, so when q's turn comes a
+ * member (k, d) is skipped iff d == INT_MAX or some accepting query j < q with claim_idx[j] == k has best_dist[j] <= d.  That is a
+ * triangular system like the claim rule: re-evaluating all queries against the previous round's (claim_idx, best_dist) reaches the
+ * sequential answer as its only fixed point, every query up to the smallest one that moved is final, so there are at most nq rounds.
+ * After the fixed point matches21[k] is the largest accepting q on k, matches12[q] = claim_idx[q] iff q is that one, and n_matches is the
+ * number of keypoints with an acceptor.  Three kernels: per query the nearest xfh_init_list_entries() members of its window; the resolver
+ * (one workgroup per problem, the acceptors of every keypoint chained in LDS, no global atomics, no waiting between workgroups, the round
+ * count decided on the device); and every query's turn against the final chains.  A query whose list runs out before its state is known
+ * is searched again in full inside the resolver, under the budget of xfh_search_projection_device.  The worst cases -- thousands of
+ * acceptors on one keypoint, thousands of queries on one spot -- cost what that call says of its worst case: exact and terminating, but
+ * seconds.
+ *
+ *   xfh_init_accept       host, stateless, thread-safe: the `accept` line for best_idx >= 0 (best == INT_MAX stands for "none": 0), 1 or 0.
+ *                         The same source line as the kernels (init_math.h).
+ *   xfh_init_list_entries   the length K of the per-query lists this build was made with (tests and tools ask; nothing depends on it).
+ *   xfh_init_search_workspace_bytes   bytes of d_workspace for B problems (0 for sizes the call would refuse).
+ *   xfh_init_search_device   B problems with the same nq, nt, window and thresholds.  d_query_desc [B][nq][64], d_prev_matched [B][nq][2],
+ *                         d_query_flags [B][nq] bytes or NULL; grid b at d_grids + b * xfh_grid_bytes(nt), target rows of problem b at
+ *                         d_targets + b * target_stride_bytes (0: one frame for all), d_target_xy [B][nt][2] or NULL: the layout of
+ *                         xfh_search_projection_device.  Outputs d_status [B][nq] bytes, d_claim_idx / d_matches12 / d_best_dist /
+ *                         d_second_dist / d_n_window / d_n_tested [B][nq] ints, d_matches21 / d_matched_distance [B][nt] ints, d_n_matches
+ *                         [B] ints, d_prev_out [B][nq][2] or NULL.  The first four ints of problem b's part of the workspace (which
+ *                         starts b * xfh_init_search_workspace_bytes(nq, nt, 1) bytes in) hold afterwards: rounds of the resolver,
+ *                         queries it searched again in full, lists that ran out (summed over the rounds), K.  All pointers are device
+ *                         pointers; asynchronous on the ctx stream, no allocation, no host synchronisation, THREE kernel launches.  nq, nt
+ *                         in 1 .. XFH_GRID_MAX_N, B in 1 .. 65535.  XFH_ERR_INVALID_ARG before anything is queued: those ranges, a
+ *                         non-finite window, nn_ratio negative or not finite, th_low < 0, target_xy without prev_out or the reverse, a
+ *                         NULL required pointer, misaligned pointers (16 bytes for descriptors, targets, the target stride, grids and the
+ *                         workspace, 4 otherwise).  Descriptors and coordinates may hold anything, NaN and Inf included: no load leaves
+ *                         the buffers the caller named, and no index outside [0, nt) is ever reported.
+ *   xfh_init_search       host-pointer convenience form for ONE problem: stages the inputs and the workspace, builds the grid of the nt
+ *                         keypoints (x, y = the undistorted coordinates, which are also target_xy) with flags 0 and `bounds`, runs the
+ *                         call and copies the results back; prev_out may be NULL or prev_matched itself.  XFH_ERR_INVALID_ARG for the
+ *                         device form's classes of error (and bounds no grid can be built from) before anything is staged or queued. */
+#define XFH_INIT_FLAG_ACTIVE 1        /* d_query_flags bit0 */
+enum { XFH_INIT_INACTIVE = 0, XFH_INIT_NO_CANDIDATES = 1, XFH_INIT_REJECTED = 2, XFH_INIT_MATCHED = 3 };
+int xfh_init_accept(int best, int second, int th_low, float nn_ratio);
+int xfh_init_list_entries(void);
+size_t xfh_init_search_workspace_bytes(int nq, int nt, int B);
+int xfh_init_search_device(xfh_ctx* ctx, int B, int nq, const float* d_query_desc, const float* d_prev_matched, const uint8_t* d_query_flags_or_null,
+                           float window, const void* d_grids, const float* d_targets, size_t target_stride_bytes, const float* d_target_xy_or_null, int nt,
+                           int th_low, float nn_ratio, void* d_workspace, uint8_t* d_status, int* d_claim_idx, int* d_matches12, int* d_best_dist,
+                           int* d_second_dist, int* d_n_window, int* d_n_tested, int* d_matches21, int* d_matched_distance, int* d_n_matches,
+                           float* d_prev_out_or_null);
+int xfh_init_search(xfh_ctx* ctx, int nq, const float* query_desc, const float* prev_matched, const uint8_t* query_flags_or_null, float window,
+                    const xfh_keypoint* kps, const xfh_grid_bounds* bounds, const float* targets, int nt, int th_low, float nn_ratio, uint8_t* status,
+                    int* claim_idx, int* matches12, int* best_dist, int* second_dist, int* n_window, int* n_tested, int* matches21,
+                    int* matched_distance, int* n_matches, float* prev_out_or_null);
 
 /* MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:329-403), batched over map points: group g observes the
  * descriptor rows indices[offsets[g] .. offsets[g+1]) of `table` (n_rows x 64).  Pairwise DescriptorDistance inside

@@ -26,6 +26,9 @@
 //                   the window walk with the K best candidates; k_proj_resolve / k_proj_count settle the claims behind it (mapproj_search.hip.h).
 //   k_sim3_search / k_sim3_agree : ORBmatcher::SearchBySim3 up to vpMatches12, B keyframe pairs per call: both directions of the projection through
 //                   S21 / S12 with the range and level culls and the window walk in one launch, then the agreement step (sim3_search.hip.h).
+//   k_init_candidates / k_init_resolve / k_init_final : ORBmatcher::SearchForInitialization, B frame pairs per call: per query the nearest members of
+//                   its window, then the reference's retraction order resolved per problem with the acceptors of every keypoint chained in LDS, then
+//                   every query's turn against the final chains (init_search.hip.h).
 //   k_distinctive_csr : MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:329-403), one wave per map point.
 //
 // Numerics: normalised rows and the 64-term dot products are bit-identical to the oracle
@@ -108,6 +111,7 @@ hipError_t launch_best2(xfh_ctx* c, const float* q, int nq, const float* tg, con
 #include "bow_search.hip.h"
 #include "mapproj_search.hip.h"
 #include "sim3_search.hip.h"
+#include "init_search.hip.h"
 
 // ---- k_distinctive_csr: MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:329-403), batched -------
 // One wave per group (map point).  Rows are taken 64 at a time, lane = row: the lane keeps its descriptor in

@@ -140,7 +140,8 @@ hipError_t launch_grid_build(xfh_ctx* c, const void* kps, size_t kps_stride, con
 //   window_walk   deals the positions to the lanes, applies the window test and the static filters plus the caller's `extra(slot, x, y)`
 //                 (x, y: the item's coordinates),
 //                 and calls visit(key, slot) for every survivor with key = dist << 32 | position (DIST = false: no descriptor is
-//                 read and the key's distance is 0); returns the number of survivors of the whole wave
+//                 read and the key's distance is 0; SAT = true: a distance the conversion cannot hold is INT_MAX); returns the number of
+//                 survivors of the whole wave
 //   window_slot   the slot number at a position of the walk
 //   window_best2  butterfly merge of the lanes' two smallest keys and the reference's initial values (k_best2_csr's rule)
 // one key into a lane's two smallest: if (key < b) { s2 = b; b = key; } else if (key < s2) s2 = key; -- written as minima so that the pair
@@ -197,7 +198,7 @@ __device__ __forceinline__ int window_slot(const WindowWalk& w, const char* __re
     return ((const GridItem*)(grid + XFH_GRID_ITEMS_OFF))[window_base(w, p) + p].index;
 }
 
-template <bool DIST, typename Extra, typename Visit>
+template <bool DIST, bool SAT = false, typename Extra, typename Visit>
 __device__ __forceinline__ int window_walk(const WindowWalk& w, const char* __restrict__ grid, const float* __restrict__ qr, float u, float v, float r,
                                            const float* __restrict__ tg, int nt, const uint8_t* __restrict__ skip, const float* __restrict__ uright,
                                            float urq, int lane, Extra extra, Visit visit) {
@@ -230,6 +231,7 @@ __device__ __forceinline__ int window_walk(const WindowWalk& w, const char* __re
                 }
                 const float nd = (float)acc;
                 dist = (int)(nd * 512.0f);
+                if (SAT && !(nd < 4194304.0f)) dist = 0x7fffffff;      // SAT: a squared norm that is Inf, NaN or >= 2^31 / 512 is INT_MAX (init_search.hip.h)
             }
             visit(((u64)(unsigned)dist << 32) | (u64)(unsigned)p, idx);
         }

@@ -32,6 +32,7 @@ class Context:
         self.device = device
         self.nfeatures = nfeatures
         self.max_batch = max_batch
+        self.max_height, self.max_width = max_height, max_width
         self.rec_bytes = int(lib().xfh_record_bytes(nfeatures))
         self.kps_off = int(lib().xfh_record_kps_offset())
         self.desc_off = int(lib().xfh_record_desc_offset(nfeatures))
@@ -696,6 +697,61 @@ class Context:
         return r
 
     # -- timing ---------------------------------------------------------------------------
+    # -- SearchForInitialization with the reference's retraction order (xfh_init_accept / xfh_init_search*) --------------------------------
+    INIT_OUT_Q = ("claim_idx", "matches12", "best_dist", "second_dist", "n_window", "n_tested")
+    INIT_OUT_T = ("matches21", "matched_distance")
+
+    @staticmethod
+    def init_accept(best: int, second: int, th_low: int, nn_ratio: float) -> bool:
+        """xfh_init_accept (host): the acceptance line of SearchForInitialization"""
+        return bool(lib().xfh_init_accept(int(best), int(second), int(th_low), float(nn_ratio)))
+
+    @staticmethod
+    def init_search_workspace_bytes(nq: int, nt: int, B: int = 1) -> int:
+        return int(lib().xfh_init_search_workspace_bytes(nq, nt, B))
+
+    @staticmethod
+    def init_search_layout(B: int, nq: int, nt: int, guard: int = 0):
+        """byte offsets of the outputs of init_search_device inside one buffer (its size under "bytes", the library's list length under
+        "K"); guard as in search_projection_layout.  The workspace is a buffer of its own (init_search_workspace_bytes)."""
+        al = lambda x: (x + 255) & ~255
+        o, off = {}, al(guard)
+        for name, nbytes in ([(k, 4 * B * nq) for k in Context.INIT_OUT_Q] + [(k, 4 * B * nt) for k in Context.INIT_OUT_T] +
+                             [("n_matches", 4 * B), ("status", B * nq), ("prev_out", 8 * B * nq)]):
+            o[name] = off; off += al(nbytes) + al(guard)
+        o["bytes"] = off
+        o["K"] = int(lib().xfh_init_list_entries())
+        return o
+
+    def init_search_device(self, B: int, nq: int, d_query_desc, d_prev_matched, d_grids, d_targets, target_stride: int, nt: int, d_workspace, d_out,
+                           window: float = 100.0, d_query_flags=None, d_target_xy=None, d_prev_out=None, th_low: int = 100, nn_ratio: float = 0.9, guard: int = 0):
+        """xfh_init_search_device on device pointers; asynchronous.  d_out: pointer to the outputs laid out as init_search_layout(B, nq, nt,
+        guard) says.  d_target_xy given: prev_out is written, into d_prev_out if that is given (it may be d_prev_matched) or into the layout's
+        own array"""
+        o = self.init_search_layout(B, nq, nt, guard)
+        po = None if d_target_xy is None else (d_prev_out if d_prev_out is not None else d_out + o["prev_out"])
+        check(lib().xfh_init_search_device(self.h, B, nq, d_query_desc, d_prev_matched, d_query_flags, float(window), d_grids, d_targets, target_stride,
+                                           d_target_xy, nt, int(th_low), float(nn_ratio), d_workspace, d_out + o["status"],
+                                           *[d_out + o[k] for k in self.INIT_OUT_Q + self.INIT_OUT_T], d_out + o["n_matches"], po), self.h)
+
+    def init_search(self, query_desc, prev_matched, kps, bounds, targets, window: float = 100.0, query_flags=None, th_low: int = 100, nn_ratio: float = 0.9,
+                    in_place: bool = False):
+        """xfh_init_search (host pointers, one problem) -> dict(status, claim_idx, matches12, best_dist, second_dist, n_window, n_tested,
+        matches21, matched_distance, n_matches, prev_out); in_place: prev_out is the (copied) prev_matched array itself"""
+        q = np.ascontiguousarray(query_desc, np.float32); pm = np.array(prev_matched, np.float32, order="C").reshape(-1, 2)
+        k = np.ascontiguousarray(kps, KP_DTYPE); tg = np.ascontiguousarray(targets, np.float32)
+        fl = None if query_flags is None else np.ascontiguousarray(query_flags, np.uint8)
+        nq, nt = len(q), len(k)
+        assert len(pm) == nq and len(tg) == nt and (fl is None or len(fl) == nq)
+        st = np.zeros(nq, np.uint8); oq = [np.zeros(nq, np.int32) for _ in self.INIT_OUT_Q]; ot = [np.zeros(nt, np.int32) for _ in self.INIT_OUT_T]
+        nm = np.zeros(1, np.int32); po = pm if in_place else np.zeros((nq, 2), np.float32)
+        check(lib().xfh_init_search(self.h, nq, q.ctypes.data, pm.ctypes.data, None if fl is None else fl.ctypes.data, float(window), k.ctypes.data,
+                                    C.byref(capi.GridBounds(*bounds)), tg.ctypes.data, nt, int(th_low), float(nn_ratio), st.ctypes.data,
+                                    *[o.ctypes.data for o in oq + ot], nm.ctypes.data, po.ctypes.data), self.h)
+        r = dict(zip(self.INIT_OUT_Q + self.INIT_OUT_T, oq + ot))
+        r.update(status=st, n_matches=int(nm[0]), prev_out=po)
+        return r
+
     def timing_enable(self, kernel_id: int, layer_mask: int = 0):
         check(lib().xfh_timing_enable(self.h, kernel_id, layer_mask), self.h)
 
@@ -847,6 +903,18 @@ class ORBmatcher:
             ratio_max = Context.scale_level_thresholds(float(sf[1]) if len(sf) > 1 else 1.2, len(sf))
         r = self.ctx.sim3_search(side1, side2, M21, M12, cam, bounds, th, sf, ratio_max, th_high=self.TH_HIGH)
         return r["n_found"], r["match12"], r
+
+    def SearchForInitialization(self, kps1, desc1, kps2, desc2, prev_matched, windowSize: int = 10, bounds=None):
+        """`ORBmatcher::SearchForInitialization(F1, F2, vbPrevMatched, vnMatches12, windowSize)` (ORBmatcher.cc:833-948).  kps1 / kps2: the
+        frames' undistorted keypoints (KP_DTYPE; of kps1 only the count is used: every XFeat keypoint has octave 0, so `level1 > 0` skips
+        none, and the rotation histogram removes nothing); prev_matched [n1][2]; bounds: F2's image bounds (default: 0, 0 and the ctx' image
+        size).  -> (nmatches, vnMatches12, the updated prev_matched); the result dict of Context.init_search is kept in self.last_init"""
+        k2 = np.ascontiguousarray(kps2, KP_DTYPE)
+        b = bounds if bounds is not None else (0.0, 0.0, float(self.ctx.max_width), float(self.ctx.max_height))
+        assert len(kps1) == len(desc1)
+        r = self.ctx.init_search(desc1, prev_matched, k2, b, desc2, window=float(windowSize), th_low=self.TH_LOW, nn_ratio=self.mfNNratio)
+        self.last_init = r
+        return r["n_matches"], r["matches12"], r["prev_out"]
 
     def match(self, desc1: np.ndarray, desc2: np.ndarray, min_cossim: float = -1.0):
         """-> list of (queryIdx, trainIdx, distance) like std::vector<cv::DMatch>"""
