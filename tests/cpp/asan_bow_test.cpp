@@ -1,5 +1,6 @@
 // asan_bow_test.cpp -- the host side of the SearchByBoW entry points under AddressSanitizer + UBSan: nodes_clamp.h, the very lines the
-// kernels of bow_search.hip.h read node blobs through, walked the way the kernels walk them over well-formed and hostile blobs that live in
+// kernels of bow_search.hip.h and k_triangulation_search (triangulation_search.hip.h, which walks side 2's blob as k_bow_candidates does)
+// read node blobs through, walked the way the kernels walk them over well-formed and hostile blobs that live in
 // heap buffers of EXACTLY xfh_nodes_bytes(n) bytes (a byte too far is a finding); xfh_bow_accept and the argument checks that return
 // before any HIP call, linked against the sanitizer build of libxfeat_hip (make -C xfeatslam_amd/csrc asan).  Exit code 0 = clean.
 // The hostile blobs are those of tests/test_gpu_bow.py::test_hostile_blobs: the items of a node replaced by out-of-range values, a

@@ -161,6 +161,20 @@ def test_host_code_under_sanitizers(tmp_path):
     assert r.returncode == 0 and "asan_host_test ok" in r.stdout, r.stderr[-3000:]
 
 
+def test_search_common_pieces_under_sanitizers(tmp_path):
+    """the lane-local pieces every search kernel shares (xfeatslam_amd/csrc/search_common.hip.h: klist_insert<K>, top2_insert / top2_merge,
+    the key packing, descriptor_distance<SAT>) compiled for the host with AddressSanitizer + UBSan and checked against the obvious form --
+    sorting the stream, sorting the union, xfh_descriptor_distance of the sanitizer build: tests/cpp/search_common_test.cpp"""
+    subprocess.check_call(["make", "-C", os.path.join(ROOT, "xfeatslam_amd", "csrc"), "asan", "-s", "-j8"])
+    exe = str(tmp_path / "search_common_test")
+    subprocess.check_call(["/opt/rocm/lib/llvm/bin/clang++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                           "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "xfeatslam_amd", "csrc"),
+                           os.path.join(ROOT, "tests", "cpp", "search_common_test.cpp"), "-L" + os.path.join(ROOT, "xfeatslam_amd"), "-lxfeat_hip_asan",
+                           "-Wl,-rpath," + os.path.join(ROOT, "xfeatslam_amd"), "-Wl,-rpath,/opt/rocm/lib", "-o", exe])
+    r = subprocess.run([exe], capture_output=True, text=True, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0"))
+    assert r.returncode == 0 and "search_common_test ok" in r.stdout, (r.stdout[-1000:], r.stderr[-3000:])
+
+
 def test_host_entry_points_under_thread_sanitizer(tmp_path):
     """the entry points the headers call "host, stateless, thread-safe" (include/xfeat_hip.h), entered by eight threads
     at the same moment, the first call of the process included: libxfeat_hip's HOST code built with ThreadSanitizer (make -C xfeatslam_amd/csrc
@@ -363,21 +377,26 @@ def test_many_pairs_work_plan_invariants():
     assert L.xfh_debug_match_plan(0, None, None, 256, None, None, None, None, None, None) == 1
 
 
-def test_match_gemm_register_contract():
-    """k_mnn_gemm_img and k_mnn_gemm_seg run two waves per SIMD on a budget of 256 VGPRs each: accumulators 128 + (seg: the d1 strip 64 + operands 32).  A spill
-    inside the K loop would put scratch traffic in front of every MFMA group; the one spill that exists (a 64-bit constant of the rare new-d1-panel path of
-    k_mnn_gemm_seg) must stay the only one."""
-    import re
-    import shutil
-    import subprocess
-    if not shutil.which("c++filt") or not os.path.exists("/opt/rocm/bin/hipcc"):
-        pytest.skip("needs hipcc and c++filt")
-    out = subprocess.run(["bash", os.path.join(ROOT, "tools", "kres.sh"), "kernels_mnn_gemm.hip", "-fno-honor-nans"], capture_output=True, text=True, timeout=600).stdout
+def _kres_rows(out):
+    """tools/kres.sh output -> {kernel: (vgpr, agpr, scratch, occupancy)}"""
     rows = {}
     for line in out.splitlines():
         m = re.match(r"(?:void )?(\S.*?)\s+vgpr\s+(\d+)\s+agpr\s+(\d+)\s+scratch\s+(\d+)\s+occ\s+(\d+)", line)
         if m:
             rows[m.group(1)] = tuple(int(x) for x in m.groups()[1:])
+    return rows
+
+
+def test_match_gemm_register_contract():
+    """k_mnn_gemm_img and k_mnn_gemm_seg run two waves per SIMD on a budget of 256 VGPRs each: accumulators 128 + (seg: the d1 strip 64 + operands 32).  A spill
+    inside the K loop would put scratch traffic in front of every MFMA group; the one spill that exists (a 64-bit constant of the rare new-d1-panel path of
+    k_mnn_gemm_seg) must stay the only one."""
+    import shutil
+    import subprocess
+    if not shutil.which("c++filt") or not os.path.exists("/opt/rocm/bin/hipcc"):
+        pytest.skip("needs hipcc and c++filt")
+    out = subprocess.run(["bash", os.path.join(ROOT, "tools", "kres.sh"), "kernels_mnn_gemm.hip", "-fno-honor-nans"], capture_output=True, text=True, timeout=600).stdout
+    rows = _kres_rows(out)
     img = [k for k in rows if k.startswith("k_mnn_gemm_img")]; seg = [k for k in rows if k.startswith("k_mnn_gemm_seg")]
     assert len(img) == 1 and len(seg) == 1, out[-1500:]
     assert rows[img[0]][2] == 0 and rows[img[0]][0] + rows[img[0]][1] <= 256 and rows[img[0]][3] >= 2, rows[img[0]]
@@ -389,17 +408,12 @@ def test_kernel_occupancy_contract():
     two 8-wave workgroups per CU (<= 128 VGPRs), and a refactor that nudges the allocator over the edge halves their occupancy
     without any test failing (it happened twice in round 3: 118 -> 130 and 127 -> 166 VGPRs, +15 % / +30 % on those kernels).
     tools/kres.sh reads clang's kernel-resource-usage remarks (no GPU needed); no kernel may spill to scratch."""
-    import re
     import shutil
     import subprocess
     if not shutil.which("c++filt") or not os.path.exists("/opt/rocm/bin/hipcc"):
         pytest.skip("needs hipcc and c++filt")
     out = subprocess.run(["bash", os.path.join(ROOT, "tools", "kres.sh"), "kernels_conv.hip"], capture_output=True, text=True, timeout=600).stdout
-    rows = {}
-    for line in out.splitlines():
-        m = re.match(r"(?:void )?(\S.*?)\s+vgpr\s+(\d+)\s+agpr\s+(\d+)\s+scratch\s+(\d+)\s+occ\s+(\d+)", line)
-        if m:
-            rows[m.group(1)] = tuple(int(x) for x in m.groups()[1:])
+    rows = _kres_rows(out)
     assert len(rows) > 40, out[-2000:]
     spills = {k: v for k, v in rows.items() if v[2] != 0}
     assert not spills, spills
@@ -408,3 +422,37 @@ def test_kernel_occupancy_contract():
     for k in edge:
         vgpr, agpr, _, occ = rows[k]
         assert vgpr + agpr <= 128 and occ >= 4, (k, rows[k])
+
+
+# kernels_match.hip at the commit before the search kernels were moved onto search_common.hip.h: VGPRs and occupancy
+# (waves per SIMD) as tools/kres.sh printed them for that commit with clang 22 / ROCm 7.2.  Every kernel was at scratch 0.
+SEARCH_KERNELS_BEFORE = {
+    "k_best2_csr": (120, 4), "k_search_window": (86, 5), "k_proj_candidates": (102, 4), "k_proj_resolve<false>": (105, 4), "k_proj_resolve<true>": (105, 4),
+    "k_proj_count<false>": (10, 8), "k_proj_count<true>": (10, 8), "k_fuse_search": (107, 4), "k_triangulation_search": (91, 5), "k_bow_candidates": (103, 4),
+    "k_bow_resolve": (56, 8), "k_mapproj_candidates": (116, 4), "k_sim3_search": (100, 4), "k_init_candidates": (66, 7), "k_init_resolve": (102, 4),
+    "k_init_final": (107, 4), "k_distinctive_csr": (82, 5), "k_grid_build": (14, 8),
+}
+
+
+def test_search_kernel_register_contract():
+    """The search kernels share their wave primitives (search_common.hip.h), so one edit there moves the register allocation of every kernel at
+    once.  No kernel of kernels_match.hip may spill to scratch -- for the two 1024-thread
+    resolvers that is the statement that they fit 128 VGPRs under their launch bounds -- and none may run at a lower occupancy than it did
+    before the pieces were shared (SEARCH_KERNELS_BEFORE).  tools/kres.sh reads clang's kernel-resource-usage remarks (no GPU needed)."""
+    import shutil
+    import subprocess
+    if not shutil.which("c++filt") or not os.path.exists("/opt/rocm/bin/hipcc"):
+        pytest.skip("needs hipcc and c++filt")
+    out = subprocess.run(["bash", os.path.join(ROOT, "tools", "kres.sh"), "kernels_match.hip"], capture_output=True, text=True, timeout=600).stdout
+    rows = _kres_rows(out)
+    assert len(rows) >= len(SEARCH_KERNELS_BEFORE), out[-2000:]
+    spills = {k: v for k, v in rows.items() if v[2] != 0}
+    assert not spills, spills
+    for name, (_, occ_before) in SEARCH_KERNELS_BEFORE.items():
+        hit = [k for k in rows if k.split("(")[0] == name]
+        assert len(hit) == 1, (name, sorted(rows))
+        vgpr, agpr, _, occ = rows[hit[0]]
+        assert occ >= occ_before, (name, rows[hit[0]], SEARCH_KERNELS_BEFORE[name])
+    for name in ("k_proj_resolve<false>", "k_proj_resolve<true>", "k_init_resolve"):
+        k = [k for k in rows if k.split("(")[0] == name][0]
+        assert rows[k][0] + rows[k][1] <= 128, (name, rows[k])

@@ -40,8 +40,27 @@
 #include "ctx.h"
 #include "bow_math.h"
 #include "nodes_clamp.h"
-#include "projection_search.hip.h"                         // wave_min_u64
-#include "triangulation_search.hip.h"                      // tri_descriptor_distance, wave_sum_i32
+#include "search_common.hip.h"
+
+// The members of side 2's node `r`, dealt to the lanes 64 at a time in stored order, for k_bow_candidates and the re-search of k_bow_resolve: the
+// eligibility test (a keypoint of side 2, eligible2), the claimed bitmap over the positions when there is one, DescriptorDistance, and visit(key) for
+// every member below init_dist (one at or above it can never pass `d < best` nor `d < second`).  Returns how many THIS LANE found eligible and unclaimed.
+template <typename Visit>
+__device__ __forceinline__ int bow_walk(const char* nb2, int n2, const NodeRange r, const uint8_t* el, const char* tg, const float* qr, int init_dist,
+                                        const unsigned* claimed, int lane, Visit visit) {
+    int n = 0;
+    for (int p0 = 0; p0 < r.len; p0 += 64) {
+        const int p = p0 + lane;
+        if (p >= r.len) continue;
+        const int idx = nodes_item(nb2, n2, r.start + p);
+        if (idx < 0 || (el && el[idx] == 0) || (claimed && ((claimed[p >> 5] >> (p & 31)) & 1u))) continue;
+        ++n;
+        const int dist = descriptor_distance(qr, (const f32x4*)(tg + (size_t)idx * 256));
+        if (dist < 0 || dist >= init_dist) continue;
+        visit(key_pack(dist, (unsigned)p));
+    }
+    return n;
+}
 
 __global__ __launch_bounds__(256)
 void k_bow_candidates(BowArgs a) {
@@ -55,9 +74,9 @@ void k_bow_candidates(BowArgs a) {
     const float* __restrict__ qr = (const float*)(a.s1.desc + (size_t)pb * a.s1.desc_stride) + (size_t)qi * 64;
     const uint32_t node = nodes_node_of(nb1, n1, qi);
     const int active = __builtin_amdgcn_readfirstlane(a.s1.flag[(size_t)pb * a.s1.elem_stride + qi] != 0 ? 1 : 0);
-    const u64 NONE = ~0ull;
-    u64 k0 = NONE, k1 = NONE, k2 = NONE, k3 = NONE;                    // the lane's K least keys, ascending
-    static_assert(XFH_BOW_K == 4, "the per-lane insertion below is written for four entries");
+    u64 lk[XFH_BOW_K];                                                 // the lane's K least keys, ascending
+#pragma unroll
+    for (int j = 0; j < XFH_BOW_K; ++j) lk[j] = XFH_KEY_NONE;
     int st = XFH_BOW_INACTIVE, slot = -1, ntot = 0, nlow = 0;
     if (active) {                                                      // (uniform)
         st = XFH_BOW_NO_NODE;
@@ -67,38 +86,20 @@ void k_bow_candidates(BowArgs a) {
             const NodeRange r = nodes_range(nb2, n2, slot);
             const uint8_t* __restrict__ el = a.s2.flag ? a.s2.flag + (size_t)pb * a.s2.elem_stride : nullptr;
             const char* __restrict__ tg = a.s2.desc + (size_t)pb * a.s2.desc_stride;
-            for (int p0 = 0; p0 < r.len; p0 += 64) {
-                const int p = p0 + lane;
-                if (p >= r.len) continue;
-                const int idx = nodes_item(nb2, n2, r.start + p);
-                if (idx < 0 || (el && el[idx] == 0)) continue;
-                ++ntot;
-                const int dist = tri_descriptor_distance(qr, (const f32x4*)(tg + (size_t)idx * 256));
-                if (dist < 0 || dist >= a.init_dist) continue;         // it can never pass `d < best` nor `d < second`
-                ++nlow;
-                const u64 key = ((u64)(unsigned)dist << 32) | (u64)(unsigned)p;
-                if (key < k3) {
-                    k3 = key;
-                    if (k3 < k2) { const u64 t = k2; k2 = k3; k3 = t; }
-                    if (k2 < k1) { const u64 t = k1; k1 = k2; k2 = t; }
-                    if (k1 < k0) { const u64 t = k0; k0 = k1; k1 = t; }
-                }
-            }
+            ntot = bow_walk(nb2, n2, r, el, tg, qr, a.init_dist, nullptr, lane, [&](u64 key) { ++nlow; klist_insert(lk, key); });
             ntot = wave_sum_i32(ntot); nlow = wave_sum_i32(nlow);
         }
     }
     const BowWs L = bow_ws_layout(n1, 1);
     char* ws = a.ws + bow_ws_layout(n1, (int)gridDim.y).first + (size_t)pb * L.stride;
-    // the wave's K least: K times the minimum of the lanes' heads (keys are distinct: they carry the position); its owner writes and pops
+    // the wave's K least, ascending
     int* ld = (int*)(ws + L.ldist) + (size_t)qi * XFH_BOW_K;
     int* lp = (int*)(ws + L.lpos) + (size_t)qi * XFH_BOW_K;
     for (int j = 0; j < XFH_BOW_K; ++j) {
-        const u64 m = wave_min_u64(k0);
-        if (m == NONE) break;                                          // (uniform)
-        if (k0 == m) {
-            ld[j] = (int)(m >> 32); lp[j] = (int)(m & 0xFFFFFFFFull);
-            k0 = k1; k1 = k2; k2 = k3; k3 = NONE;
-        }
+        const u64 m = klist_head(lk);
+        if (m == XFH_KEY_NONE) break;                                  // (uniform)
+        if (lane == 0) { ld[j] = key_dist(m); lp[j] = key_pos(m); }
+        klist_drop(lk, m);
     }
     if (lane == 0) {
         ((int*)(ws + L.slot))[qi] = slot; ((int*)(ws + L.ntot))[qi] = ntot; ((int*)(ws + L.nlow))[qi] = nlow;
@@ -135,7 +136,6 @@ void k_bow_resolve(BowArgs a) {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    const u64 NONE = ~0ull;
     int nclaimed = 0, nmatch = 0, nsearch = 0, nsteps = 0;
     for (int t = 0; t < r1.len; ++t) {                                 // the queries of the node in stored order; everything is uniform
         const int i = nodes_item(nb1, n1, r1.start + t);
@@ -151,26 +151,12 @@ void k_bow_resolve(BowArgs a) {
         }
         if (nlow > XFH_BOW_K && found < 2) {                           // the truncated list ran out: the full walk with the claim test inside
             ++nsearch;
-            const float* qr = (const float*)q1 + (size_t)i * 64;
-            u64 b = NONE, s2 = NONE;
-            for (int p0 = 0; p0 < r2.len; p0 += 64) {
-                const int p = p0 + lane;
-                if (p >= r2.len) continue;
-                const int idx = nodes_item(nb2, n2, r2.start + p);
-                if (idx < 0 || (el && el[idx] == 0) || ((claim[p >> 5] >> (p & 31)) & 1u)) continue;
-                const int dist = tri_descriptor_distance(qr, (const f32x4*)(tg + (size_t)idx * 256));
-                if (dist < 0 || dist >= a.init_dist) continue;
-                const u64 key = ((u64)(unsigned)dist << 32) | (u64)(unsigned)p;
-                if (key < b) { s2 = b; b = key; } else if (key < s2) s2 = key;
-            }
-#pragma unroll
-            for (int m = 32; m >= 1; m >>= 1) {
-                const u64 ob = __shfl_xor(b, m), os = __shfl_xor(s2, m);
-                top2_merge(b, s2, ob, os);
-            }
+            u64 b = XFH_KEY_NONE, s2 = XFH_KEY_NONE;
+            bow_walk(nb2, n2, r2, el, tg, (const float*)q1 + (size_t)i * 64, a.init_dist, claim, lane, [&](u64 key) { top2_insert(b, s2, key); });
+            wave_top2(b, s2);
             bp = -1; bd = a.init_dist; sd = a.init_dist;
-            if (b != NONE) { bp = (int)(b & 0xFFFFFFFFull); bd = (int)(b >> 32); }          // (bp < r2.len: the position the key was made of)
-            if (s2 != NONE) sd = (int)(s2 >> 32);
+            if (b != XFH_KEY_NONE) { bp = key_pos(b); bd = key_dist(b); }                       // (bp < r2.len: the position the key was made of)
+            if (s2 != XFH_KEY_NONE) sd = key_dist(s2);
         }
         const int bi = bp >= 0 ? nodes_item(nb2, n2, r2.start + bp) : -1;
         const int ncand = ntot > nclaimed ? ntot - nclaimed : 0;       // every claim of the node took one statically eligible member away

@@ -5,14 +5,13 @@
 #include <stddef.h>
 #include "../../include/xfeat_hip.h"
 #include "../../include/xfeat_hip_bench.h"
+#include "hd.h"                                            // XFH_HD, f32x4, u64
 
 #define XFH_NUM_LAYERS 23
 #define XFH_DESC_DIM 64
 #define CAND_CNT_STRIDE 64   // ints between per-frame candidate counters: one 256-B line each (atomics on one line serialise)
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned long long u64;
 
 // XFeatModel::XFeatModel (reference src/XFeat.cc:41-90): BasicLayer(cin, cout, k, stride)
 struct LayerSpec { int cin, cout, ks, stride; const char* name; };

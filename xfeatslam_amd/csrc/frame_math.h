@@ -12,12 +12,7 @@
 #pragma once
 #include <stdint.h>
 #include "../../include/xfeat_hip.h"
-
-#if defined(__HIPCC__) || defined(__CUDACC__)
-#define XFH_HD __host__ __device__ __forceinline__
-#else
-#define XFH_HD inline
-#endif
+#include "hd.h"
 
 // (u, v) -> (u', v').  k1 == 0 copies the point whatever the other coefficients are (Frame.cc:942).
 XFH_HD void xfh_undistort_point(const xfh_camera& cam, float u, float v, float* uo, float* vo) {

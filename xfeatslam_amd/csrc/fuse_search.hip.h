@@ -25,13 +25,8 @@
 #pragma once
 #include "ctx.h"
 #include "fuse_math.h"
+#include "search_common.hip.h"
 #include "window_search.hip.h"
-
-__device__ __forceinline__ int wave_sum_i32(int x) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) x += __shfl_xor(x, m);
-    return x;
-}
 
 __global__ __launch_bounds__(256)
 void k_fuse_search(FuseArgs a) {
@@ -56,7 +51,7 @@ void k_fuse_search(FuseArgs a) {
         const bool chi2 = (a.flags & XFH_FUSE_CHI2) != 0;
         const WindowWalk w = window_open(grid, u, v, r, a.nt, lane);
         if (level <= 1) {                                              // (uniform) kpLevel = 0 lies in [level - 1, level] (:1454)
-            u64 b = ~0ull, s2 = ~0ull;
+            u64 b = XFH_KEY_NONE, s2 = XFH_KEY_NONE;
             ntest = window_walk<true>(w, grid, qr, u, v, r, tg, a.nt, nullptr, nullptr, 0.0f, lane,
                                       [&](int idx, float xk, float yk) {
                                           ++nwin;
@@ -65,10 +60,7 @@ void k_fuse_search(FuseArgs a) {
                                       [&](u64 key, int) { top2_insert(b, s2, key); });
             int si, sd;
             window_best2(w, grid, b, s2, a.init_dist, bi, bd, si, sd);
-        } else {
-            window_walk<false>(w, grid, nullptr, u, v, r, nullptr, a.nt, nullptr, nullptr, 0.0f, lane,
-                               [&](int, float, float) { ++nwin; return false; }, [](u64, int) {});
-        }
+        } else nwin = window_count(w, grid, u, v, r, a.nt, lane);
         nwin = wave_sum_i32(nwin);
         const bool fused = bi >= 0 && bd <= a.th_low;
         st = nwin == 0 ? XFH_FUSE_NO_CANDIDATES : (fused ? XFH_FUSE_FUSED : XFH_FUSE_REJECTED);

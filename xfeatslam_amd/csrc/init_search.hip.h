@@ -6,9 +6,7 @@
 // closer than the one before), and a retracted query never searches again.  So when query q's turn comes, member (k, d) is skipped iff
 //       d == INT_MAX  (the initial vMatchedDistance blocks it)  or  some accepting j < q with claim[j] == k has dist[j] <= d,
 // where (claim[j], dist[j]) is what j wrote when ITS turn came -- whether j was retracted later does not matter.  That is a triangular
-// system like the claim rule of projection_search.hip.h: all queries are re-evaluated against the previous round's (claim, dist) until a
-// round changes none; the only fixed point is the sequential answer (induction over q), every query up to the smallest one a round changed
-// is final, so there are at most nq rounds.  What the resolver of projection_search.hip.h cannot express is the per-keypoint state: not one
+// system like the claim rule of projection_search.hip.h, settled by the same rounds (resolve_rounds.hip.h).  What differs is the per-keypoint state: not one
 // integer but the SET of (acceptor, distance) pairs, kept here as a chain through the queries -- head[nt] + next[nq] -- and the skip test
 // is an order-free "exists" over the chain of k, so the order in which the chain was linked does not matter.
 //
@@ -22,7 +20,7 @@
 //                      entries, or one whose distance is already above th_low, or a last entry above th_low, or one unblocked entry that passes the
 //                      ratio test against the last entry (a lower bound of the true second best).  A truncated list that is not
 //                      settled goes on a list, and the WAVES of the workgroup re-search those in full with the test inside the walk, under
-//                      the budget and postponement rule of k_proj_resolve (unchanged: see "Cost of the worst case" there).  The round
+//                      the budget and postponement rule of resolve_rounds.hip.h (see "Cost of the worst case" there).  The round
 //                      count is decided here: the host reads nothing back.  At the end: matches21 (the LARGEST acceptor of a keypoint =
 //                      the last writer), matched_distance (its distance), n_matches (keypoints with an acceptor: every acceptor but the
 //                      last of a keypoint was retracted), and the final chains to the workspace.
@@ -38,13 +36,14 @@
 // floats; a non-finite centre opens no window.  A distance that is not below 2^31 / 512 as a float (Inf or NaN rows) is INT_MAX: such a
 // member is always blocked, as in the reference (INT_MAX <= INT_MAX).
 //
-// Cost of the worst case: thousands of acceptors on one keypoint make every test of that keypoint a walk over a chain of thousands, and
-// thousands of queries on one spot cost what k_proj_resolve says of that case: exact and terminating, seconds, nothing more.
+// Cost of the worst case: thousands of acceptors on one keypoint make every test of that keypoint a walk over a chain of thousands; thousands of
+// queries on one spot: resolve_rounds.hip.h.
 #pragma once
 #include "ctx.h"
 #include "init_math.h"
+#include "search_common.hip.h"
+#include "resolve_rounds.hip.h"
 #include "window_search.hip.h"
-#include "projection_search.hip.h"
 
 #define XFH_INIT_RESOLVE_THREADS 1024
 static_assert(XFH_INIT_K >= 2 && XFH_INIT_K <= 16, "the per-lane list lives in registers");
@@ -69,35 +68,26 @@ void k_init_candidates(InitArgs a) {
     const char* grid = a.grids + (size_t)pb * a.grid_stride;
     const float* tg = (const float*)(a.targets + (size_t)pb * a.target_stride);
     const WindowWalk w = window_open(grid, u, v, r, a.nt, lane);
-    // the lane's K smallest keys, ascending
-    const u64 NONE = ~0ull;
-    u64 lk[XFH_INIT_K];
+    u64 lk[XFH_INIT_K];                                                // the lane's K smallest keys, ascending
 #pragma unroll
-    for (int j = 0; j < XFH_INIT_K; ++j) lk[j] = NONE;
+    for (int j = 0; j < XFH_INIT_K; ++j) lk[j] = XFH_KEY_NONE;
     int mine = 0;                                                      // members that can ever be unblocked (dist < INT_MAX)
     const int nw = window_walk<true, true>(w, grid, a.qdesc + qg * 64, u, v, r, tg, a.nt, nullptr, nullptr, 0.0f, lane, [](int, float, float) { return true; },
                                            [&](u64 key, int) {
-                                               if ((int)(key >> 32) == XFH_INIT_NONE) return;
+                                               if (key_dist(key) == XFH_INIT_NONE) return;
                                                ++mine;
-                                               u64 x = key;             // a bubble through the sorted list: every entry keeps the smaller, passes on the larger
-#pragma unroll
-                                               for (int j = 0; j < XFH_INIT_K; ++j) { const u64 lo = x < lk[j] ? x : lk[j], hi = x < lk[j] ? lk[j] : x; lk[j] = lo; x = hi; }
+                                               klist_insert(lk, key);
                                            });
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) mine += __shfl_xor(mine, m);
-    // the wave's K smallest: K times the minimum of the lanes' heads (keys are distinct: they carry the position); its owner pops
+    mine = wave_sum_i32(mine);
+    // the wave's K smallest, ascending, with the slot at each one's position
     int* ld = (int*)(ws + L.ldist) + (size_t)qi * XFH_INIT_K;
     int* li = (int*)(ws + L.lidx) + (size_t)qi * XFH_INIT_K;
     for (int j = 0; j < XFH_INIT_K; ++j) {
-        const u64 m = wave_min_u64(lk[0]);
-        if (m == NONE) break;                                          // (uniform)
-        const int slot = window_slot(w, grid, (int)(m & 0xFFFFFFFFull));      // (uniform: every lane names the same item)
-        if (lane == 0) { ld[j] = (int)(m >> 32); li[j] = slot; }
-        if (lk[0] == m) {
-#pragma unroll
-            for (int t = 0; t + 1 < XFH_INIT_K; ++t) lk[t] = lk[t + 1];
-            lk[XFH_INIT_K - 1] = NONE;
-        }
+        const u64 m = klist_head(lk);
+        if (m == XFH_KEY_NONE) break;                                  // (uniform)
+        const int slot = window_slot(w, grid, key_pos(m));             // (uniform: every lane names the same item)
+        if (lane == 0) { ld[j] = key_dist(m); li[j] = slot; }
+        klist_drop(lk, m);
     }
     if (lane == 0) { ntot[qi] = mine; a.n_window[qg] = nw; }
 }
@@ -141,7 +131,7 @@ void k_init_resolve(InitArgs a) {
     for (;;) {
         // the chains of the state so far (claim / dist are global memory written by this workgroup only; the barriers order it)
         for (int k = tid; k < nt; k += XFH_INIT_RESOLVE_THREADS) head[k] = -1;
-        if (tid == 0) { s_changed_lo = 0x7fffffff; s_defer_lo = 0x7fffffff; s_nredo = 0; }
+        if (tid == 0) { s_changed_lo = XFH_RESOLVE_NONE; s_defer_lo = XFH_RESOLVE_NONE; s_nredo = 0; }
         __syncthreads();
         for (int q = tid; q < nq; q += XFH_INIT_RESOLVE_THREADS) {
             const int c = wclaim[q];
@@ -173,7 +163,7 @@ void k_init_resolve(InitArgs a) {
         __syncthreads();
         // one wave per unsettled query: the full walk with the test inside
         const int nredo = s_nredo;
-        const int cut = nredo <= XFH_PROJ_REDO_BUDGET ? nq : lo + max(16, (int)((long long)(nq - lo) * XFH_PROJ_REDO_BUDGET / nredo));
+        const int cut = XFH_RESOLVE_CUT(lo, nq, nredo);
         if (tid == 0) s_nout += nredo;
         for (int i = wave; i < nredo; i += XFH_INIT_RESOLVE_THREADS / 64) {
             const int q = __builtin_amdgcn_readfirstlane(redo[i]);
@@ -181,10 +171,10 @@ void k_init_resolve(InitArgs a) {
             if (lane == 0) atomicAdd(&s_nwalk, 1);
             const float u = centre[(size_t)q * 4], v = centre[(size_t)q * 4 + 1], r = centre[(size_t)q * 4 + 2];
             const WindowWalk w = window_open(grid, u, v, r, nt, lane);
-            u64 b = ~0ull, s2 = ~0ull;
+            u64 b = XFH_KEY_NONE, s2 = XFH_KEY_NONE;
             window_walk<true, true>(w, grid, a.qdesc + (q0 + q) * 64, u, v, r, tg, nt, nullptr, nullptr, 0.0f, lane, [](int, float, float) { return true; },
                                     [&](u64 key, int idx) {
-                                        const int d = (int)(key >> 32);
+                                        const int d = key_dist(key);
                                         if (d != XFH_INIT_NONE && !init_blocked(head, next, snap, idx, d, q)) top2_insert(b, s2, key);
                                     });
             int bi, bd, si, sd;
@@ -195,8 +185,8 @@ void k_init_resolve(InitArgs a) {
         const int c = s_changed_lo, d = s_defer_lo;
         ++rounds;
         __syncthreads();                                               // everyone has read the round's result before it is reset
-        if (c == 0x7fffffff && d == 0x7fffffff) break;
-        lo = c == 0x7fffffff ? d : min(c + 1, d);                      // queries < min(c, d) were evaluated against a final prefix and did not move
+        if (c == XFH_RESOLVE_NONE && d == XFH_RESOLVE_NONE) break;
+        lo = XFH_RESOLVE_NEXT_LO(c, d);
     }
     // the last round changed nothing: the chains in LDS are those of the final state.  For k_init_final: head, next; and per keypoint the
     // last acceptor (the largest), its distance, and the number of keypoints that have one
@@ -239,14 +229,13 @@ void k_init_final(InitArgs a) {
         const char* grid = a.grids + (size_t)pb * a.grid_stride;
         const float* tg = (const float*)(a.targets + (size_t)pb * a.target_stride);
         const WindowWalk w = window_open(grid, u, v, r, a.nt, lane);
-        u64 b = ~0ull, s2 = ~0ull;
+        u64 b = XFH_KEY_NONE, s2 = XFH_KEY_NONE;
         window_walk<true, true>(w, grid, a.qdesc + qg * 64, u, v, r, tg, a.nt, nullptr, nullptr, 0.0f, lane, [](int, float, float) { return true; },
                                 [&](u64 key, int idx) {
-                                    const int d = (int)(key >> 32);
+                                    const int d = key_dist(key);
                                     if (d != XFH_INIT_NONE && !init_blocked(head, next, dist, idx, d, qi)) { ++ntst; top2_insert(b, s2, key); }
                                 });
-#pragma unroll
-        for (int m = 32; m >= 1; m >>= 1) ntst += __shfl_xor(ntst, m);
+        ntst = wave_sum_i32(ntst);
         int si;
         window_best2(w, grid, b, s2, XFH_INIT_NONE, bi, bd, si, sd);
         const bool accept = xfh_init_accept_line(bd, sd, a.th_low, a.nn_ratio);

@@ -30,6 +30,8 @@
 //                   its window, then the reference's retraction order resolved per problem with the acceptors of every keypoint chained in LDS, then
 //                   every query's turn against the final chains (init_search.hip.h).
 //   k_distinctive_csr : MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:329-403), one wave per map point.
+// Shared by k_best2_csr and every *_search.hip.h kernel: search_common.hip.h (keys, descriptor_distance, top-two and K-list with their wave merges, wave
+// minimum / sum), window_search.hip.h (the grid walk), nodes_clamp.h (node blobs), resolve_rounds.hip.h (the rounds of k_proj_resolve / k_init_resolve: the argument, the cut, the advance of lo).
 //
 // Numerics: normalised rows and the 64-term dot products are bit-identical to the oracle
 // (fp64 sum of squares -> fp32 sqrt/max/div; one fp32 fma chain in k order, which is what
@@ -42,17 +44,13 @@
 #include <stdlib.h>
 
 #include "dist_mfma.hip.h"
+#include "search_common.hip.h"
 
 // ---- k_best2_csr: best / second-best integer distance over per-query candidate lists -----------
 // One wave per query (the query row comes through the scalar cache); lane l visits candidates
 // l, l+64, ... and keeps its two smallest (dist << 32 | position) keys, which reproduces the
 // reference's sequential rule exactly (strict '<' in list order = smallest (dist, position)); a
-// butterfly merges the 64 lane pairs.  Distances are the exact DescriptorDistance arithmetic.
-__device__ __forceinline__ void top2_merge(u64& b, u64& s, u64 ob, u64 os) {
-    const u64 lo = b < ob ? b : ob, hi = b < ob ? ob : b;
-    const u64 ms = s < os ? s : os;
-    b = lo; s = hi < ms ? hi : ms;
-}
+// butterfly merges the 64 lane pairs.  Keys, distance and merge: search_common.hip.h.
 __global__ __launch_bounds__(256)
 void k_best2_csr(const float* __restrict__ q, int nq, const float* __restrict__ tg, const int* __restrict__ offsets,
                  const int* __restrict__ indices, int init_dist, int* __restrict__ best_idx, int* __restrict__ best_dist,
@@ -62,34 +60,16 @@ void k_best2_csr(const float* __restrict__ q, int nq, const float* __restrict__ 
     if (qi >= nq) return;
     const float* qr = q + (size_t)qi * 64;
     const int beg = offsets[qi], end = offsets[qi + 1];
-    const u64 NONE = ~0ull;
-    u64 b = NONE, s2 = NONE;
-    for (int p = beg + lane; p < end; p += 64) {
-        const int idx = indices[p];
-        const f32x4* tr = (const f32x4*)(tg + (size_t)idx * 64);
-        double acc = 0.0;
-#pragma unroll
-        for (int g = 0; g < 16; ++g) {
-            const f32x4 tv = tr[g];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) { const double df = (double)(qr[g * 4 + e] - tv[e]); acc = fma(df, df, acc); }
-        }
-        const float nd = (float)acc;
-        const int dist = (int)(nd * 512.0f);
-        const u64 key = ((u64)(unsigned)dist << 32) | (u64)(unsigned)(p - beg);
-        if (key < b) { s2 = b; b = key; } else if (key < s2) s2 = key;
-    }
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) {
-        const u64 ob = __shfl_xor(b, m), os = __shfl_xor(s2, m);
-        top2_merge(b, s2, ob, os);
-    }
+    u64 b = XFH_KEY_NONE, s2 = XFH_KEY_NONE;
+    for (int p = beg + lane; p < end; p += 64)
+        top2_insert(b, s2, key_pack(descriptor_distance(qr, (const f32x4*)(tg + (size_t)indices[p] * 64)), (unsigned)(p - beg)));
+    wave_top2(b, s2);
     if (lane == 0) {
         // apply the reference's initial values: a candidate only counts if dist < init_dist
         int bd = init_dist, bi = -1, sd = init_dist, si = -1;
-        if (b != NONE && (int)(b >> 32) < init_dist) {
-            bd = (int)(b >> 32); bi = indices[beg + (int)(b & 0xFFFFFFFFull)];
-            if (s2 != NONE && (int)(s2 >> 32) < init_dist) { sd = (int)(s2 >> 32); si = indices[beg + (int)(s2 & 0xFFFFFFFFull)]; }
+        if (b != XFH_KEY_NONE && key_dist(b) < init_dist) {
+            bd = key_dist(b); bi = indices[beg + key_pos(b)];
+            if (s2 != XFH_KEY_NONE && key_dist(s2) < init_dist) { sd = key_dist(s2); si = indices[beg + key_pos(s2)]; }
         }
         best_idx[qi] = bi; best_dist[qi] = bd; second_idx[qi] = si; second_dist[qi] = sd;
     }
@@ -159,8 +139,7 @@ void k_distinctive_csr(const float* __restrict__ table, const int* __restrict__ 
             best = key < best ? key : best;
         }
     }
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) { const u64 o = __shfl_xor(best, m); best = o < best ? o : best; }
+    best = wave_min_u64(best);
     if (lane == 0) { best_pos[g] = (int)(best & 0xFFFFFFFFull); best_median[g] = (int)(best >> 32); }
 }
 

@@ -19,8 +19,9 @@
 #pragma once
 #include "ctx.h"
 #include "mapproj_math.h"
-#include "projection_search.hip.h"
-#include "fuse_search.hip.h"
+#include "search_common.hip.h"
+#include "window_search.hip.h"
+#include "projection_search.hip.h"                         // k_proj_resolve, k_proj_count
 
 __global__ __launch_bounds__(256)
 void k_mapproj_candidates(MapProjArgs m) {
@@ -39,10 +40,10 @@ void k_mapproj_candidates(MapProjArgs m) {
         st = xfh_mapproj_point(a.Tcw + (size_t)pb * 12, m.Ow + (size_t)pb * 3, a.cam, a.bounds, m.th, m.lv, m.form, a.pts + qg * 3, m.normals + qg * 3,
                                m.dist + qg * 3, &u, &v, &r, &level);
     st = __builtin_amdgcn_readfirstlane(st); level = __builtin_amdgcn_readfirstlane(level);      // (computed from uniform values: say so to the compiler)
-    const u64 NONE = ~0ull;
-    u64 k0 = NONE, k1 = NONE, k2 = NONE, k3 = NONE;                    // the lane's K smallest keys, ascending, and their slots
-    int i0 = -1, i1 = -1, i2 = -1, i3 = -1;
-    static_assert(XFH_PROJ_K == 4, "the per-lane insertion below is written for four entries");
+    u64 lk[XFH_PROJ_K];                                                // the lane's K smallest keys, ascending, and their slots
+    int ls[XFH_PROJ_K];
+#pragma unroll
+    for (int j = 0; j < XFH_PROJ_K; ++j) { lk[j] = XFH_KEY_NONE; ls[j] = -1; }
     int nwin = 0, nc = 0;
     if (st == XFH_MAPPROJ_VISIBLE) {                                   // (uniform) a culled query never touches the grid
         const char* __restrict__ grid = a.grids + (size_t)pb * a.grid_stride;
@@ -52,32 +53,12 @@ void k_mapproj_candidates(MapProjArgs m) {
         if (level <= 1) {                                              // (uniform) kpLevel = 0 lies in [level - 1, level]
             nc = window_walk<true>(w, grid, qr, u, v, r, tg, a.nt, nullptr, nullptr, 0.0f, lane,
                                    [&](int idx, float, float) { ++nwin; return !(taken && taken[idx] != 0); },
-                                   [&](u64 key, int idx) {
-                                       if (key < k3) {
-                                           k3 = key; i3 = idx;
-                                           if (k3 < k2) { const u64 t = k2; k2 = k3; k3 = t; const int ti = i2; i2 = i3; i3 = ti; }
-                                           if (k2 < k1) { const u64 t = k1; k1 = k2; k2 = t; const int ti = i1; i1 = i2; i2 = ti; }
-                                           if (k1 < k0) { const u64 t = k0; k0 = k1; k1 = t; const int ti = i0; i0 = i1; i1 = ti; }
-                                       }
-                                   });
-        } else {
-            window_walk<false>(w, grid, nullptr, u, v, r, nullptr, a.nt, nullptr, nullptr, 0.0f, lane,
-                               [&](int, float, float) { ++nwin; return false; }, [](u64, int) {});
-        }
+                                   [&](u64 key, int idx) { klist_insert(lk, key, ls, idx); });
+        } else nwin = window_count(w, grid, u, v, r, a.nt, lane);
         nwin = wave_sum_i32(nwin);
     }
-    // the stores of the kernel, behind every load.  The wave's K smallest: K times the minimum of the lanes' heads (keys are distinct: they
-    // carry the position); its owner writes and pops
-    int* ld = (int*)(ws + L.ldist) + (size_t)qi * XFH_PROJ_K;
-    int* li = (int*)(ws + L.lidx) + (size_t)qi * XFH_PROJ_K;
-    for (int j = 0; j < XFH_PROJ_K; ++j) {
-        const u64 mk = wave_min_u64(k0);
-        if (mk == NONE) break;                                         // (uniform)
-        if (k0 == mk) {
-            ld[j] = (int)(mk >> 32); li[j] = i0;
-            k0 = k1; i0 = i1; k1 = k2; i1 = i2; k2 = k3; i2 = i3; k3 = NONE;
-        }
-    }
+    // the stores of the kernel, behind every load
+    proj_store_list(ws, L, qi, lk, ls);
     if (lane == 0) {
         a.status[qg] = (uint8_t)st;                                    // XFH_MAPPROJ_VISIBLE is XFH_MAPPROJ_NO_CANDIDATES until k_proj_resolve has found one
         a.match_idx[qg] = -1; a.best_dist[qg] = a.init_dist; a.second_dist[qg] = a.init_dist; a.n_candidates[qg] = 0;

@@ -1,10 +1,11 @@
 // nodes_clamp.h -- reading a node blob (nodes_layout.h) that may hold ANYTHING: every count, range and item is clamped or checked here
-// before a caller indexes with it.  Plain C++, host and device: the kernels of bow_search.hip.h read blobs through these functions only,
+// before a caller indexes with it.  Plain C++, host and device: the kernels of bow_search.hip.h and triangulation_search.hip.h read blobs through these functions only,
 // and tests/cpp/asan_bow_test.cpp runs the very same lines under AddressSanitizer on heap buffers of exactly xfh_nodes_bytes(n) bytes.
 //
 // Every array of the blob has nodes_cap(n) >= n + 1 entries, so with the number of nodes clamped to [0, n], both ends of a range to [0, n]
 // and a position < n nothing below reads outside the blob, whatever it holds.  A blob is 16-byte aligned (the entry points check).
 #pragma once
+#include "../../include/xfeat_hip.h"                         // XFH_NODE_NONE
 #include "nodes_layout.h"
 
 struct NodeRange { int start, len; };                       // items[start .. start + len), inside [0, n]

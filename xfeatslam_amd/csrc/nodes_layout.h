@@ -12,7 +12,8 @@
 // Unused entries are zero: packing the same input twice gives identical bytes.
 #pragma once
 #include <stdint.h>
-#include "projection_math.h"                                // XFH_HD
+#include <stddef.h>
+#include "hd.h"
 
 #define XFH_NODES_MAGIC 0x314e4658                          // "XFN1"
 #define XFH_NODES_HDR 64

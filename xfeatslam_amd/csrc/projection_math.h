@@ -13,14 +13,7 @@
 #pragma once
 #include <stdint.h>
 #include "../../include/xfeat_hip.h"
-
-#ifndef XFH_HD
-#if defined(__HIPCC__) || defined(__CUDACC__)
-#define XFH_HD __host__ __device__ __forceinline__
-#else
-#define XFH_HD inline
-#endif
-#endif
+#include "hd.h"
 
 // -> XFH_PROJ_BEHIND (u = v = ur = 0), XFH_PROJ_OUT_OF_BOUNDS or XFH_PROJ_VISIBLE (both with u, v, ur as computed)
 XFH_HD int xfh_project_point(const float* T, const xfh_camera& cam, const xfh_grid_bounds& b, float X, float Y, float Z, float* u, float* v, float* ur) {

@@ -3,12 +3,9 @@
 // claim order (xfh_search_projection_device; the contract is the sequential loop written out in include/xfeat_hip.h).
 //
 // The claim rule makes the loop sequential: CurrentFrame.mvpMapPoints is all NULL before the call (Tracking.cc:2914), so every entry
-// the candidate test (:1932-1934) sees was written by an earlier iteration (:1957).  It is a triangular system -- query q depends on
-// queries < q only.  With claim_min[k] = min{ j : match[j] == k and j claims } (a statically skipped k: -1), query q skips k iff
-// claim_min[k] < q.  All queries are re-evaluated against the previous round's claim_min until a round changes no match; the only
-// fixed point of that iteration is the sequential answer (induction over q), and when the smallest query a round changed is c, every
-// query <= c is final -- queries < c were evaluated against a final prefix and did not move, and c itself was evaluated against that
-// same prefix -- so round r + 1 starts at c + 1: at most nq rounds, whatever the data.
+// the candidate test (:1932-1934) sees was written by an earlier iteration (:1957): query q depends on queries < q only.  With
+// claim_min[k] = min{ j : match[j] == k and j claims } (a statically skipped k: -1), query q skips k iff claim_min[k] < q; the rounds that
+// settle this, why they end at the sequential answer and what the worst case costs: resolve_rounds.hip.h.
 //
 //   k_proj_candidates  many workgroups, one wave per query: flags, projection (projection_math.h) or the caller's (u, v, r), cull,
 //                      then the window walk of window_search.hip.h with the STATIC filters only.  Writes status and proj, and
@@ -30,29 +27,26 @@
 // Bounds: slot numbers come from the blob and are checked against nt in the walk (window_walk) before anything is indexed with them;
 // list entries are such slot numbers; point coordinates and poses are only ever used as floats; a non-finite (u, v, r) opens no
 // window.  Nothing is read through a float.
-//
-// Cost of the worst case.  The lists and the round loop are sized for the usual scene, where a handful of rounds settle everything and
-// few lists run out.  When many queries sit on one spot, every round settles one query (lo advances by one) and every later query's
-// list is exhausted.  Searching all of those again each round would be about nq^2 / 2 full walks on one CU, every one of them stale
-// but the first; so a round walks only the queries below a cut T = lo + max(16, (nq - lo) * XFH_PROJ_REDO_BUDGET / nredo), which holds
-// about XFH_PROJ_REDO_BUDGET of them when they are spread evenly, and postpones the rest: their match stays as it was, the smallest
-// postponed query bounds the next round's lo from above, and the loop does not end while one is postponed (lo itself is always below
-// the cut, so every round still settles at least one query).  The worst case is then nq rounds of at most max(16, BUDGET) walks of up
-// to nt candidates each -- nq = nt = XFH_GRID_MAX_N on one spot is about 10^6 walks of 16384 distances on ONE CU, i.e. seconds, not
-// milliseconds: exact and terminating, as the contract asks, and nothing more.  A caller with such input should not expect frame rate.
 #pragma once
 #include "ctx.h"
 #include "projection_math.h"
 #include "projection_layout.h"
+#include "search_common.hip.h"
+#include "resolve_rounds.hip.h"
 #include "window_search.hip.h"
 
 #define XFH_PROJ_RESOLVE_THREADS 1024
-#define XFH_PROJ_REDO_BUDGET 64                                        // full walks k_proj_resolve aims at per round (four per wave)
 
-__device__ __forceinline__ u64 wave_min_u64(u64 x) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) { const u64 o = __shfl_xor(x, m); x = o < x ? o : x; }
-    return x;
+// the wave's K smallest (dist, slot), ascending, into the query's list in the workspace: the owner of each writes it
+__device__ __forceinline__ void proj_store_list(char* ws, const ProjWs& L, int qi, u64 (&lk)[XFH_PROJ_K], int (&ls)[XFH_PROJ_K]) {
+    int* ld = (int*)(ws + L.ldist) + (size_t)qi * XFH_PROJ_K;
+    int* li = (int*)(ws + L.lidx) + (size_t)qi * XFH_PROJ_K;
+    for (int j = 0; j < XFH_PROJ_K; ++j) {
+        int slot;
+        const u64 m = klist_head(lk);
+        if (m == XFH_KEY_NONE) break;                                  // (uniform)
+        if (klist_drop(lk, m, ls, &slot)) { ld[j] = key_dist(m); li[j] = slot; }
+    }
 }
 
 __global__ __launch_bounds__(256)
@@ -82,32 +76,14 @@ void k_proj_candidates(ProjArgs a) {
     const char* grid = a.grids + (size_t)pb * a.grid_stride;
     const float* tg = (const float*)(a.targets + (size_t)pb * a.target_stride);
     const WindowWalk w = window_open(grid, u, v, r, a.nt, lane);
-    // the lane's K smallest keys, ascending, and their slots
-    const u64 NONE = ~0ull;
-    u64 k0 = NONE, k1 = NONE, k2 = NONE, k3 = NONE;
-    int i0 = -1, i1 = -1, i2 = -1, i3 = -1;
-    static_assert(XFH_PROJ_K == 4, "the per-lane insertion below is written for four entries");
+    u64 lk[XFH_PROJ_K];                                                // the lane's K smallest keys, ascending, and their slots
+    int ls[XFH_PROJ_K];
+#pragma unroll
+    for (int j = 0; j < XFH_PROJ_K; ++j) { lk[j] = XFH_KEY_NONE; ls[j] = -1; }
     const int nc = window_walk<true>(w, grid, a.qdesc + qg * 64, u, v, r, tg, a.nt, a.skip ? a.skip + (size_t)pb * a.nt : nullptr,
                                      a.uright ? a.uright + (size_t)pb * a.nt : nullptr, ur, lane, [](int, float, float) { return true; },
-                                     [&](u64 key, int idx) {
-                                         if (key < k3) {
-                                             k3 = key; i3 = idx;
-                                             if (k3 < k2) { const u64 t = k2; k2 = k3; k3 = t; const int ti = i2; i2 = i3; i3 = ti; }
-                                             if (k2 < k1) { const u64 t = k1; k1 = k2; k2 = t; const int ti = i1; i1 = i2; i2 = ti; }
-                                             if (k1 < k0) { const u64 t = k0; k0 = k1; k1 = t; const int ti = i0; i0 = i1; i1 = ti; }
-                                         }
-                                     });
-    // the wave's K smallest: K times the minimum of the lanes' heads (keys are distinct: they carry the position); its owner writes and pops
-    int* ld = (int*)(ws + L.ldist) + (size_t)qi * XFH_PROJ_K;
-    int* li = (int*)(ws + L.lidx) + (size_t)qi * XFH_PROJ_K;
-    for (int j = 0; j < XFH_PROJ_K; ++j) {
-        const u64 m = wave_min_u64(k0);
-        if (m == NONE) break;                                          // (uniform)
-        if (k0 == m) {
-            ld[j] = (int)(m >> 32); li[j] = i0;
-            k0 = k1; i0 = i1; k1 = k2; i1 = i2; k2 = k3; i2 = i3; k3 = NONE;
-        }
-    }
+                                     [&](u64 key, int idx) { klist_insert(lk, key, ls, idx); });
+    proj_store_list(ws, L, qi, lk, ls);
     if (lane == 0) ntot[qi] = nc;
 }
 
@@ -146,7 +122,7 @@ void k_proj_resolve(ProjArgs a) {
     for (;;) {
         // claim_min of the matches so far (match_idx is global memory written by this workgroup only; the barriers order it)
         for (int k = tid; k < nt; k += XFH_PROJ_RESOLVE_THREADS) claim[k] = (skip && skip[k]) ? -1 : 0x7fffffff;
-        if (tid == 0) { s_changed_lo = 0x7fffffff; s_defer_lo = 0x7fffffff; s_nredo = 0; }
+        if (tid == 0) { s_changed_lo = XFH_RESOLVE_NONE; s_defer_lo = XFH_RESOLVE_NONE; s_nredo = 0; }
         __syncthreads();
         for (int q = tid; q < nq; q += XFH_PROJ_RESOLVE_THREADS) {
             const int m = a.match_idx[q0 + q];
@@ -174,14 +150,14 @@ void k_proj_resolve(ProjArgs a) {
         __syncthreads();
         // one wave per truncated query: the full walk with the claim test inside
         const int nredo = s_nredo;
-        const int cut = nredo <= XFH_PROJ_REDO_BUDGET ? nq : lo + max(16, (int)((long long)(nq - lo) * XFH_PROJ_REDO_BUDGET / nredo));
+        const int cut = XFH_RESOLVE_CUT(lo, nq, nredo);
         for (int i = wave; i < nredo; i += XFH_PROJ_RESOLVE_THREADS / 64) {
             const int q = __builtin_amdgcn_readfirstlane(redo[i]);
-            if (q >= cut) { if (lane == 0) atomicMin(&s_defer_lo, q); continue; }     // (uniform) postponed: see "Cost of the worst case"
+            if (q >= cut) { if (lane == 0) atomicMin(&s_defer_lo, q); continue; }     // (uniform) postponed (resolve_rounds.hip.h)
             if (lane == 0) atomicAdd(&s_nwalk, 1);
             const float u = proj[(size_t)q * 4], v = proj[(size_t)q * 4 + 1], ur = proj[(size_t)q * 4 + 2], r = proj[(size_t)q * 4 + 3];
             const WindowWalk w = window_open(grid, u, v, r, nt, lane);
-            u64 b = ~0ull, s2 = ~0ull;
+            u64 b = XFH_KEY_NONE, s2 = XFH_KEY_NONE;
             const int nc = window_walk<true>(w, grid, a.qdesc + (q0 + q) * 64, u, v, r, tg, nt, skip, uright, ur, lane,
                                              [&](int idx, float, float) { return claim[idx] >= q; },
                                              [&](u64 key, int) { top2_insert(b, s2, key); });
@@ -193,8 +169,8 @@ void k_proj_resolve(ProjArgs a) {
         const int c = s_changed_lo, d = s_defer_lo;
         ++rounds;
         __syncthreads();                                               // everyone has read the round's result before it is reset
-        if (c == 0x7fffffff && d == 0x7fffffff) break;
-        lo = c == 0x7fffffff ? d : min(c + 1, d);                      // queries < min(c, d) were evaluated against a final prefix and did not move
+        if (c == XFH_RESOLVE_NONE && d == XFH_RESOLVE_NONE) break;
+        lo = XFH_RESOLVE_NEXT_LO(c, d);
     }
     // claim_min is the one of the final matches: for k_proj_count
     int* wclaim = (int*)(ws + L.claim);

@@ -18,7 +18,8 @@
 #include <limits.h>
 #include "ctx.h"
 #include "sim3_math.h"
-#include "fuse_search.hip.h"
+#include "search_common.hip.h"
+#include "window_search.hip.h"
 
 __global__ __launch_bounds__(256)
 void k_sim3_search(Sim3Args a) {
@@ -44,16 +45,13 @@ void k_sim3_search(Sim3Args a) {
         const float* __restrict__ tg = (const float*)(G.desc + gp * G.desc_stride);
         const WindowWalk w = window_open(grid, u, v, r, G.n, lane);
         if (level <= 1) {                                              // (uniform) kp.octave = 0 lies in [level - 1, level] (:1740)
-            u64 b = ~0ull, s2 = ~0ull;
+            u64 b = XFH_KEY_NONE, s2 = XFH_KEY_NONE;
             ntest = window_walk<true>(w, grid, qr, u, v, r, tg, G.n, nullptr, nullptr, 0.0f, lane,
                                       [&](int, float, float) { ++nwin; return true; },
                                       [&](u64 key, int) { top2_insert(b, s2, key); });
             int si, sd;
             window_best2(w, grid, b, s2, INT_MAX, bi, bd, si, sd);
-        } else {
-            window_walk<false>(w, grid, nullptr, u, v, r, nullptr, G.n, nullptr, nullptr, 0.0f, lane,
-                               [&](int, float, float) { ++nwin; return false; }, [](u64, int) {});
-        }
+        } else nwin = window_count(w, grid, u, v, r, G.n, lane);
         nwin = wave_sum_i32(nwin);
         const bool found = bi >= 0 && bd <= a.th_high;
         st = nwin == 0 ? XFH_SIM3_NO_CANDIDATES : (found ? XFH_SIM3_FOUND : XFH_SIM3_REJECTED);

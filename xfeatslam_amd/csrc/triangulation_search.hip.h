@@ -5,7 +5,7 @@
 //   k_triangulation_search   one wave per (problem, keypoint of KF1), four per workgroup.  The wave reads the query's flag byte, node id,
 //                   coordinates and right coordinate, the pair's F12 and epipole from wave-uniform addresses and evaluates the epipolar
 //                   line of tri_math.h once; the query's descriptor row comes through the scalar cache as in k_fuse_search.  The node
-//                   is looked up in KF2's ascending id list by a wave-uniform binary search, and the node's members are dealt to the
+//                   is looked up in KF2's ascending id list by a wave-uniform binary search (nodes_clamp.h), and the node's members are dealt to the
 //                   lanes 64 at a time in stored order: map-point flag, stereo gate, epipole radius and epipolar distance first
 //                   (xfh_tri_member, the host's own lines), DescriptorDistance only for the survivors.  Each lane keeps ONE key
 //                   dist << 32 | ~position: the reference lowers bestDist on `dist <= bestDist` (:1202 is `continue` on strictly greater),
@@ -18,27 +18,15 @@
 // the same keypoint of KF2, nothing is resolved afterwards and the call needs no workspace.  With a shared side 1 the B problems read
 // the same KF1 arrays (LocalMapping::CreateNewMapPoints: the new keyframe against every neighbour); its rows are then served from L2.
 //
-// Bounds: n_nodes and both ends of a node's range are clamped to [0, n2] before they index anything (every array of the blob has more
-// than n2 entries), an item is checked against n2 before has, xy, uright or a descriptor row is indexed with it, and nothing is read
-// through a float.
+// Bounds: both blobs are read through nodes_clamp.h only -- n_nodes and both ends of a node's range are clamped to [0, n2] before they
+// index anything (every array of the blob has more than n2 entries), an item is checked against n2 before has, xy, uright or a
+// descriptor row is indexed with it -- and nothing is read through a float.
 #pragma once
 #include "ctx.h"
 #include "tri_math.h"
 #include "nodes_layout.h"
-#include "fuse_search.hip.h"
-
-// ORBmatcher::DescriptorDistance, the lines of window_walk (window_search.hip.h): qr wave-uniform, tr this lane's row
-__device__ __forceinline__ int tri_descriptor_distance(const float* __restrict__ qr, const f32x4* __restrict__ tr) {
-    double acc = 0.0;
-#pragma unroll
-    for (int g = 0; g < 16; ++g) {
-        const f32x4 tv = tr[g];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { const double df = (double)(qr[g * 4 + e] - tv[e]); acc = fma(df, df, acc); }
-    }
-    const float nd = (float)acc;
-    return (int)(nd * 512.0f);
-}
+#include "nodes_clamp.h"
+#include "search_common.hip.h"
 
 __global__ __launch_bounds__(256)
 void k_triangulation_search(TriArgs a) {
@@ -53,7 +41,7 @@ void k_triangulation_search(TriArgs a) {
     const char* __restrict__ nb2 = a.s2.nodes + (size_t)pb * a.s2.nodes_stride;
     const float* __restrict__ qr = (const float*)(a.s1.desc + (size_t)pb * a.s1.desc_stride) + (size_t)qi * 64;
     const float* __restrict__ F = a.F12 + (size_t)pb * 9;
-    const uint32_t node = ((const uint32_t*)(nb1 + nodes_of_off(n1)))[qi];
+    const uint32_t node = nodes_node_of(nb1, n1, qi);
     const float x1 = a.s1.xy[(e1 + qi) * 2], y1 = a.s1.xy[(e1 + qi) * 2 + 1];
     const float ur1 = a.s1.uright ? a.s1.uright[e1 + qi] : -1.0f;
     const float ex = a.ep[(size_t)pb * 2], ey = a.ep[(size_t)pb * 2 + 1];
@@ -64,46 +52,31 @@ void k_triangulation_search(TriArgs a) {
     int st = XFH_TRI_INACTIVE, ncand = 0, ngeom = 0, bi = -1, bd = a.th_low;
     if (active) {                                                      // (uniform)
         st = XFH_TRI_NO_NODE;
-        const uint32_t* __restrict__ ids = (const uint32_t*)(nb2 + nodes_ids_off(n2));
-        int nn = ((const NodesHeader*)nb2)->n_nodes;
-        nn = nn < 0 ? 0 : (nn > n2 ? n2 : nn);
-        int lo = 0, hi = nn;                                           // the first id >= node (uniform)
-        while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            if (ids[mid] < node) lo = mid + 1; else hi = mid;
-        }
-        if (node != XFH_NODE_NONE && lo < nn && ids[lo] == node) {
-            const int* __restrict__ ns = (const int*)(nb2 + nodes_start_off(n2));
-            const int* __restrict__ items = (const int*)(nb2 + nodes_items_off(n2));
-            int s = ns[lo], e = ns[lo + 1];
-            s = s < 0 ? 0 : (s > n2 ? n2 : s); e = e < 0 ? 0 : (e > n2 ? n2 : e);
-            const int len = e > s ? e - s : 0;
+        const int slot = nodes_find(nb2, n2, nodes_count(nb2, n2), node);                       // (uniform)
+        if (slot >= 0) {
+            const NodeRange nr = nodes_range(nb2, n2, slot);
             const float* __restrict__ xy2 = a.s2.xy + e2 * 2;
             const float* __restrict__ ur2 = a.s2.uright ? a.s2.uright + e2 : nullptr;
             const uint8_t* __restrict__ has2 = a.s2.has + e2;
             const char* __restrict__ tg = a.s2.desc + (size_t)pb * a.s2.desc_stride;
-            u64 best = ~0ull;
-            for (int p0 = 0; p0 < len; p0 += 64) {
+            u64 best = XFH_KEY_NONE;
+            for (int p0 = 0; p0 < nr.len; p0 += 64) {
                 const int p = p0 + lane;
-                int g = XFH_TRI_GATE_SKIPPED, idx = 0;
-                if (p < len) {
-                    idx = items[s + p];
-                    if (idx >= 0 && idx < n2 && has2[idx] == 0)                                    // :1189
-                        g = xfh_tri_member(l, ex, ey, a.epipole_r2, a.unc, a.flags, stereo1, xy2[(size_t)idx * 2], xy2[(size_t)idx * 2 + 1], ur2 ? ur2[idx] : -1.0f);
-                }
+                const int idx = p < nr.len ? nodes_item(nb2, n2, nr.start + p) : -1;
+                int g = XFH_TRI_GATE_SKIPPED;
+                if (idx >= 0 && has2[idx] == 0)                                                    // :1189
+                    g = xfh_tri_member(l, ex, ey, a.epipole_r2, a.unc, a.flags, stereo1, xy2[(size_t)idx * 2], xy2[(size_t)idx * 2 + 1], ur2 ? ur2[idx] : -1.0f);
                 ncand += g >= XFH_TRI_GATE_REJECTED ? 1 : 0; ngeom += g == XFH_TRI_GATE_PASSED ? 1 : 0;
                 if (g == XFH_TRI_GATE_PASSED) {
-                    const int dist = tri_descriptor_distance(qr, (const f32x4*)(tg + (size_t)idx * 256));
-                    const u64 key = ((u64)(unsigned)dist << 32) | (u64)(0xFFFFFFFFu - (unsigned)p);
+                    const u64 key = key_pack(descriptor_distance(qr, (const f32x4*)(tg + (size_t)idx * 256)), 0xFFFFFFFFu - (unsigned)p);
                     best = key < best ? key : best;
                 }
             }
-#pragma unroll
-            for (int m = 32; m >= 1; m >>= 1) { const u64 o = __shfl_xor(best, m); best = o < best ? o : best; }
+            best = wave_min_u64(best);
             ncand = wave_sum_i32(ncand); ngeom = wave_sum_i32(ngeom);
-            if (best != ~0ull && (int)(best >> 32) <= a.th_low) {
-                const int p = (int)(0xFFFFFFFFu - (unsigned)(best & 0xFFFFFFFFull));           // < len: the position the key was made of
-                bd = (int)(best >> 32); bi = items[s + p];
+            if (best != XFH_KEY_NONE && key_dist(best) <= a.th_low) {
+                const int p = (int)(0xFFFFFFFFu - (unsigned)key_pos(best));                    // < nr.len: the position the key was made of
+                bd = key_dist(best); bi = nodes_item(nb2, n2, nr.start + p);
             }
             st = bi >= 0 ? XFH_TRI_MATCHED : (ncand == 0 ? XFH_TRI_NO_CANDIDATES : XFH_TRI_REJECTED);
         }

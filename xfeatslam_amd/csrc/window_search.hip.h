@@ -10,6 +10,7 @@
 #pragma once
 #include "ctx.h"
 #include "window_layout.h"
+#include "search_common.hip.h"
 
 // ---- k_grid_build ---------------------------------------------------------------------------------------------------------
 // Every slot gets the key (cell << 20 | slot) -- slots that PosInGrid drops (:925) or that the caller leaves out get the largest
@@ -123,7 +124,7 @@ hipError_t launch_grid_build(xfh_ctx* c, const void* kps, size_t kps_stride, con
 
 // ---- k_search_window ------------------------------------------------------------------------------------------------------
 // One wave per query, four per workgroup, the query row through the scalar cache, (dist << 32 | position) keys and the butterfly
-// merge of k_best2_csr; the candidate list is replaced by the grid walk.  With cell = ix * 48 + iy the cells c0y .. c1y of column
+// merge of search_common.hip.h, as k_best2_csr; the candidate list is replaced by the grid walk.  With cell = ix * 48 + iy the cells c0y .. c1y of column
 // ix are ONE contiguous range of items, so the reference's visiting order (ix outer, iy inner, cell order inside, :884-911) is
 // the concatenation of at most 64 ranges: lane c takes column c0x + c, a wave scan of the range lengths gives every column its
 // first position, and position p of the walk is item adj[col(p)] + p.  Lanes are dealt positions of that walk (all members of
@@ -142,14 +143,9 @@ hipError_t launch_grid_build(xfh_ctx* c, const void* kps, size_t kps_stride, con
 //                 and calls visit(key, slot) for every survivor with key = dist << 32 | position (DIST = false: no descriptor is
 //                 read and the key's distance is 0; SAT = true: a distance the conversion cannot hold is INT_MAX); returns the number of
 //                 survivors of the whole wave
+//   window_count  the walk without descriptors: the window members this lane was dealt
 //   window_slot   the slot number at a position of the walk
-//   window_best2  butterfly merge of the lanes' two smallest keys and the reference's initial values (k_best2_csr's rule)
-// one key into a lane's two smallest: if (key < b) { s2 = b; b = key; } else if (key < s2) s2 = key; -- written as minima so that the pair
-// stays in registers when it is captured by reference
-__device__ __forceinline__ void top2_insert(u64& b, u64& s2, u64 key) {
-    const u64 hi = key < b ? b : key;
-    b = key < b ? key : b; s2 = hi < s2 ? hi : s2;
-}
+//   window_best2  the wave's two smallest keys (wave_top2) under the reference's initial values (k_best2_csr's rule), and their slots
 struct WindowWalk { int ncols, first, adj, T; };            // first / adj: of this lane's column; item = adj + position
 
 __device__ __forceinline__ WindowWalk window_open(const char* __restrict__ grid, float u, float v, float r, int nt, int lane) {
@@ -219,37 +215,26 @@ __device__ __forceinline__ int window_walk(const WindowWalk& w, const char* __re
         }
         ncand += __popcll(__ballot(pass));
         if (pass) {
-            int dist = 0;
-            if (DIST) {
-                const f32x4* tr = (const f32x4*)(tg + (size_t)idx * 64);
-                double acc = 0.0;
-#pragma unroll
-                for (int g = 0; g < 16; ++g) {
-                    const f32x4 tv = tr[g];
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) { const double df = (double)(qr[g * 4 + e] - tv[e]); acc = fma(df, df, acc); }
-                }
-                const float nd = (float)acc;
-                dist = (int)(nd * 512.0f);
-                if (SAT && !(nd < 4194304.0f)) dist = 0x7fffffff;      // SAT: a squared norm that is Inf, NaN or >= 2^31 / 512 is INT_MAX (init_search.hip.h)
-            }
-            visit(((u64)(unsigned)dist << 32) | (u64)(unsigned)p, idx);
+            const int dist = DIST ? descriptor_distance<SAT>(qr, (const f32x4*)(tg + (size_t)idx * 64)) : 0;
+            visit(key_pack(dist, (unsigned)p), idx);
         }
     }
     return ncand;
 }
 
+// the members of the window (u, v, r) THIS LANE was dealt, whatever else they are: no descriptor is read
+__device__ __forceinline__ int window_count(const WindowWalk& w, const char* __restrict__ grid, float u, float v, float r, int nt, int lane) {
+    int n = 0;
+    window_walk<false>(w, grid, nullptr, u, v, r, nullptr, nt, nullptr, nullptr, 0.0f, lane, [&](int, float, float) { ++n; return false; }, [](u64, int) {});
+    return n;
+}
+
 // every lane gets the merged pair of the wave; the reference's initial values: a candidate only counts if dist < init_dist (k_best2_csr)
 __device__ __forceinline__ void window_best2(const WindowWalk& w, const char* __restrict__ grid, u64 b, u64 s2, int init_dist,
                                              int& bi, int& bd, int& si, int& sd) {
-    const u64 NONE = ~0ull;
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) {
-        const u64 ob = __shfl_xor(b, m), os = __shfl_xor(s2, m);
-        top2_merge(b, s2, ob, os);
-    }
-    const bool hb = b != NONE && (int)(b >> 32) < init_dist, hs = hb && s2 != NONE && (int)(s2 >> 32) < init_dist;
-    const int wb = hb ? (int)(b & 0xFFFFFFFFull) : 0, ws = hs ? (int)(s2 & 0xFFFFFFFFull) : 0;
+    wave_top2(b, s2);
+    const bool hb = b != XFH_KEY_NONE && key_dist(b) < init_dist, hs = hb && s2 != XFH_KEY_NONE && key_dist(s2) < init_dist;
+    const int wb = hb ? key_pos(b) : 0, ws = hs ? key_pos(s2) : 0;
     // the items of the two winning positions (window_base for both in one pass over the columns)
     int pb = 0, ps = 0;
     for (int c = 0; c < w.ncols; ++c) {
@@ -258,8 +243,8 @@ __device__ __forceinline__ void window_best2(const WindowWalk& w, const char* __
     }
     const GridItem* items = (const GridItem*)(grid + XFH_GRID_ITEMS_OFF);
     bd = init_dist; bi = -1; sd = init_dist; si = -1;
-    if (hb) { bd = (int)(b >> 32); bi = items[pb + wb].index; }
-    if (hs) { sd = (int)(s2 >> 32); si = items[ps + ws].index; }
+    if (hb) { bd = key_dist(b); bi = items[pb + wb].index; }
+    if (hs) { sd = key_dist(s2); si = items[ps + ws].index; }
 }
 
 __global__ __launch_bounds__(256)
@@ -274,7 +259,7 @@ void k_search_window(const float* __restrict__ q, const float* __restrict__ uvr,
     const float u = uvr[(size_t)qi * 3], v = uvr[(size_t)qi * 3 + 1], r = uvr[(size_t)qi * 3 + 2];
     const float urq = ur_query ? ur_query[qi] : 0.0f;
     const WindowWalk w = window_open(grid, u, v, r, nt, lane);
-    u64 b = ~0ull, s2 = ~0ull;
+    u64 b = XFH_KEY_NONE, s2 = XFH_KEY_NONE;
     const int ncand = window_walk<true>(w, grid, qr, u, v, r, tg, nt, skip, uright, urq, lane, [](int, float, float) { return true; },
                                         [&](u64 key, int) { top2_insert(b, s2, key); });
     int bi, bd, si, sd;
