@@ -21,6 +21,8 @@
  *   XFmatcher::searchForInitialization: ORBmatcher::SearchForInitialization (ORBmatcher.cc:833-948), the matcher of
  *        Tracking::MonocularInitialization, with the reference's retraction order as one call; vbPrevMatched travels as (x, y) floats and is
  *        updated in place
+ *   XFvocabulary: the DBoW2 vocabulary as a blob in device memory and Frame::ComputeBoW / KeyFrame::ComputeBoW on it (TemplatedVocabulary::transform):
+ *        mBowVec, mFeatVec and, without a host step, the node blob searchByBoW / searchForTriangulation read in their device forms
  *   best2 / distinctive: the batched inner loops of SearchBy* (ORBmatcher.cc:75-119) and of
  *        MapPoint::ComputeDistinctiveDescriptors (MapPoint.cc:329-403)
  *
@@ -1014,6 +1016,108 @@ protected:
     std::vector<int> bowBest, bowSecond, bowCandidates;
     std::vector<unsigned char> initStatus;                  // results of searchForInitialization
     std::vector<int> initClaim, initBest, initSecond, initWindow, initTested, initMatches21, initMatchedDistance;
+};
+
+// The DBoW2 vocabulary in device memory and Frame::ComputeBoW / KeyFrame::ComputeBoW on it (xfh_vocab_pack, xfh_bow_transform_device;
+// TemplatedVocabulary::transform, thirdparty/DBoW2/DBoW2/TemplatedVocabulary.h:1127-1194, for ORBvoc's TF_IDF / L1_NORM).  The constructor takes
+// m_nodes flattened in node-id order (INTEGRATION.md has the loop) and uploads the blob once; the object owns it and the outputs of the last
+// transform().  transform(d_desc, n) runs every one of the n rows of a descriptor block that is already in device memory (a record's) down
+// the tree: deviceNodes() is then the node blob XFmatcher::searchByBoW / searchForTriangulation take in their device forms, with no host step
+// between; bowVec() is mBowVec (word id, value) in ascending word id and nodeOf()[i] the NodeId of keypoint i in mFeatVec (XFH_NODE_NONE: a
+// stopped feature, in no node).  Blocks until bowVec() and nodeOf() are on the host.
+class XFvocabulary {
+public:
+    using Mat = xfeat::cvx::Mat;
+    XFvocabulary(xfh_ctx* shared_ctx, int L, const std::vector<uint32_t>& parent, const std::vector<uint32_t>& wordId, const std::vector<double>& weight,
+                 const std::vector<unsigned char>& desc32) : ctx(shared_ctx) {
+        const size_t n = parent.size();
+        if (n > 0x7fffffffu || wordId.size() != n || weight.size() != n || desc32.size() != 32 * n) throw std::runtime_error("XFvocabulary: sizes do not fit");
+        vocabBytes = xfh_vocab_bytes((int)n);
+        std::vector<unsigned char> blob(vocabBytes ? vocabBytes : 1);
+        int rc = xfh_vocab_pack((int)n, L, parent.data(), wordId.data(), weight.data(), desc32.data(), blob.data(), &maxChildren_, &depth_);
+        if (rc != XFH_OK) throw std::runtime_error(std::string("XFvocabulary: ") + xfh_strerror(rc));
+        if (xfh_dev_alloc(&d_vocab, vocabBytes) != XFH_OK) throw std::runtime_error("XFvocabulary: out of device memory");
+        rc = xfh_memcpy_h2d(d_vocab, blob.data(), vocabBytes);
+        if (rc != XFH_OK) { xfh_dev_free(d_vocab); throw std::runtime_error(std::string("XFvocabulary: ") + xfh_strerror(rc)); }
+        nodes_ = (int)n; levels_ = L;
+    }
+    ~XFvocabulary() { if (d_vocab) xfh_dev_free(d_vocab); if (d_out) xfh_dev_free(d_out); if (d_rows) xfh_dev_free(d_rows); }
+    XFvocabulary(const XFvocabulary&) = delete;
+    XFvocabulary& operator=(const XFvocabulary&) = delete;
+
+    int size() const { return nodes_; }
+    int levels() const { return levels_; }
+    int maxChildren() const { return maxChildren_; }
+    int depth() const { return depth_; }
+    const void* device() const { return d_vocab; }
+    size_t deviceBytes() const { return vocabBytes; }
+
+    // n rows of 64 floats at d_desc (device memory, 16-byte aligned); returns the number of words of the BowVector
+    int transform(const float* d_desc, int n, int levelsup = 4) {
+        bow.clear(); nodeOf_.clear(); n_ = 0;
+        if (n <= 0) return 0;
+        auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+        const size_t b4 = al((size_t)n * 4), b8 = al((size_t)n * 8), bn = al(xfh_nodes_bytes(n)), bw = al(xfh_bow_transform_workspace_bytes(n, 1));
+        if (bw == 0) throw std::runtime_error("XFvocabulary::transform: sizes out of range");
+        const size_t need = bw + 3 * b4 + 2 * b8 + bn + 256;
+        if (need > outBytes) {
+            if (d_out) xfh_dev_free(d_out);
+            d_out = nullptr; outBytes = 0;
+            if (xfh_dev_alloc(&d_out, need) != XFH_OK) throw std::runtime_error("XFvocabulary::transform: out of device memory");
+            outBytes = need;
+        }
+        char* p = (char*)d_out;
+        void* ws = p; p += bw;
+        uint32_t* dword = (uint32_t*)p; p += b4; uint32_t* dno = (uint32_t*)p; p += b4; uint32_t* dids = (uint32_t*)p; p += b4;
+        double* dwt = (double*)p; p += b8; double* dvals = (double*)p; p += b8;
+        d_nodes = p; p += bn;
+        int* dnw = (int*)p;
+        int rc = xfh_bow_transform_device(ctx, 1, n, levelsup, XFH_BOWT_TF_IDF_L1, d_vocab, vocabBytes, d_desc, 0, ws, dword, dno, dwt, d_nodes, dids, dvals, dnw);
+        if (rc == XFH_OK) rc = xfh_synchronize(ctx);
+        int nw = 0;
+        if (rc == XFH_OK) rc = xfh_memcpy_d2h(&nw, dnw, 4);
+        nodeOf_.resize(n);
+        std::vector<uint32_t> ids(nw > 0 ? nw : 0); std::vector<double> vals(ids.size());
+        if (rc == XFH_OK) rc = xfh_memcpy_d2h(nodeOf_.data(), dno, (size_t)n * 4);
+        if (rc == XFH_OK && nw > 0) rc = xfh_memcpy_d2h(ids.data(), dids, ids.size() * 4);
+        if (rc == XFH_OK && nw > 0) rc = xfh_memcpy_d2h(vals.data(), dvals, vals.size() * 8);
+        if (rc != XFH_OK) { nodeOf_.clear(); throw std::runtime_error(std::string("XFvocabulary::transform: ") + xfh_strerror(rc)); }
+        bow.reserve(ids.size());
+        for (size_t k = 0; k < ids.size(); ++k) bow.push_back(std::make_pair(ids[k], vals[k]));
+        n_ = n;
+        return nw;
+    }
+    // the same on host rows (mDescriptors: CV_32F, 64 columns, continuous): uploads them first
+    int transform(const Mat& descriptors, int levelsup = 4) {
+        const int n = descriptors.rows;
+        if (n <= 0) { bow.clear(); nodeOf_.clear(); n_ = 0; return 0; }
+        const size_t bytes = (size_t)n * 256;
+        if (bytes > rowBytes) {
+            if (d_rows) xfh_dev_free(d_rows);
+            d_rows = nullptr; rowBytes = 0;
+            if (xfh_dev_alloc(&d_rows, bytes) != XFH_OK) throw std::runtime_error("XFvocabulary::transform: out of device memory");
+            rowBytes = bytes;
+        }
+        int rc = xfh_synchronize(ctx);                       // (the copy below is synchronous: nothing queued earlier may still read the buffer)
+        if (rc == XFH_OK) rc = xfh_memcpy_h2d(d_rows, descriptors.template ptr<float>(0), bytes);
+        if (rc != XFH_OK) throw std::runtime_error(std::string("XFvocabulary::transform: ") + xfh_strerror(rc));
+        return transform((const float*)d_rows, n, levelsup);
+    }
+    // of the last transform(): mBowVec, mFeatVec flattened, and the node blob in device memory (valid until the next transform())
+    const std::vector<std::pair<uint32_t, double>>& bowVec() const { return bow; }
+    const std::vector<uint32_t>& nodeOf() const { return nodeOf_; }
+    const void* deviceNodes() const { return n_ > 0 ? d_nodes : nullptr; }
+    int rows() const { return n_; }
+
+private:
+    xfh_ctx* ctx;
+    void* d_vocab = nullptr; size_t vocabBytes = 0;
+    void* d_out = nullptr; size_t outBytes = 0;
+    void* d_rows = nullptr; size_t rowBytes = 0;
+    void* d_nodes = nullptr;
+    int nodes_ = 0, levels_ = 0, maxChildren_ = 0, depth_ = 0, n_ = 0;
+    std::vector<std::pair<uint32_t, double>> bow;
+    std::vector<uint32_t> nodeOf_;
 };
 
 }  // namespace ORB_SLAM3

@@ -26,7 +26,8 @@
  *     several threads at once (without a device each call returns XFH_ERR_NO_DEVICE).
  *     xfh_map_project, xfh_sim3_project and xfh_map_projection_search_workspace_bytes are stateless in the same way (a loop over
  *     one pure function, no static data); they are not part of the ThreadSanitizer run.  So are xfh_init_accept,
- *     xfh_init_list_entries and xfh_init_search_workspace_bytes.
+ *     xfh_init_list_entries and xfh_init_search_workspace_bytes, and xfh_vocab_bytes, xfh_vocab_pack, xfh_vocab_unpack, xfh_vocab_descend
+ *     and xfh_bow_transform_workspace_bytes.
  *
  * The C++ wrappers that restore the reference's class surface on top of this ABI are
  * include/xfeat/XFextractor.h and include/xfeat/ORBmatcher_xfeat.h; INTEGRATION.md shows
@@ -594,8 +595,8 @@ int xfh_fuse_search(xfh_ctx* ctx, int nq, const float* points, const float* norm
  *
  * Node index.  TemplatedVocabulary::transform visits the features in ascending index and FeatureVector::addFeature push_backs, so
  * mFeatVec is "node id ascending, keypoint index ascending inside a node": a function of node_of[i], the NodeId of keypoint i
- * (XFH_NODE_NONE: keypoint i is in no node; every other uint32 is a valid id).  DBoW2 itself stays with the caller, who
- * flattens mFeatVec into node_of on the host, where it was computed.
+ * (XFH_NODE_NONE: keypoint i is in no node; every other uint32 is a valid id).  node_of comes either from the caller's own DBoW2 (mFeatVec
+ * flattened on the host) or, without a host step, from xfh_bow_transform_device below, which writes the blob itself.
  *   xfh_nodes_bytes / xfh_nodes_pack   host, stateless: node_of[n] -> an opaque, self-contained blob of xfh_nodes_bytes(n) bytes (a multiple
  *                         of 16): a header, the distinct node ids ascending, node_start, the items (keypoint indices, nodes in id order,
  *                         ascending inside a node) and a copy of node_of.  The caller uploads it with xfh_memcpy_h2d (16-byte aligned); one
@@ -738,7 +739,7 @@ int xfh_triangulation_search(xfh_ctx* ctx, int n1, int n2, int flags, int th_low
  *   xfh_bow_search        host-pointer convenience form for ONE problem: packs both node blobs, stages the inputs and the workspace, runs
  *                         the call and copies the results back.  XFH_ERR_INVALID_ARG for the device form's classes of error before
  *                         anything is staged or queued.
- * Out of scope: the Nleft != -1 branches (fisheye stereo); computing the BoW or feature vector (DBoW2 stays with the caller);
+ * Out of scope: the Nleft != -1 branches (fisheye stereo); computing the BoW or feature vector (xfh_bow_transform_device below);
  * (SearchForInitialization is xfh_init_search_device, the relocalisation and Sim3 SearchByProjection forms are
  * xfh_map_projection_search_device, SearchBySim3 is xfh_sim3_search_device, all below); the PnP and Sim3 solvers that consume the matches. */
 #define XFH_BOW_STRICT_LOW 1          /* flags: accept on best < th_low (the keyframe form) instead of best <= th_low */
@@ -752,6 +753,82 @@ int xfh_bow_search_device(xfh_ctx* ctx, int B, int n1, int n2, int shared, int f
 int xfh_bow_search(xfh_ctx* ctx, int n1, int n2, int flags, int init_dist, int th_low, float nn_ratio, const uint32_t* node_of1, const uint8_t* active1,
                    const float* desc1, const uint32_t* node_of2, const uint8_t* eligible2_or_null, const float* desc2, uint8_t* status, int* match12,
                    int* best_dist, int* second_dist, int* n_candidates, int* assigned2, int* n_matches);
+
+/* ---- The vocabulary transform: BowVector and node blobs, device resident -------------------------------------------------------------------
+ * TemplatedVocabulary::transform(features, v, fv, levelsup) of DBoW2 (thirdparty/DBoW2/DBoW2/TemplatedVocabulary.h:1127-1194; Frame::ComputeBoW
+ * and KeyFrame::ComputeBoW: Tracking.cc:2750, :3661, :2563-2564, LocalMapping.cc:307) for B frames of n rows per call, for the weighting and
+ * norm ORBvoc.txt's header `10 6 0 0` selects: TF_IDF, L1_NORM.  It removes the last host round trip between xfh_extract_batch_device and
+ * xfh_bow_search_device / xfh_triangulation_search_device: the node blob those two read is written on the device.
+ *
+ * DBoW2 treats an XFeat row as a 256-bit ORB descriptor: FORB::distance (FORB.cpp:81-101) popcounts the XOR of the first 8
+ * int32 of the row, i.e. of the bit patterns of its first 8 floats.  The library reads those 32 bytes as 8 uint32 and never as floats: NaN
+ * and Inf patterns are just bits.  Everything here is integers and IEEE doubles in a fixed order, so every output is exact.
+ *
+ * The vocabulary.  The caller keeps its DBoW2 vocabulary (KeyFrameDatabase needs it) and flattens m_nodes, in node-id order, into parent[],
+ * word_id[], weight[] and desc[][32] (FORB::L); INTEGRATION.md has the loop.  Node 0 is the root; its parent, descriptor and weight are
+ * ignored.  CONTRACT: the children of a node are the nodes that name it as parent, in ascending id -- loadFromTextFile's push_back order
+ * (TemplatedVocabulary.h:1385-1392).  A node is a leaf iff it has no children (isLeaf()), whatever its word_id and whatever the text file's
+ * leaf flag said: loadFromTextFile's `while(!f.eof())` loop turns a trailing newline into one extra node under the root with a zero
+ * descriptor, weight 0, word_id 0 and no children; it is accepted, and a feature that lands on it is stopped like any w <= 0.
+ *   xfh_vocab_bytes / xfh_vocab_pack   host, stateless: the arrays -> an opaque, self-contained blob of xfh_vocab_bytes(n_nodes) bytes
+ *                         (0 for n_nodes < 1).  The nodes are reordered into slots so that the children of a node are one contiguous,
+ *                         32-byte aligned run of descriptors in child order; per slot {first_child_slot, n_children, node_id, word_id} and,
+ *                         in an array apart, weight.  Padding is zeroed: two packs of the same input give identical bytes.  The caller uploads
+ *                         it once with xfh_memcpy_h2d (16-byte aligned).  XFH_ERR_INVALID_ARG: n_nodes < 2, parent[i] >= i for an i >= 1 (the
+ *                         reference would index past m_nodes), a root without children, more than XFH_VOCAB_MAX_CHILDREN children of one
+ *                         node, a tree deeper than XFH_VOCAB_MAX_DEPTH, L outside 1 .. 10 (the loader's own range), a NULL array.
+ *   xfh_vocab_unpack      the test and debug inverse, in node-id order (parent[0] = 0; the root's weight and row come back as zero).  A
+ *                         truncated or inconsistent blob is XFH_ERR_INVALID_ARG, never an out-of-bounds access.
+ *   xfh_vocab_descend     host, stateless, thread-safe: transform(feature, word_id, weight, nid, levelsup) (:1218-1259) for ONE row, the same
+ *                         source lines as the kernel (vocab_math.h).  row32: 32 bytes.  Start at the root; at each level d(child) is the
+ *                         popcount of the XOR over the 8 words and the first child with the least d wins (strict `<` over the children in
+ *                         order); stop at a node without children.  *word_id and *weight are that leaf's.  nid_level = L - levelsup:
+ *                         *node_id is 0 when nid_level <= 0, the path's node at level nid_level when the path is that long, otherwise the
+ *                         leaf -- a documented deviation: the reference leaves nid uninitialised there (:1150-1155, :1251).  levelsup < 0 is
+ *                         XFH_ERR_INVALID_ARG.  Hostile blobs: the node count is clamped to what nbytes holds, every slot index and child
+ *                         count is clamped before it indexes anything, and the loop runs at most XFH_VOCAB_MAX_DEPTH levels, so such a
+ *                         blob can neither leave the buffer nor loop forever; results for a blob xfh_vocab_pack did not write are
+ *                         unspecified.
+ *
+ * Per frame, over ALL n rows in index order (zero padding rows included: the reference hands every row of mDescriptors to DBoW2):
+ *   word[i], weight[i] = the leaf's (also when stopped);  node_of[i] = the node id above, or XFH_NODE_NONE when !(weight[i] > 0) (a NaN
+ *   weight stops the feature too) -- `if(w > 0)` (:1152)
+ *   nodes     byte for byte what xfh_nodes_pack(node_of) writes: FeatureVector::addFeature in feature order
+ *   BowVector the distinct words of the features that are not stopped, ascending;  val(word) = ((w + w') + w'') ..., ONE double add per
+ *             feature in index order (BowVector::addWeight; the iterated sum is not count * w in general);  norm = the left-to-right double
+ *             sum of |val| over ascending word id, from 0.0;  val /= norm when norm > 0 (BowVector::normalize(L1));  bow_ids / bow_vals hold
+ *             them in that order, unused entries are id 0xFFFFFFFF, value 0;  n_words is the count
+ *
+ *   xfh_bow_transform_workspace_bytes   bytes of d_workspace for B frames of n rows (0 for sizes the call would refuse).
+ *   xfh_bow_transform_device   flags = XFH_BOWT_TF_IDF_L1.  d_vocab: the uploaded blob, vocab_bytes its size.  Frame b reads its rows b *
+ *                         desc_stride_bytes in (xfh_record_bytes(nfeatures) lets d_desc point at the desc block of record 0 of a batch) and
+ *                         writes d_word / d_node_of / d_bow_ids [B][n] uint32, d_weight / d_bow_vals [B][n] doubles, d_nodes [B] blobs of
+ *                         xfh_nodes_bytes(n) bytes (ready for xfh_bow_search_device and xfh_triangulation_search_device), d_n_words [B]
+ *                         ints.  All pointers are device pointers; asynchronous on the ctx stream, no allocation, no host
+ *                         synchronisation, two kernel launches; two runs give identical bytes.  XFH_ERR_INVALID_ARG before anything is
+ *                         queued: n outside 1 .. XFH_GRID_MAX_N, B outside 1 .. 65535, levelsup < 0, any other flags (the other
+ *                         weightings and norms), vocab_bytes < xfh_vocab_bytes(2), a NULL pointer, misaligned pointers (16 bytes for the
+ *                         vocabulary, the rows and their stride, the workspace and d_nodes, 8 for the doubles, 4 for the rest).  The
+ *                         vocabulary blob may hold anything (see xfh_vocab_descend).
+ *   xfh_bow_transform     host-pointer convenience form for ONE frame: stages the vocabulary blob (all of it, per call: a test and
+ *                         debugging form), the rows and the workspace, runs the call and copies the results back.
+ * Out of scope: KeyFrameDatabase and L1Scoring::score; the yml and binary vocabulary loaders (and the text loader: the caller has DBoW2's);
+ * vocabulary creation; the other weightings and norms; skipping padding rows. */
+#define XFH_VOCAB_MAX_CHILDREN 32     /* children of one vocabulary node (ORBvoc: k = 10) */
+#define XFH_VOCAB_MAX_DEPTH 32        /* levels below the root (ORBvoc: L = 6) */
+#define XFH_BOWT_TF_IDF_L1 0          /* flags: WeightingType TF_IDF, ScoringType L1_NORM */
+size_t xfh_vocab_bytes(int n_nodes);
+int xfh_vocab_pack(int n_nodes, int L, const uint32_t* parent, const uint32_t* word_id, const double* weight, const uint8_t* desc /* [n_nodes][32] */,
+                   void* blob /* xfh_vocab_bytes(n_nodes) */, int* max_children_or_null, int* depth_or_null);
+int xfh_vocab_unpack(const void* blob, size_t nbytes, int n_nodes, int* L, uint32_t* parent, uint32_t* word_id, double* weight,
+                     uint8_t* desc /* [n_nodes][32] */, int* max_children_or_null, int* depth_or_null);
+int xfh_vocab_descend(const void* blob, size_t nbytes, int levelsup, const void* row32, uint32_t* word_id, uint32_t* node_id, double* weight);
+size_t xfh_bow_transform_workspace_bytes(int n, int B);
+int xfh_bow_transform_device(xfh_ctx* ctx, int B, int n, int levelsup, int flags, const void* d_vocab, size_t vocab_bytes, const float* d_desc,
+                             size_t desc_stride_bytes, void* d_workspace, uint32_t* d_word, uint32_t* d_node_of, double* d_weight, void* d_nodes,
+                             uint32_t* d_bow_ids, double* d_bow_vals, int* d_n_words);
+int xfh_bow_transform(xfh_ctx* ctx, int n, int levelsup, int flags, const void* vocab, size_t vocab_bytes, const float* desc, uint32_t* word,
+                      uint32_t* node_of, double* weight, void* nodes /* xfh_nodes_bytes(n) */, uint32_t* bow_ids, double* bow_vals, int* n_words);
 
 /* ---- SearchByProjection of map points with a claim: the Sim3 forms and the relocalisation form, device resident -----------------------
  * Three reference functions as one call (src/ORBmatcher.cc):

@@ -222,6 +222,8 @@ struct Sim3Args;
 hipError_t launch_sim3_search(xfh_ctx* c, const Sim3Args& a, int B);                  // sim3_search.hip.h
 struct InitArgs;
 hipError_t launch_init_search(xfh_ctx* c, const InitArgs& a, int B);                  // init_search.hip.h
+struct VocabArgs;
+hipError_t launch_bow_transform(xfh_ctx* c, const VocabArgs& a, int B);             // vocab_transform.hip.h
 struct BowArgs;
 hipError_t launch_bow_search(xfh_ctx* c, const BowArgs& a, int B);                    // bow_search.hip.h
 hipError_t launch_best2(xfh_ctx* c, const float* q, int nq, const float* tg, const int* offsets, const int* indices, int init_dist,

@@ -22,6 +22,8 @@
 //                   reference's last-wins tie (triangulation_search.hip.h).
 //   k_bow_candidates / k_bow_resolve : both ORBmatcher::SearchByBoW overloads, B problems per call: per query the least members of its node, then
 //                   the reference's claim order resolved per node, one wave each, the claimed set in LDS (bow_search.hip.h).
+//   k_vocab_descend / k_vocab_finish : TemplatedVocabulary::transform of DBoW2 for B frames per call: every row down the vocabulary tree, 16 lanes per
+//                   feature, then per frame the node blob of the two kernels above and the normalised BowVector, sorted in LDS (vocab_transform.hip.h).
 //   k_mapproj_candidates : the front kernel of the Sim3 and relocalisation forms of SearchByProjection: per map point the projection, the culls, the level and
 //                   the window walk with the K best candidates; k_proj_resolve / k_proj_count settle the claims behind it (mapproj_search.hip.h).
 //   k_sim3_search / k_sim3_agree : ORBmatcher::SearchBySim3 up to vpMatches12, B keyframe pairs per call: both directions of the projection through
@@ -89,6 +91,7 @@ hipError_t launch_best2(xfh_ctx* c, const float* q, int nq, const float* tg, con
 #include "fuse_search.hip.h"
 #include "triangulation_search.hip.h"
 #include "bow_search.hip.h"
+#include "vocab_transform.hip.h"
 #include "mapproj_search.hip.h"
 #include "sim3_search.hip.h"
 #include "init_search.hip.h"

@@ -560,6 +560,89 @@ class Context:
         r.update(status=st, assigned2=as2, n_matches=int(nm[0]))
         return r
 
+    # -- the vocabulary transform: BowVector and node blobs (xfh_vocab_* / xfh_bow_transform*) ------------------------------------------------
+    @staticmethod
+    def vocab_bytes(n_nodes: int) -> int:
+        return int(lib().xfh_vocab_bytes(n_nodes))
+
+    @staticmethod
+    def vocab_pack(parent, word_id, weight, desc, L: int):
+        """xfh_vocab_pack (host): m_nodes flattened in node-id order (parent[n], word_id[n], weight[n], desc[n][32] bytes; node 0 = the root)
+        -> (the vocabulary blob as bytes, ready for upload, max_children, depth)"""
+        pa, wi = np.ascontiguousarray(parent, np.uint32), np.ascontiguousarray(word_id, np.uint32)
+        wt, de = np.ascontiguousarray(weight, np.float64), np.ascontiguousarray(desc, np.uint8)
+        n = len(pa)
+        assert len(wi) == n and len(wt) == n and de.shape == (n, 32)
+        blob = np.full(max(Context.vocab_bytes(n), 16), 0xA5, np.uint8)
+        mc, dp = C.c_int(0), C.c_int(0)
+        check(lib().xfh_vocab_pack(n, int(L), pa.ctypes.data, wi.ctypes.data, wt.ctypes.data, de.ctypes.data, blob.ctypes.data, C.byref(mc), C.byref(dp)))
+        return blob, mc.value, dp.value
+
+    @staticmethod
+    def vocab_unpack(blob: np.ndarray, n_nodes: int):
+        """xfh_vocab_unpack (host): a vocabulary blob -> dict(L, parent, word_id, weight, desc, max_children, depth) in node-id order"""
+        b = np.ascontiguousarray(blob, np.uint8)
+        n = max(n_nodes, 1)
+        pa, wi, wt, de = np.zeros(n, np.uint32), np.zeros(n, np.uint32), np.zeros(n, np.float64), np.zeros((n, 32), np.uint8)
+        L, mc, dp = C.c_int(0), C.c_int(0), C.c_int(0)
+        check(lib().xfh_vocab_unpack(b.ctypes.data, b.nbytes, n_nodes, C.byref(L), pa.ctypes.data, wi.ctypes.data, wt.ctypes.data, de.ctypes.data,
+                                     C.byref(mc), C.byref(dp)))
+        return dict(L=L.value, parent=pa, word_id=wi, weight=wt, desc=de, max_children=mc.value, depth=dp.value)
+
+    @staticmethod
+    def vocab_descend(blob: np.ndarray, rows, levelsup: int = 4):
+        """xfh_vocab_descend (host) for every row (float32 [n][>= 8] or any array with >= 32 bytes per row) -> (word[n], node[n], weight[n])"""
+        b = np.ascontiguousarray(blob, np.uint8)
+        r = np.ascontiguousarray(rows)
+        r = r.reshape(len(r), -1).view(np.uint8)
+        n = len(r)
+        first = np.ascontiguousarray(r[:, :32])
+        word, node, wt = np.zeros(n, np.uint32), np.zeros(n, np.uint32), np.zeros(n, np.float64)
+        L = lib()
+        for i in range(n):
+            check(L.xfh_vocab_descend(b.ctypes.data, b.nbytes, int(levelsup), first.ctypes.data + 32 * i, word.ctypes.data + 4 * i, node.ctypes.data + 4 * i,
+                                      wt.ctypes.data + 8 * i))
+        return word, node, wt
+
+    @staticmethod
+    def bow_transform_workspace_bytes(n: int, B: int = 1) -> int:
+        return int(lib().xfh_bow_transform_workspace_bytes(n, B))
+
+    @staticmethod
+    def bow_transform_layout(B: int, n: int, guard: int = 0):
+        """byte offsets of the outputs of bow_transform_device inside one buffer (and its size under "bytes"); guard as in fuse_search_layout.
+        The workspace is a buffer of its own (bow_transform_workspace_bytes)."""
+        al = lambda x: (x + 255) & ~255
+        o, off = {}, al(guard)
+        for name, nbytes in (("word", 4 * B * n), ("node_of", 4 * B * n), ("weight", 8 * B * n), ("nodes", B * Context.nodes_bytes(n)), ("bow_ids", 4 * B * n),
+                             ("bow_vals", 8 * B * n), ("n_words", 4 * B)):
+            o[name] = off; off += al(nbytes) + al(guard)
+        o["bytes"] = off
+        return o
+
+    def bow_transform_device(self, B: int, n: int, d_vocab, vocab_bytes: int, d_desc, desc_stride: int, d_workspace, d_out, levelsup: int = 4, guard: int = 0):
+        """xfh_bow_transform_device on device pointers; asynchronous.  d_out: pointer to the outputs laid out as bow_transform_layout(B, n,
+        guard) says; d_out + layout["nodes"] then feeds bow_search_device / triangulation_search_device"""
+        o = self.bow_transform_layout(B, n, guard)
+        check(lib().xfh_bow_transform_device(self.h, B, n, int(levelsup), capi.BOWT_TF_IDF_L1, d_vocab, vocab_bytes, d_desc, desc_stride, d_workspace,
+                                             d_out + o["word"], d_out + o["node_of"], d_out + o["weight"], d_out + o["nodes"], d_out + o["bow_ids"],
+                                             d_out + o["bow_vals"], d_out + o["n_words"]), self.h)
+
+    def bow_transform(self, vocab_blob, desc, levelsup: int = 4):
+        """xfh_bow_transform (host pointers, one frame) -> dict(word, node_of, weight, nodes (the node blob as bytes), bow_ids, bow_vals
+        (both cut to n_words), n_words)"""
+        b = np.ascontiguousarray(vocab_blob, np.uint8)
+        d = np.ascontiguousarray(desc, np.float32)
+        n = len(d)
+        assert d.shape == (n, 64)
+        word, node_of, ids = np.zeros(n, np.uint32), np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+        wt, vals = np.zeros(n, np.float64), np.zeros(n, np.float64)
+        nodes = np.zeros(self.nodes_bytes(n), np.uint8); nw = np.zeros(1, np.int32)
+        check(lib().xfh_bow_transform(self.h, n, int(levelsup), capi.BOWT_TF_IDF_L1, b.ctypes.data, b.nbytes, d.ctypes.data, word.ctypes.data, node_of.ctypes.data,
+                                      wt.ctypes.data, nodes.ctypes.data, ids.ctypes.data, vals.ctypes.data, nw.ctypes.data), self.h)
+        k = int(nw[0])
+        return dict(word=word, node_of=node_of, weight=wt, nodes=nodes, bow_ids=ids[:k].copy(), bow_vals=vals[:k].copy(), n_words=k)
+
     # -- SearchByProjection of map points with a claim: the Sim3 and relocalisation forms (xfh_map_project / xfh_map_projection_search*) ----
     MAPPROJ_OUT_INT = ("match_idx", "best_dist", "n_window", "n_tested", "level")
 
@@ -849,6 +932,13 @@ class ORBmatcher:
                                           epipole_r2=float(np.float32(100) * np.float32(scale_factor0)), unc=level_sigma2_0)
         m = r["match12"]
         return r["n_matches"], [(int(i), int(m[i])) for i in np.nonzero(m >= 0)[0]], r
+
+    def ComputeBoW(self, vocab_blob, desc, levelsup: int = 4):
+        """`Frame::ComputeBoW` / `KeyFrame::ComputeBoW` (Frame.cc:936, KeyFrame.cc:105: mpORBvocabulary->transform(vCurrentDesc, mBowVec, mFeatVec, 4)) on a
+        vocabulary blob of Context.vocab_pack, over every row of desc.  -> (mBowVec as a list of (word id, value) in ascending word id,
+        node_of = mFeatVec flattened for search_by_bow / search_for_triangulation, result dict of Context.bow_transform)"""
+        r = self.ctx.bow_transform(vocab_blob, desc, levelsup)
+        return list(zip(r["bow_ids"].tolist(), r["bow_vals"].tolist())), r["node_of"], r
 
     def search_by_bow(self, node_of1, has1, desc1, node_of2, desc2):
         """`ORBmatcher::SearchByBoW(KeyFrame*, Frame&, vpMapPointMatches)` (ORBmatcher.cc:408-610): side 1 = the keyframe (has1[i] != 0 where
