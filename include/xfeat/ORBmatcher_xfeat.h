@@ -1120,5 +1120,155 @@ private:
     std::vector<uint32_t> nodeOf_;
 };
 
+// KeyFrameDatabase without the inverted file (reference include/KeyFrameDatabase.h; DetectRelocalizationCandidates, src/KeyFrameDatabase.cc:733-845,
+// and DetectNBestCandidates, :604-730, with L1Scoring::score): the BowVectors of the keyframes live in device arrays, one SLOT per keyframe, and a
+// query scans them (xfh_bowdb_query_device).  A slot is the caller's handle for a keyframe: the caller keeps the KeyFrame pointers (slot ->
+// KeyFrame*), erases a keyframe before it turns bad, and owns the maps.  add() takes mBowVec and the slots of GetBestCovisibilityKeyFrames(nn);
+// deviceIds / deviceVals / deviceWords(slot) let xfh_bow_transform_device write a keyframe straight into its slot (stride == the transform's
+// n), after which stamp(slot) puts it at the end of the insertion order.  The two persistent scores (mRelocScore, mPlaceRecognitionScore) are
+// two device arrays of the database, zero at the start.  The candidate functions block until the answer is on the host; the sequence before the
+// map tests and the caps is kept in candSlot / candAcc, the scored list in listSlot / listAcc / listBest, the header in nListed ... bestAcc.
+class XFkeyframeDatabase {
+public:
+    typedef std::vector<std::pair<uint32_t, double>> BowVec;
+    XFkeyframeDatabase(xfh_ctx* shared_ctx, int nSlots, int stride, int nNeighbours = 10) : ctx(shared_ctx), n(nSlots), st(stride), nn(nNeighbours) {
+        const size_t wsb = xfh_bowdb_query_workspace_bytes(n, 1);
+        if (wsb == 0 || st < 1 || st > XFH_GRID_MAX_N || nn < 0 || nn > XFH_BOWDB_MAX_NEIGHBOURS) throw std::runtime_error("XFkeyframeDatabase: sizes out of range");
+        const size_t N = (size_t)n, S = (size_t)st, K = (size_t)(nn > 0 ? nn : 1);
+        const size_t sizes[] = {N * S * 4, N * S * 8, N * 4, N * 4, N * K * 4, N * 4, N * 4, S * 4, S * 8, 4, N, wsb,
+                                N * 4, N * 8, N, XFH_BOWDB_HEADER_INTS * 4, 4, N * 4, N * 4, N * 4, N * 4, N * 4};
+        size_t off[sizeof sizes / sizeof *sizes], total = 0;
+        for (size_t i = 0; i < sizeof sizes / sizeof *sizes; ++i) { off[i] = total; total += (sizes[i] + 255) & ~(size_t)255; }
+        if (xfh_dev_alloc(&d_all, total) != XFH_OK) throw std::runtime_error("XFkeyframeDatabase: out of device memory");
+        std::vector<unsigned char> zero(total, 0);
+        memset(zero.data() + off[4], 0xFF, sizes[4]);                   // neighbours: -1
+        if (xfh_memcpy_h2d(d_all, zero.data(), total) != XFH_OK) { xfh_dev_free(d_all); d_all = nullptr; throw std::runtime_error("XFkeyframeDatabase: upload failed"); }
+        char* p = (char*)d_all;
+        d_ids = (uint32_t*)(p + off[0]); d_vals = (double*)(p + off[1]); d_nw = (int*)(p + off[2]); d_seq = (uint32_t*)(p + off[3]); d_neigh = (int32_t*)(p + off[4]);
+        d_state[0] = (float*)(p + off[5]); d_state[1] = (float*)(p + off[6]);
+        d_qi = (uint32_t*)(p + off[7]); d_qv = (double*)(p + off[8]); d_qn = (int*)(p + off[9]); d_ex = (uint8_t*)(p + off[10]); d_ws = p + off[11];
+        d_common = (int32_t*)(p + off[12]); d_score = (double*)(p + off[13]); d_status = (uint8_t*)(p + off[14]); d_header = (int32_t*)(p + off[15]);
+        d_best = (float*)(p + off[16]); d_ls = (int32_t*)(p + off[17]); d_la = (float*)(p + off[18]); d_lb = (int32_t*)(p + off[19]);
+        d_cs = (int32_t*)(p + off[20]); d_ca = (float*)(p + off[21]);
+    }
+    ~XFkeyframeDatabase() { if (d_all) xfh_dev_free(d_all); }
+    XFkeyframeDatabase(const XFkeyframeDatabase&) = delete;
+    XFkeyframeDatabase& operator=(const XFkeyframeDatabase&) = delete;
+
+    int slots() const { return n; }
+    int stride() const { return st; }
+    uint32_t* deviceIds(int slot) const { return d_ids + (size_t)slot * st; }
+    double* deviceVals(int slot) const { return d_vals + (size_t)slot * st; }
+    int* deviceWords(int slot) const { return d_nw + slot; }
+
+    // KeyFrameDatabase::add(pKF): mBowVec (ascending word id) into a slot, at the end of the insertion order
+    void add(int slot, const BowVec& bow, const std::vector<int>& neighbours = std::vector<int>()) {
+        if (slot < 0 || slot >= n || bow.size() > (size_t)st) throw std::runtime_error("XFkeyframeDatabase::add: out of range");
+        std::vector<uint32_t> ids(bow.size()); std::vector<double> vals(bow.size());
+        for (size_t k = 0; k < bow.size(); ++k) { ids[k] = bow[k].first; vals[k] = bow[k].second; }
+        const int nw = (int)bow.size();
+        sync();
+        if (nw > 0) { put(deviceIds(slot), ids.data(), ids.size() * 4); put(deviceVals(slot), vals.data(), vals.size() * 8); }
+        put(deviceWords(slot), &nw, 4);
+        stamp(slot);
+        setNeighbours(slot, neighbours);
+    }
+    // the slot's place in the insertion order: now the last
+    void stamp(int slot) { const uint32_t s = nextSeq++; sync(); put(d_seq + slot, &s, 4); }
+    // the slots of GetBestCovisibilityKeyFrames(nn) in its order (an entry outside 0 .. slots-1 means none)
+    void setNeighbours(int slot, const std::vector<int>& neighbours) {
+        if (slot < 0 || slot >= n) throw std::runtime_error("XFkeyframeDatabase::setNeighbours: out of range");
+        if (nn == 0) return;
+        std::vector<int32_t> ng(nn, -1);
+        for (size_t k = 0; k < neighbours.size() && k < (size_t)nn; ++k) ng[k] = neighbours[k];
+        sync();
+        put(d_neigh + (size_t)slot * nn, ng.data(), (size_t)nn * 4);
+    }
+    // KeyFrameDatabase::erase(pKF)
+    void erase(int slot) {
+        if (slot < 0 || slot >= n) throw std::runtime_error("XFkeyframeDatabase::erase: out of range");
+        const int zero = 0;
+        sync();
+        put(deviceWords(slot), &zero, 4);
+    }
+
+    // one query; fills the members below.  exclude: the slots of the connected keyframes (and of the query keyframe itself)
+    void query(int form, const BowVec& bow, const std::vector<int>& exclude = std::vector<int>()) {
+        if (bow.size() > (size_t)st) throw std::runtime_error("XFkeyframeDatabase::query: the vector does not fit the stride");
+        std::vector<uint32_t> ids(bow.size()); std::vector<double> vals(bow.size());
+        for (size_t k = 0; k < bow.size(); ++k) { ids[k] = bow[k].first; vals[k] = bow[k].second; }
+        std::vector<uint8_t> ex(n, 0);
+        for (int s : exclude) if (s >= 0 && s < n) ex[s] = 1;
+        const int nw = (int)bow.size();
+        sync();
+        if (nw > 0) { put(d_qi, ids.data(), ids.size() * 4); put(d_qv, vals.data(), vals.size() * 8); }
+        put(d_qn, &nw, 4); put(d_ex, ex.data(), ex.size());
+        int rc = xfh_bowdb_query_device(ctx, 1, n, form, d_qi, d_qv, d_qn, st, d_ids, d_vals, d_nw, st, d_seq, nn > 0 ? d_neigh : nullptr, nn, d_ex,
+                                        d_state[form == XFH_BOWDB_FORM_NBEST ? 1 : 0], d_ws, d_common, d_score, d_status, d_header, d_best, d_ls, d_la, d_lb, d_cs, d_ca);
+        if (rc == XFH_OK) rc = xfh_synchronize(ctx);
+        int32_t h[XFH_BOWDB_HEADER_INTS] = {};
+        common.resize(n); score.resize(n); status.resize(n); listSlot.resize(n); listAcc.resize(n); listBest.resize(n); candSlot.resize(n); candAcc.resize(n);
+        if (rc == XFH_OK) rc = xfh_memcpy_d2h(h, d_header, sizeof h);
+        if (rc == XFH_OK) rc = xfh_memcpy_d2h(&bestAcc, d_best, 4);
+        if (rc == XFH_OK) rc = xfh_memcpy_d2h(common.data(), d_common, (size_t)n * 4);
+        if (rc == XFH_OK) rc = xfh_memcpy_d2h(score.data(), d_score, (size_t)n * 8);
+        if (rc == XFH_OK) rc = xfh_memcpy_d2h(status.data(), d_status, (size_t)n);
+        if (rc == XFH_OK) rc = xfh_memcpy_d2h(listSlot.data(), d_ls, (size_t)n * 4);
+        if (rc == XFH_OK) rc = xfh_memcpy_d2h(listAcc.data(), d_la, (size_t)n * 4);
+        if (rc == XFH_OK) rc = xfh_memcpy_d2h(listBest.data(), d_lb, (size_t)n * 4);
+        if (rc == XFH_OK) rc = xfh_memcpy_d2h(candSlot.data(), d_cs, (size_t)n * 4);
+        if (rc == XFH_OK) rc = xfh_memcpy_d2h(candAcc.data(), d_ca, (size_t)n * 4);
+        if (rc != XFH_OK) throw std::runtime_error(std::string("XFkeyframeDatabase::query: ") + xfh_strerror(rc));
+        nListed = h[0]; maxCommon = h[1]; minCommon = h[2]; nScored = h[3]; nCandidates = h[4];
+    }
+
+    // DetectRelocalizationCandidates(F, pMap): the candidate slots in the reference's order.  mapOfSlot[s] is compared with map
+    // (`if (pKFi->GetMap() != pMap) continue;`, :834); an empty mapOfSlot keeps every candidate
+    std::vector<int> DetectRelocalizationCandidates(const BowVec& bow, const std::vector<int>& mapOfSlot = std::vector<int>(), int map = 0) {
+        query(XFH_BOWDB_FORM_RELOC, bow);
+        std::vector<int> out;
+        for (int k = 0; k < nCandidates; ++k) {
+            const int s = candSlot[k];
+            if (mapOfSlot.empty() || mapOfSlot[s] == map) out.push_back(s);
+        }
+        return out;
+    }
+    // DetectNBestCandidates(pKF, vpLoopCand, vpMergeCand, nNumCandidates): connected = the slots of pKF->GetConnectedKeyFrames() (and of pKF itself
+    // when it is in the database), queryMap = pKF->GetMap(), badMaps = the maps with IsBad()
+    void DetectNBestCandidates(const BowVec& bow, const std::vector<int>& connected, std::vector<int>& vpLoopCand, std::vector<int>& vpMergeCand, int nNumCandidates,
+                               const std::vector<int>& mapOfSlot, int queryMap, const std::vector<int>& badMaps = std::vector<int>()) {
+        query(XFH_BOWDB_FORM_NBEST, bow, connected);
+        vpLoopCand.clear(); vpMergeCand.clear();
+        for (int k = 0; k < nCandidates && ((int)vpLoopCand.size() < nNumCandidates || (int)vpMergeCand.size() < nNumCandidates); ++k) {
+            const int s = candSlot[k], m = mapOfSlot[s];
+            bool bad = false;
+            for (int b : badMaps) bad = bad || b == m;
+            if (m == queryMap && (int)vpLoopCand.size() < nNumCandidates) vpLoopCand.push_back(s);
+            else if (m != queryMap && (int)vpMergeCand.size() < nNumCandidates && !bad) vpMergeCand.push_back(s);
+        }
+    }
+
+    // of the last query
+    int nListed = 0, maxCommon = 0, minCommon = 0, nScored = 0, nCandidates = 0;
+    float bestAcc = 0.f;
+    std::vector<int32_t> common, listSlot, listBest, candSlot;
+    std::vector<double> score;
+    std::vector<uint8_t> status;
+    std::vector<float> listAcc, candAcc;
+
+private:
+    void sync() { if (xfh_synchronize(ctx) != XFH_OK) throw std::runtime_error("XFkeyframeDatabase: the stream failed"); }   // (the copies are synchronous: nothing queued may still read)
+    static void put(void* dst, const void* src, size_t bytes) { if (xfh_memcpy_h2d(dst, src, bytes) != XFH_OK) throw std::runtime_error("XFkeyframeDatabase: upload failed"); }
+    xfh_ctx* ctx;
+    int n, st, nn;
+    uint32_t nextSeq = 0;
+    void* d_all = nullptr;
+    uint32_t* d_ids = nullptr; double* d_vals = nullptr; int* d_nw = nullptr; uint32_t* d_seq = nullptr; int32_t* d_neigh = nullptr;
+    float* d_state[2] = {nullptr, nullptr};
+    uint32_t* d_qi = nullptr; double* d_qv = nullptr; int* d_qn = nullptr; uint8_t* d_ex = nullptr; void* d_ws = nullptr;
+    int32_t* d_common = nullptr; double* d_score = nullptr; uint8_t* d_status = nullptr; int32_t* d_header = nullptr; float* d_best = nullptr;
+    int32_t* d_ls = nullptr; float* d_la = nullptr; int32_t* d_lb = nullptr; int32_t* d_cs = nullptr; float* d_ca = nullptr;
+};
+
 }  // namespace ORB_SLAM3
 #endif

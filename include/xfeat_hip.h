@@ -27,7 +27,7 @@
  *     xfh_map_project, xfh_sim3_project and xfh_map_projection_search_workspace_bytes are stateless in the same way (a loop over
  *     one pure function, no static data); they are not part of the ThreadSanitizer run.  So are xfh_init_accept,
  *     xfh_init_list_entries and xfh_init_search_workspace_bytes, and xfh_vocab_bytes, xfh_vocab_pack, xfh_vocab_unpack, xfh_vocab_descend
- *     and xfh_bow_transform_workspace_bytes.
+ *     and xfh_bow_transform_workspace_bytes, and xfh_bow_score and xfh_bowdb_query_workspace_bytes.
  *
  * The C++ wrappers that restore the reference's class surface on top of this ABI are
  * include/xfeat/XFextractor.h and include/xfeat/ORBmatcher_xfeat.h; INTEGRATION.md shows
@@ -812,8 +812,8 @@ int xfh_bow_search(xfh_ctx* ctx, int n1, int n2, int flags, int init_dist, int t
  *                         vocabulary blob may hold anything (see xfh_vocab_descend).
  *   xfh_bow_transform     host-pointer convenience form for ONE frame: stages the vocabulary blob (all of it, per call: a test and
  *                         debugging form), the rows and the workspace, runs the call and copies the results back.
- * Out of scope: KeyFrameDatabase and L1Scoring::score; the yml and binary vocabulary loaders (and the text loader: the caller has DBoW2's);
- * vocabulary creation; the other weightings and norms; skipping padding rows. */
+ * Out of scope: the yml and binary vocabulary loaders (and the text loader: the caller has DBoW2's);
+ * vocabulary creation; the other weightings and norms; skipping padding rows.  (KeyFrameDatabase and L1Scoring::score: the next section.) */
 #define XFH_VOCAB_MAX_CHILDREN 32     /* children of one vocabulary node (ORBvoc: k = 10) */
 #define XFH_VOCAB_MAX_DEPTH 32        /* levels below the root (ORBvoc: L = 6) */
 #define XFH_BOWT_TF_IDF_L1 0          /* flags: WeightingType TF_IDF, ScoringType L1_NORM */
@@ -829,6 +829,98 @@ int xfh_bow_transform_device(xfh_ctx* ctx, int B, int n, int levelsup, int flags
                              uint32_t* d_bow_ids, double* d_bow_vals, int* d_n_words);
 int xfh_bow_transform(xfh_ctx* ctx, int n, int levelsup, int flags, const void* vocab, size_t vocab_bytes, const float* desc, uint32_t* word,
                       uint32_t* node_of, double* weight, void* nodes /* xfh_nodes_bytes(n) */, uint32_t* bow_ids, double* bow_vals, int* n_words);
+
+/* ---- KeyFrameDatabase query: shared words, L1 score, candidates, device resident ---------------------------------------------------------
+ * The two database functions the reference calls (src/KeyFrameDatabase.cc), with L1Scoring::score (thirdparty/DBoW2/DBoW2/ScoringObject.cpp:23-68):
+ *   DetectRelocalizationCandidates(Frame*, Map*)                              :733-845    Tracking.cc:3665 (Relocalization)         XFH_BOWDB_FORM_RELOC
+ *   DetectNBestCandidates(KeyFrame*, vpLoopCand, vpMergeCand, nNumCandidates) :604-730    LoopClosing.cc:491 (every keyframe)       XFH_BOWDB_FORM_NBEST
+ * They are pure functions of the query BowVector, the database BowVectors, the insertion order of the keyframes, each keyframe's first
+ * covisibility neighbours, a connected-keyframe set and ONE persistent float per keyframe (mRelocScore resp. mPlaceRecognitionScore).
+ * Everything is integers, IEEE doubles and fp32 adds in a fixed order, so every output is exact.
+ *
+ * The database is plain device arrays in the layout xfh_bow_transform_device writes: d_db_ids [n_slots][db_stride] uint32 ascending,
+ * d_db_vals [n_slots][db_stride] doubles, d_db_n_words [n_slots] ints.  A slot with n_words <= 0 is empty (erase = write 0); entries past
+ * n_words are never read.  With db_stride == n, xfh_bow_transform_device called with d_bow_ids + slot * n, d_bow_vals + slot * n and
+ * d_n_words + slot writes a keyframe straight into its slot.  There is no database object, no inverted file and no `add` entry point: a
+ * query scans every slot.  PRECONDITION: a bad keyframe is erased before the query (the reference's `if(pKFi->isBad()) continue;` at :712
+ * does not advance its iterator and would spin forever; it is not modelled).
+ *
+ * What one query computes, per problem b, with v1 = the query and slot s = keyframe s:
+ *   common[s]   = |ids(v1) AND ids(s)| (mnRelocWords / mnPlaceRecognitionWords of a listed keyframe: mvInvertedFile[w] holds a keyframe at
+ *                 most once), 0 for an empty slot
+ *   score[s]    = L1Scoring::score(v1, s): sum = 0.0; for the shared ids in ASCENDING id: sum += (fabs(vi - wi) - fabs(vi)) - fabs(wi), vi of
+ *                 v1, wi of s; score = -sum / 2.0.  -0.0 where nothing is shared.  Computed for every slot.
+ *   first[s]    = the least shared id (internal: the workspace)
+ *   status[s]   = XFH_BOWDB_EMPTY        n_words <= 0
+ *                 XFH_BOWDB_NOT_SHARING  common == 0 (also when the slot is excluded)
+ *                 XFH_BOWDB_EXCLUDED     d_exclude[b][s] != 0: spConnectedKF (:626), and the query keyframe itself when it is in the database
+ *                 XFH_BOWDB_BELOW_MIN / XFH_BOWDB_SCORED   the LISTED slots (lKFsSharingWords), see below
+ *   max_common  = max of common over the listed slots; min_common = (int)((float)max_common * 0.8f); a listed slot is SCORED iff
+ *                 common > min_common (strictly), otherwise BELOW_MIN
+ *   state[s]    = (float)score[s] for the SCORED slots ONLY (`pKFi->mRelocScore=si`); every other entry keeps its value
+ *   the list    = the SCORED slots ordered by (first[s], seq[s], s): the order in which the walk over the inverted file lists them (the
+ *                 query's words ascending, inside a word the order of the `add` calls).  For list entry r with slot s, si = (float)score[s]:
+ *                   acc = si; best = s; best_score = si;
+ *                   for j in 0 .. nn-1: t = neigh[s][j]; skip when t < 0, t >= n_slots or t is not LISTED;
+ *                       acc += state[t];                                   (fp32, in neighbour order)
+ *                       if (state[t] > best_score) { best = t; best_score = state[t]; }
+ *                 state[t] is read AFTER the writes above: a neighbour that is BELOW_MIN contributes the value an EARLIER query left in
+ *                 d_state, as mRelocScore / mPlaceRecognitionScore do in the reference.  The caller owns d_state and zero-fills it once
+ *                 (the KeyFrame constructors initialise mPlaceRecognitionScore(0) and leave mRelocScore uninitialised).
+ *                 list_slot / list_acc / list_best [r] = s / acc / best, -1 / 0 / -1 past n_scored
+ *   best_acc    = 0; over the list: if (acc > best_acc) best_acc = acc
+ *   candidates  RELOC: the list entries with acc > 0.75f * best_acc, in list order;
+ *               NBEST: all list entries, stable-sorted by acc descending (list::sort with a.first > b.first);
+ *               then, in that order, an entry is dropped when an EARLIER entry of the sequence has the same best (spAlreadyAddedKF).
+ *               cand_slot / cand_acc [k] = best / acc of the k-th survivor, -1 / 0 past n_candidates.
+ *   header      d_header[b][XFH_BOWDB_HEADER_INTS] = n_listed, max_common, min_common, n_scored, n_candidates, 0, 0, 0;  d_best_acc[b]
+ * The map tests (GetMap(), IsBad()) and the nNumCandidates caps select from cand_slot without changing it; they stay with the caller, as
+ * do the KeyFrame pointers.
+ *
+ *   xfh_bow_score         host, stateless, thread-safe: L1Scoring::score on two ascending id arrays through the kernel's own source lines
+ *                         (bowdb_math.h); *n_common and *first_common (0xFFFFFFFF when nothing is shared) as above.  n1 or n2 < 0, or a
+ *                         NULL pointer (an array may be NULL when its count is 0): XFH_ERR_INVALID_ARG.
+ *   xfh_bowdb_query_workspace_bytes   bytes of d_workspace for B queries against n_slots slots (0 for sizes the call would refuse).
+ *   xfh_bowdb_query_device   B queries against ONE database.  Queries in the transform's layout: d_q_ids / d_q_vals [B][q_stride], d_q_n_words
+ *                         [B].  Shared: the database; d_seq [n_slots] uint32 insertion sequence, or NULL (= the slot index; a reused slot
+ *                         needs it; equal values order by slot); d_neigh [n_slots][nn] int32, the first nn entries of
+ *                         GetBestCovisibilityKeyFrames in its order, an entry < 0 or >= n_slots means none (NULL allowed when nn == 0).  Per
+ *                         problem: d_exclude [B][n_slots] bytes or NULL; d_state [B][n_slots] floats, in/out; outputs d_common (int32),
+ *                         d_score (double), d_status (bytes), d_list_slot / d_list_best / d_cand_slot (int32), d_list_acc / d_cand_acc
+ *                         (float), all [B][n_slots]; d_header, d_best_acc.  All pointers are device pointers; asynchronous on the ctx
+ *                         stream, no allocation, no host synchronisation, two kernel launches; two runs from the same inputs give identical
+ *                         bytes.  XFH_ERR_INVALID_ARG before anything is queued: n_slots outside 1 .. XFH_BOWDB_MAX_SLOTS, B outside 1 ..
+ *                         65535, a stride < 1 or > XFH_GRID_MAX_N, nn outside 0 .. XFH_BOWDB_MAX_NEIGHBOURS, an unknown form, a NULL
+ *                         required pointer, misaligned pointers (8 bytes for doubles, 4 for 32-bit entries, 16 for the workspace).
+ *                         Hostile input: every n_words is clamped to [0, stride] before use and neighbour entries are range-checked before
+ *                         they index; ids that are not ascending give unspecified results but no out-of-bounds access and no endless
+ *                         loop; NaN values give unspecified ordering.
+ *   xfh_bowdb_query       host-pointer convenience form for ONE query: stages everything, runs the call and copies state and the outputs back.
+ * Design note: the dense scan reads the whole database per query where the host's inverted file touches only the shared postings.  Whether
+ * the scan wins at a given database size has NOT been measured against the host walk; profiles/bow_database.md has the kernel times alone.
+ * Out of scope: the inverted file itself, the map tests and caps, DetectCandidates / DetectLoopCandidates / DetectBestCandidates (never called). */
+#define XFH_BOWDB_MAX_SLOTS 8192       /* keyframe slots per database (the select kernel sorts one query's list in the LDS of one workgroup) */
+#define XFH_BOWDB_MAX_NEIGHBOURS 16    /* covisibility neighbours per keyframe (the reference asks for 10) */
+#define XFH_BOWDB_HEADER_INTS 8
+#define XFH_BOWDB_FORM_RELOC 0         /* DetectRelocalizationCandidates */
+#define XFH_BOWDB_FORM_NBEST 1         /* DetectNBestCandidates */
+#define XFH_BOWDB_EMPTY 0
+#define XFH_BOWDB_NOT_SHARING 1
+#define XFH_BOWDB_EXCLUDED 2
+#define XFH_BOWDB_BELOW_MIN 3
+#define XFH_BOWDB_SCORED 4
+int xfh_bow_score(const uint32_t* ids1, const double* vals1, int n1, const uint32_t* ids2, const double* vals2, int n2, double* score,
+                  int* n_common, uint32_t* first_common);
+size_t xfh_bowdb_query_workspace_bytes(int n_slots, int B);
+int xfh_bowdb_query_device(xfh_ctx* ctx, int B, int n_slots, int form, const uint32_t* d_q_ids, const double* d_q_vals, const int* d_q_n_words,
+                           int q_stride, const uint32_t* d_db_ids, const double* d_db_vals, const int* d_db_n_words, int db_stride,
+                           const uint32_t* d_seq_or_null, const int32_t* d_neigh, int nn, const uint8_t* d_exclude_or_null, float* d_state,
+                           void* d_workspace, int32_t* d_common, double* d_score, uint8_t* d_status, int32_t* d_header, float* d_best_acc,
+                           int32_t* d_list_slot, float* d_list_acc, int32_t* d_list_best, int32_t* d_cand_slot, float* d_cand_acc);
+int xfh_bowdb_query(xfh_ctx* ctx, int n_slots, int form, const uint32_t* q_ids, const double* q_vals, int q_n_words, const uint32_t* db_ids,
+                    const double* db_vals, const int* db_n_words, int db_stride, const uint32_t* seq_or_null, const int32_t* neigh, int nn,
+                    const uint8_t* exclude_or_null, float* state, int32_t* common, double* score, uint8_t* status, int32_t* header,
+                    float* best_acc, int32_t* list_slot, float* list_acc, int32_t* list_best, int32_t* cand_slot, float* cand_acc);
 
 /* ---- SearchByProjection of map points with a claim: the Sim3 forms and the relocalisation form, device resident -----------------------
  * Three reference functions as one call (src/ORBmatcher.cc):

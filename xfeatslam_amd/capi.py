@@ -29,7 +29,7 @@ ERR_EMPTY_IMAGE = 2
 ERR_NO_DEVICE = 7
 ERR_COMM = 11
 
-K = dict(NONE=0, MNN_GEMM=1, CONV_MFMA=2, CONV_DIRECT=3, NMS=4, SELECT=5, DESC=6, HEADS=7, DIST_I32=8, PREPROC=9, BEST2=10, DISTINCTIVE=11, MNN_GEMM_SEG=12, GRID_BUILD=13, SEARCH_WINDOW=14, FRAME_FINISH=15, PROJ_CANDIDATES=16, PROJ_RESOLVE=17, PROJ_COUNT=18, FUSE_SEARCH=19, TRIANGULATION_SEARCH=20, BOW_CANDIDATES=21, BOW_RESOLVE=22, MAPPROJ_CANDIDATES=23, SIM3_SEARCH=24, SIM3_AGREE=25, INIT_CANDIDATES=27, INIT_RESOLVE=28, INIT_FINAL=29, VOCAB_DESCEND=31, VOCAB_FINISH=32)
+K = dict(NONE=0, MNN_GEMM=1, CONV_MFMA=2, CONV_DIRECT=3, NMS=4, SELECT=5, DESC=6, HEADS=7, DIST_I32=8, PREPROC=9, BEST2=10, DISTINCTIVE=11, MNN_GEMM_SEG=12, GRID_BUILD=13, SEARCH_WINDOW=14, FRAME_FINISH=15, PROJ_CANDIDATES=16, PROJ_RESOLVE=17, PROJ_COUNT=18, FUSE_SEARCH=19, TRIANGULATION_SEARCH=20, BOW_CANDIDATES=21, BOW_RESOLVE=22, MAPPROJ_CANDIDATES=23, SIM3_SEARCH=24, SIM3_AGREE=25, INIT_CANDIDATES=27, INIT_RESOLVE=28, INIT_FINAL=29, VOCAB_DESCEND=31, VOCAB_FINISH=32, BOWDB_SCORE=33, BOWDB_SELECT=34)
 T = dict(X=0, XSTAT=1, SKIP_POOL=2, FEATS=6, H1=8, K1H=9, RAW0=16, STAT0=48, SEL=80)
 
 
@@ -79,6 +79,10 @@ TRI_GATE_SKIPPED, TRI_GATE_REJECTED, TRI_GATE_PASSED = range(3)
 BOW_STRICT_LOW = 1
 VOCAB_MAX_CHILDREN, VOCAB_MAX_DEPTH = 32, 32
 BOWT_TF_IDF_L1 = 0
+BOWDB_MAX_SLOTS, BOWDB_MAX_NEIGHBOURS, BOWDB_HEADER_INTS = 8192, 16, 8
+BOWDB_FORM_RELOC, BOWDB_FORM_NBEST = 0, 1
+BOWDB_EMPTY, BOWDB_NOT_SHARING, BOWDB_EXCLUDED, BOWDB_BELOW_MIN, BOWDB_SCORED = range(5)
+BOWDB_NO_WORD = 0xFFFFFFFF
 BOW_INACTIVE, BOW_NO_NODE, BOW_NO_CANDIDATES, BOW_REJECTED, BOW_MATCHED = range(5)
 MAPPROJ_INACTIVE, MAPPROJ_BEHIND, MAPPROJ_OUT_OF_IMAGE, MAPPROJ_OUT_OF_RANGE, MAPPROJ_BAD_ANGLE, MAPPROJ_NO_CANDIDATES, MAPPROJ_REJECTED, MAPPROJ_MATCHED = range(8)
 MAPPROJ_VISIBLE = 5
@@ -176,6 +180,11 @@ SYMBOLS = [
     ("xfh_bow_transform_workspace_bytes", _sz, [_i, _i]),
     ("xfh_bow_transform_device", _i, [_vp, _i, _i, _i, _i, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("xfh_bow_transform", _i, [_vp, _i, _i, _i, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("xfh_bow_score", _i, [_vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp]),
+    ("xfh_bowdb_query_workspace_bytes", _sz, [_i, _i]),
+    ("xfh_bowdb_query_device", _i, [_vp, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                    _vp, _vp]),
+    ("xfh_bowdb_query", _i, [_vp, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("xfh_map_project", _i, [_vp, _vp, C.POINTER(Camera), C.POINTER(GridBounds), _f, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
     ("xfh_map_projection_search_workspace_bytes", _sz, [_i, _i, _i]),
     ("xfh_map_projection_search_device", _i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(Camera), C.POINTER(GridBounds), _f, _vp, _vp, _i,

@@ -224,6 +224,8 @@ struct InitArgs;
 hipError_t launch_init_search(xfh_ctx* c, const InitArgs& a, int B);                  // init_search.hip.h
 struct VocabArgs;
 hipError_t launch_bow_transform(xfh_ctx* c, const VocabArgs& a, int B);             // vocab_transform.hip.h
+struct BowDbArgs;
+hipError_t launch_bowdb_query(xfh_ctx* c, const BowDbArgs& a, int B);               // bowdb_query.hip.h
 struct BowArgs;
 hipError_t launch_bow_search(xfh_ctx* c, const BowArgs& a, int B);                    // bow_search.hip.h
 hipError_t launch_best2(xfh_ctx* c, const float* q, int nq, const float* tg, const int* offsets, const int* indices, int init_dist,

@@ -24,6 +24,9 @@
 //                   the reference's claim order resolved per node, one wave each, the claimed set in LDS (bow_search.hip.h).
 //   k_vocab_descend / k_vocab_finish : TemplatedVocabulary::transform of DBoW2 for B frames per call: every row down the vocabulary tree, 16 lanes per
 //                   feature, then per frame the node blob of the two kernels above and the normalised BowVector, sorted in LDS (vocab_transform.hip.h).
+//   k_bowdb_score / k_bowdb_select : KeyFrameDatabase::DetectRelocalizationCandidates / DetectNBestCandidates with L1Scoring::score, B queries against one
+//                   database per call: one wave per (query, slot) with the ordered double sum, then one workgroup per query for the threshold, the
+//                   list order, the covisibility accumulation and the form's tail (bowdb_query.hip.h).
 //   k_mapproj_candidates : the front kernel of the Sim3 and relocalisation forms of SearchByProjection: per map point the projection, the culls, the level and
 //                   the window walk with the K best candidates; k_proj_resolve / k_proj_count settle the claims behind it (mapproj_search.hip.h).
 //   k_sim3_search / k_sim3_agree : ORBmatcher::SearchBySim3 up to vpMatches12, B keyframe pairs per call: both directions of the projection through
@@ -92,6 +95,7 @@ hipError_t launch_best2(xfh_ctx* c, const float* q, int nq, const float* tg, con
 #include "triangulation_search.hip.h"
 #include "bow_search.hip.h"
 #include "vocab_transform.hip.h"
+#include "bowdb_query.hip.h"
 #include "mapproj_search.hip.h"
 #include "sim3_search.hip.h"
 #include "init_search.hip.h"

@@ -1,5 +1,5 @@
 // search_common.hip.h -- what a wave does in every device-side ORBmatcher search (k_best2_csr and the *_search.hip.h kernels), written once: the
-// keys, DescriptorDistance, a lane's two / K smallest keys with their wave-wide merges, the wave minimum and sum.  The lane-local pieces are plain
+// keys, DescriptorDistance, a lane's two / K smallest keys with their wave-wide merges, the wave minimum and sum, one lane's double for all.  The lane-local pieces are plain
 // C++ (XFH_HD): tests/cpp/search_common_test.cpp runs these very lines on the host against the obvious form.
 #pragma once
 #include <math.h>
@@ -65,6 +65,11 @@ __device__ __forceinline__ int wave_sum_i32(int x) {
 #pragma unroll
     for (int m = 32; m >= 1; m >>= 1) x += __shfl_xor(x, m);
     return x;
+}
+// every lane gets lane l's double; l is the same on all lanes
+__device__ __forceinline__ double wave_readlane_f64(double x, int l) {
+    const int sl = __builtin_amdgcn_readfirstlane(l);
+    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(x), sl), __builtin_amdgcn_readlane(__double2loint(x), sl));
 }
 // every lane gets the two smallest keys of the wave's 64 pairs
 __device__ __forceinline__ void wave_top2(u64& b, u64& s2) {

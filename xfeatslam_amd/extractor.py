@@ -643,6 +643,88 @@ class Context:
         k = int(nw[0])
         return dict(word=word, node_of=node_of, weight=wt, nodes=nodes, bow_ids=ids[:k].copy(), bow_vals=vals[:k].copy(), n_words=k)
 
+    # -- the keyframe database query: shared words, L1 score, candidates (xfh_bow_score / xfh_bowdb_query*) -----------------------------------
+    BOWDB_OUT = (("common", np.int32), ("score", np.float64), ("status", np.uint8), ("list_slot", np.int32), ("list_acc", np.float32), ("list_best", np.int32),
+                 ("cand_slot", np.int32), ("cand_acc", np.float32))
+    BOWDB_HEADER = ("n_listed", "max_common", "min_common", "n_scored", "n_candidates")
+
+    @staticmethod
+    def bow_score(ids1, vals1, ids2, vals2):
+        """xfh_bow_score (host): L1Scoring::score(v1, v2) on two BowVectors in ascending word id -> (score, n_common, first_common)"""
+        i1, v1 = np.ascontiguousarray(ids1, np.uint32), np.ascontiguousarray(vals1, np.float64)
+        i2, v2 = np.ascontiguousarray(ids2, np.uint32), np.ascontiguousarray(vals2, np.float64)
+        assert len(i1) == len(v1) and len(i2) == len(v2)
+        sc, nc, fc = C.c_double(0), C.c_int(0), C.c_uint32(0)
+        check(lib().xfh_bow_score(i1.ctypes.data if len(i1) else None, v1.ctypes.data if len(i1) else None, len(i1), i2.ctypes.data if len(i2) else None,
+                                  v2.ctypes.data if len(i2) else None, len(i2), C.byref(sc), C.byref(nc), C.byref(fc)))
+        return sc.value, nc.value, fc.value
+
+    @staticmethod
+    def bowdb_query_workspace_bytes(n_slots: int, B: int = 1) -> int:
+        return int(lib().xfh_bowdb_query_workspace_bytes(n_slots, B))
+
+    @staticmethod
+    def bowdb_query_layout(B: int, n_slots: int, guard: int = 0):
+        """byte offsets of the outputs of bowdb_query_device inside one buffer (and its size under "bytes"); guard as in fuse_search_layout.
+        The workspace and d_state are buffers of their own."""
+        al = lambda x: (x + 255) & ~255
+        o, off = {}, al(guard)
+        for name, dt in Context.BOWDB_OUT:
+            o[name] = off; off += al(np.dtype(dt).itemsize * B * n_slots) + al(guard)
+        for name, nbytes in (("header", 4 * capi.BOWDB_HEADER_INTS * B), ("best_acc", 4 * B)):
+            o[name] = off; off += al(nbytes) + al(guard)
+        o["bytes"] = off
+        return o
+
+    @staticmethod
+    def bowdb_query_parse(raw: np.ndarray, lay, B: int, n_slots: int):
+        """the bytes of an output buffer of bowdb_query_device -> one dict per query (the arrays at full length, the header fields as ints)"""
+        res = []
+        for b in range(B):
+            o = {}
+            for name, dt in Context.BOWDB_OUT:
+                w = np.dtype(dt).itemsize * n_slots
+                o[name] = raw[lay[name] + b * w: lay[name] + (b + 1) * w].view(dt)
+            h = raw[lay["header"] + 4 * capi.BOWDB_HEADER_INTS * b: lay["header"] + 4 * capi.BOWDB_HEADER_INTS * (b + 1)].view(np.int32)
+            o.update({k: int(h[i]) for i, k in enumerate(Context.BOWDB_HEADER)})
+            o["header"] = h
+            o["best_acc"] = raw[lay["best_acc"] + 4 * b: lay["best_acc"] + 4 * b + 4].view(np.float32)[0]
+            res.append(o)
+        return res
+
+    def bowdb_query_device(self, B: int, n_slots: int, form: int, d_q_ids, d_q_vals, d_q_n_words, q_stride: int, d_db_ids, d_db_vals, d_db_n_words,
+                           db_stride: int, d_seq, d_neigh, nn: int, d_exclude, d_state, d_workspace, d_out, guard: int = 0):
+        """xfh_bowdb_query_device on device pointers; asynchronous.  d_out: pointer to the outputs laid out as bowdb_query_layout(B, n_slots,
+        guard) says; d_state [B][n_slots] floats is updated in place"""
+        o = self.bowdb_query_layout(B, n_slots, guard)
+        check(lib().xfh_bowdb_query_device(self.h, B, n_slots, int(form), d_q_ids, d_q_vals, d_q_n_words, q_stride, d_db_ids, d_db_vals, d_db_n_words, db_stride,
+                                           d_seq, d_neigh, nn, d_exclude, d_state, d_workspace, d_out + o["common"], d_out + o["score"], d_out + o["status"],
+                                           d_out + o["header"], d_out + o["best_acc"], d_out + o["list_slot"], d_out + o["list_acc"], d_out + o["list_best"],
+                                           d_out + o["cand_slot"], d_out + o["cand_acc"]), self.h)
+
+    def bowdb_query(self, form: int, q_ids, q_vals, db_ids, db_vals, db_n_words, neigh, state, seq=None, exclude=None):
+        """xfh_bowdb_query (host pointers, one query).  db_ids / db_vals [n_slots][db_stride], neigh [n_slots][nn]; state: float32 [n_slots],
+        updated IN PLACE.  -> dict as bowdb_query_parse gives it"""
+        qi, qv = np.ascontiguousarray(q_ids, np.uint32), np.ascontiguousarray(q_vals, np.float64)
+        di, dv, dn = np.ascontiguousarray(db_ids, np.uint32), np.ascontiguousarray(db_vals, np.float64), np.ascontiguousarray(db_n_words, np.int32)
+        n, stride = di.shape
+        ng = np.ascontiguousarray(neigh, np.int32)
+        ng = ng.reshape(n, -1) if ng.size else ng.reshape(n, 0)                                 # nn = 0: no neighbours at all
+        nn = ng.shape[1]
+        sq = None if seq is None else np.ascontiguousarray(seq, np.uint32)
+        ex = None if exclude is None else np.ascontiguousarray(exclude, np.uint8)
+        assert len(qi) == len(qv) and dv.shape == di.shape and len(dn) == n and state.dtype == np.float32 and state.flags.c_contiguous and len(state) == n
+        o = {name: np.zeros(n, dt) for name, dt in self.BOWDB_OUT}
+        hd, ba = np.zeros(capi.BOWDB_HEADER_INTS, np.int32), np.zeros(1, np.float32)
+        p = lambda a: None if a is None or a.size == 0 else a.ctypes.data
+        check(lib().xfh_bowdb_query(self.h, n, int(form), p(qi), p(qv), len(qi), di.ctypes.data, dv.ctypes.data, dn.ctypes.data, stride, p(sq), p(ng), nn, p(ex),
+                                    state.ctypes.data, o["common"].ctypes.data, o["score"].ctypes.data, o["status"].ctypes.data, hd.ctypes.data, ba.ctypes.data,
+                                    o["list_slot"].ctypes.data, o["list_acc"].ctypes.data, o["list_best"].ctypes.data, o["cand_slot"].ctypes.data,
+                                    o["cand_acc"].ctypes.data), self.h)
+        o.update({k: int(hd[i]) for i, k in enumerate(self.BOWDB_HEADER)})
+        o["header"], o["best_acc"] = hd, ba[0]
+        return o
+
     # -- SearchByProjection of map points with a claim: the Sim3 and relocalisation forms (xfh_map_project / xfh_map_projection_search*) ----
     MAPPROJ_OUT_INT = ("match_idx", "best_dist", "n_window", "n_tested", "level")
 
@@ -1010,3 +1092,90 @@ class ORBmatcher:
         """-> list of (queryIdx, trainIdx, distance) like std::vector<cv::DMatch>"""
         i1, i2, d = self.ctx.match_mnn(desc1, desc2, min_cossim)
         return list(zip(i1.tolist(), i2.tolist(), d.tolist()))
+
+
+class KeyFrameDatabase:
+    """`ORB_SLAM3::KeyFrameDatabase` without the inverted file (reference include/KeyFrameDatabase.h, src/KeyFrameDatabase.cc): the BowVectors of
+    the keyframes live in device arrays, one slot per keyframe, and a query scans them (Context.bowdb_query_device).  A slot is the caller's
+    handle for a keyframe; the caller keeps the KeyFrame objects, erases a keyframe before it turns bad and owns the maps.  The two persistent
+    scores (mRelocScore, mPlaceRecognitionScore) are two device arrays of the database, zero at the start."""
+
+    def __init__(self, ctx: Context, n_slots: int, stride: int, nn: int = 10):
+        assert 1 <= n_slots <= capi.BOWDB_MAX_SLOTS and 1 <= stride <= capi.GRID_MAX_N and 0 <= nn <= capi.BOWDB_MAX_NEIGHBOURS
+        self.ctx, self.n_slots, self.stride, self.nn = ctx, n_slots, stride, nn
+        self.next_seq = 0
+        D = capi.DeviceBuffer
+        z = lambda nbytes, fill=0: D(nbytes).upload(np.full(nbytes, fill, np.uint8))
+        self.ids, self.vals, self.n_words, self.seq = z(4 * n_slots * stride, 0xFF), z(8 * n_slots * stride), z(4 * n_slots), z(4 * n_slots)
+        self.neigh = z(4 * n_slots * max(nn, 1), 0xFF)                                         # -1: no neighbour
+        self.state = {capi.BOWDB_FORM_RELOC: z(4 * n_slots), capi.BOWDB_FORM_NBEST: z(4 * n_slots)}
+        self.q_ids, self.q_vals, self.q_n, self.excl = D(4 * stride), D(8 * stride), D(4), D(n_slots)
+        self.ws = D(Context.bowdb_query_workspace_bytes(n_slots, 1))
+        self.lay = Context.bowdb_query_layout(1, n_slots)
+        self.out = D(self.lay["bytes"])
+
+    def close(self):
+        for b in (self.ids, self.vals, self.n_words, self.seq, self.neigh, self.q_ids, self.q_vals, self.q_n, self.excl, self.ws, self.out, *self.state.values()):
+            b.free()
+
+    @staticmethod
+    def _put(buf, offset, arr):
+        a = np.ascontiguousarray(arr)
+        assert offset + a.nbytes <= buf.nbytes
+        if a.nbytes:
+            check(lib().xfh_memcpy_h2d(buf.ptr + offset, a.ctypes.data, a.nbytes))
+
+    def add(self, slot: int, ids, vals, neighbours=()):
+        """`KeyFrameDatabase::add(pKF)`: the keyframe's mBowVec (ascending word id) into a slot, at the end of the insertion order.
+        neighbours: the slots of GetBestCovisibilityKeyFrames(nn), in its order (set_neighbours updates them later)"""
+        i, v = np.ascontiguousarray(ids, np.uint32), np.ascontiguousarray(vals, np.float64)
+        assert 0 <= slot < self.n_slots and len(i) == len(v) <= self.stride
+        self._put(self.ids, 4 * slot * self.stride, i); self._put(self.vals, 8 * slot * self.stride, v)
+        self._put(self.n_words, 4 * slot, np.array([len(i)], np.int32)); self._put(self.seq, 4 * slot, np.array([self.next_seq], np.uint32))
+        self.next_seq += 1
+        self.set_neighbours(slot, neighbours)
+
+    def set_neighbours(self, slot: int, neighbours):
+        ng = np.full(max(self.nn, 1), -1, np.int32)
+        k = min(len(neighbours), self.nn)
+        ng[:k] = np.asarray(neighbours, np.int32)[:k]
+        self._put(self.neigh, 4 * slot * max(self.nn, 1), ng)
+
+    def erase(self, slot: int):
+        """`KeyFrameDatabase::erase(pKF)`: the slot is empty from now on"""
+        assert 0 <= slot < self.n_slots
+        self._put(self.n_words, 4 * slot, np.zeros(1, np.int32))
+
+    def query(self, form: int, ids, vals, exclude=()):
+        """one query -> dict as Context.bowdb_query_parse gives it.  exclude: the slots of the connected keyframes (and of the query keyframe)"""
+        i, v = np.ascontiguousarray(ids, np.uint32), np.ascontiguousarray(vals, np.float64)
+        assert len(i) == len(v) <= self.stride
+        ex = np.zeros(self.n_slots, np.uint8)
+        ex[np.asarray(list(exclude), np.int64)] = 1
+        self._put(self.q_ids, 0, i); self._put(self.q_vals, 0, v); self._put(self.q_n, 0, np.array([len(i)], np.int32)); self._put(self.excl, 0, ex)
+        self.ctx.bowdb_query_device(1, self.n_slots, form, self.q_ids.ptr, self.q_vals.ptr, self.q_n.ptr, self.stride, self.ids.ptr, self.vals.ptr,
+                                    self.n_words.ptr, self.stride, self.seq.ptr, self.neigh.ptr if self.nn else None, self.nn, self.excl.ptr,
+                                    self.state[form].ptr, self.ws.ptr, self.out.ptr)
+        self.ctx.synchronize()
+        return Context.bowdb_query_parse(self.out.download(np.uint8, self.lay["bytes"]), self.lay, 1, self.n_slots)[0]
+
+    def DetectRelocalizationCandidates(self, ids, vals, map_of_slot=None, pMap=None):
+        """`DetectRelocalizationCandidates(F, pMap)` (:733-845) -> the candidate slots in the reference's order.  map_of_slot[s] is compared with pMap
+        (`if (pKFi->GetMap() != pMap) continue;`, :834); without it every candidate is returned"""
+        r = self.query(capi.BOWDB_FORM_RELOC, ids, vals)
+        cand = r["cand_slot"][:r["n_candidates"]].tolist()
+        return [s for s in cand if map_of_slot is None or map_of_slot[s] == pMap]
+
+    def DetectNBestCandidates(self, ids, vals, connected, nNumCandidates: int, map_of_slot, query_map, bad_maps=()):
+        """`DetectNBestCandidates(pKF, vpLoopCand, vpMergeCand, nNumCandidates)` (:604-730) -> (vpLoopCand, vpMergeCand) as slots.  connected: the slots
+        of pKF->GetConnectedKeyFrames() (add the slot of pKF itself when it is in the database); query_map: pKF->GetMap()"""
+        r = self.query(capi.BOWDB_FORM_NBEST, ids, vals, exclude=connected)
+        loop, merge = [], []
+        for s in r["cand_slot"][:r["n_candidates"]].tolist():
+            if not (len(loop) < nNumCandidates or len(merge) < nNumCandidates):
+                break
+            if map_of_slot[s] == query_map and len(loop) < nNumCandidates:
+                loop.append(s)
+            elif map_of_slot[s] != query_map and len(merge) < nNumCandidates and map_of_slot[s] not in bad_maps:
+                merge.append(s)
+        return loop, merge
