@@ -1215,6 +1215,83 @@ int xfh_init_search(xfh_ctx* ctx, int nq, const float* query_desc, const float* 
                     int* claim_idx, int* matches12, int* best_dist, int* second_dist, int* n_window, int* n_tested, int* matches21,
                     int* matched_distance, int* n_matches, float* prev_out_or_null);
 
+/* ---- PoseOptimization: the motion-only pose refinement behind every tracking search, device resident ------------------------------------
+ * Optimizer::PoseOptimization(Frame*) (src/Optimizer.cc:814-1114), the conventional-camera branch (!pFrame->mpCamera2) with a Pinhole camera.  This
+ * is not a graph optimiser: it is the one fixed problem that function sets up -- one SE3 vertex, unary reprojection edges, Levenberg on a dense
+ * 6x6 system -- for B frames per call.  It reads what the searches leave in device memory (assigned[k], the world points, the xy_un / uright of
+ * xfh_frame_finish_records_device) and writes what the next search reads (Tcw for XFH_PROJ_POINTS, the outlier flags for the query flags).
+ *
+ * Edges.  Keypoint k of problem b has an edge iff assigned[k] is in [0, nq); its map point is points[assigned[k]] (float -> double), its
+ *   measurement xy_un[k] (and uright[k]).  The edge is mono (EdgeSE3ProjectXYZOnlyPose, 2 rows, threshold 5.991f, Huber delta (float)sqrt(5.991))
+ *   when d_uright is NULL or uright[k] < 0, otherwise stereo (EdgeStereoSE3ProjectXYZOnlyPose, 3 rows, 7.815f, (float)sqrt(7.815)); a NaN uright
+ *   is stereo, as `mvuRight[i] < 0` decides.  Information = inv_sigma2 * I: every XFeat keypoint has octave 0, so mvInvLevelSigma2[octave] is one
+ *   float per call.  n_initial = number of edges.  n_initial < 3: the call returns 0 for that problem, Tcw_out = the 12 input floats, every flag 0 (:996).
+ * Pose.  State = SE3Quat: unit quaternion (x, y, z, w) + translation, doubles.  Tcw is the library's row-major 3x4 float [R|t]; R is converted by
+ *   Eigen's matrix-to-quaternion rule written out in poseopt_math.h (trace > 0: the trace branch, else the largest diagonal entry, a later index
+ *   winning only when strictly larger), then normalizeRotation (w < 0 flips, divide by the norm).  An update u = (omega, upsilon) is applied as
+ *   SE3Quat::exp(u) * estimate: Rodrigues with the theta < 1e-5 branch R = V = I + Omega + Omega^2, the matrix-to-quaternion rule again, the
+ *   quaternion product, normalizeRotation.  Tcw_out = (float) of [toRotationMatrix | t] of the final estimate.  Bit equality with the
+ *   reference's own Sophus / Eigen quaternion path is NOT claimed (summation orders inside Eigen, libm's sin / cos); the decisions below are.
+ * Edge arithmetic.  pc = q * X + t.  Mono: e = obs - (fx*x/z + cx, fy*y/z + cy) (Pinhole::project, double); J = -projectJac(pc) * SE3deriv.
+ *   Stereo: invz = (float)(1.0 / z) as the reference's cam_project has it, e = obs - (x*invz*fx + cx, y*invz*fy + cy, u - bf*invz); J as
+ *   types_six_dof_expmap.cpp:375-404 (there invz is a double).  chi2 = sum_r e_r * (inv_sigma2 * e_r).  Huber (robust_kernel_impl.cpp:78):
+ *   chi2 <= delta^2 -> rho = (chi2, 1), else (2 sqrt(chi2) delta - delta^2, delta / sqrt(chi2)).  An edge adds A^T (rho[1] w) A to H and subtracts
+ *   rho[1] A^T (w e) from b (base_unary_edge.hpp:43-72; robustInformation = rho[1] * information, the second-order term is commented out there).
+ * Rounds.  Four rounds of optimize(10).  EVERY round starts from the INPUT pose (:1008-1009 reads pFrame->GetPose(), which is not written before
+ *   :1111) and uses the level-0 edges only: those not flagged by the previous round.  A round without a level-0 edge runs no iteration.  After a
+ *   round every edge is classified: an edge flagged by the previous round computes its error afresh at the round's final estimate; an unflagged edge
+ *   reads _error as the last computeActiveErrors() left it -- when the last Levenberg trial of the round was rejected and popped, that is the
+ *   error at the REJECTED estimate, not at the restored one.  flag = (float)chi2 > 5.991f (7.815f stereo); flagged edges go to level 1, the others
+ *   back to level 0.  The Huber kernel is removed after the third round.  n_initial < 10: one round only (:1102 counts all edges).
+ * Levenberg (optimization_algorithm_levenberg.cpp:61-194).  Per iteration: errors, currentChi = iniChi = the robust chi2 sum, H and b.  Iteration 0
+ *   of a round: lambda = 1e-5 * max_j |H_jj| (std::max(fabs(H_jj), m): a NaN diagonal replaces m and is replaced by the next one), ni = 2.  Up to 10
+ *   trials: solve (H + lambda I) x = b, estimate <- exp(x) * estimate, tempChi = the robust chi2 sum there, DBL_MAX when the factorisation
+ *   failed; rho = (currentChi - tempChi) / (sum_j x_j (lambda x_j + b_j) + 1e-3); rho > 0 and tempChi finite: lambda *= max(1/3, min(1 - (2 rho
+ *   - 1)^3, 2/3)), ni = 2, currentChi = tempChi; otherwise lambda *= ni, ni *= 2 and the estimate is restored.  Another trial while rho < 0.  The
+ *   round ends when 10 trials ran or rho == 0, or at the third iteration in a row with (iniChi - currentChi) * 1e3 < iniChi, or after 10
+ *   iterations.  NaN: every comparison above is false for a NaN, so a NaN rho ends the trials with the estimate restored and the iteration counts
+ *   as progress; at most 4 x 10 x 10 trials run whatever the data.  The factorisation is an unpivoted LDL^T that fails at the first pivot that is
+ *   not > 0 (Eigen's pivoting LDLT with isPositive() in the reference; no bit claim); after a failure x keeps the previous solve's values (zero
+ *   before the first), which the reference leaves uninitialised.
+ * Sums.  H, b and the chi2 sums are folded in a fixed order that is part of the contract of the _device call only in that it is FIXED: lane l of
+ *   256 adds its keypoints l, l + 256, ... in that order, 64 lanes fold by the xor butterfly 32, 16, .. 1, the four partial sums are added in
+ *   order.  Two runs on the same input give identical bytes, and a problem's result does not depend on B or on its neighbours.
+ *
+ *   xfh_pose_from_tcw / _to_tcw / _oplus / _solve / xfh_pose_edge
+ *                         host, stateless, thread-safe, no ctx: the kernel's own source lines.  pose7 = (qx, qy, qz, qw, tx, ty, tz).
+ *                         xfh_pose_solve: H21 = the upper triangle row by row; returns 1, or 0 (x untouched) when a pivot is not > 0.
+ *                         xfh_pose_edge: one edge at one pose -> error[3], chi2, jacobian[18] (3x6 row-major; a mono edge (uright < 0) has a
+ *                         zero third row and error[2] = 0) and rho[1] of its Huber kernel (1 when robust == 0); any output may be NULL.
+ *   xfh_pose_optimize_workspace_bytes
+ *                         bytes of d_workspace for B problems of nt keypoints (0 for arguments the call would refuse).  For nt <= 4096 the kernel
+ *                         keeps every edge in registers and does not touch it; for larger nt an edge's state word and stored chi2 live there.
+ *   xfh_pose_optimize_device
+ *                         B problems, ONE launch, one workgroup each, asynchronous on the ctx stream: no host synchronisation, no allocation.
+ *                         d_Tcw [B][12], d_xy_un [B][nt][2], d_uright_or_null [B][nt], d_assigned [B][nt], d_points [B][nq][3] in;
+ *                         d_Tcw_out [B][12] (may be d_Tcw), d_outlier [B][nt] bytes (mvbOutlier; 0 where there is no edge), d_chi2 [B][nt]
+ *                         floats (the chi2 each edge's LAST classification read; 0 where there is no edge), d_header [B][8] ints: n_initial,
+ *                         n_bad, the reference's return value n_initial - n_bad of the last round that ran (0 when refused at < 3), rounds
+ *                         run, Levenberg iterations, trials, rejected trials, factorisation failures; d_final_chi2 [B] doubles: currentChi
+ *                         of the last iteration that ran (0 if none).  cam (host memory): fx, fy, cx, cy, bf are read.
+ *                         XFH_ERR_INVALID_ARG before any launch: B < 1 (or > 65535), nt or nq outside 1 .. XFH_GRID_MAX_N, a NULL required
+ *                         pointer, a misaligned pointer (16 bytes for the workspace, 8 for d_final_chi2, 4 for floats and ints), an
+ *                         inv_sigma2 that is not finite or not > 0.  Points, poses, observations and camera values may be anything, NaN and
+ *                         Inf included: the call terminates, and no load or store leaves the buffers the caller named.
+ *   xfh_pose_optimize     host-pointer convenience form for ONE problem: stages the arrays, runs the call, copies the results back. */
+int xfh_pose_from_tcw(const float* Tcw, double* pose7);
+int xfh_pose_to_tcw(const double* pose7, float* Tcw);
+int xfh_pose_oplus(const double* pose7, const double* update6, double* pose7_out);
+int xfh_pose_solve(const double* H21, double lambda, const double* b6, double* x6);
+int xfh_pose_edge(const double* pose7, const xfh_camera* cam, const float* point3, const float* xy, float uright, float inv_sigma2, int robust,
+                  double* error3, double* chi2, double* jacobian18, double* rho1);
+size_t xfh_pose_optimize_workspace_bytes(int nt, int B);
+int xfh_pose_optimize_device(xfh_ctx* ctx, int B, int nt, int nq, const float* d_Tcw, const xfh_camera* cam, const float* d_xy_un,
+                             const float* d_uright_or_null, const int* d_assigned, const float* d_points, float inv_sigma2, void* d_workspace,
+                             float* d_Tcw_out, uint8_t* d_outlier, float* d_chi2, int* d_header, double* d_final_chi2);
+int xfh_pose_optimize(xfh_ctx* ctx, int nt, int nq, const float* Tcw, const xfh_camera* cam, const float* xy_un, const float* uright_or_null,
+                      const int* assigned, const float* points, float inv_sigma2, float* Tcw_out, uint8_t* outlier, float* chi2, int* header,
+                      double* final_chi2);
+
 /* MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:329-403), batched over map points: group g observes the
  * descriptor rows indices[offsets[g] .. offsets[g+1]) of `table` (n_rows x 64).  Pairwise DescriptorDistance inside
  * the group (diagonal 0), per row the median sorted[(N-1)/2], and the FIRST row with the least median wins:

@@ -25,7 +25,8 @@ enum {
     XFH_K_MAPPROJ_CANDIDATES = 23, XFH_K_SIM3_SEARCH = 24, XFH_K_SIM3_AGREE = 25,
     /* 26 and 30 are unassigned */
     XFH_K_INIT_CANDIDATES = 27, XFH_K_INIT_RESOLVE = 28, XFH_K_INIT_FINAL = 29,
-    XFH_K_VOCAB_DESCEND = 31, XFH_K_VOCAB_FINISH = 32, XFH_K_BOWDB_SCORE = 33, XFH_K_BOWDB_SELECT = 34, XFH_K_COUNT = 35
+    XFH_K_VOCAB_DESCEND = 31, XFH_K_VOCAB_FINISH = 32, XFH_K_BOWDB_SCORE = 33, XFH_K_BOWDB_SELECT = 34,
+    XFH_K_POSE_OPTIMIZE = 35, XFH_K_COUNT = 36
 };
 /* layer_mask selects conv layers for XFH_K_CONV_*: 0 = every layer, else bit i = BasicLayer i
  * (0..22 in XFeatModel order) and bit 23 = block_fusion.2 */

@@ -222,6 +222,8 @@ struct Sim3Args;
 hipError_t launch_sim3_search(xfh_ctx* c, const Sim3Args& a, int B);                  // sim3_search.hip.h
 struct InitArgs;
 hipError_t launch_init_search(xfh_ctx* c, const InitArgs& a, int B);                  // init_search.hip.h
+struct PoseArgs;
+hipError_t launch_pose_optimize(xfh_ctx* c, const PoseArgs& a, int B);              // poseopt.hip.h
 struct VocabArgs;
 hipError_t launch_bow_transform(xfh_ctx* c, const VocabArgs& a, int B);             // vocab_transform.hip.h
 struct BowDbArgs;

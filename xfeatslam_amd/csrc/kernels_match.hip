@@ -34,6 +34,8 @@
 //   k_init_candidates / k_init_resolve / k_init_final : ORBmatcher::SearchForInitialization, B frame pairs per call: per query the nearest members of
 //                   its window, then the reference's retraction order resolved per problem with the acceptors of every keypoint chained in LDS, then
 //                   every query's turn against the final chains (init_search.hip.h).
+//   k_pose_optimize : Optimizer::PoseOptimization for B frames in one launch, one workgroup per frame: the edges in registers, H, b and the chi2 sums
+//                   folded in a fixed order, the Levenberg state machine on one lane (poseopt.hip.h, poseopt_math.h).
 //   k_distinctive_csr : MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:329-403), one wave per map point.
 // Shared by k_best2_csr and every *_search.hip.h kernel: search_common.hip.h (keys, descriptor_distance, top-two and K-list with their wave merges, wave
 // minimum / sum), window_search.hip.h (the grid walk), nodes_clamp.h (node blobs), resolve_rounds.hip.h (the rounds of k_proj_resolve / k_init_resolve: the argument, the cut, the advance of lo).
@@ -99,6 +101,7 @@ hipError_t launch_best2(xfh_ctx* c, const float* q, int nq, const float* tg, con
 #include "mapproj_search.hip.h"
 #include "sim3_search.hip.h"
 #include "init_search.hip.h"
+#include "poseopt.hip.h"
 
 // ---- k_distinctive_csr: MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:329-403), batched -------
 // One wave per group (map point).  Rows are taken 64 at a time, lane = row: the lane keeps its descriptor in

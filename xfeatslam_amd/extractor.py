@@ -917,6 +917,31 @@ class Context:
         r.update(status=st, n_matches=int(nm[0]), prev_out=po)
         return r
 
+    # -- PoseOptimization --------------------------------------------------------------------
+    POSE_HEADER = ("n_initial", "n_bad", "ret", "rounds", "iterations", "trials", "rejected", "ldlt_failures")
+
+    @staticmethod
+    def pose_optimize_workspace_bytes(nt: int, B: int = 1) -> int:
+        return int(lib().xfh_pose_optimize_workspace_bytes(nt, B))
+
+    def pose_optimize_device(self, B: int, nt: int, nq: int, d_Tcw, cam, d_xy_un, d_uright, d_assigned, d_points, d_workspace, d_Tcw_out, d_outlier, d_chi2,
+                             d_header, d_final_chi2, inv_sigma2: float = 1.0):
+        """xfh_pose_optimize_device on device pointers; asynchronous.  d_uright may be None (all edges mono), d_Tcw_out may be d_Tcw"""
+        check(lib().xfh_pose_optimize_device(self.h, B, nt, nq, d_Tcw, C.byref(cam), d_xy_un, d_uright, d_assigned, d_points, float(inv_sigma2), d_workspace,
+                                             d_Tcw_out, d_outlier, d_chi2, d_header, d_final_chi2), self.h)
+
+    def pose_optimize(self, Tcw, cam, xy_un, uright, assigned, points, inv_sigma2: float = 1.0):
+        """xfh_pose_optimize (host pointers, one frame) -> dict(ret, Tcw, outlier, chi2, header, final_chi2); ret is the reference's return value"""
+        T = np.ascontiguousarray(Tcw, np.float32).reshape(12); xy = np.ascontiguousarray(xy_un, np.float32).reshape(-1, 2)
+        a = np.ascontiguousarray(assigned, np.int32); p = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+        ur = None if uright is None else np.ascontiguousarray(uright, np.float32)
+        nt = len(a)
+        assert len(xy) == nt and (ur is None or len(ur) == nt)
+        To, ol, c2, hd, fc = np.zeros(12, np.float32), np.zeros(nt, np.uint8), np.zeros(nt, np.float32), np.zeros(8, np.int32), np.zeros(1, np.float64)
+        check(lib().xfh_pose_optimize(self.h, nt, len(p), T.ctypes.data, C.byref(cam), xy.ctypes.data, None if ur is None else ur.ctypes.data, a.ctypes.data,
+                                      p.ctypes.data, float(inv_sigma2), To.ctypes.data, ol.ctypes.data, c2.ctypes.data, hd.ctypes.data, fc.ctypes.data), self.h)
+        return dict(ret=int(hd[2]), Tcw=To.reshape(3, 4), outlier=ol, chi2=c2, header=dict(zip(self.POSE_HEADER, hd.tolist())), final_chi2=float(fc[0]))
+
     def timing_enable(self, kernel_id: int, layer_mask: int = 0):
         check(lib().xfh_timing_enable(self.h, kernel_id, layer_mask), self.h)
 
