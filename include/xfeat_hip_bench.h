@@ -63,8 +63,9 @@ const char* xfh_kernel_name(int kernel_id);
  * XFH_ERR_INVALID_ARG for a tensor the last call did not write: RAW0 + 0 always, RAW0 + 18 (heatmap_head.0, handed on inside one
  * kernel) with folded BatchNorms at batches <= 8. */
 enum {
-    XFH_T_X = 0, XFH_T_XSTAT = 1, XFH_T_SKIP_POOL = 2,                               /* 3, 4, 5, 7 (unfold2d(x), x1 + skip, fusion input, normalised features) */
-    XFH_T_FEATS = 6, XFH_T_H1 = 8, XFH_T_K1H = 9,                                   /* are never materialised on the GPU: fused into consumers */
+    XFH_T_X = 0, XFH_T_XSTAT = 1, XFH_T_SKIP_POOL = 2,                               /* 3, 4, 5 (unfold2d(x), x1 + skip, fusion input) are never */
+    XFH_T_FEATS = 6, XFH_T_M1N = 7, XFH_T_H1 = 8, XFH_T_K1H = 9,                    /* materialised on the GPU: fused into consumers.  M1N (normalised */
+                                                                                    /* features): the GPU holds the norm per pixel, the call divides FEATS by it */
     XFH_T_RAW0 = 16, XFH_T_STAT0 = 48, XFH_T_SEL = 80                               /* RAW0 + 0 (block1.0) likewise: recomputed inside block1.1 */
 };
 int xfh_debug_tensor(xfh_ctx* ctx, int id, int frame, float* out, size_t capacity, size_t* count_out);

@@ -30,7 +30,7 @@ ERR_NO_DEVICE = 7
 ERR_COMM = 11
 
 K = dict(NONE=0, MNN_GEMM=1, CONV_MFMA=2, CONV_DIRECT=3, NMS=4, SELECT=5, DESC=6, HEADS=7, DIST_I32=8, PREPROC=9, BEST2=10, DISTINCTIVE=11, MNN_GEMM_SEG=12, GRID_BUILD=13, SEARCH_WINDOW=14, FRAME_FINISH=15, PROJ_CANDIDATES=16, PROJ_RESOLVE=17, PROJ_COUNT=18, FUSE_SEARCH=19, TRIANGULATION_SEARCH=20, BOW_CANDIDATES=21, BOW_RESOLVE=22, MAPPROJ_CANDIDATES=23, SIM3_SEARCH=24, SIM3_AGREE=25, INIT_CANDIDATES=27, INIT_RESOLVE=28, INIT_FINAL=29, VOCAB_DESCEND=31, VOCAB_FINISH=32, BOWDB_SCORE=33, BOWDB_SELECT=34, POSE_OPTIMIZE=35)
-T = dict(X=0, XSTAT=1, SKIP_POOL=2, FEATS=6, H1=8, K1H=9, RAW0=16, STAT0=48, SEL=80)
+T = dict(X=0, XSTAT=1, SKIP_POOL=2, FEATS=6, M1N=7, H1=8, K1H=9, RAW0=16, STAT0=48, SEL=80)
 
 
 class Config(C.Structure):

@@ -121,6 +121,20 @@ int xfh_debug_tensor(xfh_ctx* c, int id, int frame, float* out, size_t cap, size
         case XFH_T_FEATS: src = c->feats + frame * c->raw_stride[17]; n = (size_t)h8 * w8 * 64; break;
         case XFH_T_H1: src = c->H1 + frame * (xs / 64); n = (size_t)h8 * w8; break;
         case XFH_T_K1H: src = c->K1h + frame * xs; n = (size_t)H * W; break;
+        case XFH_T_M1N: {
+            // the normalised map is never written on the GPU: k_desc divides the pixels a sample touches by their stored norm.  This is that
+            // quotient for every pixel, formed on the host (IEEE fp32 division) from the two tensors the GPU does hold.
+            n = (size_t)h8 * w8 * 64;
+            *count_out = n;
+            if (!out) return XFH_OK;
+            if (cap < n) return XFH_ERR_INVALID_ARG;
+            std::vector<float> nrm((size_t)h8 * w8);
+            HIPCK(c, hipMemcpy(out, c->feats + frame * c->raw_stride[17], n * sizeof(float), hipMemcpyDeviceToHost));
+            HIPCK(c, hipMemcpy(nrm.data(), c->feat_nrm + frame * (xs / 64), nrm.size() * sizeof(float), hipMemcpyDeviceToHost));
+            for (size_t p = 0; p < nrm.size(); ++p)
+                for (int ch = 0; ch < 64; ++ch) out[p * 64 + ch] = out[p * 64 + ch] / nrm[p];
+            return XFH_OK;
+        }
         default:
             if (id >= XFH_T_RAW0 && id < XFH_T_RAW0 + XFH_NUM_LAYERS) {
                 const int i = id - XFH_T_RAW0;

@@ -88,7 +88,7 @@ struct xfh_ctx {
     bool no_nms_heat = false;                   // XFH_NO_NMS_HEAT=1 (tests)
     bool no_ride = false;                       // XFH_NO_RIDE=1: no riders (tests)
     bool select_legacy = false;                 // XFH_SELECT_LEGACY=1: k_select takes its radix-select + bitonic form (tests)
-    float* feat_nrm = nullptr;                  // [h8*w8] L2 norm of every feature pixel (k_feat_norm)
+    float* feat_nrm = nullptr;                  // [h8*w8] L2 norm of every feature pixel (feat_norm_px on the NMS launch; k_chain1x1<FNRM> for batches > 8)
     u64* cand = nullptr; size_t cand_cap = 0;   // keys per frame (power of two >= Hmax*Wmax)
     int* cand_count = nullptr;                  // [B]
     int* slot_src = nullptr;                    // [B][nfeatures]

@@ -26,7 +26,8 @@ struct Kp4Args {
     int Hh, Wh; float* K1h; size_t k1h_stride;
 };
 
-// k_heads_kp4: the small-batch form (B <= 8) of k_heads_kp.  One frame gives k_heads_kp 38 workgroups of two waves, and every lane
+// k_heads_kp4: the small-batch form (B <= 8) of k_heads_kp.  With one pixel per lane (k_heads_kp's form through round 6; its MFMA form
+// needs thousands of cells to fill its persistent grid) one frame gives 38 workgroups of two waves, and every lane
 // walks 64 x 65 dependent-free but sequentially issued fmas plus 65 expf and 64 quotients: 35 us of a 0.37-ms frame on a mostly
 // idle GPU.  Here FOUR lanes share a pixel (lane j takes outputs 16 j .. 16 j + 15, lane 3 also the dustbin), a workgroup is 32
 // pixels, so four times as many waves run chains a quarter as long.  Every output is the same fma chain over k, the maximum is exact

@@ -1433,10 +1433,14 @@ struct ChainArgs {
     const float* w1; const float* bias1;      // stage 1
     const float* w2; const float* bias2;      // stage 2 (NL == 3)
     float* mid_out; size_t mid_stride;        // MID_BIAS_STORE: where stage 0's map is stored
+    float* nrm; size_t nrm_stride;            // FNRM: where the L2 norm of every pixel of stage 0's map is stored
 };
 // SSTAT (batches <= 8): the producer's statistics are staged in LDS per frame -- folded from its partials by this workgroup when no
 // k_bn_finalize runs (stage_stat) -- instead of being read from the finalized slots.
-template <int NL, int WM, int PRO, int MID0, int EPI, bool SSTAT = false>
+// FNRM (batches > 8, MID_BIAS_STORE): F::normalize's divisor of every pixel of stage 0's map (feats) is computed here, from the rows the
+// wave has just handed back into LDS, instead of by a launch that reads the whole map again (through round 6: k_feat_norm, 24 us per
+// 64 VGA frames at 5 % of the pipe; k_desc, which that launch left a warm cache, pays 3 us of it back: profiles/heads_kp_mfma.md).  One lane per pixel, the expression and the channel order of feat_norm_px: the same bits.
+template <int NL, int WM, int PRO, int MID0, int EPI, bool SSTAT = false, bool FNRM = false>
 __global__ __launch_bounds__(64 * WM)
 void k_chain1x1(ChainArgs ca, int ntile, int total) {
     constexpr int CIN = 64, COUT = 64, NT = 2, WW = 16, WH = 2, TH = WM * WH, TW = WW;
@@ -1567,6 +1571,28 @@ void k_chain1x1(ChainArgs ca, int ntile, int total) {
                     float v = acc[n][r] + bv;
                     if (!store_mid) v = fmaxf(v, 0.f);
                     mid_row[((r & 3) + 8 * (r >> 2)) * CP + pos] = v;
+                }
+            }
+            if constexpr (FNRM && MID0 == MID_BIAS_STORE) {
+                if (l == 0) {
+                    // the wave's own rows: its LDS operations complete in order, the fence only keeps the compiler from moving the reads up
+                    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+                    if (h == 0) {                         // lane i: pixel i of the wave's 2 x 16 block
+                        const float* row = s_in + (wm * 32 + i) * CP;
+                        double ss = 0.0;
+#pragma unroll
+                        for (int kk = 0; kk < CIN / 8; ++kk) {
+                            // inverse k permutation: channels 8 kk + 2 j sit at 8 kk + j, channels 8 kk + 2 j + 1 at 8 kk + 4 + j
+                            const f32x4 ev = *(const f32x4*)(row + kk * 8), od = *(const f32x4*)(row + kk * 8 + 4);
+#pragma unroll
+                            for (int j = 0; j < 4; ++j) {
+                                ss = fma((double)ev[j], (double)ev[j], ss);
+                                ss = fma((double)od[j], (double)od[j], ss);
+                            }
+                        }
+                        const int oy = oy0 + i / WW, ox = tx0 + i % WW;
+                        if (oy < a.Hout && ox < a.Wout) ca.nrm[(size_t)b * ca.nrm_stride + (size_t)oy * a.Wout + ox] = fmaxf((float)sqrt(ss), 1e-12f);
+                    }
                 }
             }
         }
@@ -1998,7 +2024,7 @@ hipError_t launch_block1_stats(xfh_ctx* c, const StatSrc& xs, int H, int W, int 
 }
 
 // ---- chains of 1x1 layers (k_chain1x1) ----------------------------------------------------------
-template <int NL, int WM, int PRO, int MID0, int EPI, bool SSTAT = false>
+template <int NL, int WM, int PRO, int MID0, int EPI, bool SSTAT = false, bool FNRM = false>
 static hipError_t chain_launch(xfh_ctx* c, const ChainArgs& ca, int B, int* npart_out, int layer) {
     constexpr int TH = 2 * WM, TW = 16;
     constexpr size_t LDS = sizeof(float) * ((size_t)TH * TW * 68 + (size_t)NL * 64 * 68 + (SSTAT ? 128 : 0)) + sizeof(double) * WM * 64 * 2;
@@ -2007,7 +2033,7 @@ static hipError_t chain_launch(xfh_ctx* c, const ChainArgs& ca, int B, int* npar
     aa.a.tiles_x = (ca.a.Wout + TW - 1) / TW;
     const int ntile = aa.a.tiles_x * ((ca.a.Hout + TH - 1) / TH);
     if (npart_out) *npart_out = ntile;
-    auto kern = k_chain1x1<NL, WM, PRO, MID0, EPI, SSTAT>;
+    auto kern = k_chain1x1<NL, WM, PRO, MID0, EPI, SSTAT, FNRM>;
     XFH_SET_LDS_ATTR_ONCE(c, kern, LDS);
     const int total = ntile * B;
     const int per_cu = (int)((160 * 1024) / LDS);
@@ -2026,6 +2052,7 @@ hipError_t launch_fusion_chain(xfh_ctx* c, int Hh, int Wh, int B, int* done) {
     a.in = c->raw[17]; a.st = stat_src(c, 17, B); a.in_stride = c->raw_stride[17]; a.Hin = Hh; a.Win = Wh; a.Hout = Hh; a.Wout = Wh;
     a.w = c->w.fus2; a.bias = c->w.fus2_bias;
     ca.mid_out = c->feats; ca.mid_stride = c->raw_stride[17];
+    ca.nrm = c->feat_nrm; ca.nrm_stride = (size_t)c->Hmax * c->Wmax / 64;        // batches > 8: the feature norms are computed in the chain (FNRM)
     ca.w1 = c->w.mfma[18];
     int np = 0;
     hipError_t e;
@@ -2054,7 +2081,7 @@ hipError_t launch_fusion_chain(xfh_ctx* c, int Hh, int Wh, int B, int* done) {
     }
     if (!folded) {
         a.out = c->raw[18]; a.out_stride = c->raw_stride[18]; a.part = c->part[18]; a.part_stride = c->part_stride[18];
-        e = chain_launch<2, 4, PRO_BN, MID_BIAS_STORE, EPI_STATS>(c, ca, B, &np, 18);
+        e = chain_launch<2, 4, PRO_BN, MID_BIAS_STORE, EPI_STATS, false, true>(c, ca, B, &np, 18);
         if (e != hipSuccess) return e;
         mark_written(c, XFH_T_FEATS); mark_written(c, XFH_T_RAW0 + 18);
         c->lh[18] = Hh; c->lw[18] = Wh; c->npart[18] = np;
@@ -2071,7 +2098,7 @@ hipError_t launch_fusion_chain(xfh_ctx* c, int Hh, int Wh, int B, int* done) {
     // VALU work of staging / handing on), not by the 315 MB each intermediate map costs in HBM traffic, so only this one is kept
     ca.bias1 = c->w.bn_bias[18];
     a.out = c->raw[18]; a.out_stride = c->raw_stride[18];
-    e = chain_launch<2, 4, PRO_BN, MID_BIAS_STORE, EPI_BIAS_RELU>(c, ca, B, &np, 18);
+    e = chain_launch<2, 4, PRO_BN, MID_BIAS_STORE, EPI_BIAS_RELU, false, true>(c, ca, B, &np, 18);
     if (e != hipSuccess) return e;
     mark_written(c, XFH_T_FEATS); mark_written(c, XFH_T_RAW0 + 18);
     c->lh[18] = Hh; c->lw[18] = Wh; c->npart[18] = np;

@@ -152,65 +152,161 @@ void k_heads_heat(const float* __restrict__ rawH, StatSrc sH,     // heatmap_hea
     if (pix < npix) H1[(size_t)b * h1_stride + pix] = 1.0f / (1.0f + xfh_expf(0.f - acc));
 }
 
-// keypoint head: 64 -> 65, softmax, drop dustbin, depth-to-space (XFeat.cc:89, XFextractor.cc:204-217).
+// keypoint head for batches > 8: 64 -> 65, softmax, drop dustbin, depth-to-space (XFeat.cc:89, XFextractor.cc:204-217).
 // Runs on the ctx's second stream together with keypoint_head.0-2: the whole branch only depends on the
 // normalised image, not on the backbone.
-__global__ __launch_bounds__(HF_PX)
+// Outputs 0 .. 63 are a 64 x 64 product on v_mfma_f32_32x32x2_f32 like every other 1x1 layer (k_chain1x1: the same LDS layouts, the
+// same k order, one accumulator from 0 -- bitwise the fmaf chain over k); through round 6 this was the last 64-wide product on the
+// VALU, 4 160 v_fmac per lane with a scalar-cache weight row per k (81 us per 64 VGA frames, 45 % of them stall).  Persistent
+// workgroups of four waves over blocks of 128 consecutive cells of a frame; the weights go to LDS once per workgroup in the B-operand
+// layout.  A wave owns its 32 cells from staging to store -- its 32 LDS rows hold relu(bn(raw)) as the A operand first and the logits
+// afterwards -- so the one barrier of the kernel is the one behind the weights.  The dustbin output 64 is the fmaf chain on the VALU,
+// one cell per lane (both halves of the wave carry it), its weights held one per lane and read by v_readlane.  Softmax: two lanes per
+// cell, lane half h owns outputs 32 h .. 32 h + 31 (= rows 4 h .. 4 h + 3 of the 8 x 8 cell), half 1 the dustbin too; the maximum is
+// exact in any order, the sum keeps the reference order n = 0 .. 64 by handing half 0's sum to half 1 (as heads_kp4_body does with
+// four lanes): the bits of k_heads_kp4.
+// Statistics: finalised per frame for these batch sizes (stat_src: no partials to fold), read with the frame's raw values.
+#define HKM_PX 128
+#define HKM_CP 68
+#define HKM_WG_PER_CU 3          // 51 KB of LDS per workgroup
+__global__ __launch_bounds__(256)
 void k_heads_kp(const float* __restrict__ rawK, StatSrc sK,      // keypoint_head.2
                 size_t raw_stride, const float* __restrict__ wk /* [64][68] */, const float* __restrict__ bk /* [65] */,
-                int Hh, int Wh, float* __restrict__ K1h, size_t k1h_stride) {
-    __shared__ float sA[64 * HF_LD];
-    __shared__ float st[128];
-    const int t = threadIdx.x, b = blockIdx.z;
-    const int npix = Hh * Wh, p0 = blockIdx.x * HF_PX;
-    const int pix = p0 + t;
-    // the workgroup's 128 x 64 raw values: all sixteen loads of a thread are issued up front (clamped addresses, no branch around
-    // them -- behind a branch they ran as sixteen dependent round trips: 36 us of this kernel's single-frame time), the statistics
-    // are staged while they fly
-    f32x4 rv[16];
-    {
-        const float* rp = rawK + (size_t)b * raw_stride;
+                int Hh, int Wh, float* __restrict__ K1h, size_t k1h_stride, int nblk, int total) {
+    __shared__ __attribute__((aligned(16))) float s_w[64 * HKM_CP];          // [n][k-permuted]: B operand
+    __shared__ __attribute__((aligned(16))) float s_a[HKM_PX * HKM_CP];      // [cell][k-permuted]: A operand, then [cell][n]: logits
+    const int t = threadIdx.x;
+    const int wave = __builtin_amdgcn_readfirstlane(t >> 6), lane = t & 63, i = lane & 31, h = lane >> 5, g = lane & 7;
+    const int npix = Hh * Wh;
 #pragma unroll
-        for (int k = 0; k < 16; ++k) {
-            const int item = t + k * HF_PX, lp = item >> 4, g = item & 15;
-            rv[k] = *(const f32x4*)(rp + (size_t)min(p0 + lp, npix - 1) * 64 + g * 4);
-        }
+    for (int q = 0; q < 4; ++q) {
+        const int f = t + q * 256, k = f >> 4, nq = f & 15;
+        const f32x4 w = *(const f32x4*)(wk + k * 68 + nq * 4);
+        const int pos = (k & ~7) + 4 * (k & 1) + ((k & 7) >> 1);             // k permutation inside each group of 8 (k_chain1x1)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) s_w[(nq * 4 + j) * HKM_CP + pos] = w[j];
     }
-    stage_stat(sK, b, 64, blockIdx.x == 0, st, (double*)sA, t, HF_PX);
-#pragma unroll
-    for (int k = 0; k < 16; ++k) {
-        const int item = t + k * HF_PX, lp = item >> 4, g = item & 15;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) sA[(g * 4 + j) * HF_LD + lp] = fmaxf(fmaf(rv[k][j], st[64 + g * 4 + j], st[g * 4 + j]), 0.f);
-    }
+    const float wd = wk[lane * 68 + 64];                  // dustbin column: lane k holds w[k][64]
+    const float bias0 = bk[i], bias1 = bk[32 + i], biasd = bk[64];
     __syncthreads();
-    float acc[65];
+
+    float* const rows = s_a + wave * 32 * HKM_CP;         // this wave's 32 cells
+    // the wave's 32 x 64 raw values (eight channels of four cells per lane) and the statistics of their frame: all loads of a tile are
+    // issued up front with clamped addresses, one tile ahead of the arithmetic
+    f32x4 v0[4], v1[4], sm0, sm1, sr0, sr1;
+    auto load_tile = [&](int tile) {
+        const int b = tile / nblk, p0 = (tile - b * nblk) * HKM_PX + wave * 32;
+        const float* rp = rawK + (size_t)b * raw_stride + g * 8;
 #pragma unroll
-    for (int n = 0; n < 65; ++n) acc[n] = 0.f;
-#pragma unroll 2
-    for (int k = 0; k < 64; ++k) {
-        const float a = sA[k * HF_LD + t];
-        const XFH_CONST float* wr = (const XFH_CONST float*)wk + k * 68;                 // wave-uniform row, constant address space: scalar loads
-#pragma unroll
-        for (int n = 0; n < 65; ++n) acc[n] = fmaf(a, wr[n], acc[n]);
-    }
-    float mx = -__builtin_huge_valf();
-#pragma unroll
-    for (int n = 0; n < 65; ++n) { acc[n] += bk[n]; mx = fmaxf(mx, acc[n]); }
-    float sum = 0.f;
-#pragma unroll
-    for (int n = 0; n < 65; ++n) { acc[n] = xfh_expf(acc[n] - mx); sum += acc[n]; }
-    const Recip ks = recip_of(sum);                       // 64 softmax quotients share the divisor
-    if (pix < npix) {
-        const int y = pix / Wh, x = pix % Wh;
-        float* o = K1h + (size_t)b * k1h_stride + (size_t)(8 * y) * (8 * Wh) + 8 * x;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            *(f32x4*)(o + (size_t)i * 8 * Wh) = f32x4{div_by(acc[i * 8], ks), div_by(acc[i * 8 + 1], ks), div_by(acc[i * 8 + 2], ks), div_by(acc[i * 8 + 3], ks)};
-            *(f32x4*)(o + (size_t)i * 8 * Wh + 4) = f32x4{div_by(acc[i * 8 + 4], ks), div_by(acc[i * 8 + 5], ks), div_by(acc[i * 8 + 6], ks), div_by(acc[i * 8 + 7], ks)};
+        for (int q = 0; q < 4; ++q) {
+            const float* p = rp + (size_t)min(p0 + (lane >> 3) + q * 8, npix - 1) * 64;
+            v0[q] = *(const f32x4*)p; v1[q] = *(const f32x4*)(p + 4);
         }
+        const float* st = sK.stat + (size_t)b * 128 + g * 8;
+        sm0 = *(const f32x4*)st; sm1 = *(const f32x4*)(st + 4); sr0 = *(const f32x4*)(st + 64); sr1 = *(const f32x4*)(st + 68);
+    };
+    auto store_tile = [&]() {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            f32x4 x0 = v0[q], x1 = v1[q];
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                x0[c] = fmaxf(fmaf(x0[c], sr0[c], sm0[c]), 0.f);
+                x1[c] = fmaxf(fmaf(x1[c], sr1[c], sm1[c]), 0.f);
+            }
+            float* d = rows + ((lane >> 3) + q * 8) * HKM_CP + g * 8;
+            *(f32x4*)d = f32x4{x0.x, x0.z, x1.x, x1.z};
+            *(f32x4*)(d + 4) = f32x4{x0.y, x0.w, x1.y, x1.w};
+        }
+    };
+
+    int tile = blockIdx.x;                                // (the grid never exceeds `total`)
+    load_tile(tile);
+    while (true) {
+        const int b = tile / nblk, p0 = (tile - b * nblk) * HKM_PX + wave * 32;
+        store_tile();
+        const int next = tile + gridDim.x;
+        const bool has_next = next < total;
+        if (has_next) load_tile(next);
+        // rows are this wave's alone and its LDS operations complete in order: the fences only keep the compiler from reordering across them
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        if (p0 < npix) {                                  // (wave-uniform: the last block of a frame may leave waves without cells)
+            f32x16 acc[2];
+#pragma unroll
+            for (int n = 0; n < 2; ++n)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) acc[n][r] = 0.f;
+            float accd = 0.f;
+            const float* pa = rows + i * HKM_CP;
+            const float* pw = s_w + i * HKM_CP + 4 * h;
+#pragma unroll
+            for (int kk = 0; kk < 8; ++kk) {
+                // channels 8 kk + 2 j (a0) and 8 kk + 2 j + 1 (a1) of cell i: half h feeds its own as the A operand, the dustbin chain takes both
+                const f32x4 a0 = *(const f32x4*)(pa + kk * 8), a1 = *(const f32x4*)(pa + kk * 8 + 4);
+                const f32x4 b0 = *(const f32x4*)(pw + kk * 8), b1 = *(const f32x4*)(pw + 32 * HKM_CP + kk * 8);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const float av = h ? a1[j] : a0[j];
+                    acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, b0[j], acc[0], 0, 0, 0);
+                    acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, b1[j], acc[1], 0, 0, 0);
+                }
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    accd = fmaf(a0[j], __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, wd), kk * 8 + 2 * j)), accd);
+                    accd = fmaf(a1[j], __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, wd), kk * 8 + 2 * j + 1)), accd);
+                }
+            }
+            XFH_MFMA_SETTLE();
+            // C/D layout (lane = output, register r = cell (r&3) + 8*(r>>2) + 4*h) -> [cell][output] over the wave's rows, the bias added after the chain
+            {
+                float* lrow = rows + 4 * h * HKM_CP + i;
+#pragma unroll
+                for (int n = 0; n < 2; ++n)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) lrow[((r & 3) + 8 * (r >> 2)) * HKM_CP + n * 32] = acc[n][r] + (n ? bias1 : bias0);
+            }
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            float lg[32];
+#pragma unroll
+            for (int q = 0; q < 8; ++q) {
+                const f32x4 v = *(const f32x4*)(rows + i * HKM_CP + 32 * h + q * 4);
+                lg[q * 4] = v.x; lg[q * 4 + 1] = v.y; lg[q * 4 + 2] = v.z; lg[q * 4 + 3] = v.w;
+            }
+            const float ld = accd + biasd;
+            float mx = ld;
+#pragma unroll
+            for (int n = 0; n < 32; ++n) mx = fmaxf(mx, lg[n]);
+            mx = fmaxf(mx, __shfl_xor(mx, 32));
+#pragma unroll
+            for (int n = 0; n < 32; ++n) lg[n] = xfh_expf(lg[n] - mx);
+            const float ed = xfh_expf(ld - mx);
+            // sum over n = 0 .. 64 in that order: half 0 sums its terms from 0, half 1 continues from there and ends with the dustbin
+            float s0 = 0.f;
+#pragma unroll
+            for (int n = 0; n < 32; ++n) s0 += lg[n];
+            float s1 = __shfl(s0, i);
+#pragma unroll
+            for (int n = 0; n < 32; ++n) s1 += lg[n];
+            s1 += ed;
+            const Recip ks = recip_of(__shfl(s1, 32 + i));     // 64 softmax quotients share the divisor
+            const int pix = p0 + i;
+            if (pix < npix) {
+                const int y = pix / Wh, x = pix % Wh;
+                // outputs 32 h .. 32 h + 31 = rows 4 h .. 4 h + 3 of the cell (depth-to-space)
+                float* o = K1h + (size_t)b * k1h_stride + (size_t)(8 * y + 4 * h) * (8 * Wh) + 8 * x;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    *(f32x4*)(o + (size_t)r * 8 * Wh) = f32x4{div_by(lg[r * 8], ks), div_by(lg[r * 8 + 1], ks), div_by(lg[r * 8 + 2], ks), div_by(lg[r * 8 + 3], ks)};
+                    *(f32x4*)(o + (size_t)r * 8 * Wh + 4) = f32x4{div_by(lg[r * 8 + 4], ks), div_by(lg[r * 8 + 5], ks), div_by(lg[r * 8 + 6], ks), div_by(lg[r * 8 + 7], ks)};
+                }
+            }
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        }
+        if (!has_next) break;
+        tile = next;
     }
 }
+
 
 // k_heads_kp4 (heads_kp4.hip.h): the small-batch form of k_heads_kp as a kernel of its own (eval()-BatchNorm modes; in the reference's
 // batch-statistics mode the same body rides on block3.0's launch, kernels_conv.hip)
@@ -220,13 +316,15 @@ void k_heads_kp4(Kp4Args k) {
     heads_kp4_body(k, blockIdx.x, blockIdx.z, smem_kp4);
 }
 
-// ---- k_feat_norm: ||feats(p)||_2 of every feature pixel, one thread per pixel -------------------
+// ---- feat_norm_px: ||feats(p)||_2 of every feature pixel, one thread per pixel -------------------
 // F::normalize(M1, dim=1) (XFextractor.cc:273) divides every pixel of the feature map by max(||.||_2, 1e-12): the norm is the
 // oracle's expression (fp64 sum of squares over the channels in order, fp32 sqrt, max) and is all that is stored -- the
 // normalised map itself is never written, k_desc divides the four pixels a sample touches.  A thread walks the 64 channels
 // of its pixel: 128 fp64 operations per pixel, where a cross-lane reduction per sampled pixel cost ten times that.
-// For batches <= 8 the same blocks ride on the k_nms_score launch instead (its grid is extended by fn_blocks workgroups that take
+// For batches <= 8 these blocks ride on the k_nms_score launch (its grid is extended by fn_blocks workgroups that take
 // this path): the norms depend on feats only, and a launch of their own was 5 us on the critical path of a single frame.
+// For batches > 8 the kernel that produces feats computes the same expression from its LDS rows (k_chain1x1<.., FNRM>,
+// kernels_conv.hip); through round 6 a launch of this function (k_feat_norm) read the whole map again for it.
 __device__ __forceinline__ void feat_norm_px(const float* __restrict__ feats, size_t m_stride, int npix, float* __restrict__ nrm, size_t n_stride, int b, int p) {
     if (p >= npix) return;
     const float* m = feats + (size_t)b * m_stride + (size_t)p * 64;
@@ -238,10 +336,6 @@ __device__ __forceinline__ void feat_norm_px(const float* __restrict__ feats, si
         for (int q = 0; q < 4; ++q) ss = fma((double)v[q], (double)v[q], ss);
     }
     nrm[(size_t)b * n_stride + p] = fmaxf((float)sqrt(ss), 1e-12f);
-}
-__global__ __launch_bounds__(256)
-void k_feat_norm(const float* __restrict__ feats, size_t m_stride, int npix, float* __restrict__ nrm, size_t n_stride) {
-    feat_norm_px(feats, m_stride, npix, nrm, n_stride, blockIdx.z, blockIdx.x * 256 + threadIdx.x);
 }
 
 // ---- k_nms_score: 64x16 pixels per workgroup ---------------------------------------------------
@@ -273,7 +367,7 @@ void k_nms_score(const float* __restrict__ K1h, size_t k_stride, const float* __
     __shared__ float s_hst[HEAT ? 128 : 1];
     __shared__ float s_h1[HEAT ? NMS_HC : 1];
     const int t = threadIdx.x, b = blockIdx.z;
-    if ((int)blockIdx.x >= nms_blocks) {          // riding feat-norm blocks (batches <= 8, see k_feat_norm)
+    if ((int)blockIdx.x >= nms_blocks) {          // riding feat-norm blocks (batches <= 8, see feat_norm_px)
         feat_norm_px(fn_feats, fn_m_stride, fn_npix, fn_nrm, fn_n_stride, b, ((int)blockIdx.x - nms_blocks) * 256 + t);
         return;
     }
@@ -856,7 +950,7 @@ void k_desc(const float* __restrict__ feats, size_t m_stride, const float* __res
     const int x0 = (int)xw, y0 = (int)yn, x1 = x0 + 1, y1 = y0 + 1;
     const bool vx0 = x0 >= 0 && x0 < Wh, vx1 = x1 >= 0 && x1 < Wh, vy0 = y0 >= 0 && y0 < Hh, vy1 = y1 >= 0 && y1 < Hh;
     // the four feature pixels the sample touches (zero outside the map: grid_sample padding_mode zeros), each divided by its
-    // norm (k_feat_norm): the values a normalised copy of the map would hold
+    // norm (feat_norm_px): the values a normalised copy of the map would hold
     const float* m = feats + (size_t)b * m_stride + l * 4;
     const float* fn = fnorm + (size_t)b * n_stride;
     const int cx0 = min(max(x0, 0), Wh - 1), cx1 = min(max(x1, 0), Wh - 1), cy0 = min(max(y0, 0), Hh - 1), cy1 = min(max(y1, 0), Hh - 1);
@@ -958,9 +1052,11 @@ hipError_t run_extract(xfh_ctx* c, const uint8_t* d_gray, int B, int H0, int W0,
             if (consumer_fold(B))        // small batches (at 256 frames it measured 287 vs 263 us): four lanes per pixel (k_heads_kp4), the same bits
                 launch_k(c, XFH_K_HEADS, -1, k_heads_kp4, dim3((h8 * w8 + HK4_PX - 1) / HK4_PX, 1, B), dim3(4 * HK4_PX), 0,
                          Kp4Args{(const float*)c->raw[22], stat_src(c, 22, B), c->raw_stride[22], (const float*)c->w.kp3_w, (const float*)c->w.kp3_b, h8, w8, c->K1h, xs});
-            else
-            launch_k(c, XFH_K_HEADS, -1, k_heads_kp, dim3((h8 * w8 + HF_PX - 1) / HF_PX, 1, B), dim3(HF_PX), 0,
-                     (const float*)c->raw[22], stat_src(c, 22, B), c->raw_stride[22], (const float*)c->w.kp3_w, (const float*)c->w.kp3_b, h8, w8, c->K1h, xs);
+            else {                       // persistent: as many workgroups as the CUs hold at once, each walking 128-cell blocks of the batch
+                const int nblk = (h8 * w8 + HKM_PX - 1) / HKM_PX, total = nblk * B;
+                launch_k(c, XFH_K_HEADS, -1, k_heads_kp, dim3(total < 256 * HKM_WG_PER_CU ? total : 256 * HKM_WG_PER_CU), dim3(256), 0,
+                         (const float*)c->raw[22], stat_src(c, 22, B), c->raw_stride[22], (const float*)c->w.kp3_w, (const float*)c->w.kp3_b, h8, w8, c->K1h, xs, nblk, total);
+            }
             e = hipGetLastError();
             mark_written(c, XFH_T_K1H);
         }
@@ -1032,6 +1128,7 @@ hipError_t run_extract(xfh_ctx* c, const uint8_t* d_gray, int B, int H0, int W0,
                        nms_blocks, (const float*)c->feats, c->raw_stride[17], h8 * w8, c->feat_nrm, xs / 64,
                        fn_blocks ? (const float*)c->raw[19] : (const float*)nullptr, stat_src(c, 19, B), c->raw_stride[19], (const float*)c->w.heat2_w, (const float*)c->w.heat2_b, c->H1);
     CK(hipGetLastError());
+    mark_written(c, XFH_T_M1N);         // the feature norms: riders of the launch above, or (batches > 8) computed by the fusion chain
     if (nf <= SEL_FAST_MAX) {
         XFH_SET_LDS_ATTR_ONCE(c, k_select, SEL_LDS_BYTES);
         launch_k(c, XFH_K_SELECT, -1, k_select, dim3(B), dim3(1024), SEL_LDS_BYTES, (const u64*)c->cand, c->cand_cap, (const int*)c->cand_count, W, nf,
@@ -1043,10 +1140,6 @@ hipError_t run_extract(xfh_ctx* c, const uint8_t* d_gray, int B, int H0, int W0,
     }
     CK(hipGetLastError());
     mark_written(c, XFH_T_SEL);
-    if (!fn_blocks) {
-        hipLaunchKernelGGL(k_feat_norm, dim3((h8 * w8 + 255) / 256, 1, B), dim3(256), 0, s, (const float*)c->feats, c->raw_stride[17], h8 * w8, c->feat_nrm, xs / 64);
-        CK(hipGetLastError());
-    }
     const int dslots = d_images ? (nf + MNN_PANEL - 1) / MNN_PANEL * MNN_PANEL : nf;      // image rows run to the panel boundary
     launch_k(c, XFH_K_DESC, -1, k_desc, dim3((dslots + 15) / 16, 1, B), dim3(256), 0, c->feats, c->raw_stride[17], (const float*)c->feat_nrm, xs / 64, c->slot_src, c->sel_key, H, W, nf, rw, rh,
                        d_records, rec, xfh_record_kps_offset(), xfh_record_desc_offset(nf), write_padding ? 1 : 0,
