@@ -14,6 +14,8 @@
  *        and of the SearchLocalPoints form (:42-141): projection, cull, windowed best two and the reference's claim order in one call
  *   XFmatcher::fuse / searchForTriangulation: the two matchers of LocalMapping, ORBmatcher::Fuse (ORBmatcher.cc:1333-1640) up to the map
  *        bookkeeping and ORBmatcher::SearchForTriangulation (:1092-1331) over the nodes of the DBoW2 feature vectors, each as one call
+ *   XFmatcher::triangulate: the loop body of LocalMapping::CreateNewMapPoints (LocalMapping.cc:481-710) behind searchForTriangulation for all
+ *        neighbours at once: the new map points with their normals and distance bounds, the first accepted neighbour owning a keypoint
  *   XFmatcher::searchByProjection(Sim3Form / RelocForm, ...) / searchBySim3: the matchers of LoopClosing and Tracking::Relocalization, the Sim3
  *        forms of SearchByProjection (ORBmatcher.cc:612-717, :719-831), the relocalisation form (:2074-2195) and SearchBySim3 (:1642-1859), each
  *        as one call.  The caller keeps what needs Sophus or the map: the decomposition of Scw into Tcw = [R | t/s] and Ow (:621-622), S12 and its
@@ -228,6 +230,16 @@ private:
     std::vector<float> host_x, host_y;
 };
 
+// What XFmatcher::triangulate reads of a keyframe.  keysUn = mvKeysUn as (x, y) pairs, keys = mvKeys[i].pt likewise (nullptr: the camera has no
+// distortion, keysUn is read), uright = mvuRight and depth = mvDepth (both nullptr: a monocular keyframe), Tcw = GetPose() row-major 3x4, Ow =
+// GetCameraCenter().  Host form: pointers to host arrays of n (2n) floats; device form: device pointers, and for the neighbours of one call the
+// arrays of all B keyframes one behind the other (Tcw [B][12], Ow [B][3]).
+struct XFtriKeyFrame { const float* keysUn; const float* keys; const float* uright; const float* depth; const float* Tcw; const float* Ow; };
+// One new map point of LocalMapping::CreateNewMapPoints: the caller runs :694-709 on it (new MapPoint(x3D, ..), AddObservation(KF1, idx1),
+// AddObservation(neighbour's keyframe, idx2), AddMapPoint on both).  normal / minDistance / maxDistance are what UpdateNormalAndDepth would store;
+// fuseDistances is the triple xfh_fuse_search_device reads (0.8f * min, 1.2f * max, max).
+struct XFnewMapPoint { int idx1, neighbour, idx2; float x3D[3], normal[3], minDistance, maxDistance, fuseDistances[3]; bool stereo; };
+
 class XFmatcher {
 public:
     using Mat = xfeat::cvx::Mat;
@@ -324,7 +336,7 @@ public:
             for (int k = 0; k < n; ++k) _matches[p].emplace_back(DMatch(i1[k], i2[k], d[k]));
         }
     }
-    ~XFmatcher() { if (d_out) xfh_dev_free(d_out); if (d_proj) xfh_dev_free(d_proj); }
+    ~XFmatcher() { if (d_out) xfh_dev_free(d_out); if (d_proj) xfh_dev_free(d_proj); if (d_triang) xfh_dev_free(d_triang); }
     XFmatcher(const XFmatcher&) = delete;
     XFmatcher& operator=(const XFmatcher&) = delete;
 
@@ -826,6 +838,106 @@ public:
     const std::vector<int>& lastTriangulationCandidates() const { return triCandidates; }
     const std::vector<int>& lastTriangulationGeom() const { return triGeom; }
 
+    // The loop body of LocalMapping::CreateNewMapPoints (LocalMapping.cc:481-710) for ALL neighbours of the new keyframe in one call
+    // (xfh_triangulate_device with XFH_TRIANG_CLAIM): parallax, triangulation or stereo unprojection, cheirality, reprojection and scale gates, and
+    // the reference's rule that the first neighbour that creates a point at a keypoint of KF1 keeps it.  match12 [B][n1] is what the batched
+    // searchForTriangulation (xfh_triangulation_search_device, side1_shared = 1) wrote.  levelSigma2_0 = mvLevelSigma2[0], scaleFactor = mfScaleFactor,
+    // scaleFactorLast = mvScaleFactors[nLevels - 1], thFarPoints = mThFarPoints (<= 0: mbFarPoints off).  The list comes back in the reference's
+    // creation order (neighbour ascending, then idx1).  The device form reads everything where the searches left it and only the list travels back;
+    // the points, normals and distance triples also stay on the device for fuse (deviceNewPoints() / deviceNewNormals() / deviceNewDistances()).
+    // ComputeDistinctiveDescriptors of a new point is the caller's: with two observations either row is a legal outcome, KF1's is recommended.
+    int triangulate(const xfh_camera& cam, int B, int n1, int n2, const XFtriKeyFrame& d_kf1, const XFtriKeyFrame& d_neighbours, const int* d_match12,
+                    std::vector<XFnewMapPoint>& vNew, float levelSigma2_0 = 1.f, float scaleFactor = 1.2f, float scaleFactorLast = 1.f, float thFarPoints = 0.f,
+                    bool bInertial = false) {
+        vNew.clear();
+        triangHeader.assign(B > 0 ? (size_t)B * 8 : 0, 0);
+        if (B <= 0 || n1 <= 0 || n2 <= 0) return 0;
+        auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+        const size_t P = (size_t)B * n1, bst = al(P), bx = al(P * 12), bh = al((size_t)B * 32), bi = al((size_t)n1 * 4), bf = al((size_t)n1 * 12);
+        reserve(d_triang, d_triang_bytes, 2 * bst + bx + bh + 4 * bi + 3 * bf + 256, "XFmatcher::triangulate");
+        char* p = (char*)d_triang;
+        unsigned char* dst = (unsigned char*)p; p += bst; unsigned char* dkd = (unsigned char*)p; p += bst; float* dxyz = (float*)p; p += bx; int* dh = (int*)p; p += bh;
+        int* di[4];
+        for (int k = 0; k < 4; ++k) { di[k] = (int*)p; p += bi; }
+        d_new[0] = (float*)p; p += bf; d_new[1] = (float*)p; p += bf; d_new[2] = (float*)p; p += bf; int* dn = (int*)p;
+        int rc = xfh_triangulate_device(ctx, B, n1, n2, 1, XFH_TRIANG_CLAIM | (bInertial ? XFH_TRIANG_INERTIAL : 0), &cam, levelSigma2_0, 1.5f * scaleFactor, scaleFactorLast,
+                                        thFarPoints, d_kf1.keysUn, d_kf1.keys, d_kf1.uright, d_kf1.depth, d_kf1.Tcw, d_kf1.Ow, d_neighbours.keysUn, d_neighbours.keys,
+                                        d_neighbours.uright, d_neighbours.depth, d_neighbours.Tcw, d_neighbours.Ow, d_match12, dst, dkd, dxyz, dh, di[0], di[1], di[2],
+                                        di[3], d_new[0], d_new[1], d_new[2], dn);
+        if (rc == XFH_OK) rc = xfh_synchronize(ctx);
+        int nNew = 0;
+        if (rc == XFH_OK) rc = xfh_memcpy_d2h(&nNew, dn, 4);
+        if (rc == XFH_OK) rc = xfh_memcpy_d2h(triangHeader.data(), dh, (size_t)B * 32);
+        std::vector<int> idx[3];
+        std::vector<float> f[3];
+        std::vector<unsigned char> kind(P);
+        if (rc == XFH_OK) rc = xfh_memcpy_d2h(kind.data(), dkd, P);
+        for (int k = 0; k < 3 && rc == XFH_OK && nNew > 0; ++k) {
+            idx[k].resize(nNew); f[k].resize((size_t)nNew * 3);
+            rc = xfh_memcpy_d2h(idx[k].data(), di[k + 1], (size_t)nNew * 4);
+            if (rc == XFH_OK) rc = xfh_memcpy_d2h(f[k].data(), d_new[k], (size_t)nNew * 12);
+        }
+        if (rc != XFH_OK) throw std::runtime_error(std::string("XFmatcher::triangulate: ") + xfh_strerror(rc));
+        vNew.resize(nNew);
+        for (int j = 0; j < nNew; ++j) {
+            XFnewMapPoint& q = vNew[j];
+            q.idx1 = idx[0][j]; q.neighbour = idx[1][j]; q.idx2 = idx[2][j];
+            for (int k = 0; k < 3; ++k) { q.x3D[k] = f[0][3 * j + k]; q.normal[k] = f[1][3 * j + k]; q.fuseDistances[k] = f[2][3 * j + k]; }
+            q.maxDistance = q.fuseDistances[2]; q.minDistance = q.maxDistance / scaleFactorLast;
+            q.stereo = kind[(size_t)q.neighbour * n1 + q.idx1] != 0;
+        }
+        nTriangNew = nNew;
+        return nNew;
+    }
+    // The same on host containers: kf1 and each of the B neighbours (all with n2 keypoints) as host arrays, match12 [B][n1] on the host.
+    int triangulate(const xfh_camera& cam, int n1, int n2, const XFtriKeyFrame& kf1, const std::vector<XFtriKeyFrame>& neighbours, const std::vector<int>& match12,
+                    std::vector<XFnewMapPoint>& vNew, float levelSigma2_0 = 1.f, float scaleFactor = 1.2f, float scaleFactorLast = 1.f, float thFarPoints = 0.f,
+                    bool bInertial = false) {
+        const int B = (int)neighbours.size();
+        vNew.clear();
+        if (B == 0 || n1 <= 0 || n2 <= 0) return 0;
+        if ((int)match12.size() != B * n1 || !kf1.keysUn || !kf1.Tcw || !kf1.Ow) throw std::runtime_error("XFmatcher::triangulate: sizes do not fit");
+        const bool raw = neighbours[0].keys != nullptr, st = neighbours[0].uright != nullptr;
+        std::vector<float> xy((size_t)B * n2 * 2), xr(raw ? xy.size() : 0), ur(st ? (size_t)B * n2 : 0), z(ur.size()), T((size_t)B * 12), O((size_t)B * 3);
+        for (int b = 0; b < B; ++b) {
+            const XFtriKeyFrame& k = neighbours[b];
+            if (!k.keysUn || !k.Tcw || !k.Ow || (k.keys != nullptr) != raw || (k.uright != nullptr) != st || (st && !k.depth))
+                throw std::runtime_error("XFmatcher::triangulate: the neighbours must name the same arrays");
+            std::copy(k.keysUn, k.keysUn + 2 * n2, xy.begin() + (size_t)b * n2 * 2);
+            if (raw) std::copy(k.keys, k.keys + 2 * n2, xr.begin() + (size_t)b * n2 * 2);
+            if (st) { std::copy(k.uright, k.uright + n2, ur.begin() + (size_t)b * n2); std::copy(k.depth, k.depth + n2, z.begin() + (size_t)b * n2); }
+            std::copy(k.Tcw, k.Tcw + 12, T.begin() + (size_t)b * 12); std::copy(k.Ow, k.Ow + 3, O.begin() + (size_t)b * 3);
+        }
+        const size_t P = (size_t)B * n1;
+        std::vector<unsigned char> status(P), kind(P);
+        std::vector<float> xyz(P * 3), nx((size_t)n1 * 3), nn((size_t)n1 * 3), nd((size_t)n1 * 3);
+        std::vector<int> winner(n1), i1v(n1), bv(n1), i2v(n1);
+        triangHeader.assign((size_t)B * 8, 0);
+        int nNew = 0;
+        const int rc = xfh_triangulate(ctx, B, n1, n2, XFH_TRIANG_CLAIM | (bInertial ? XFH_TRIANG_INERTIAL : 0), &cam, levelSigma2_0, 1.5f * scaleFactor, scaleFactorLast,
+                                       thFarPoints, kf1.keysUn, kf1.keys, kf1.uright, kf1.depth, kf1.Tcw, kf1.Ow, xy.data(), raw ? xr.data() : nullptr, st ? ur.data() : nullptr,
+                                       st ? z.data() : nullptr, T.data(), O.data(), match12.data(), status.data(), kind.data(), xyz.data(), triangHeader.data(), winner.data(),
+                                       i1v.data(), bv.data(), i2v.data(), nx.data(), nn.data(), nd.data(), &nNew);
+        if (rc != XFH_OK) throw std::runtime_error(std::string("XFmatcher::triangulate: ") + xfh_strerror(rc));
+        vNew.resize(nNew);
+        for (int j = 0; j < nNew; ++j) {
+            XFnewMapPoint& q = vNew[j];
+            q.idx1 = i1v[j]; q.neighbour = bv[j]; q.idx2 = i2v[j];
+            for (int k = 0; k < 3; ++k) { q.x3D[k] = nx[3 * j + k]; q.normal[k] = nn[3 * j + k]; q.fuseDistances[k] = nd[3 * j + k]; }
+            q.maxDistance = q.fuseDistances[2]; q.minDistance = q.maxDistance / scaleFactorLast;
+            q.stereo = kind[(size_t)q.neighbour * n1 + q.idx1] != 0;
+        }
+        nTriangNew = nNew;
+        return nNew;
+    }
+    // of the last triangulate: per neighbour the eight counts of xfh_triangulate_device (matched, triangulation attempts, stereo attempts, accepted, new,
+    // new stereo (countStereo), superseded, 0); and of its device form the new points in device memory, nTriangNew rows each, as fuse takes them
+    const std::vector<int>& lastTriangulateHeader() const { return triangHeader; }
+    const float* deviceNewPoints() const { return d_new[0]; }
+    const float* deviceNewNormals() const { return d_new[1]; }
+    const float* deviceNewDistances() const { return d_new[2]; }
+    int lastTriangulateCount() const { return nTriangNew; }
+
     // ORBmatcher::SearchByBoW, both overloads (ORBmatcher.cc:408-610 and :950-1090; no second camera; the rotation histogram removes nothing
     // because every XFeat angle is -1, so mbCheckOrientation stays without effect) as ONE call (xfh_bow_search).  Side 1 is the keyframe whose
     // map points are matched: desc1 = mDescriptors, nodeOf1[i] = the NodeId of keypoint i in mFeatVec (XFH_NODE_NONE: in none), active1[i] != 0
@@ -1012,6 +1124,9 @@ protected:
     std::vector<int> sim3Match[2], sim3Best[2], sim3Window[2], sim3Tested[2], sim3Level[2];
     std::vector<unsigned char> triStatus;                   // results of searchForTriangulation
     std::vector<int> triMatch, triBest, triCandidates, triGeom;
+    void* d_triang = nullptr; size_t d_triang_bytes = 0;    // outputs of triangulate (device form)
+    float* d_new[3] = {nullptr, nullptr, nullptr};
+    std::vector<int> triangHeader; int nTriangNew = 0;
     std::vector<unsigned char> bowStatus;                   // results of searchByBoW
     std::vector<int> bowBest, bowSecond, bowCandidates;
     std::vector<unsigned char> initStatus;                  // results of searchForInitialization

@@ -658,7 +658,8 @@ int xfh_fuse_search(xfh_ctx* ctx, int nq, const float* points, const float* norm
  *                         or queued.
  * Out of scope: mbCheckOrientation and the rotation histogram (:1272-1318; the only caller builds ORBmatcher(0.6f, false),
  * LocalMapping.cc:412); fisheye stereo (mpCamera2, NLeft != -1, the four T12 variants of :1221-1255); KannalaBrandt8::epipolarConstrain;
- * computing F12 or the epipole; computing the feature vector (DBoW2); and the triangulation itself.  (SearchByBoW, which has a real claim
+ * computing F12 or the epipole; and computing the feature vector (DBoW2).  The triangulation of the matched pairs is
+ * xfh_triangulate_device; with B > 1 its claim is what makes the batched search equal the per-neighbour reference.  (SearchByBoW, which has a real claim
  * order and a ratio test, is xfh_bow_search_device below.) */
 #define XFH_NODE_NONE 0xFFFFFFFFu     /* node_of: the keypoint is in no node of the feature vector */
 #define XFH_TRI_ONLY_STEREO 1         /* flags: bOnlyStereo */
@@ -1291,6 +1292,114 @@ int xfh_pose_optimize_device(xfh_ctx* ctx, int B, int nt, int nq, const float* d
 int xfh_pose_optimize(xfh_ctx* ctx, int nt, int nq, const float* Tcw, const xfh_camera* cam, const float* xy_un, const float* uright_or_null,
                       const int* assigned, const float* points, float inv_sigma2, float* Tcw_out, uint8_t* outlier, float* chi2, int* header,
                       double* final_chi2);
+
+/* ---- CreateNewMapPoints: triangulation of the matched pairs of a new keyframe, device resident ---------------------------------------------
+ * The loop body of LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:481-710) behind SearchForTriangulation, for B neighbours of one keyframe
+ * per call, conventional Pinhole keyframes (mpCamera2 == NULL, NLeft == -1): the ray-parallax test, the choice between two-view triangulation and
+ * KeyFrame::UnprojectStereo, GeometricTools::Triangulate, the cheirality test, the two reprojection gates, the scale-consistency test and
+ * MapPoint::UpdateNormalAndDepth of the fresh point.  It reads the match12[B][n1] that xfh_triangulation_search_device left in device memory and
+ * writes the points, normals and distance triples that xfh_fuse_search_device takes as d_points / d_normals / d_distances.
+ *
+ * The claim.  The reference searches one neighbour at a time, and a keypoint of KF1 that received a map point at neighbour b' is skipped as a query
+ * at every b > b' (ORBmatcher.cc:1156-1159).  The batched search sees one has1 snapshot, so the same idx1 may come back matched at several
+ * neighbours.  The search is pure per query and has2 of neighbour b does not depend on the neighbours before it, so the reference's answer is: the
+ * LOWEST b whose pair (b, i) passes every gate below owns keypoint i, and the pairs of i at every later b never happened.  With XFH_TRIANG_CLAIM
+ * (side1_shared = 1 required) the call decides exactly that: winner[i], the later matched pairs of i marked SUPERSEDED, and the new points as a
+ * compact list in the reference's creation order, b ascending, then idx1 ascending.
+ *
+ * Problem b is the pair (KF1, KF2_b).  Per side and problem: xy [n][2] (mvKeysUn: xy_un of xfh_frame_finish_records_device), xy_raw [n][2]
+ * (mvKeys[i].pt, which KeyFrame::UnprojectStereo reads, KeyFrame.cc:760-761; NULL = use xy), uright [n] (mvuRight; NULL = a monocular keyframe),
+ * depth [n] (mvDepth; required when uright is given, not read otherwise), Tcw [12] row-major [R|t], Ow [3] (GetCameraCenter()).  With
+ * side1_shared = 1 every problem reads side 1 at offset 0; with 0 problem b reads its own block.  cam (host memory, one for both sides): fx, fy,
+ * cx, cy, bf are read; invfx = 1.0f / fx, invfy = 1.0f / fy, mb = bf / fx in float, as Frame computes them.  Scalars: sigma2 = mvLevelSigma2[0]
+ * (every XFeat keypoint has octave 0, so ratioOctave == 1.0f), ratio_factor = 1.5f * mfScaleFactor, scale_last = mvScaleFactors[nLevels - 1],
+ * far_th = mThFarPoints (<= 0: mbFarPoints is off).  flags: XFH_TRIANG_INERTIAL (the literal 0.9996 instead of 0.9998), XFH_TRIANG_CLAIM.
+ *
+ * The rule for keypoint i of KF1 at problem b.  All arithmetic is fp32 in the order written unless marked (the library is built with
+ * -ffp-contract=off); dot(a, b) = (a0*b0 + a1*b1) + a2*b2 everywhere.
+ *   m = match12[b][i];  m outside 0 .. n2 - 1                                   -> NO_MATCH
+ *   stereo1 = uright1[i] >= 0, stereo2 = uright2[m] >= 0 (NULL or NaN: false)                                              (:492, :501)
+ *   1. Rays.  xn = ((x - cx) / fx, (y - cy) / fy, 1) from xy (Pinhole.cpp:61-64); ray = Rwc * xn with Rwc = Rcw^T:
+ *        ray[k] = (R[0][k]*xn[0] + R[1][k]*xn[1]) + R[2][k]*1;  norm = sqrtf(dot(ray, ray));  cosRays = dot(ray1, ray2) / (norm1 * norm2)      (:558-563)
+ *      Eigen's unrolled 3-term reductions may associate differently: bit equality with the reference's own cosParallaxRays is not claimed (as
+ *      for x3Dc in SearchByProjection); the decisions are.
+ *   2. Stereo cosines (:565-576, including the `else if`).  cos1 = cos2 = cosRays + 1;  stereo1: cos1 = C(depth1[i]);  else stereo2: cos2 =
+ *      C(depth2[m]) -- when both are stereo only cos1 is computed.  cosStereo = cos2 < cos1 ? cos2 : cos1.  The reference computes
+ *      cosf(2 * atan2f(mb / 2, depth)), and device libm and glibc differ in the last bits; the rule is the identity
+ *        C(z) = (float)(((double)z*z - h*h) / ((double)z*z + h*h)),  h = (double)(mb / 2.0f)                  -- in double, rounded once
+ *      A stated deviation: at most about 2e-7 from the reference's float (two sub-ulp libm calls and one doubling); tests bound it by 1e-6.
+ *   3. Branch (:582-604).  cosRays < cosStereo && cosRays > 0 && (stereo1 || stereo2 || (double)cosRays < 0.9998 (0.9996 with
+ *      XFH_TRIANG_INERTIAL))  -> two-view triangulation, kind 0;  else stereo1 && cos1 < cos2 -> UnprojectStereo from KF1, kind 1;  else stereo2 &&
+ *      cos2 < cos1 -> from KF2, kind 2;  else                                   -> LOW_PARALLAX
+ *      UnprojectStereo (KeyFrame.cc:755-772): z = depth; !(z > 0)               -> STEREO_NO_DEPTH
+ *        x = (u - cx) * z * invfx, y = (v - cy) * z * invfy from the RAW key;  x3D[k] = ((R[0][k]*x + R[1][k]*y) + R[2][k]*z) + Ow[k]
+ *   4. GeometricTools::Triangulate (GeometricTools.cc:47-66).  The rows of the 4x4 A in fp32 exactly as written: A[0] = xn1[0] * T1[2] - T1[0],
+ *      A[1] = xn1[1] * T1[2] - T1[1], A[2] = xn2[0] * T2[2] - T2[0], A[3] = xn2[1] * T2[2] - T2[1] (T[r] = row r of Tcw, 4 floats).  Then the right
+ *      singular vector of the smallest singular value of A IN FP64: one-sided (Hestenes) Jacobi on the columns of U = (double)A with V = I
+ *      accumulated, cyclic pair order (0,1) (0,2) (0,3) (1,2) (1,3) (2,3); for a pair (p, q): alpha = |U_p|^2, beta = |U_q|^2, gamma = U_p . U_q
+ *      (four terms, left to right); rotate iff fabs(gamma) > 1e-15 * sqrt(alpha * beta) with zeta = (beta - alpha) / (2 gamma), t = sign(zeta) /
+ *      (fabs(zeta) + sqrt(1 + zeta^2)) (sign(0) = +1), c = 1 / sqrt(1 + t^2), s = c t, (U_p, U_q) <- (c U_p - s U_q, s U_p + c U_q), V likewise.
+ *      Stop after the first sweep that rotates nothing, at most 30 sweeps.  x3Dh = the column of V whose column of U has the least squared
+ *      norm (the first on a tie), rounded to float.  x3Dh[3] == 0                -> DEGENERATE;  x3D = x3Dh[0..2] / x3Dh[3] in float.
+ *      The reference's Eigen::JacobiSVD<Matrix4f> cannot be reproduced bit for bit; the same iteration in fp32 is 10-50x farther from the exact
+ *      null vector than an fp32 LAPACK SVD, worst at low parallax, while in fp64 and rounded once it equals the fp64 SVD to within one float
+ *      step.  The rule therefore returns the answer Eigen approximates, not an imitation of its rounding.  A stated deviation.
+ *   5. Gates (:612-691), comparisons literally as written; a NaN behaves as in the reference (it passes `z <= 0` and every `>` gate).
+ *      z1 = dot(R1[2], x3D) + t1[2];  z1 <= 0 -> BEHIND1;   z2 likewise         -> BEHIND2
+ *      per view, x = dot(R[0], x3D) + t[0], y = dot(R[1], x3D) + t[1];  mono: u = fx*x/z + cx, v = fy*y/z + cy (Pinhole.cpp:30-33), ex = u - kp.x,
+ *      ey = v - kp.y, (double)(ex*ex + ey*ey) > 5.991 * (double)sigma2 -> REPROJ1 / REPROJ2;  stereo: invz = (float)(1.0 / (double)z), u =
+ *      fx*x*invz + cx, u_r = u - bf*invz, v = fy*y*invz + cy, er = u_r - uright, (double)(ex*ex + ey*ey + er*er) > 7.8 * (double)sigma2 likewise
+ *      dist1 = sqrtf(dot(x3D - Ow1, x3D - Ow1)), dist2 likewise;  dist1 == 0 || dist2 == 0 -> ZERO_DIST
+ *      far_th > 0 && (dist1 >= far_th || dist2 >= far_th)                       -> FAR
+ *      ratioDist = dist2 / dist1;  ratioDist * ratio_factor < 1.0f || ratioDist > 1.0f * ratio_factor -> SCALE;  everything else -> ACCEPTED
+ *   6. UpdateNormalAndDepth of the fresh point with its two observations (MapPoint.cc:426-494): n1 = x3D - Ow1, n2 = x3D - Ow2,
+ *      normal[k] = ((0 + n1[k] / |n1|) + n2[k] / |n2|) / 2 (a two-term sum from zero does not depend on the std::map's pointer order),
+ *      mfMax = |n1| * 1.0f, mfMin = mfMax / scale_last, dist[3] = (0.8f * mfMin, 1.2f * mfMax, mfMax).
+ * Outputs, all in device memory; the integers are exact.  Per (b, i): status (XFH_TRIANG_*), kind (0 two-view, 1 stereo of KF1, 2 stereo of KF2:
+ * bPointStereo = kind != 0; 0 for NO_MATCH and LOW_PARALLAX), xyz[3] (zeros unless a 3-D point was formed).  Per problem an eight-int header:
+ * matched pairs, triangulation attempts, stereo attempts (countStereoAttempt), accepted pairs -- these four of the snapshot, before the claim --
+ * new points after the claim, new stereo points (countStereo), superseded pairs, 0.  With XFH_TRIANG_CLAIM: winner[n1] (b or -1); status[b][i]
+ * = SUPERSEDED for every matched pair with b > winner[i] >= 0 (its kind and xyz stay those of the snapshot evaluation); the compact list
+ * new_idx1 / new_b / new_idx2 [n1], new_xyz / new_normal / new_dist [n1][3] with n_new entries and -1 / 0 behind them; n_new.  Without it the
+ * claim outputs are not touched (they may be NULL) and header[4], [5] count the accepted pairs.  The caller runs :694-709 (new MapPoint,
+ * AddObservation, AddMapPoint) over the list in order.  Two runs on the same input give identical bytes.
+ *
+ *   xfh_triangulate_pair  host, stateless, thread-safe, no ctx: the whole rule for ONE pair from the header the kernels compile (triangulate_math.h)
+ *                         -> status, kind, x3D[3], and for an ACCEPTED pair normal[3], dist[3] (zeros otherwise); x3Dh_or_null[4]: the fp64 null
+ *                         vector before rounding (zeros unless step 4 ran).  flags: XFH_TRIANG_INERTIAL only.
+ *   xfh_triangulate_device   B problems with the same n1, n2.  d_match12 [B][n1]; d_status, d_kind [B][n1] bytes, d_xyz [B][n1][3], d_header
+ *                         [B][8].  All arrays are device pointers; asynchronous on the ctx stream, no allocation, no workspace, no atomics: one
+ *                         launch for the pairs, one for winner[] (with the claim), one for the headers and the list.  XFH_ERR_INVALID_ARG
+ *                         before anything is queued: n1 or n2 outside 1 .. XFH_GRID_MAX_N, B outside 1 .. 65535, side1_shared other than 0 or 1,
+ *                         unknown flag bits, XFH_TRIANG_CLAIM without a shared side 1, a NULL required pointer (depth beside a given uright; the
+ *                         claim outputs with the claim), a pointer that is not 4-byte aligned, a non-finite scalar.  Coordinates, depths, poses
+ *                         and camera values may hold anything, NaN and Inf included; a match12 entry outside 0 .. n2 - 1 is -1: no load or store
+ *                         leaves the buffers the caller named, and the call terminates (at most 30 sweeps per pair).
+ *   xfh_triangulate       host-pointer convenience form for one call with a shared side 1: stages the arrays, runs the call, copies the results back.
+ * Out of scope: a second camera (mpCamera2, NLeft != -1, the four pose variants of :505-555) and KannalaBrandt8; per-keypoint octaves (sigma2 and
+ * ratioOctave are per call); the baseline test of :443-460 and CheckNewKeyFrames() (the caller passes the neighbours it wants); creating the
+ * MapPoint objects and their observations; MapPoint::ComputeDistinctiveDescriptors of a new point (with two observations both medians are 0 and
+ * the reference keeps whichever keyframe pointer sorts first: either row is a legal outcome, KF1's is recommended). */
+#define XFH_TRIANG_INERTIAL 1         /* flags: mbInertial (0.9996) */
+#define XFH_TRIANG_CLAIM 2            /* flags: the first accepted neighbour owns a keypoint of KF1; needs side1_shared = 1 */
+enum { XFH_TRIANG_NO_MATCH = 0, XFH_TRIANG_LOW_PARALLAX = 1, XFH_TRIANG_STEREO_NO_DEPTH = 2, XFH_TRIANG_DEGENERATE = 3, XFH_TRIANG_BEHIND1 = 4,
+       XFH_TRIANG_BEHIND2 = 5, XFH_TRIANG_REPROJ1 = 6, XFH_TRIANG_REPROJ2 = 7, XFH_TRIANG_ZERO_DIST = 8, XFH_TRIANG_FAR = 9, XFH_TRIANG_SCALE = 10,
+       XFH_TRIANG_ACCEPTED = 11, XFH_TRIANG_SUPERSEDED = 12 };
+int xfh_triangulate_pair(const xfh_camera* cam, int flags, float sigma2, float ratio_factor, float scale_last, float far_th, const float* xy1,
+                         const float* xy_raw1_or_null, float uright1, float depth1, const float* Tcw1, const float* Ow1, const float* xy2,
+                         const float* xy_raw2_or_null, float uright2, float depth2, const float* Tcw2, const float* Ow2, int* status, int* kind,
+                         float* x3D, float* normal, float* dist, double* x3Dh_or_null);
+int xfh_triangulate_device(xfh_ctx* ctx, int B, int n1, int n2, int side1_shared, int flags, const xfh_camera* cam, float sigma2, float ratio_factor,
+                           float scale_last, float far_th, const float* d_xy1, const float* d_xy_raw1_or_null, const float* d_uright1_or_null,
+                           const float* d_depth1_or_null, const float* d_Tcw1, const float* d_Ow1, const float* d_xy2, const float* d_xy_raw2_or_null,
+                           const float* d_uright2_or_null, const float* d_depth2_or_null, const float* d_Tcw2, const float* d_Ow2, const int* d_match12,
+                           uint8_t* d_status, uint8_t* d_kind, float* d_xyz, int* d_header, int* d_winner, int* d_new_idx1, int* d_new_b,
+                           int* d_new_idx2, float* d_new_xyz, float* d_new_normal, float* d_new_dist, int* d_n_new);
+int xfh_triangulate(xfh_ctx* ctx, int B, int n1, int n2, int flags, const xfh_camera* cam, float sigma2, float ratio_factor, float scale_last, float far_th,
+                    const float* xy1, const float* xy_raw1_or_null, const float* uright1_or_null, const float* depth1_or_null, const float* Tcw1,
+                    const float* Ow1, const float* xy2, const float* xy_raw2_or_null, const float* uright2_or_null, const float* depth2_or_null,
+                    const float* Tcw2, const float* Ow2, const int* match12, uint8_t* status, uint8_t* kind, float* xyz, int* header, int* winner,
+                    int* new_idx1, int* new_b, int* new_idx2, float* new_xyz, float* new_normal, float* new_dist, int* n_new);
 
 /* MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:329-403), batched over map points: group g observes the
  * descriptor rows indices[offsets[g] .. offsets[g+1]) of `table` (n_rows x 64).  Pairwise DescriptorDistance inside

@@ -224,6 +224,8 @@ struct InitArgs;
 hipError_t launch_init_search(xfh_ctx* c, const InitArgs& a, int B);                  // init_search.hip.h
 struct PoseArgs;
 hipError_t launch_pose_optimize(xfh_ctx* c, const PoseArgs& a, int B);              // poseopt.hip.h
+struct TriangArgs;
+hipError_t launch_triangulate(xfh_ctx* c, const TriangArgs& a);                        // triangulate.hip.h
 struct VocabArgs;
 hipError_t launch_bow_transform(xfh_ctx* c, const VocabArgs& a, int B);             // vocab_transform.hip.h
 struct BowDbArgs;

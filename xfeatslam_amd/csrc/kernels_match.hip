@@ -36,6 +36,9 @@
 //                   every query's turn against the final chains (init_search.hip.h).
 //   k_pose_optimize : Optimizer::PoseOptimization for B frames in one launch, one workgroup per frame: the edges in registers, H, b and the chi2 sums
 //                   folded in a fixed order, the Levenberg state machine on one lane (poseopt.hip.h, poseopt_math.h).
+//   k_triangulate_pairs / k_triangulate_winner / k_triangulate_finish : the triangulation half of LocalMapping::CreateNewMapPoints for B neighbours per call:
+//                   one lane per matched pair (parallax, fp64 null vector or stereo unprojection, the gates), then the least accepted neighbour per
+//                   keypoint, then per neighbour the header and the ordered compact list (triangulate.hip.h, triangulate_math.h).
 //   k_distinctive_csr : MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:329-403), one wave per map point.
 // Shared by k_best2_csr and every *_search.hip.h kernel: search_common.hip.h (keys, descriptor_distance, top-two and K-list with their wave merges, wave
 // minimum / sum), window_search.hip.h (the grid walk), nodes_clamp.h (node blobs), resolve_rounds.hip.h (the rounds of k_proj_resolve / k_init_resolve: the argument, the cut, the advance of lo).
@@ -102,6 +105,7 @@ hipError_t launch_best2(xfh_ctx* c, const float* q, int nq, const float* tg, con
 #include "sim3_search.hip.h"
 #include "init_search.hip.h"
 #include "poseopt.hip.h"
+#include "triangulate.hip.h"
 
 // ---- k_distinctive_csr: MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:329-403), batched -------
 // One wave per group (map point).  Rows are taken 64 at a time, lane = row: the lane keeps its descriptor in

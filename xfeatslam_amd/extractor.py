@@ -942,6 +942,88 @@ class Context:
                                       p.ctypes.data, float(inv_sigma2), To.ctypes.data, ol.ctypes.data, c2.ctypes.data, hd.ctypes.data, fc.ctypes.data), self.h)
         return dict(ret=int(hd[2]), Tcw=To.reshape(3, 4), outlier=ol, chi2=c2, header=dict(zip(self.POSE_HEADER, hd.tolist())), final_chi2=float(fc[0]))
 
+    # -- CreateNewMapPoints: triangulation of the matched pairs (xfh_triangulate*) ----------------------------------------------
+    TRIANG_HEADER = ("matched", "tri_attempts", "stereo_attempts", "accepted", "new", "new_stereo", "superseded", "reserved")
+    TRIANG_CLAIM_OUT = ("winner", "new_idx1", "new_b", "new_idx2", "new_xyz", "new_normal", "new_dist", "n_new")
+
+    @staticmethod
+    def triangulate_layout(B: int, n1: int, guard: int = 0):
+        """byte offsets of the outputs of triangulate_device inside one buffer (and its size under "bytes"); guard as in fuse_search_layout"""
+        al = lambda x: (x + 255) & ~255
+        o, off = {}, al(guard)
+        for name, nbytes in (("status", B * n1), ("kind", B * n1), ("xyz", 12 * B * n1), ("header", 32 * B), ("winner", 4 * n1), ("new_idx1", 4 * n1),
+                             ("new_b", 4 * n1), ("new_idx2", 4 * n1), ("new_xyz", 12 * n1), ("new_normal", 12 * n1), ("new_dist", 12 * n1), ("n_new", 4)):
+            o[name] = off; o[name + "_bytes"] = nbytes; off += al(nbytes) + al(guard)
+        o["bytes"] = off
+        return o
+
+    @staticmethod
+    def triangulate_parse(raw: np.ndarray, lay, B: int, n1: int, claim: bool):
+        """the bytes of a buffer laid out by triangulate_layout -> dict of arrays"""
+        cut = lambda k, dt: raw[lay[k]:lay[k] + lay[k + "_bytes"]].view(dt).copy()
+        r = dict(status=cut("status", np.uint8).reshape(B, n1), kind=cut("kind", np.uint8).reshape(B, n1), xyz=cut("xyz", np.float32).reshape(B, n1, 3),
+                 header=cut("header", np.int32).reshape(B, 8))
+        if claim:
+            r.update(winner=cut("winner", np.int32), new_idx1=cut("new_idx1", np.int32), new_b=cut("new_b", np.int32), new_idx2=cut("new_idx2", np.int32),
+                     new_xyz=cut("new_xyz", np.float32).reshape(n1, 3), new_normal=cut("new_normal", np.float32).reshape(n1, 3),
+                     new_dist=cut("new_dist", np.float32).reshape(n1, 3), n_new=int(cut("n_new", np.int32)[0]))
+        return r
+
+    def triangulate_device(self, B: int, n1: int, n2: int, side1_shared: bool, cam, side1, side2, d_match12, d_out, sigma2: float = 1.0,
+                           ratio_factor: float = 1.8, scale_last: float = 1.0, far_th: float = 0.0, inertial: bool = False, claim: bool = False, guard: int = 0):
+        """xfh_triangulate_device on device pointers; asynchronous.  side1 / side2: (d_xy, d_xy_raw or None, d_uright or None, d_depth or None, d_Tcw, d_Ow);
+        d_out: pointer to the outputs laid out as triangulate_layout(B, n1, guard) says"""
+        o = self.triangulate_layout(B, n1, guard)
+        flags = (capi.TRIANG_INERTIAL if inertial else 0) | (capi.TRIANG_CLAIM if claim else 0)
+        co = [d_out + o[k] if claim else None for k in self.TRIANG_CLAIM_OUT]
+        check(lib().xfh_triangulate_device(self.h, B, n1, n2, 1 if side1_shared else 0, flags, C.byref(cam), float(sigma2), float(ratio_factor), float(scale_last),
+                                           float(far_th), *side1, *side2, d_match12, d_out + o["status"], d_out + o["kind"], d_out + o["xyz"], d_out + o["header"],
+                                           *co), self.h)
+
+    @staticmethod
+    def _triang_side(k, B=None):
+        """dict(xy, xy_raw (optional), ur, depth, Tcw, Ow) of one keyframe, or a list of B of them -> contiguous float32 arrays (None where absent)"""
+        ks = [k] if B is None else list(k)
+        f32 = lambda a: np.ascontiguousarray(a, np.float32)
+        cat = lambda key: None if ks[0].get(key) is None else f32(np.concatenate([np.asarray(q[key], np.float32).reshape(len(q["xy"]), -1) for q in ks]))
+        return [cat("xy"), cat("xy_raw"), cat("ur"), cat("depth") if ks[0].get("ur") is not None else None,
+                f32(np.stack([np.asarray(q["Tcw"], np.float32).reshape(12) for q in ks])), f32(np.stack([np.asarray(q["Ow"], np.float32).reshape(3) for q in ks]))]
+
+    def triangulate(self, cam, k1, k2s, match12, sigma2: float = 1.0, ratio_factor: float = 1.8, scale_last: float = 1.0, far_th: float = 0.0,
+                    inertial: bool = False, claim: bool = True):
+        """xfh_triangulate (host pointers): KF1 = k1 against the neighbours k2s (dicts with xy, xy_raw (optional), ur, depth, Tcw, Ow), match12 [B][n1]
+        -> dict(status, kind, xyz, header and, with the claim, winner, new_idx1, new_b, new_idx2, new_xyz, new_normal, new_dist, n_new)"""
+        B, n1, n2 = len(k2s), len(k1["xy"]), len(k2s[0]["xy"])
+        s1, s2 = self._triang_side(k1), self._triang_side(k2s, B)
+        m = np.ascontiguousarray(match12, np.int32).reshape(B, n1)
+        st, kd, xyz, hd = np.zeros((B, n1), np.uint8), np.zeros((B, n1), np.uint8), np.zeros((B, n1, 3), np.float32), np.zeros((B, 8), np.int32)
+        co = [np.zeros(n1, np.int32) for _ in range(4)] + [np.zeros((n1, 3), np.float32) for _ in range(3)] + [np.zeros(1, np.int32)]
+        ptr = lambda a: None if a is None else a.ctypes.data
+        flags = (capi.TRIANG_INERTIAL if inertial else 0) | (capi.TRIANG_CLAIM if claim else 0)
+        check(lib().xfh_triangulate(self.h, B, n1, n2, flags, C.byref(cam), float(sigma2), float(ratio_factor), float(scale_last), float(far_th),
+                                    *[ptr(a) for a in s1], *[ptr(a) for a in s2], ptr(m), ptr(st), ptr(kd), ptr(xyz), ptr(hd),
+                                    *[ptr(a) if claim else None for a in co]), self.h)
+        r = dict(status=st, kind=kd, xyz=xyz, header=hd)
+        if claim:
+            r.update(zip(self.TRIANG_CLAIM_OUT, co)); r["n_new"] = int(co[7][0])
+        return r
+
+    @staticmethod
+    def triangulate_pair(cam, o1, o2, sigma2: float = 1.0, ratio_factor: float = 1.8, scale_last: float = 1.0, far_th: float = 0.0, inertial: bool = False):
+        """xfh_triangulate_pair: o1 / o2 = dict(xy, xy_raw (optional), ur, depth, Tcw, Ow) of ONE keypoint each
+        -> dict(status, kind, x3D, normal, dist, x3Dh)"""
+        f32 = lambda a: np.ascontiguousarray(a, np.float32).ravel()
+        a = []
+        for o in (o1, o2):
+            raw = o.get("xy_raw")
+            a += [f32(o["xy"]), None if raw is None else f32(raw), float(o["ur"]), float(o["depth"]), f32(o["Tcw"]), f32(o["Ow"])]
+        ptr = lambda v: None if v is None else (v.ctypes.data if isinstance(v, np.ndarray) else v)
+        st, kd = C.c_int(0), C.c_int(0)
+        X, nrm, dst, xh = np.zeros(3, np.float32), np.zeros(3, np.float32), np.zeros(3, np.float32), np.zeros(4, np.float64)
+        check(lib().xfh_triangulate_pair(C.byref(cam), capi.TRIANG_INERTIAL if inertial else 0, float(sigma2), float(ratio_factor), float(scale_last), float(far_th),
+                                         *[ptr(v) for v in a], C.byref(st), C.byref(kd), ptr(X), ptr(nrm), ptr(dst), ptr(xh)))
+        return dict(status=st.value, kind=kd.value, x3D=X, normal=nrm, dist=dst, x3Dh=xh)
+
     def timing_enable(self, kernel_id: int, layer_mask: int = 0):
         check(lib().xfh_timing_enable(self.h, kernel_id, layer_mask), self.h)
 
@@ -1039,6 +1121,19 @@ class ORBmatcher:
                                           epipole_r2=float(np.float32(100) * np.float32(scale_factor0)), unc=level_sigma2_0)
         m = r["match12"]
         return r["n_matches"], [(int(i), int(m[i])) for i in np.nonzero(m >= 0)[0]], r
+
+    def triangulate(self, cam, k1, k2s, match12, level_sigma2_0: float = 1.0, scale_factor: float = 1.2, scale_factor_last: float = 1.0, far_th: float = 0.0,
+                    inertial: bool = False):
+        """The loop body of `LocalMapping::CreateNewMapPoints` (LocalMapping.cc:481-710) for all neighbours at once, with the claim
+        -> list of (idx1, neighbour, idx2, x3D, normal, (mfMinDistance bound, mfMaxDistance bound, mfMaxDistance), bPointStereo) in the reference's creation
+        order, and the result dict of Context.triangulate; the caller runs :694-709 over the list"""
+        r = self.ctx.triangulate(cam, k1, k2s, match12, sigma2=level_sigma2_0, ratio_factor=float(np.float32(1.5) * np.float32(scale_factor)),
+                                 scale_last=scale_factor_last, far_th=far_th, inertial=inertial, claim=True)
+        out = []
+        for j in range(r["n_new"]):
+            i, b = int(r["new_idx1"][j]), int(r["new_b"][j])
+            out.append((i, b, int(r["new_idx2"][j]), r["new_xyz"][j], r["new_normal"][j], r["new_dist"][j], bool(r["kind"][b, i] != 0)))
+        return out, r
 
     def ComputeBoW(self, vocab_blob, desc, levelsup: int = 4):
         """`Frame::ComputeBoW` / `KeyFrame::ComputeBoW` (Frame.cc:936, KeyFrame.cc:105: mpORBvocabulary->transform(vCurrentDesc, mBowVec, mFeatVec, 4)) on a
