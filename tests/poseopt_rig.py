@@ -1,6 +1,7 @@
 """Seeded scenes for xfh_pose_optimize_device and its restatements (tests/ref_poseopt.py): map points in front of a pinhole camera, observations =
-their projection at the true pose + noise, a perturbed start pose.  SCENES is the table the CPU test checks the condition of and the GPU tests
-compare on; PoseRig runs them on the device between guard bytes."""
+their projection at the true pose + noise, a perturbed start pose.  SCENES and EDGE_SCENES are the tables the CPU test checks the 1e-9 condition of
+and the GPU tests compare on exactly; MONO_SCENES (all-mono, ten or more edges) hold a condition on their outputs only and are compared within
+MONO_TOL; PoseRig runs them on the device, outputs and workspace between guard bytes."""
 import ctypes as C
 
 import numpy as np
@@ -14,10 +15,10 @@ INV_SIGMA2 = 1.0
 GUARD = 256
 
 
-def make(seed, n_edges, nt, kind="mono", outliers=0.0, noise=0.7, start=(0.02, 0.05), beyond=0, identical=False, spare=5):
+def make(seed, n_edges, nt, kind="mono", outliers=0.0, noise=0.7, start=(0.02, 0.05), beyond=0, identical=False, spare=5, pin=None):
     """-> dict(Tcw, xy_un, uright, assigned, points, nt, nq).  kind: mono (uright None), stereo, mixed (uright < 0 on half), mono_ur (an all-negative
     uright array).  start = (rotation [rad], translation [m]) size of the perturbation.  beyond = keypoints whose assigned entry is >= nq.
-    identical: every edge sees the same map point."""
+    identical: every edge sees the same map point.  pin: keypoint numbers that carry an edge whatever the seed (the others are drawn)."""
     rng = np.random.RandomState(seed)
     fx, fy, cx, cy, bf = CAM
     nq = n_edges + spare
@@ -30,9 +31,17 @@ def make(seed, n_edges, nt, kind="mono", outliers=0.0, noise=0.7, start=(0.02, 0
     inv = RP.normalize([-true[0], -true[1], -true[2], true[3]])          # world = R^T (Xc - t)
     d = Xc - np.array(true[4:7])
     points = np.stack(RP.rotate(inv, [d[:, 0], d[:, 1], d[:, 2]]), 1).astype(F)
-    slots = np.sort(rng.choice(nt, n_edges + beyond, replace=False))
+    if pin:
+        pinned = np.array(sorted(pin))
+        assert len(pinned) <= n_edges and pinned[0] >= 0 and pinned[-1] < nt
+        rest = rng.choice(np.setdiff1d(np.arange(nt), pinned), n_edges + beyond - len(pinned), replace=False)
+        slots = np.sort(np.r_[pinned, rest])
+    else:
+        slots = np.sort(rng.choice(nt, n_edges + beyond, replace=False))
     assigned = np.full(nt, -1, np.int32)
     which = rng.permutation(n_edges + beyond)
+    if pin:                                                              # the pinned slots among those that get an edge, not an entry >= nq
+        which = np.r_[which[np.isin(slots[which], pinned)], which[~np.isin(slots[which], pinned)]]
     pid = rng.permutation(nq)[:n_edges]
     assigned[slots[which[:n_edges]]] = pid
     assigned[slots[which[n_edges:]]] = nq + rng.randint(0, 3, beyond)
@@ -76,13 +85,57 @@ SCENES = {
 }
 BATCH3 = ("n64_stereo", "n2", "n257")                                   # B = 3: different edge counts, the middle one refused at < 3
 
+# All-mono scenes of ten or more edges that converge: what a monocular tracker has, and what the 1e-9 condition shuts out (the last round converges into
+# rounding noise, where rho is noise / 1e-3 and the number of trials is chance).  Their condition is tests/test_poseopt_ref.py::test_mono_scene_condition:
+# every classification farther than 1e-4 from its cut, every pivot farther than 1e-9 from 0, in both forms; they are compared through
+# ref_poseopt.outputs_agree with MONO_TOL.  Both ways of being mono (uright None: "null"; an all-negative array: "neg"), 0 % and 20 % outliers, and nt
+# in each of the three ranges that select a kernel instance (<= 1024, 1025 .. 4096, above), so that each instance meets a null uright.
+MONO_SCENES = {
+    "m100_null": dict(seed=1, n_edges=100, nt=400),
+    "m100_neg_out": dict(seed=1, n_edges=100, nt=400, kind="mono_ur", outliers=0.2),
+    "m200_null_out": dict(seed=1, n_edges=200, nt=1024, outliers=0.2, pin={0, 255, 256, 1023}),
+    "m300_null": dict(seed=1, n_edges=300, nt=1025, pin={1024}),
+    "m1000_neg_out": dict(seed=1, n_edges=1000, nt=4096, kind="mono_ur", outliers=0.2, pin={4095}),
+    "m700_null_out": dict(seed=1, n_edges=700, nt=5000, outliers=0.2, pin={4096, 4999}),
+    "m700_neg": dict(seed=1, n_edges=700, nt=5000, kind="mono_ur"),
+    "m400_null_max": dict(seed=1, n_edges=400, nt=16384, pin={0, 16383}),
+}
+# The spread of the float64 forms among themselves on all-mono scenes (literal, rule, rule with three libm jitters; MONO_SCENES and 200 stream scenes),
+# measured by tests/test_poseopt_ref.py::test_mono_spread_of_the_reference: twice the largest value seen there (pose 1 and chi2 53 float32 steps -- on
+# a chi2 of 5e-4, where obs - projection cancels -- and final_chi2 9.8e-14 relative), not below 1 step and 1e-13.  That test fails if it sees more
+# than half of these constants; profiles/pose_optimization.md has the table.  Nothing from the device is in them.
+MONO_TOL = RP.Tol(pose=2, chi2=106, final=2e-13)
+
+
+def edge_pins(nt):
+    """the first keypoint, both sides of the first stride of 256 lanes, the last partial stride and the last keypoint, and both sides of the sizes at
+    which the instance changes"""
+    return {0, 255, 256, nt - 257, nt - 256, nt - 1} | {k for k in (1023, 1024, 4095, 4096) if k < nt}
+
+
+# nt at the last size of k_pose_optimize<4>, the first and last of <16>, the first of the workspace instance and XFH_GRID_MAX_N, with edges at
+# edge_pins(nt).  Stereo or mixed, so that the 1e-9 condition can hold (test_rig_condition) and the comparison is the exact one.
+EDGE_SCENES = {
+    "e1024": dict(seed=3, n_edges=200, nt=1024, kind="stereo", outliers=0.2, pin=edge_pins(1024)),
+    "e1025": dict(seed=3, n_edges=257, nt=1025, kind="mixed", outliers=0.2, pin=edge_pins(1025)),
+    "e4096": dict(seed=1, n_edges=300, nt=4096, kind="mixed", outliers=0.1, pin=edge_pins(4096)),
+    "e4097": dict(seed=2, n_edges=300, nt=4097, kind="stereo", outliers=0.2, pin=edge_pins(4097)),
+    "e16384": dict(seed=1, n_edges=400, nt=16384, kind="mixed", outliers=0.2, beyond=10, pin=edge_pins(16384)),
+}
+WS_BATCH3 = ("big", "m700_null_out", "n2")                              # B = 3 at nt = 5000: conditioned mixed, all-mono (neighbours in the workspace), refused
+NULL_BATCH2 = ("m300_null", "m1000_neg_out")                            # B = 2 at nt = 4096, run with a null uright
+
 
 def scene(name):
-    return make(**SCENES[name])
+    for table in (SCENES, MONO_SCENES, EDGE_SCENES):
+        if name in table:
+            return make(**table[name])
+    raise KeyError(name)
 
 
-def batch(names):
-    """scenes padded to one (nt, nq): -> list of scenes with common shapes (padding keypoints have no edge, padding points are never named)"""
+def batch(names, null_uright=False):
+    """scenes padded to one (nt, nq): -> list of scenes with common shapes (padding keypoints have no edge, padding points are never named).
+    null_uright: the scenes are all-mono and stay without a uright array (the call gets a null pointer)"""
     sc = [scene(n) for n in names]
     nt, nq = max(s["nt"] for s in sc), max(s["nq"] for s in sc)
     out = []
@@ -91,9 +144,10 @@ def batch(names):
         xy = np.zeros((nt, 2), F); xy[:s["nt"]] = s["xy_un"]
         ur = np.full(nt, -1.0, F)
         if s["uright"] is not None:
+            assert not null_uright or not (s["uright"] >= 0).any(), "a scene with stereo edges cannot go without uright"
             ur[:s["nt"]] = s["uright"]
         p = np.zeros((nq, 3), F); p[:s["nq"]] = s["points"]
-        out.append(dict(Tcw=s["Tcw"], xy_un=xy, uright=ur, assigned=a, points=p, nt=nt, nq=nq))
+        out.append(dict(Tcw=s["Tcw"], xy_un=xy, uright=None if null_uright else ur, assigned=a, points=p, nt=nt, nq=nq))
     return out
 
 
@@ -112,7 +166,8 @@ OUTS = (("Tcw_out", F, 12), ("outlier", np.uint8, None), ("chi2", F, None), ("he
 
 
 class PoseRig:
-    """device buffers for B problems of (nt, nq); run() -> per problem dict of outputs, the raw output bytes, guards checked"""
+    """device buffers for B problems of (nt, nq); run() -> per problem dict of outputs, the raw output bytes, guards checked; .workspace is the
+    workspace as the last run left it"""
 
     def __init__(self, L):
         from xfeatslam_amd.extractor import Context
@@ -123,9 +178,12 @@ class PoseRig:
     def close(self):
         self.ctx.close()
 
-    def run(self, scenes, fill=0xA5, uright=True, in_place=False):
+    def run(self, scenes, fill=0xA5, uright=True, in_place=False, ws_fill=0x3C):
+        """fill: the byte around and under the outputs and around the workspace; ws_fill: the byte the workspace holds before the call.  Scenes
+        whose uright is None (all of them, or none) give the call a null pointer."""
         L, B, nt, nq = self.L, len(scenes), scenes[0]["nt"], scenes[0]["nq"]
         assert all(s["nt"] == nt and s["nq"] == nq for s in scenes)
+        assert len({s["uright"] is None for s in scenes}) == 1, "uright is one pointer for the whole call"
         has_ur = uright and scenes[0]["uright"] is not None
         ins = [np.stack([s["Tcw"] for s in scenes]).astype(F), np.stack([s["xy_un"] for s in scenes]).astype(F),
                np.stack([s["uright"] for s in scenes]).astype(F) if has_ur else None,
@@ -137,14 +195,21 @@ class PoseRig:
             off[name] = pos
             pos = al(pos + B * (per or nt) * np.dtype(dt).itemsize + GUARD)
         out = capi.DeviceBuffer(pos).upload(np.full(pos, fill, np.uint8))
-        ws = capi.DeviceBuffer(max(16, int(L.xfh_pose_optimize_workspace_bytes(nt, B))))
+        ws_bytes = int(L.xfh_pose_optimize_workspace_bytes(nt, B))      # exactly what the call may use, between two guards
+        assert ws_bytes > 0 and ws_bytes % 16 == 0
+        ws_host = np.full(GUARD + ws_bytes + GUARD, fill, np.uint8)
+        ws_host[GUARD:GUARD + ws_bytes] = ws_fill
+        ws = capi.DeviceBuffer(ws_host.nbytes).upload(ws_host)
         tcw_out = dev[0].ptr if in_place else out.ptr + off["Tcw_out"]
         rc = L.xfh_pose_optimize_device(self.ctx.h, B, nt, nq, dev[0].ptr, C.byref(self.cam), dev[1].ptr, dev[2].ptr if has_ur else None, dev[3].ptr,
-                                        dev[4].ptr, INV_SIGMA2, ws.ptr, tcw_out, out.ptr + off["outlier"], out.ptr + off["chi2"], out.ptr + off["header"],
+                                        dev[4].ptr, INV_SIGMA2, ws.ptr + GUARD, tcw_out, out.ptr + off["outlier"], out.ptr + off["chi2"], out.ptr + off["header"],
                                         out.ptr + off["final_chi2"])
         assert rc == 0, rc
         self.ctx.synchronize()
         raw = out.download(np.uint8, pos)
+        ws_after = ws.download(np.uint8, ws_host.nbytes)
+        assert np.all(ws_after[:GUARD] == fill) and np.all(ws_after[GUARD + ws_bytes:] == fill), "bytes outside the workspace were written"
+        self.workspace = ws_after[GUARD:GUARD + ws_bytes].copy()        # as the call left it: B strides of xfh_pose_optimize_workspace_bytes(nt, 1)
         written = np.zeros(pos, bool)
         res = [dict() for _ in range(B)]
         for name, dt, per in OUTS:

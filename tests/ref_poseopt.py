@@ -7,8 +7,12 @@
                 the chi2 sums folded in the kernel's order (lane l of 256 adds keypoints l, l + 256, ...; xor butterfly 32 .. 1 over 64 lanes;
                 four waves in order).
 
+  rule(..., libm_jitter=seed)  the rule with every sqrt / sin / cos result moved by up to one double ulp: the device's libm is not the host's.
+
 Both use the same per-edge arithmetic (the lines of poseopt_math.h, operation by operation), so they differ in summation order and in
-bookkeeping only.  Every decision also records how far it was from its decision point (`margins`), which is what the rig's condition is."""
+bookkeeping only.  Every decision also records how far it was from its decision point (`margins`), which is what the rig's condition is.
+same_decisions() compares two results with their trajectories, outputs_agree() their outputs alone."""
+import collections
 import math
 
 import numpy as np
@@ -28,12 +32,25 @@ def _cut(thr):
 
 CUT_MONO, CUT_STEREO = _cut(CHI2_MONO), _cut(CHI2_STEREO)
 
+_JITTER = None                                                          # a RandomState while rule(..., libm_jitter=seed) runs
+
+
+def _libm(v):
+    """a sqrt / sin / cos result (a float or an array): as the host's libm gave it, or -- under rule(..., libm_jitter=seed) -- moved by -1, 0 or +1
+    double ulp, which is how another libm may answer"""
+    if _JITTER is None:
+        return v
+    k = _JITTER.randint(-1, 2, np.shape(v))
+    with np.errstate(all="ignore"):
+        r = np.where(k < 0, np.nextafter(v, -np.inf), np.where(k > 0, np.nextafter(v, np.inf), v))
+    return r if np.ndim(v) else float(r)
+
 
 # ---- the pose: SE3Quat as [qx, qy, qz, qw, tx, ty, tz] of Python floats ----------------------------------------------------------------------
 def normalize(q):
     if q[3] < 0.0:
         q = [-q[0], -q[1], -q[2], -q[3]]
-    n = math.sqrt(((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]) + q[3] * q[3])
+    n = _libm(math.sqrt(((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]) + q[3] * q[3]))
     return [q[0] / n, q[1] / n, q[2] / n, q[3] / n]
 
 
@@ -41,7 +58,7 @@ def quat_from_matrix(R):
     t = (R[0] + R[4]) + R[8]
     q = [0.0] * 4
     if t > 0.0:
-        t = math.sqrt(t + 1.0)
+        t = _libm(math.sqrt(t + 1.0))
         q[3] = 0.5 * t
         t = 0.5 / t
         q[0], q[1], q[2] = (R[7] - R[5]) * t, (R[2] - R[6]) * t, (R[3] - R[1]) * t
@@ -53,7 +70,7 @@ def quat_from_matrix(R):
             i = 2
         j = (i + 1) % 3
         k = (j + 1) % 3
-        t = math.sqrt(((R[4 * i] - R[4 * j]) - R[4 * k]) + 1.0)
+        t = _libm(math.sqrt(((R[4 * i] - R[4 * j]) - R[4 * k]) + 1.0))
         q[i] = 0.5 * t
         t = 0.5 / t
         q[3] = (R[3 * k + j] - R[3 * j + k]) * t
@@ -90,7 +107,7 @@ def oplus(u, p):
     """SE3Quat::exp(u) * p"""
     u = [float(v) for v in u]
     wx, wy, wz = u[0], u[1], u[2]
-    theta = math.sqrt((wx * wx + wy * wy) + wz * wz)
+    theta = _libm(math.sqrt((wx * wx + wy * wy) + wz * wz))
     O = [0.0, -wz, wy, wz, 0.0, -wx, -wy, wx, 0.0]
     O2 = [(O[3 * r] * O[c] + O[3 * r + 1] * O[3 + c]) + O[3 * r + 2] * O[6 + c] for r in range(3) for c in range(3)]
     I = [1.0 if k % 4 == 0 else 0.0 for k in range(9)]
@@ -98,7 +115,7 @@ def oplus(u, p):
         R = [(I[k] + O[k]) + O2[k] for k in range(9)]
         V = list(R)
     else:
-        s, c, t2 = math.sin(theta), math.cos(theta), theta * theta
+        s, c, t2 = _libm(math.sin(theta)), _libm(math.cos(theta)), theta * theta
         a, b, d = s / theta, (1.0 - c) / t2, (theta - s) / (t2 * theta)
         R = [(I[k] + a * O[k]) + b * O2[k] for k in range(9)]
         V = [(I[k] + b * O[k]) + d * O2[k] for k in range(9)]
@@ -159,7 +176,7 @@ def huber(chi2, stereo):
     delta = np.where(stereo, DELTA_STEREO, DELTA_MONO)
     dsqr = delta * delta
     with np.errstate(all="ignore"):
-        sq = np.sqrt(chi2)
+        sq = _libm(np.sqrt(chi2))
         inl = chi2 <= dsqr
         return np.where(inl, chi2, 2.0 * sq * delta - dsqr), np.where(inl, 1.0, delta / sq)
 
@@ -426,7 +443,18 @@ def fold(per_keypoint):
         return ((v[0, 0] + v[1, 0]) + v[2, 0]) + v[3, 0]
 
 
-def rule(Tcw, cam, xy_un, uright, assigned, points, inv_sigma2):
+def rule(Tcw, cam, xy_un, uright, assigned, points, inv_sigma2, libm_jitter=None):
+    """libm_jitter=seed: every sqrt, sin and cos result is moved by -1, 0 or +1 double ulp from a stream seeded with it.  That is how the device may
+    differ from this form: its fold is this one, only its libm is not the host's."""
+    global _JITTER
+    _JITTER = None if libm_jitter is None else np.random.RandomState(libm_jitter)
+    try:
+        return _rule(Tcw, cam, xy_un, uright, assigned, points, inv_sigma2)
+    finally:
+        _JITTER = None
+
+
+def _rule(Tcw, cam, xy_un, uright, assigned, points, inv_sigma2):
     cam, w = cam_of(cam), float(F(inv_sigma2))
     nt = len(assigned)
     tr = Trace()
@@ -506,6 +534,44 @@ def same_decisions(a, b):
     """names of what differs between two results in decisions: flags, the header, the accept / reject sequence, the reasons"""
     bad = [k for k in ("outlier", "header") if not np.array_equal(a[k], b[k])]
     return bad + [k for k in ("events", "reasons") if a[k] != b[k]]
+
+
+Tol = collections.namedtuple("Tol", "pose chi2 final")                   # float32 steps, float32 steps, relative
+
+
+def header_in_bounds(h):
+    """header[4:8] within what the loop's limits allow, whatever the trajectory: iterations <= 40, iterations <= trials <= 400, rejected and
+    ldlt_failures <= trials"""
+    return bool(0 <= h[4] <= 40 and h[4] <= h[5] <= 400 and 0 <= h[6] <= h[5] and 0 <= h[7] <= h[5])
+
+
+def outputs_agree(a, b, tol):
+    """what differs between two results in their OUTPUTS, as a list of strings; nothing about the trajectory (events, reasons, header[4:8] beyond
+    their static bounds): where a rho lies in rounding noise two correct evaluations take different numbers of trials to the same answer"""
+    bad = []
+    if not np.array_equal(a["outlier"], b["outlier"]):
+        k = np.nonzero(np.asarray(a["outlier"]) != np.asarray(b["outlier"]))[0]
+        bad.append(f"outlier differs at {len(k)} keypoints, first {k[:8].tolist()}")
+    ha, hb = np.asarray(a["header"]), np.asarray(b["header"])
+    if not np.array_equal(ha[:4], hb[:4]):
+        bad.append(f"header[0:4] {ha[:4].tolist()} != {hb[:4].tolist()}")
+    for tag, h in (("first", ha), ("second", hb)):
+        if not header_in_bounds(h):
+            bad.append(f"header[4:8] of the {tag} out of bounds: {h[4:].tolist()}")
+    ut, uc = ulps(a["Tcw_out"], b["Tcw_out"]), ulps(a["chi2"], b["chi2"])
+    if not ut.max() <= tol.pose:
+        bad.append(f"Tcw_out {int(ut.max())} float steps apart at entry {int(ut.argmax())} (allowed {tol.pose})")
+    if not uc.max() <= tol.chi2:
+        bad.append(f"chi2 {int(uc.max())} float steps apart at keypoint {int(uc.argmax())} (allowed {tol.chi2})")
+    rel = final_rel(a, b)
+    if not rel <= tol.final:
+        bad.append(f"final_chi2 {a['final_chi2']:.17g} and {b['final_chi2']:.17g}: {rel:.2e} relative (allowed {tol.final:.1e})")
+    return bad
+
+
+def final_rel(a, b):
+    fa, fb = float(a["final_chi2"]), float(b["final_chi2"])
+    return 0.0 if fa == fb else abs(fa - fb) / max(abs(fa), abs(fb))
 
 
 def ulps(a, b):

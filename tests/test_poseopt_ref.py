@@ -3,14 +3,19 @@ and on random small scenes, the host lines of the library (xfh_pose_edge, _oplus
 difference, hand-made cases whose answers are written out, every class of refusal, the condition of the rig's scenes, and the C lines -- the
 state machine and the fold of k_pose_optimize run by one host thread, under AddressSanitizer + UBSan -- against the rule bit by bit.  No GPU.
 
+Two kinds of scene, two comparisons.  SCENES and EDGE_SCENES hold the 1e-9 condition (test_rig_condition: every decision of the Levenberg loop stays
+that far from its decision point), so two correct evaluations walk the same trajectory and everything is compared, the header's counts included.
+Stereo edges keep such scenes conditioned: cam_project's float invz makes the cost a staircase whose steps (1e-5) dwarf rounding noise.  All-mono
+scenes of ten or more edges that converge never hold that condition (the unrobustified round converges quadratically into rounding noise, where rho is
+noise / 1e-3 and its sign is chance), but their OUTPUTS are determined all the same: MONO_SCENES hold a condition on the classifications and the pivots
+only (test_mono_scene_condition) and are compared through ref_poseopt.outputs_agree, which leaves the trajectory out, within R.MONO_TOL -- the spread
+of the float64 forms among themselves, a libm that is off by an ulp included (test_mono_spread_of_the_reference).
+
 What the rig could NOT be given: a scene in which the stale-error rule changes a flag or a float chi2.  A round's last trial is rejected only when ten
 trials in a row fail or rho == 0, and both happen only at convergence, where the rejected estimate differs from the restored one by less than the
-outputs resolve (test_rig_condition prints the count; the rule itself is exercised: rounds of the rig end on ten rejected trials).  And all-mono
-scenes of ten or more edges that converge do not hold the 1e-9 condition (the unrobustified round converges quadratically into rounding noise, where
-rho is noise / 1e-3): of 300 seeds none did, so the all-mono scenes are the 9-edge one, a far start that uses all 40 iterations and one that loses
-every edge; the mono edge at scale is in the mixed scenes.  Stereo edges keep scenes conditioned because cam_project's float invz makes the cost a
-staircase whose steps (1e-5) dwarf rounding noise."""
+outputs resolve (test_rig_condition prints the count; the rule itself is exercised: rounds of the rig end on ten rejected trials)."""
 import ctypes as C
+import functools
 import os
 import struct
 import subprocess
@@ -37,8 +42,14 @@ def _built_library():
 
 @pytest.fixture(scope="module")
 def models():
-    """both forms of every rig scene, computed once"""
-    return {n: (R.model(R.scene(n), RP.literal), R.model(R.scene(n), RP.rule)) for n in R.SCENES}
+    """both forms of every rig scene that is compared exactly, computed once"""
+    return {n: (R.model(R.scene(n), RP.literal), R.model(R.scene(n), RP.rule)) for n in list(R.SCENES) + list(R.EDGE_SCENES)}
+
+
+@pytest.fixture(scope="module")
+def mono_models():
+    """both forms of the all-mono scenes, computed once"""
+    return {n: (R.model(R.scene(n), RP.literal), R.model(R.scene(n), RP.rule)) for n in R.MONO_SCENES}
 
 
 def _ptr(a):
@@ -251,6 +262,137 @@ def test_rig_condition(models):
     assert int((s["assigned"] >= s["nq"]).sum()) == 6 and lit["n65_mixed"]["header"][0] == 65
     assert lit["identical"]["header"][7] == 0 and lit["identical"]["margins"]["pivot"] < 1e-3         # rank-deficient, yet no pivot fails: lambda > 0
     assert all(m["header"][7] == 0 for m in lit.values())
+    # the scenes at the sizes where the kernel instance changes: conditioned in the rule's form too, the pinned keypoints carry edges, and the
+    # last keypoint, the last partial stride of 256 and both sides of 1024 / 4096 are among them
+    assert sorted(kw["nt"] for kw in R.EDGE_SCENES.values()) == [1024, 1025, 4096, 4097, capi.GRID_MAX_N]
+    for n, kw in R.EDGE_SCENES.items():
+        s, nt = R.scene(n), kw["nt"]
+        assert min(models[n][1]["margins"].values()) > MARGIN, (n, models[n][1]["margins"])
+        assert kw["kind"] in ("stereo", "mixed") and 200 <= kw["n_edges"] <= 400 and int(lit[n]["header"][0]) == kw["n_edges"]
+        want = {0, 255, 256, nt - 257, nt - 256, nt - 1} | {k for k in (1023, 1024, 4095, 4096) if k < nt}
+        assert kw["pin"] == want and all(0 <= s["assigned"][k] < s["nq"] for k in want), n
+        assert (s["uright"] >= 0).any()
+
+
+def test_mono_scene_condition(mono_models):
+    """the all-mono scenes the GPU tests compare through outputs_agree: ten or more edges, no stereo edge, and in BOTH forms every classification
+    stays farther than 1e-4 (relative) from its cut and every pivot farther than 1e-9 from 0, no solve fails; and each is a scene the 1e-9 condition
+    of test_rig_condition excludes (a rho within 1e-9 of 0 in at least one form), which is why it is here.  1e-4 is a condition, not a measurement:
+    rounding noise on a chi2 is near 1e-13 relative, so no evaluation in doubles, whatever its order or libm, moves a classification."""
+    kinds = set()
+    for n, (a, b) in mono_models.items():
+        s, kw = R.scene(n), R.MONO_SCENES[n]
+        print(n, a["header"].tolist(), b["header"].tolist(), a["reasons"], {k: f"{v:.1e}" for k, v in a["margins"].items()}, {k: f"{v:.1e}" for k, v in b["margins"].items()})
+        assert a["header"][0] == kw["n_edges"] >= 10 and (s["uright"] is None or not (s["uright"] >= 0).any())
+        for m in (a, b):
+            assert m["margins"]["classify"] > 1e-4 and m["margins"]["pivot"] > MARGIN and m["header"][7] == 0 and m["header"][3] == 4, (n, m["margins"])
+        assert min(a["margins"]["rho"], b["margins"]["rho"]) <= MARGIN, n
+        assert all(0 <= s["assigned"][k] < s["nq"] for k in kw.get("pin", ())), n
+        kinds.add((s["uright"] is None, kw.get("outliers", 0.0) > 0, 0 if kw["nt"] <= 1024 else 1 if kw["nt"] <= 4096 else 2))
+    assert {(True, i) for i in range(3)} <= {(k[0], k[2]) for k in kinds}                              # every instance meets a null uright
+    assert {k[0] for k in kinds} == {True, False} and {k[1] for k in kinds} == {True, False}
+    assert any(int(b["header"][1]) > 0 for _, b in mono_models.values())
+
+
+def _spread(results):
+    """largest disagreement among results of one scene: (pose steps, chi2 steps, final_chi2 relative, the chi2 that is that many steps off); flags
+    and header[0:4] must be equal"""
+    pose = chi = 0
+    fin = at = 0.0
+    for i, a in enumerate(results):
+        assert np.array_equal(a["outlier"], results[0]["outlier"]) and np.array_equal(a["header"][:4], results[0]["header"][:4]), (i, a["header"], results[0]["header"])
+        assert RP.header_in_bounds(a["header"])
+        for b in results[:i]:
+            pose = max(pose, int(RP.ulps(a["Tcw_out"], b["Tcw_out"]).max()))
+            uc = RP.ulps(a["chi2"], b["chi2"])
+            if uc.max() > chi:
+                chi, at = int(uc.max()), float(a["chi2"][uc.argmax()])
+            fin = max(fin, RP.final_rel(a, b))
+    return pose, chi, fin, at
+
+
+JITTER_SEEDS = (11, 12, 13)
+
+
+def test_mono_spread_of_the_reference(mono_models):
+    """where R.MONO_TOL comes from: how far the float64 forms lie apart on all-mono scenes -- the literal form, the rule, and the rule with three
+    libm jitters (every sqrt / sin / cos moved by up to one double ulp) -- over MONO_SCENES and 200 all-mono scenes of 10 .. 1000 edges drawn from
+    one seeded stream that hold the condition of test_mono_scene_condition (the others are counted; at most half may be dropped).  Flags and
+    header[0:4] are equal throughout.  The tolerance is twice the largest value seen, at least one float32 step (1e-13 for final_chi2): twice for the
+    finite sample; what the device may vary (its libm, the rule's fold) is part of what these forms vary (libm and the whole summation order).
+    The constants are held to that here, so they cannot go stale; nothing from the device enters them."""
+    forms = [functools.partial(RP.rule, libm_jitter=j) for j in JITTER_SEEDS]
+    worst = [0, 0, 0.0]
+    for n, (a, b) in mono_models.items():
+        sp = _spread([a, b] + [R.model(R.scene(n), f) for f in forms])
+        print(f"{n}: pose {sp[0]}, chi2 {sp[1]} float steps (at a chi2 of {sp[3]:.3g}), final_chi2 {sp[2]:.1e}; trials literal {a['header'][5]}, rule {b['header'][5]}")
+        worst = [max(w, v) for w, v in zip(worst, sp)]
+    kept = dropped = excluded = 0
+    seed = 5000
+    stream, at = [0, 0, 0.0], (0.0, 0)
+    while kept < 200:
+        rng = np.random.RandomState(seed)
+        n = int(round(10 ** rng.uniform(1.0, 3.0)))
+        s = R.make(seed, n, n + int(rng.randint(3, 3 * n + 10)), kind=["mono", "mono_ur"][seed % 2], outliers=float(rng.choice([0.0, 0.2])),
+                   noise=float(rng.choice([0.5, 1.0])), beyond=int(rng.randint(0, 3)))
+        seed += 1
+        a, b = R.model(s, RP.literal), R.model(s, RP.rule)
+        if not all(m["margins"]["classify"] > 1e-4 and m["margins"]["pivot"] > MARGIN and m["header"][7] == 0 for m in (a, b)):
+            dropped += 1
+            assert dropped <= 200, "more than half of the stream does not hold the condition"
+            continue
+        excluded += min(a["margins"]["rho"], b["margins"]["rho"]) <= MARGIN
+        try:
+            sp = _spread([a, b] + [R.model(s, f) for f in forms])
+        except AssertionError as e:
+            raise AssertionError(f"stream scene of seed {seed - 1} ({n} edges): {e}")
+        at = (sp[3], n) if sp[1] > stream[1] else at
+        stream = [max(w, v) for w, v in zip(stream, sp)]
+        kept += 1
+    print(f"stream: {kept} scenes compared, {dropped} dropped, {excluded} of the compared ones excluded by the 1e-9 condition; "
+          f"pose {stream[0]}, chi2 {stream[1]} float steps (at a chi2 of {at[0]:.3g}, a scene of {at[1]} edges), final_chi2 {stream[2]:.1e}")
+    worst = [max(w, v) for w, v in zip(worst, stream)]
+    need = RP.Tol(pose=max(1, 2 * worst[0]), chi2=max(1, 2 * worst[1]), final=max(1e-13, 2.0 * worst[2]))
+    print(f"largest seen: pose {worst[0]}, chi2 {worst[1]} float steps, final_chi2 {worst[2]:.2e} -> {need}; MONO_TOL {R.MONO_TOL}")
+    assert need.pose <= R.MONO_TOL.pose and need.chi2 <= R.MONO_TOL.chi2 and need.final <= R.MONO_TOL.final
+    assert excluded >= 100                                                # the stream is of the kind the tolerance is for
+
+
+def test_outputs_agree_has_teeth(mono_models):
+    """one pose entry one step too far, one flag, one chi2 of the input pose, n_bad, the number of rounds, a header count out of bounds: each is
+    reported, and alone; an unchanged result and the two forms of every mono scene are not"""
+    name, tol = "m100_neg_out", R.MONO_TOL
+    s, m = R.scene(name), mono_models[name][1]
+    copy = lambda: dict(m, Tcw_out=m["Tcw_out"].copy(), outlier=m["outlier"].copy(), chi2=m["chi2"].copy(), header=m["header"].copy())
+    assert RP.outputs_agree(copy(), m, tol) == []
+    assert all(RP.outputs_agree(a, b, tol) == [] for a, b in mono_models.values())
+    idx, X, obs, st = RP.edges_of(s["xy_un"], s["uright"], s["assigned"], s["points"])
+    at_input = RP.edge_error(RP.from_tcw(s["Tcw"]), RP.cam_of(R.CAM), X, obs, st, float(F(R.INV_SIGMA2)))[2].astype(F)
+    e = int(np.argmin(RP.ulps(at_input, m["chi2"][idx])))                # the edge whose chi2 the optimisation changed least: still far more than tol
+    assert RP.ulps(at_input[e], m["chi2"][idx[e]]) > 100 * tol.chi2
+    k = int(idx[0])
+
+    def pose(r):
+        for _ in range(tol.pose + 1):
+            r["Tcw_out"][7] = np.nextafter(r["Tcw_out"][7], F(np.inf))
+
+    def flag(r): r["outlier"][k] ^= 1
+    def chi(r): r["chi2"][idx[e]] = at_input[e]
+    def n_bad(r): r["header"][1] += 1
+    def rounds(r): r["header"][3] = 3
+    def trials(r): r["header"][5] = 401
+    def final(r): r["final_chi2"] = m["final_chi2"] * (1.0 + 2.0 * tol.final)
+
+    for mutate, word in ((pose, "Tcw_out"), (flag, "outlier"), (chi, "chi2 "), (n_bad, "header[0:4]"), (rounds, "header[0:4]"), (trials, "header[4:8]"), (final, "final_chi2")):
+        r = copy()
+        mutate(r)
+        bad = RP.outputs_agree(r, m, tol)
+        assert len(bad) == 1 and bad[0].startswith(word), (mutate.__name__, bad)
+        assert RP.outputs_agree(m, r, tol) != []
+    r = copy()                                                            # at the tolerance itself: not reported
+    for _ in range(tol.pose):
+        r["Tcw_out"][7] = np.nextafter(r["Tcw_out"][7], F(np.inf))
+    assert RP.outputs_agree(r, m, tol) == []
 
 
 def _asan_exe(tmp_path_factory):
@@ -275,10 +417,12 @@ def test_header_helper_under_sanitizers(asan_exe):
     assert r.returncode == 0 and "asan_poseopt_test ok" in r.stdout, (r.stdout[-1000:], r.stderr[-3000:])
 
 
-@pytest.mark.parametrize("name", ["n2", "n9_mixed", "n63_mono_lost", "n64_stereo", "n65_mixed", "n257", "identical", "big"])
-def test_the_kernels_loop_on_the_host_equals_the_rule(asan_exe, tmp_path, models, name):
+@pytest.mark.parametrize("name", ["n2", "n9_mixed", "n63_mono_lost", "n64_stereo", "n65_mixed", "n257", "identical", "big"] + list(R.EDGE_SCENES) + list(R.MONO_SCENES))
+def test_the_kernels_loop_on_the_host_equals_the_rule(asan_exe, tmp_path, models, mono_models, name):
     """the state machine, the per-edge lines and the fold of k_pose_optimize, run by one thread of the sanitizer program: every output byte equals
-    the rule's (the host's libm is the restatement's, so here even the doubles agree)"""
+    the rule's (the host's libm is the restatement's, so here even the doubles agree) -- on the all-mono scenes too, whose trajectory is decided in
+    rounding noise: same fold, same libm, same noise"""
+    models = dict(models, **mono_models)
     s = R.scene(name)
     with open(tmp_path / "in.bin", "wb") as f:
         f.write(struct.pack("<3i", s["nt"], s["nq"], int(s["uright"] is not None)) + s["Tcw"].astype(F).tobytes() + np.array(R.CAM, F).tobytes() + struct.pack("<f", R.INV_SIGMA2))
