@@ -1401,6 +1401,110 @@ int xfh_triangulate(xfh_ctx* ctx, int B, int n1, int n2, int flags, const xfh_ca
                     const float* Tcw2, const float* Ow2, const int* match12, uint8_t* status, uint8_t* kind, float* xyz, int* header, int* winner,
                     int* new_idx1, int* new_b, int* new_idx2, float* new_xyz, float* new_normal, float* new_dist, int* n_new);
 
+/* ---- TwoViewReconstruction::Reconstruct (src/TwoViewReconstruction.cc), the second half of Tracking::MonocularInitialization -----------------
+ * (src/Tracking.cc:2531, mpCamera->ReconstructWithTwoViews for the Pinhole camera), for B problems per call, on the arrays that
+ * xfh_init_search_device leaves in device memory: d_xy1 [B][n1][2] and d_xy2 [B][n2][2] are the undistorted keypoints (mvKeysUn) of the
+ * reference and the current frame, d_matches12 [B][n1] is vnMatches12 (an entry outside 0 .. n2 - 1 is "no match").  The rule, written once in
+ * xfeatslam_amd/csrc/twoview_math.h and compiled for the kernels and for the host entry points below; fp32 in the order written unless a double
+ * is named:
+ *   1. The compact match list (:50-66) in idx1 order; N matches.  N < 8 -> status TOO_FEW: the reference's set generation is undefined there; the
+ *      header is written (N, status, -1 for the winners and the chosen hypothesis, 0 elsewhere) and NOTHING else.
+ *   2. The minimal sets (:78-98) from the CALLER's raw draws: d_draws holds iters x 8 values of the caller's rand() (after its SeedRandOnce(0),
+ *      in the order the reference consumes them) and rand_max its RAND_MAX; problem b reads d_draws + b * draws_problem_stride (ints; 0 = all
+ *      problems share one list).  Draw j of an iteration indexes the shrinking vAvailableIndices of size d = N - j at int(((double)draw /
+ *      ((double)rand_max + 1.0)) * d), followed by the swap-remove; only the at most eight overwritten positions are tracked.  This reproduces
+ *      mvSets for any N without a host round trip for N, and the library holds no generator.  A draw outside 0 .. rand_max is clamped into
+ *      0 .. d - 1.
+ *   3. Normalize (:737-784) over ALL keypoints of a frame, as in the reference: mean = sum / n, s = (float)(1.0 / (double)(sum |x - mean| / n)),
+ *      normalised point ((x - meanX) * sX, (y - meanY) * sY).  A stated deviation: every float sum of the rule (these four per frame, and the score
+ *      sums of step 5) is not sequential but has ONE fixed parallel order, whatever the grid or B: 256 lanes, lane l adds the terms l, l + 256, ...
+ *      in order to 0.0f; the 256 partial sums fold s[l] += s[l + h] for h = 128, 64, .. 1.
+ *   4. ComputeH21 / ComputeF21 (:232-308) per iteration.  The rows of the 16 x 9 / 8 x 9 A in fp32 as the reference writes them.  Every
+ *      Eigen::JacobiSVD<float> of the rule (16 x 9, 8 x 9, 3 x 3) is the one-sided Jacobi of xfh_triangulate_device's step 4 IN FP64 (same
+ *      rotation -- the two share its code --, cyclic pairs p < q in lexicographic order, column dot products over the rows in order starting from
+ *      row 0's product, stop after the first sweep that rotates nothing, at most 30 sweeps), rounded to float once.  A stated deviation, for the
+ *      reason given there.  Null vector = V's column whose column of U has the least squared norm, the first on a tie.  For a full 3 x 3 SVD the
+ *      columns are ordered by squared norm descending (stable), w_i = sqrt |a_i|^2, u_i = a_i / w_i with a_i the columns of A V.  The rank-2
+ *      projection of F is a_i0 v_i0^T + a_i1 v_i1^T in double over the two largest columns.  For the rank-2 E of DecomposeE the third column of U
+ *      cannot come from a_2 / w_2 (0 / 0 up to rounding): it is the cross product u_0 x u_1 in double.
+ *      H21i = T2inv Hn T1 and F21i = T2^T Fn T1 with the triangular T written out: M = X T1: M[r][0] = X[r][0] sX, M[r][1] = X[r][1] sY, M[r][2] =
+ *      (X[r][0] tx + X[r][1] ty) + X[r][2], tx = -meanX sX;  T2inv = [1/sX 0 meanX; 0 1/sY meanY; 0 0 1] analytically (the reference inverts T2
+ *      numerically);  H12i = the cofactor inverse of H21i times 1.0f / det, det = (a(ei - fh) - b(di - fg)) + c(dh - eg).
+ *   5. CheckHomography / CheckFundamental (:310-473) per (iteration, match), as written with each three-term dot product (x*a + y*b) + c,
+ *      w = (float)(1.0 / (double)den), invSigmaSquare = (float)(1.0 / (double)(sigma * sigma)), th 5.991f (H), 3.841f with score threshold 5.991f
+ *      (F).  A match's share = (chi1 > th ? 0 : th - chi1) + (chi2 > th ? 0 : th - chi2), summed over the matches in the order of step 3 (the
+ *      reference adds the two halves to the running sum one after the other).  The argmax with the strict >: the first iteration with the
+ *      highest score wins; a score that is not > 0 -- zero, or the NaN of a rank-deficient fit -- never wins.  Only the scores are stored; the
+ *      inlier flags of the two winners are recomputed.
+ *   6. SH + SF == 0 -> BOTH_ZERO.  RH = SH / (SH + SF); (double)RH > 0.50 -> ReconstructH, else ReconstructF.
+ *   7. ReconstructF (:475-569): E = K^T (F K) with K's zeros not multiplied; DecomposeE from the SVD of step 4: t = u_2 / |u_2|, R1 = U W V^T =
+ *      (u_1 v_0^T - u_0 v_1^T) + u_2 v_2^T, R2 = (u_0 v_1^T - u_1 v_0^T) + u_2 v_2^T, each negated when its float determinant is < 0; hypotheses
+ *      0 .. 3 = (R1, t) (R2, t) (R1, -t) (R2, -t).  ReconstructH (:571-734): A = K^-1 (H K) with K^-1 = [1/fx 0 -cx/fx; 0 1/fy -cy/fy; 0 0 1]
+ *      written out, the SVD, s = det U * det V, (double)(d1 / d2) < 1.00001 || (double)(d2 / d3) < 1.00001 -> H_DEGENERATE (an H that is a
+ *      similarity to five digits: a pair without motion or a pure zoom, which F fits as well as H, so SH and SF tie and RH is 0.5 up to the
+ *      rounding of the two sums: whether such a pair ends here or on the F path is decided by rounding, in the reference as here), and the eight
+ *      Faugeras hypotheses in the reference's order, R = s * ((X V^T)) with X = U Rp, t = U tp normalised.  The sign and pairing ambiguities of an
+ *      SVD permute the hypotheses against Eigen's: the SET is the contract, the index reported is that of this rule.
+ *   8. CheckRT (:786-901) per (hypothesis, inlier of the chosen model): P1 = K [I|0], P2 = K [R|t], the 4 x 4 A and the fp64 null vector of
+ *      xfh_triangulate_device's step 4, p = h[0..2] / h[3] in float; a non-finite p is skipped; O2 = -R^T t; cosParallax as written; the two
+ *      depth tests with (double)cos < 0.99998; invZ = (float)(1.0 / (double)z); squared errors against th2 = (float)(4.0 * (double)(sigma *
+ *      sigma)).  A pair that passes is counted (nGood, its cosine, its point) and is good (vbGood) when (double)cos < 0.99998.  The cosine at
+ *      sorted index min(50, nGood - 1) is selected by value over the floats' order keys; 1.0f with nGood = 0.  Parallax, a stated deviation: the
+ *      reference converts with acos(..) * 180 / CV_PI and compares degrees; the device compares the cosine with the double min_parallax_cos =
+ *      cos(minParallax * pi / 180) the caller passes (F: (double)cos < min_parallax_cos; H, whose test is >=: (double)cos <= min_parallax_cos)
+ *      and reports the cosine.
+ *   9. The decision.  F: maxGood, nMinGood = max((int)(0.9 * (double)N_inliers), min_triangulated), nsimilar over (double)nGood > 0.7 *
+ *      (double)maxGood; maxGood < nMinGood || nsimilar > 1 -> F_NO_WINNER; the first hypothesis with nGood == maxGood: enough parallax ->
+ *      OK_F, else LOW_PARALLAX.  H: best / second best with the strict >; (double)second < 0.75 * (double)best && best > min_triangulated &&
+ *      (double)best > 0.9 * (double)N_inliers, else H_GATES; then the parallax test, else LOW_PARALLAX; -> OK_H.
+ * Outputs per problem.  d_header [B][24] ints: N, status (XFH_TWO_VIEW_*), model (0 none, 1 H, 2 F), winning iteration of H, of F (-1: none),
+ * nGood[8], the chosen hypothesis (-1), inliers of the winning H, of the winning F, triangulated count, number of hypotheses, n_matches_out
+ * (triangulated count on success, N otherwise), five zeros.  d_floats [B][48]: SH, SF, RH, H21[9], F21[9], T21[12] row-major [R|t] (zeros
+ * unless the call succeeded), the cosine at the parallax index of the eight hypotheses (1.0f where none), zeros.  Per keypoint of frame 1,
+ * indexed by idx1 (a keypoint has at most one match): d_inlier_h, d_inlier_f, d_triangulated [B][n1] bytes, d_p3d [B][n1][3] (the winning
+ * hypothesis' point for every counted pair, zeros elsewhere), d_matches_out [B][n1] = matches12 with the entries that were matched but not
+ * triangulated set to -1 on success (Tracking.cc:2533-2540) and unchanged otherwise.  On the H path the reference returns true without
+ * assigning vP3D (:725-731); this call writes the winning hypothesis' points on both paths.
+ *
+ *   xfh_two_view_workspace_bytes  bytes of d_workspace for such a call; 0 for sizes the call refuses.
+ *   xfh_two_view_device   everything in device memory; asynchronous on the ctx stream, no allocation, no host synchronisation, no global
+ *                         atomics; SIX launches whatever the data.  XFH_ERR_INVALID_ARG before anything is queued: B outside 1 .. 65535, n1 or
+ *                         n2 outside 1 .. XFH_GRID_MAX_N, iters outside 1 .. 4096, sigma not finite and > 0, rand_max < 1, min_parallax_cos not
+ *                         finite, min_triangulated < 0, a stride that is neither 0 nor >= iters * 8 with B > 1, a NULL pointer, a pointer that is
+ *                         not 4-byte (d_workspace: 16-byte) aligned.  Coordinates and camera values may hold anything, NaN and Inf included, and
+ *                         matches and draws any int: no load or store leaves the buffers, and every loop is bounded.
+ *   xfh_two_view          host-pointer form for one problem through the ctx staging arena.
+ *   xfh_two_view_host     the whole rule on ONE host thread over host pointers (workspace included): no ctx, no GPU; what the sanitizer
+ *                         program and the CPU tests run.  Stateless and thread-safe, as are the four below, each one piece of the rule:
+ *   xfh_two_view_set      the set of one iteration from its eight draws and N >= 8
+ *   xfh_two_view_fit      Hn or Fn[9] (step 4, before the composition) of eight NORMALISED point pairs [8][2]
+ *   xfh_two_view_score    chi2[2], the inlier flag and the share of the score of one match under M = H21 followed by H12 (18 floats) or F21 (9)
+ *   xfh_two_view_check_rt CheckRT's verdict for one pair under T21 [R|t]: 0 not counted, 1 counted, 2 counted and good; its cosine and point
+ * Out of scope: KannalaBrandt8::ReconstructWithTwoViews. */
+enum { XFH_TWO_VIEW_TOO_FEW = 0, XFH_TWO_VIEW_BOTH_ZERO = 1, XFH_TWO_VIEW_H_DEGENERATE = 2, XFH_TWO_VIEW_F_NO_WINNER = 3, XFH_TWO_VIEW_H_GATES = 4,
+       XFH_TWO_VIEW_LOW_PARALLAX = 5, XFH_TWO_VIEW_OK_H = 6, XFH_TWO_VIEW_OK_F = 7 };
+#define XFH_TWO_VIEW_MODEL_H 1
+#define XFH_TWO_VIEW_MODEL_F 2
+#define XFH_TWO_VIEW_HEADER_INTS 24
+#define XFH_TWO_VIEW_FLOATS 48
+#define XFH_TWO_VIEW_MAX_ITERS 4096
+size_t xfh_two_view_workspace_bytes(int n1, int n2, int iters, int B);
+int xfh_two_view_device(xfh_ctx* ctx, int B, int n1, int n2, const float* d_xy1, const float* d_xy2, const int* d_matches12, const xfh_camera* cam,
+                        float sigma, int iters, const int* d_draws, size_t draws_problem_stride, int rand_max, double min_parallax_cos,
+                        int min_triangulated, void* d_workspace, int* d_header, float* d_floats, uint8_t* d_inlier_h, uint8_t* d_inlier_f,
+                        uint8_t* d_triangulated, float* d_p3d, int* d_matches_out);
+int xfh_two_view(xfh_ctx* ctx, int n1, int n2, const float* xy1, const float* xy2, const int* matches12, const xfh_camera* cam, float sigma, int iters,
+                 const int* draws, int rand_max, double min_parallax_cos, int min_triangulated, int* header, float* floats, uint8_t* inlier_h,
+                 uint8_t* inlier_f, uint8_t* triangulated, float* p3d, int* matches_out);
+int xfh_two_view_host(int B, int n1, int n2, const float* xy1, const float* xy2, const int* matches12, const xfh_camera* cam, float sigma, int iters,
+                      const int* draws, size_t draws_problem_stride, int rand_max, double min_parallax_cos, int min_triangulated, void* workspace,
+                      int* header, float* floats, uint8_t* inlier_h, uint8_t* inlier_f, uint8_t* triangulated, float* p3d, int* matches_out);
+int xfh_two_view_set(const int* draws8, int rand_max, int N, int* set8);
+int xfh_two_view_fit(int model, const float* xy1n, const float* xy2n, float* M);
+int xfh_two_view_score(int model, const float* M, float sigma, const float* xy1, const float* xy2, float* chi2, int* inlier, float* term);
+int xfh_two_view_check_rt(const xfh_camera* cam, const float* T21, float sigma, const float* xy1, const float* xy2, int* verdict, float* cos_parallax,
+                          float* p3d);
+
 /* MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:329-403), batched over map points: group g observes the
  * descriptor rows indices[offsets[g] .. offsets[g+1]) of `table` (n_rows x 64).  Pairwise DescriptorDistance inside
  * the group (diagonal 0), per row the median sorted[(N-1)/2], and the FIRST row with the least median wins:

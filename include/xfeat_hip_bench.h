@@ -27,7 +27,9 @@ enum {
     XFH_K_INIT_CANDIDATES = 27, XFH_K_INIT_RESOLVE = 28, XFH_K_INIT_FINAL = 29,
     XFH_K_VOCAB_DESCEND = 31, XFH_K_VOCAB_FINISH = 32, XFH_K_BOWDB_SCORE = 33, XFH_K_BOWDB_SELECT = 34,
     XFH_K_POSE_OPTIMIZE = 35,
-    XFH_K_TRIANGULATE_PAIRS = 36, XFH_K_TRIANGULATE_WINNER = 37, XFH_K_TRIANGULATE_FINISH = 38, XFH_K_COUNT = 39
+    XFH_K_TRIANGULATE_PAIRS = 36, XFH_K_TRIANGULATE_WINNER = 37, XFH_K_TRIANGULATE_FINISH = 38,
+    XFH_K_TWOVIEW_PREPARE = 39, XFH_K_TWOVIEW_FIT = 40, XFH_K_TWOVIEW_SCORE = 41, XFH_K_TWOVIEW_SELECT = 42, XFH_K_TWOVIEW_CHECK_RT = 43,
+    XFH_K_TWOVIEW_FINAL = 44, XFH_K_COUNT = 45
 };
 /* layer_mask selects conv layers for XFH_K_CONV_*: 0 = every layer, else bit i = BasicLayer i
  * (0..22 in XFeatModel order) and bit 23 = block_fusion.2 */

@@ -29,7 +29,7 @@ ERR_EMPTY_IMAGE = 2
 ERR_NO_DEVICE = 7
 ERR_COMM = 11
 
-K = dict(NONE=0, MNN_GEMM=1, CONV_MFMA=2, CONV_DIRECT=3, NMS=4, SELECT=5, DESC=6, HEADS=7, DIST_I32=8, PREPROC=9, BEST2=10, DISTINCTIVE=11, MNN_GEMM_SEG=12, GRID_BUILD=13, SEARCH_WINDOW=14, FRAME_FINISH=15, PROJ_CANDIDATES=16, PROJ_RESOLVE=17, PROJ_COUNT=18, FUSE_SEARCH=19, TRIANGULATION_SEARCH=20, BOW_CANDIDATES=21, BOW_RESOLVE=22, MAPPROJ_CANDIDATES=23, SIM3_SEARCH=24, SIM3_AGREE=25, INIT_CANDIDATES=27, INIT_RESOLVE=28, INIT_FINAL=29, VOCAB_DESCEND=31, VOCAB_FINISH=32, BOWDB_SCORE=33, BOWDB_SELECT=34, POSE_OPTIMIZE=35, TRIANGULATE_PAIRS=36, TRIANGULATE_WINNER=37, TRIANGULATE_FINISH=38)
+K = dict(NONE=0, MNN_GEMM=1, CONV_MFMA=2, CONV_DIRECT=3, NMS=4, SELECT=5, DESC=6, HEADS=7, DIST_I32=8, PREPROC=9, BEST2=10, DISTINCTIVE=11, MNN_GEMM_SEG=12, GRID_BUILD=13, SEARCH_WINDOW=14, FRAME_FINISH=15, PROJ_CANDIDATES=16, PROJ_RESOLVE=17, PROJ_COUNT=18, FUSE_SEARCH=19, TRIANGULATION_SEARCH=20, BOW_CANDIDATES=21, BOW_RESOLVE=22, MAPPROJ_CANDIDATES=23, SIM3_SEARCH=24, SIM3_AGREE=25, INIT_CANDIDATES=27, INIT_RESOLVE=28, INIT_FINAL=29, VOCAB_DESCEND=31, VOCAB_FINISH=32, BOWDB_SCORE=33, BOWDB_SELECT=34, POSE_OPTIMIZE=35, TRIANGULATE_PAIRS=36, TRIANGULATE_WINNER=37, TRIANGULATE_FINISH=38, TWOVIEW_PREPARE=39, TWOVIEW_FIT=40, TWOVIEW_SCORE=41, TWOVIEW_SELECT=42, TWOVIEW_CHECK_RT=43, TWOVIEW_FINAL=44)
 T = dict(X=0, XSTAT=1, SKIP_POOL=2, FEATS=6, M1N=7, H1=8, K1H=9, RAW0=16, STAT0=48, SEL=80)
 
 
@@ -99,6 +99,10 @@ INIT_NONE = 0x7fffffff
 TRIANG_INERTIAL, TRIANG_CLAIM = 1, 2
 (TRIANG_NO_MATCH, TRIANG_LOW_PARALLAX, TRIANG_STEREO_NO_DEPTH, TRIANG_DEGENERATE, TRIANG_BEHIND1, TRIANG_BEHIND2, TRIANG_REPROJ1, TRIANG_REPROJ2,
  TRIANG_ZERO_DIST, TRIANG_FAR, TRIANG_SCALE, TRIANG_ACCEPTED, TRIANG_SUPERSEDED) = range(13)
+(TWO_VIEW_TOO_FEW, TWO_VIEW_BOTH_ZERO, TWO_VIEW_H_DEGENERATE, TWO_VIEW_F_NO_WINNER, TWO_VIEW_H_GATES, TWO_VIEW_LOW_PARALLAX, TWO_VIEW_OK_H,
+ TWO_VIEW_OK_F) = range(8)
+TWO_VIEW_MODEL_H, TWO_VIEW_MODEL_F = 1, 2
+TWO_VIEW_HEADER_INTS, TWO_VIEW_FLOATS, TWO_VIEW_MAX_ITERS = 24, 48, 4096
 
 FLAG_RESCALE_KEYPOINTS = 1
 FLAG_SERIAL_BRANCH = 2
@@ -214,6 +218,14 @@ SYMBOLS = [
     ("xfh_triangulate_pair", _i, [C.POINTER(Camera), _i, _f, _f, _f, _f, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("xfh_triangulate_device", _i, [_vp, _i, _i, _i, _i, _i, C.POINTER(Camera), _f, _f, _f, _f] + [_vp] * 25),
     ("xfh_triangulate", _i, [_vp, _i, _i, _i, _i, C.POINTER(Camera), _f, _f, _f, _f] + [_vp] * 25),
+    ("xfh_two_view_workspace_bytes", _sz, [_i, _i, _i, _i]),
+    ("xfh_two_view_device", _i, [_vp, _i, _i, _i, _vp, _vp, _vp, C.POINTER(Camera), _f, _i, _vp, _sz, _i, C.c_double, _i] + [_vp] * 8),
+    ("xfh_two_view", _i, [_vp, _i, _i, _vp, _vp, _vp, C.POINTER(Camera), _f, _i, _vp, _i, C.c_double, _i] + [_vp] * 7),
+    ("xfh_two_view_host", _i, [_i, _i, _i, _vp, _vp, _vp, C.POINTER(Camera), _f, _i, _vp, _sz, _i, C.c_double, _i] + [_vp] * 8),
+    ("xfh_two_view_set", _i, [_vp, _i, _i, _vp]),
+    ("xfh_two_view_fit", _i, [_i, _vp, _vp, _vp]),
+    ("xfh_two_view_score", _i, [_i, _vp, _f, _vp, _vp, _vp, _vp, _vp]),
+    ("xfh_two_view_check_rt", _i, [C.POINTER(Camera), _vp, _f, _vp, _vp, _vp, _vp, _vp]),
     ("xfh_distinctive_csr", _i, [_vp, _vp, _i, _vp, _vp, _i, _vp, _vp]),
     ("xfh_distinctive_csr_device", _i, [_vp, _vp, _i, _vp, _vp, _i, _i, _vp, _vp]),
     ("xfh_comm_unique_id", _i, [_vp]),

@@ -81,7 +81,8 @@ const char* xfh_kernel_name(int id) {
                                          "k_grid_build", "k_search_window", "k_frame_finish", "k_proj_candidates", "k_proj_resolve", "k_proj_count", "k_fuse_search",
                                          "k_triangulation_search", "k_bow_candidates", "k_bow_resolve", "k_mapproj_candidates", "k_sim3_search", "k_sim3_agree", "?",
                                          "k_init_candidates", "k_init_resolve", "k_init_final", "?", "k_vocab_descend", "k_vocab_finish", "k_bowdb_score", "k_bowdb_select",
-                                         "k_pose_optimize", "k_triangulate_pairs", "k_triangulate_winner", "k_triangulate_finish"};
+                                         "k_pose_optimize", "k_triangulate_pairs", "k_triangulate_winner", "k_triangulate_finish",
+                                         "k_twoview_prepare", "k_twoview_fit", "k_twoview_score", "k_twoview_select", "k_twoview_check_rt", "k_twoview_final"};
     return (id >= 0 && id < XFH_K_COUNT) ? n[id] : "?";
 }
 

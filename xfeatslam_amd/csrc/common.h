@@ -226,6 +226,8 @@ struct PoseArgs;
 hipError_t launch_pose_optimize(xfh_ctx* c, const PoseArgs& a, int B);              // poseopt.hip.h
 struct TriangArgs;
 hipError_t launch_triangulate(xfh_ctx* c, const TriangArgs& a);                        // triangulate.hip.h
+struct TvArgs;
+hipError_t launch_two_view(xfh_ctx* c, const TvArgs& a);                                 // twoview.hip.h
 struct VocabArgs;
 hipError_t launch_bow_transform(xfh_ctx* c, const VocabArgs& a, int B);             // vocab_transform.hip.h
 struct BowDbArgs;

@@ -39,6 +39,9 @@
 //   k_triangulate_pairs / k_triangulate_winner / k_triangulate_finish : the triangulation half of LocalMapping::CreateNewMapPoints for B neighbours per call:
 //                   one lane per matched pair (parallax, fp64 null vector or stereo unprojection, the gates), then the least accepted neighbour per
 //                   keypoint, then per neighbour the header and the ordered compact list (triangulate.hip.h, triangulate_math.h).
+//   k_twoview_prepare / _fit / _score / _select / _check_rt / _final : TwoViewReconstruction::Reconstruct of monocular initialisation for B problems per
+//                   call: compact matches and Normalize, 2 x iters fp64 Jacobi fits with one lane each, one workgroup per hypothesis for its score, the
+//                   argmax and the motion hypotheses, CheckRT per hypothesis, the decision (twoview.hip.h, twoview_math.h).
 //   k_distinctive_csr : MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:329-403), one wave per map point.
 // Shared by k_best2_csr and every *_search.hip.h kernel: search_common.hip.h (keys, descriptor_distance, top-two and K-list with their wave merges, wave
 // minimum / sum), window_search.hip.h (the grid walk), nodes_clamp.h (node blobs), resolve_rounds.hip.h (the rounds of k_proj_resolve / k_init_resolve: the argument, the cut, the advance of lo).
@@ -106,6 +109,7 @@ hipError_t launch_best2(xfh_ctx* c, const float* q, int nq, const float* tg, con
 #include "init_search.hip.h"
 #include "poseopt.hip.h"
 #include "triangulate.hip.h"
+#include "twoview.hip.h"
 
 // ---- k_distinctive_csr: MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:329-403), batched -------
 // One wave per group (map point).  Rows are taken 64 at a time, lane = row: the lane keeps its descriptor in

@@ -30,16 +30,24 @@ XFH_HD float triang_cos_stereo(float mb, float depth) {
     return (float)((z * z - h * h) / (z * z + h * h));
 }
 
+// the rotation of one column pair from alpha = |U_p|^2, beta = |U_q|^2, gamma = U_p . U_q; false: the pair is orthogonal enough (or a NaN) and
+// does not rotate.  Shared by the 4 x 4 instance below and the M x N one of twoview_math.h.
+XFH_HD bool triang_jacobi_rotation(double alpha, double beta, double gamma, double* c, double* s) {
+    if (!(fabs(gamma) > TRIANG_JACOBI_TOL * sqrt(alpha * beta))) return false;
+    const double zeta = (beta - alpha) / (2.0 * gamma);
+    const double t = (zeta < 0.0 ? -1.0 : 1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
+    *c = 1.0 / sqrt(1.0 + t * t); *s = *c * t;
+    return true;
+}
+
 // one rotation of the one-sided Jacobi iteration on columns P < Q of U (V accumulates); returns 1 when it rotated
 template <int P, int Q>
 XFH_HD int triang_jacobi_pair(double (&U)[4][4], double (&V)[4][4]) {
     const double alpha = ((U[0][P] * U[0][P] + U[1][P] * U[1][P]) + U[2][P] * U[2][P]) + U[3][P] * U[3][P];
     const double beta = ((U[0][Q] * U[0][Q] + U[1][Q] * U[1][Q]) + U[2][Q] * U[2][Q]) + U[3][Q] * U[3][Q];
     const double gamma = ((U[0][P] * U[0][Q] + U[1][P] * U[1][Q]) + U[2][P] * U[2][Q]) + U[3][P] * U[3][Q];
-    if (!(fabs(gamma) > TRIANG_JACOBI_TOL * sqrt(alpha * beta))) return 0;     // (a NaN does not rotate)
-    const double zeta = (beta - alpha) / (2.0 * gamma);
-    const double t = (zeta < 0.0 ? -1.0 : 1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
-    const double c = 1.0 / sqrt(1.0 + t * t), s = c * t;
+    double c, s;
+    if (!triang_jacobi_rotation(alpha, beta, gamma, &c, &s)) return 0;         // (a NaN does not rotate)
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
         const double up = U[r][P], uq = U[r][Q], vp = V[r][P], vq = V[r][Q];

@@ -1024,6 +1024,113 @@ class Context:
                                          *[ptr(v) for v in a], C.byref(st), C.byref(kd), ptr(X), ptr(nrm), ptr(dst), ptr(xh)))
         return dict(status=st.value, kind=kd.value, x3D=X, normal=nrm, dist=dst, x3Dh=xh)
 
+    # -- MonocularInitialization: TwoViewReconstruction::Reconstruct (xfh_two_view*) -------------------------------------------------------
+    TWO_VIEW_HEADER = ("N", "status", "model", "win_h", "win_f", "ngood0", "ngood1", "ngood2", "ngood3", "ngood4", "ngood5", "ngood6", "ngood7", "chosen",
+                       "inliers_h", "inliers_f", "n_tri", "n_hyp", "n_matches_out")
+    TWO_VIEW_OUT = ("header", "floats", "inl_h", "inl_f", "tri", "p3d", "matches_out")
+
+    @staticmethod
+    def two_view_cos(min_parallax_deg: float = 1.0) -> float:
+        """the double the calls compare the parallax cosine with: cos(minParallax * pi / 180)"""
+        return float(np.cos(float(min_parallax_deg) * np.pi / 180.0))
+
+    @staticmethod
+    def two_view_layout(B: int, n1: int, guard: int = 0):
+        """byte offsets of the outputs of two_view_device inside one buffer (and its size under "bytes"); guard as in fuse_search_layout"""
+        al = lambda x: (x + 255) & ~255
+        o, off = {}, al(guard)
+        for name, nbytes in (("header", 4 * capi.TWO_VIEW_HEADER_INTS * B), ("floats", 4 * capi.TWO_VIEW_FLOATS * B), ("inl_h", B * n1), ("inl_f", B * n1),
+                             ("tri", B * n1), ("p3d", 12 * B * n1), ("matches_out", 4 * B * n1)):
+            o[name] = off; o[name + "_bytes"] = nbytes; off += al(nbytes) + al(guard)
+        o["bytes"] = off
+        return o
+
+    @staticmethod
+    def two_view_parse(raw: np.ndarray, lay, B: int, n1: int):
+        """the bytes of a buffer laid out by two_view_layout -> dict of arrays"""
+        cut = lambda k, dt: raw[lay[k]:lay[k] + lay[k + "_bytes"]].view(dt).copy()
+        return dict(header=cut("header", np.int32).reshape(B, -1), floats=cut("floats", np.float32).reshape(B, -1), inl_h=cut("inl_h", np.uint8).reshape(B, n1),
+                    inl_f=cut("inl_f", np.uint8).reshape(B, n1), tri=cut("tri", np.uint8).reshape(B, n1), p3d=cut("p3d", np.float32).reshape(B, n1, 3),
+                    matches_out=cut("matches_out", np.int32).reshape(B, n1))
+
+    def two_view_device(self, B: int, n1: int, n2: int, cam, d_xy1, d_xy2, d_matches12, d_draws, draws_stride: int, iters: int, rand_max: int, d_workspace,
+                        d_out, sigma: float = 1.0, min_parallax_cos: float | None = None, min_triangulated: int = 50, guard: int = 0):
+        """xfh_two_view_device on device pointers; asynchronous.  d_out: the outputs laid out as two_view_layout(B, n1, guard) says; d_workspace:
+        xfh_two_view_workspace_bytes(n1, n2, iters, B) bytes"""
+        o = self.two_view_layout(B, n1, guard)
+        mpc = self.two_view_cos() if min_parallax_cos is None else float(min_parallax_cos)
+        check(lib().xfh_two_view_device(self.h, B, n1, n2, d_xy1, d_xy2, d_matches12, C.byref(cam), float(sigma), iters, d_draws, draws_stride, rand_max, mpc,
+                                        int(min_triangulated), d_workspace, *[d_out + o[k] for k in self.TWO_VIEW_OUT]), self.h)
+
+    @staticmethod
+    def _two_view_arrays(xy1, xy2, matches12, draws, prior=None):
+        f32 = lambda a: np.ascontiguousarray(a, np.float32)
+        m = np.ascontiguousarray(matches12, np.int32)
+        B = 1 if m.ndim == 1 else m.shape[0]
+        n1 = m.shape[-1]
+        x1, x2 = f32(xy1).reshape(B, n1, 2), f32(xy2).reshape(B, -1, 2)
+        d = np.ascontiguousarray(draws, np.int32)
+        out = dict(header=np.zeros((B, capi.TWO_VIEW_HEADER_INTS), np.int32), floats=np.zeros((B, capi.TWO_VIEW_FLOATS), np.float32),
+                   inl_h=np.zeros((B, n1), np.uint8), inl_f=np.zeros((B, n1), np.uint8), tri=np.zeros((B, n1), np.uint8),
+                   p3d=np.zeros((B, n1, 3), np.float32), matches_out=m.reshape(B, n1).copy())
+        if prior is not None:
+            for k, v in prior.items():
+                out[k] = np.ascontiguousarray(v, out[k].dtype).reshape(out[k].shape).copy()
+        return B, n1, x2.shape[1], x1, x2, m, d, out
+
+    @staticmethod
+    def two_view_host(cam, xy1, xy2, matches12, draws, rand_max: int, sigma: float = 1.0, min_parallax_cos: float | None = None, min_triangulated: int = 50,
+                      prior=None):
+        """xfh_two_view_host: the whole rule on one host thread, no ctx.  matches12 [n1] or [B][n1]; draws [iters][8] shared, or [B][iters][8]
+        -> dict(header, floats, inl_h, inl_f, tri, p3d, matches_out), each with a leading B"""
+        B, n1, n2, x1, x2, m, d, out = Context._two_view_arrays(xy1, xy2, matches12, draws, prior)
+        iters = d.shape[-2]
+        stride = 0 if d.ndim == 2 else iters * 8
+        ws = np.zeros(lib().xfh_two_view_workspace_bytes(n1, n2, iters, B) + 16, np.uint8)
+        wp = (ws.ctypes.data + 15) & ~15
+        mpc = Context.two_view_cos() if min_parallax_cos is None else float(min_parallax_cos)
+        check(lib().xfh_two_view_host(B, n1, n2, x1.ctypes.data, x2.ctypes.data, m.ctypes.data, C.byref(cam), float(sigma), iters, d.ctypes.data, stride, rand_max,
+                                      mpc, int(min_triangulated), wp, *[out[k].ctypes.data for k in Context.TWO_VIEW_OUT]))
+        return out
+
+    def two_view(self, cam, xy1, xy2, matches12, draws, rand_max: int, sigma: float = 1.0, min_parallax_cos: float | None = None, min_triangulated: int = 50,
+                 prior=None):
+        """xfh_two_view (host pointers, one problem) -> the dict of two_view_host with B = 1"""
+        B, n1, n2, x1, x2, m, d, out = self._two_view_arrays(xy1, xy2, matches12, draws, prior)
+        assert B == 1 and d.ndim == 2
+        mpc = self.two_view_cos() if min_parallax_cos is None else float(min_parallax_cos)
+        check(lib().xfh_two_view(self.h, n1, n2, x1.ctypes.data, x2.ctypes.data, m.ctypes.data, C.byref(cam), float(sigma), d.shape[0], d.ctypes.data, rand_max,
+                                 mpc, int(min_triangulated), *[out[k].ctypes.data for k in self.TWO_VIEW_OUT]), self.h)
+        return out
+
+    @staticmethod
+    def two_view_set(draws8, rand_max: int, N: int):
+        d, s = np.ascontiguousarray(draws8, np.int32), np.zeros(8, np.int32)
+        check(lib().xfh_two_view_set(d.ctypes.data, rand_max, N, s.ctypes.data))
+        return s
+
+    @staticmethod
+    def two_view_fit(model: int, xy1n, xy2n):
+        a, b, M = np.ascontiguousarray(xy1n, np.float32), np.ascontiguousarray(xy2n, np.float32), np.zeros(9, np.float32)
+        check(lib().xfh_two_view_fit(model, a.ctypes.data, b.ctypes.data, M.ctypes.data))
+        return M
+
+    @staticmethod
+    def two_view_score(model: int, M, sigma: float, xy1, xy2):
+        """-> (chi2 [2], inlier, share of the score) of one match"""
+        M, a, b = np.ascontiguousarray(M, np.float32), np.ascontiguousarray(xy1, np.float32), np.ascontiguousarray(xy2, np.float32)
+        chi, inl, term = np.zeros(2, np.float32), C.c_int(0), C.c_float(0.0)
+        check(lib().xfh_two_view_score(model, M.ctypes.data, float(sigma), a.ctypes.data, b.ctypes.data, chi.ctypes.data, C.byref(inl), C.byref(term)))
+        return chi, inl.value, np.float32(term.value)
+
+    @staticmethod
+    def two_view_check_rt(cam, T21, sigma: float, xy1, xy2):
+        """-> (verdict, cosine, p3d [3]) of one pair under T21 [3][4]"""
+        T, a, b = np.ascontiguousarray(T21, np.float32), np.ascontiguousarray(xy1, np.float32), np.ascontiguousarray(xy2, np.float32)
+        v, c, p = C.c_int(0), C.c_float(0.0), np.zeros(3, np.float32)
+        check(lib().xfh_two_view_check_rt(C.byref(cam), T.ctypes.data, float(sigma), a.ctypes.data, b.ctypes.data, C.byref(v), C.byref(c), p.ctypes.data))
+        return v.value, np.float32(c.value), p
+
     def timing_enable(self, kernel_id: int, layer_mask: int = 0):
         check(lib().xfh_timing_enable(self.h, kernel_id, layer_mask), self.h)
 
