@@ -27,7 +27,8 @@
  *     xfh_map_project, xfh_sim3_project and xfh_map_projection_search_workspace_bytes are stateless in the same way (a loop over
  *     one pure function, no static data); they are not part of the ThreadSanitizer run.  So are xfh_init_accept,
  *     xfh_init_list_entries and xfh_init_search_workspace_bytes, and xfh_vocab_bytes, xfh_vocab_pack, xfh_vocab_unpack, xfh_vocab_descend
- *     and xfh_bow_transform_workspace_bytes, and xfh_bow_score and xfh_bowdb_query_workspace_bytes.
+ *     and xfh_bow_transform_workspace_bytes, and xfh_bow_score and xfh_bowdb_query_workspace_bytes, and xfh_sim3_solve_host,
+ *     xfh_sim3_merge_matches_host, xfh_sim3_solve_iterations[_table], xfh_sim3_solve_set / _horn / _check and xfh_sim3_solve_workspace_bytes.
  *
  * The C++ wrappers that restore the reference's class surface on top of this ABI are
  * include/xfeat/XFextractor.h and include/xfeat/ORBmatcher_xfeat.h; INTEGRATION.md shows
@@ -1504,6 +1505,117 @@ int xfh_two_view_fit(int model, const float* xy1n, const float* xy2n, float* M);
 int xfh_two_view_score(int model, const float* M, float sigma, const float* xy1, const float* xy2, float* chi2, int* inlier, float* term);
 int xfh_two_view_check_rt(const xfh_camera* cam, const float* T21, float sigma, const float* xy1, const float* xy2, int* verdict, float* cos_parallax,
                           float* p3d);
+
+/* ---- Sim3Solver (src/Sim3Solver.cc) as LoopClosing::DetectCommonRegionsFromBoW drives it (src/LoopClosing.cc:645-755) ---------------------------
+ * The two steps between xfh_bow_search_device (shared = 1, the current keyframe against the J covisibles of a candidate) and the first
+ * xfh_map_projection_search_device: the merge of the per-covisible match lists (:670-687) and the RANSAC over 3-point sets with Horn's closed
+ * form (:698-710), with the composition gScm * gSmw (:746-749) so that nothing is read back between the calls.  B problems per call, each one
+ * candidate keyframe against the current keyframe.  Map points are rows of ONE table d_points [M][3] of world positions; d_point1 [n1] is the
+ * row of the current keyframe's map point at keypoint i1 (negative: no map point, a bad one, or GetIndexInKeyFrame < 0, :78-91), d_matched
+ * [B][n1] the row of vpMatched12[i1] (negative: NULL, bad, or not indexed in its keyframe); an entry outside 0 .. M - 1 is "none".  d_T1w [12]
+ * and d_T2w [B][12] are the row-major [R|t] of the two keyframes' poses (T1w_problem_stride in floats; 0 = all problems share one), cam1 / cam2
+ * the two cameras, of which only the Pinhole project is used: fx * x / z + cx.  max_err1 / max_err2: the reference stores 9.210 * sigma2 in a
+ * std::vector<size_t>, so the value is truncated (9 at level 0, and every XFeat keypoint has octave 0): pass
+ * (float)(size_t)(9.210 * mvLevelSigma2[0]).  The rule, written once in xfeatslam_amd/csrc/sim3solve_math.h and compiled for the kernels and
+ * for the host entry points below; fp32 in the order written unless a double is named:
+ *   1. The compact list (:71-115) in i1 order over the slots where both rows are valid; N entries.  X1 = R1w p + t1w, X2 likewise, each row
+ *      ((a*x + b*y) + c*z) + t; mvP1im1 = project(X1) under cam1, mvP2im2 = project(X2) under cam2.
+ *   2. Too few: N < min_inliers (the reference's bNoMore at :225-229), N < 3 (the set generation is undefined there), or the merge's count
+ *      *d_num_matches_or_null < min_matches (nBoWMatches at LoopClosing.cc:691) -> status TOO_FEW.  It does not depend on the draws.  The header
+ *      is written (N, status, 0 iterations, -1 for the winner and the best, zeros) and NOTHING else.
+ *   3. The iteration count (:123-147) needs host libm and must equal the reference's value exactly, so the caller passes a table: its =
+ *      d_iters_of_N[N] (n1 + 1 entries, xfh_sim3_solve_iterations_table), clamped into 1 .. max_iters; max_iters (1 .. 4096) is the number of
+ *      iterations d_draws holds.  xfh_sim3_solve_iterations is ceil(log(1 - p) / log(1 - pow((float)min_inliers / N, 3))) as the reference
+ *      evaluates it, then max(1, min(nIterations, max_its)); 1 for N == min_inliers; max_its where the double is not finite or does not fit an
+ *      int (the reference's cast is undefined there).
+ *   4. The minimal set (:245-259) from the CALLER's raw draws, as xfh_two_view_device takes them: iteration k reads draws 3k .. 3k + 2 of
+ *      d_draws + b * draws_problem_stride; draw j indexes the shrinking vector of size d = N - j at int(((double)draw / ((double)rand_max + 1.0))
+ *      * d) (thirdparty/DBoW2/DUtils/Random.cpp:47-50), followed by the swap-remove; only the at most three overwritten positions are tracked.
+ *      A draw outside 0 .. rand_max is clamped into 0 .. d - 1.
+ *   5. ComputeSim3 (:311-412).  Centroids ((p0 + p1) + p2) / 3.0f; M = Pr2 Pr1^T, each entry the sum over the three points in order; the ten
+ *      entries of the symmetric 4 x 4 N as the reference writes them, float expressions left to right assigned to doubles.  The eigenvector of
+ *      the largest eigenvalue, a stated deviation of the same kind and for the same reason as the fp64 Jacobi of xfh_triangulate_device's step
+ *      4: the reference runs the general Eigen::EigenSolver<Matrix4f>; the rule is a cyclic two-sided Jacobi IN FP64: pairs p < q in
+ *      lexicographic order, a pair rotates iff |a_pq| > 1e-15 |N|_F, theta = (a_qq - a_pp) / (2 a_pq), t = sgn(theta) / (|theta| + sqrt(1 +
+ *      theta^2)), c = 1 / sqrt(1 + t^2), s = c t, a_pp -= t a_pq, a_qq += t a_pq; stop after the first sweep that rotates nothing, at most 30
+ *      sweeps; the first of equal eigenvalues wins, as maxCoeff does.  The rotation, a stated deviation: the reference goes quaternion -> atan2
+ *      -> angle-axis -> Sophus::SO3f::exp; the rule builds R directly from the unit quaternion in double and rounds once.  Both are invariant
+ *      to the eigenvector's sign.  This removes the reference's 0 / 0 for an exactly zero rotation (vec.norm() == 0: the reference's T is NaN
+ *      with no inliers); the rule yields the identity.  Scale = nom / den in double over the nine products (double)Pr1 * (double)P3 resp. P3 *
+ *      P3 in column-major order, P3 = R Pr2 in float; 1.0f with fix_scale.  sR = s R; t12 = O1 - sR O2; T12 = [sR|t12]; T21 = [(float)(1.0 /
+ *      (double)s) R^T | -sRinv t12].
+ *   6. CheckInliers (:415-439) per (iteration, correspondence): err1 = |mvP1im1 - project1(T12 X2)|^2, err2 = |project2(T21 X1) - mvP2im2|^2,
+ *      inlier iff err1 < max_err1 && err2 < max_err2; a NaN never passes.  The count is an integer: no summation order enters.
+ *   7. The decision of `while(!bConverge && !bNoMore) iterate(20, ..)` (:240-293), order-free.  Converged: the winner is the first iteration k <
+ *      its with inliers_k > min_inliers (every earlier best is <= min_inliers < inliers_k, so the >= test holds there).  Otherwise NO_MORE, and
+ *      the best is the last iteration whose count is >= every earlier count (the reference reads nothing from it, but GetEstimated* would
+ *      return it).  tests/test_sim3solve_ref.py proves the equivalence against a literal transcription with the chunks of 20.
+ *   8. The composition for the next search (LoopClosing.cc:746-749, ORBmatcher.cc:621-622), in double from the floats: R = R12 R2w, t = s (R12
+ *      t2w) + t12; d_Tcw = [R | t / s], d_Ow = -R^T (t / s), each rounded to float once: exactly what xfh_map_projection_search_device takes as
+ *      d_Tcw / d_Ow.  The reference passes through g2o's quaternion here; bit equality with that round trip is not claimed.
+ * Outputs per problem.  d_header [B][16] ints: N, status (XFH_SIM3_SOLVE_*), the effective number of iterations, the winning iteration (-1),
+ * nInliers, the best iteration, the best count, the iterations consumed (winner + 1, or all: a caller that emulates one global rand() stream
+ * knows from it how many draws the reference would have used), zeros.  d_floats [B][32]: T12 [12], R12 [9], t12 [3], s12 of the winner, or of
+ * the best iteration when there is none, zeros.  d_inliers [B][n1] bytes indexed by i1 (vbInliers, :277-279): all zero unless the problem
+ * converged.  d_Tcw [B][12], d_Ow [B][3]: written only when the problem converged.
+ *
+ * The merge (LoopClosing.cc:670-687): d_match12 [J][n1] is the output of xfh_bow_search_device with covisible j as problem j, d_point2 [J][n2]
+ * the row of covisible j's map point at its keypoint (negative: none or bad).  The reference's loop, j ascending and k ascending: the first
+ * appearance of a map point inserts it into the set and writes slot k; a later covisible can overwrite slot k with a different new point.
+ * Order-free: entry (j, k) OWNS its point when no lexicographically earlier entry has the same row; slot k takes the owner entry with the
+ * largest j; numBoWMatches is the number of owners.  Outputs d_matched [n1] (the row, or -1: the form the solver reads), d_matched_kf [n1] (j or
+ * -1), *d_num_matches.  An owner table of M ints in the workspace and an integer atomicMin of j * n1 + k: deterministic.
+ *
+ *   xfh_sim3_solve_workspace_bytes  bytes of d_workspace for the solver with B problems, which also hold the merge's owner table; 0 for sizes
+ *                         the calls refuse.
+ *   xfh_sim3_solve_device everything in device memory; asynchronous on the ctx stream, no allocation, no host synchronisation; FOUR launches
+ *                         whatever the data.  XFH_ERR_INVALID_ARG before anything is queued: B outside 1 .. 65535, n1 outside 1 ..
+ *                         XFH_GRID_MAX_N, M outside 1 .. 2^24, min_inliers < 0, max_iters outside 1 .. XFH_SIM3_SOLVE_MAX_ITERS, thresholds that
+ *                         are not finite, rand_max < 1, a stride that is neither 0 nor a whole problem (3 * max_iters draws, 12 floats) with B >
+ *                         1, a NULL pointer (but d_num_matches_or_null), a pointer that is not 4-byte (d_workspace: 16-byte) aligned.  Points,
+ *                         poses and cameras may hold anything, NaN and Inf included, and d_point1, d_matched, d_draws and d_iters_of_N any int: no
+ *                         load or store leaves the buffers, and every loop is bounded.
+ *   xfh_sim3_solve        host-pointer form for one problem through the ctx staging arena.
+ *   xfh_sim3_solve_host   the whole rule on ONE host thread over host pointers (workspace included): no ctx, no GPU.  Stateless and
+ *                         thread-safe, as are the ones below, each one piece of the rule:
+ *   xfh_sim3_solve_iterations / _iterations_table   step 3
+ *   xfh_sim3_solve_set    the three indices of one iteration from its three draws and N >= 3
+ *   xfh_sim3_solve_horn   step 5 of two point triples (point j at [3j .. 3j + 3)) -> hyp [40]: T12 [12], R [9], t [3], s, T21 [12], zeros
+ *   xfh_sim3_solve_check  step 6 of one correspondence (X1, X2 in their camera frames) -> err [2] and the flag
+ *   xfh_sim3_merge_matches_device / xfh_sim3_merge_matches / xfh_sim3_merge_matches_host   the merge: three launches; J in 1 .. 65535, n1, n2 in
+ *                         1 .. XFH_GRID_MAX_N; the host form takes M ints of workspace.
+ * Out of scope: Optimizer::OptimizeSim3; the KannalaBrandt8 project; per-keypoint octaves other than 0; the 4-argument iterate / find as
+ * separate entry points (the same rule gives them: find() is iterate(mRansacMaxIts), one chunk, and the chunk length does not enter the rule;
+ * the 4-argument iterate differs from the 5-argument one only in what it returns without convergence). */
+enum { XFH_SIM3_SOLVE_TOO_FEW = 0, XFH_SIM3_SOLVE_NO_MORE = 1, XFH_SIM3_SOLVE_CONVERGED = 2 };
+#define XFH_SIM3_SOLVE_HEADER_INTS 16
+#define XFH_SIM3_SOLVE_FLOATS 32
+#define XFH_SIM3_SOLVE_HYP_FLOATS 40
+#define XFH_SIM3_SOLVE_MAX_ITERS 4096
+size_t xfh_sim3_solve_workspace_bytes(int n1, int M, int B);
+int xfh_sim3_solve_device(xfh_ctx* ctx, int B, int n1, int M, const float* d_points, const int* d_point1, const int* d_matched, const float* d_T1w,
+                          size_t T1w_problem_stride, const float* d_T2w, const xfh_camera* cam1, const xfh_camera* cam2, float max_err1, float max_err2,
+                          int fix_scale, int min_inliers, int min_matches, const int* d_num_matches_or_null, const int* d_iters_of_N, int max_iters,
+                          const int* d_draws, size_t draws_problem_stride, int rand_max, void* d_workspace, int* d_header, float* d_floats,
+                          uint8_t* d_inliers, float* d_Tcw, float* d_Ow);
+int xfh_sim3_solve(xfh_ctx* ctx, int n1, int M, const float* points, const int* point1, const int* matched, const float* T1w, const float* T2w,
+                   const xfh_camera* cam1, const xfh_camera* cam2, float max_err1, float max_err2, int fix_scale, int min_inliers, const int* iters_of_N,
+                   int max_iters, const int* draws, int rand_max, int* header, float* floats, uint8_t* inliers, float* Tcw, float* Ow);
+int xfh_sim3_solve_host(int B, int n1, int M, const float* points, const int* point1, const int* matched, const float* T1w, size_t T1w_problem_stride,
+                        const float* T2w, const xfh_camera* cam1, const xfh_camera* cam2, float max_err1, float max_err2, int fix_scale, int min_inliers,
+                        int min_matches, const int* num_matches_or_null, const int* iters_of_N, int max_iters, const int* draws, size_t draws_problem_stride,
+                        int rand_max, void* workspace, int* header, float* floats, uint8_t* inliers, float* Tcw, float* Ow);
+int xfh_sim3_solve_iterations(double prob, int min_inliers, int max_its, int N);
+int xfh_sim3_solve_iterations_table(double prob, int min_inliers, int max_its, int n1, int* iters_of_N /* n1 + 1 */);
+int xfh_sim3_solve_set(const int* draws3, int rand_max, int N, int* set3);
+int xfh_sim3_solve_horn(const float* P1, const float* P2, int fix_scale, float* hyp /* XFH_SIM3_SOLVE_HYP_FLOATS */);
+int xfh_sim3_solve_check(const float* T12, const float* T21, const xfh_camera* cam1, const xfh_camera* cam2, const float* X1, const float* X2, float max_err1,
+                         float max_err2, float* err, int* inlier);
+int xfh_sim3_merge_matches_device(xfh_ctx* ctx, int J, int n1, int n2, int M, const int* d_match12, const int* d_point2, void* d_workspace, int* d_matched,
+                                  int* d_matched_kf, int* d_num_matches);
+int xfh_sim3_merge_matches(xfh_ctx* ctx, int J, int n1, int n2, int M, const int* match12, const int* point2, int* matched, int* matched_kf, int* num_matches);
+int xfh_sim3_merge_matches_host(int J, int n1, int n2, int M, const int* match12, const int* point2, void* workspace, int* matched, int* matched_kf,
+                                int* num_matches);
 
 /* MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:329-403), batched over map points: group g observes the
  * descriptor rows indices[offsets[g] .. offsets[g+1]) of `table` (n_rows x 64).  Pairwise DescriptorDistance inside

@@ -82,7 +82,8 @@ const char* xfh_kernel_name(int id) {
                                          "k_triangulation_search", "k_bow_candidates", "k_bow_resolve", "k_mapproj_candidates", "k_sim3_search", "k_sim3_agree", "?",
                                          "k_init_candidates", "k_init_resolve", "k_init_final", "?", "k_vocab_descend", "k_vocab_finish", "k_bowdb_score", "k_bowdb_select",
                                          "k_pose_optimize", "k_triangulate_pairs", "k_triangulate_winner", "k_triangulate_finish",
-                                         "k_twoview_prepare", "k_twoview_fit", "k_twoview_score", "k_twoview_select", "k_twoview_check_rt", "k_twoview_final"};
+                                         "k_twoview_prepare", "k_twoview_fit", "k_twoview_score", "k_twoview_select", "k_twoview_check_rt", "k_twoview_final",
+                                         "k_sim3solve_prepare", "k_sim3solve_fit", "k_sim3solve_count", "k_sim3solve_decide", "k_sim3merge"};
     return (id >= 0 && id < XFH_K_COUNT) ? n[id] : "?";
 }
 

@@ -228,6 +228,10 @@ struct TriangArgs;
 hipError_t launch_triangulate(xfh_ctx* c, const TriangArgs& a);                        // triangulate.hip.h
 struct TvArgs;
 hipError_t launch_two_view(xfh_ctx* c, const TvArgs& a);                                 // twoview.hip.h
+struct S3Args;
+hipError_t launch_sim3_solve(xfh_ctx* c, const S3Args& a);                              // sim3solve.hip.h
+struct S3MergeArgs;
+hipError_t launch_sim3_merge(xfh_ctx* c, const S3MergeArgs& a);
 struct VocabArgs;
 hipError_t launch_bow_transform(xfh_ctx* c, const VocabArgs& a, int B);             // vocab_transform.hip.h
 struct BowDbArgs;

@@ -42,6 +42,9 @@
 //   k_twoview_prepare / _fit / _score / _select / _check_rt / _final : TwoViewReconstruction::Reconstruct of monocular initialisation for B problems per
 //                   call: compact matches and Normalize, 2 x iters fp64 Jacobi fits with one lane each, one workgroup per hypothesis for its score, the
 //                   argmax and the motion hypotheses, CheckRT per hypothesis, the decision (twoview.hip.h, twoview_math.h).
+//   k_sim3solve_prepare / _fit / _count / _decide, k_sim3merge_* : Sim3Solver under LoopClosing's iterate(20) loop for B candidates per call (compact
+//                   correspondences, one lane per Horn hypothesis, one wave per hypothesis for its inlier count, the decision and the composed
+//                   pose) and the merge of the per-covisible BoW match lists in front of it (sim3solve.hip.h, sim3solve_math.h).
 //   k_distinctive_csr : MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:329-403), one wave per map point.
 // Shared by k_best2_csr and every *_search.hip.h kernel: search_common.hip.h (keys, descriptor_distance, top-two and K-list with their wave merges, wave
 // minimum / sum), window_search.hip.h (the grid walk), nodes_clamp.h (node blobs), resolve_rounds.hip.h (the rounds of k_proj_resolve / k_init_resolve: the argument, the cut, the advance of lo).
@@ -110,6 +113,7 @@ hipError_t launch_best2(xfh_ctx* c, const float* q, int nq, const float* tg, con
 #include "poseopt.hip.h"
 #include "triangulate.hip.h"
 #include "twoview.hip.h"
+#include "sim3solve.hip.h"
 
 // ---- k_distinctive_csr: MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:329-403), batched -------
 // One wave per group (map point).  Rows are taken 64 at a time, lane = row: the lane keeps its descriptor in

@@ -1131,6 +1131,144 @@ class Context:
         check(lib().xfh_two_view_check_rt(C.byref(cam), T.ctypes.data, float(sigma), a.ctypes.data, b.ctypes.data, C.byref(v), C.byref(c), p.ctypes.data))
         return v.value, np.float32(c.value), p
 
+    # -- LoopClosing::DetectCommonRegionsFromBoW: the merge of the BoW match lists and Sim3Solver (xfh_sim3_merge_matches*, xfh_sim3_solve*) ------------
+    SIM3_SOLVE_HEADER = ("N", "status", "its", "winner", "n_inliers", "best", "best_count", "consumed")
+    SIM3_SOLVE_OUT = ("header", "floats", "inliers", "Tcw", "Ow")
+
+    @staticmethod
+    def sim3_max_err(sigma2: float = 1.0) -> float:
+        """(float)(size_t)(9.210 * mvLevelSigma2[0]): the reference keeps the threshold in a std::vector<size_t>"""
+        return float(int(9.210 * float(np.float32(sigma2))))
+
+    @staticmethod
+    def sim3_solve_iterations(prob: float, min_inliers: int, max_its: int, N: int) -> int:
+        return int(lib().xfh_sim3_solve_iterations(float(prob), int(min_inliers), int(max_its), int(N)))
+
+    @staticmethod
+    def sim3_solve_iterations_table(prob: float, min_inliers: int, max_its: int, n1: int) -> np.ndarray:
+        t = np.zeros(n1 + 1, np.int32)
+        check(lib().xfh_sim3_solve_iterations_table(float(prob), int(min_inliers), int(max_its), int(n1), t.ctypes.data))
+        return t
+
+    @staticmethod
+    def sim3_solve_layout(B: int, n1: int, guard: int = 0):
+        """byte offsets of the outputs of sim3_solve_device inside one buffer (and its size under "bytes"); guard as in fuse_search_layout"""
+        al = lambda x: (x + 255) & ~255
+        o, off = {}, al(guard)
+        for name, nbytes in (("header", 4 * capi.SIM3_SOLVE_HEADER_INTS * B), ("floats", 4 * capi.SIM3_SOLVE_FLOATS * B), ("inliers", B * n1), ("Tcw", 48 * B),
+                             ("Ow", 12 * B)):
+            o[name] = off; o[name + "_bytes"] = nbytes; off += al(nbytes) + al(guard)
+        o["bytes"] = off
+        return o
+
+    @staticmethod
+    def sim3_solve_parse(raw: np.ndarray, lay, B: int, n1: int):
+        cut = lambda k, dt: raw[lay[k]:lay[k] + lay[k + "_bytes"]].view(dt).copy()
+        return dict(header=cut("header", np.int32).reshape(B, -1), floats=cut("floats", np.float32).reshape(B, -1), inliers=cut("inliers", np.uint8).reshape(B, n1),
+                    Tcw=cut("Tcw", np.float32).reshape(B, 12), Ow=cut("Ow", np.float32).reshape(B, 3))
+
+    def sim3_solve_device(self, B: int, n1: int, M: int, d_points, d_point1, d_matched, d_T1w, T1w_stride: int, d_T2w, cam1, cam2, d_iters_of_N, max_iters: int,
+                          d_draws, draws_stride: int, rand_max: int, d_workspace, d_out, min_inliers: int = 15, fix_scale: bool = False, max_err1: float = 9.0,
+                          max_err2: float = 9.0, min_matches: int = 0, d_num_matches=None, guard: int = 0):
+        """xfh_sim3_solve_device on device pointers; asynchronous.  d_out: the outputs laid out as sim3_solve_layout(B, n1, guard) says; d_workspace:
+        xfh_sim3_solve_workspace_bytes(n1, M, B) bytes"""
+        o = self.sim3_solve_layout(B, n1, guard)
+        check(lib().xfh_sim3_solve_device(self.h, B, n1, M, d_points, d_point1, d_matched, d_T1w, T1w_stride, d_T2w, C.byref(cam1), C.byref(cam2), float(max_err1),
+                                          float(max_err2), int(bool(fix_scale)), int(min_inliers), int(min_matches), d_num_matches, d_iters_of_N, max_iters, d_draws,
+                                          draws_stride, rand_max, d_workspace, *[d_out + o[k] for k in self.SIM3_SOLVE_OUT]), self.h)
+
+    @staticmethod
+    def _sim3_solve_arrays(points, point1, matched, T1w, T2w, iters_of_N, draws, prior=None):
+        pts = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+        p1 = np.ascontiguousarray(point1, np.int32).ravel()
+        m = np.ascontiguousarray(matched, np.int32)
+        B = 1 if m.ndim == 1 else m.shape[0]
+        n1 = m.shape[-1]
+        assert len(p1) == n1
+        t1, t2 = np.ascontiguousarray(T1w, np.float32), np.ascontiguousarray(T2w, np.float32).reshape(B, 12)
+        t1 = t1.reshape(-1, 12)
+        tb, d = np.ascontiguousarray(iters_of_N, np.int32), np.ascontiguousarray(draws, np.int32)
+        assert len(tb) == n1 + 1 and t1.shape[0] in (1, B)
+        out = dict(header=np.zeros((B, capi.SIM3_SOLVE_HEADER_INTS), np.int32), floats=np.zeros((B, capi.SIM3_SOLVE_FLOATS), np.float32),
+                   inliers=np.zeros((B, n1), np.uint8), Tcw=np.zeros((B, 12), np.float32), Ow=np.zeros((B, 3), np.float32))
+        if prior is not None:
+            for k, v in prior.items():
+                out[k] = np.ascontiguousarray(v, out[k].dtype).reshape(out[k].shape).copy()
+        return B, n1, len(pts), pts, p1, m, t1, t2, tb, d, out
+
+    @staticmethod
+    def sim3_solve_host(cam1, cam2, points, point1, matched, T1w, T2w, iters_of_N, draws, rand_max: int, min_inliers: int = 15, fix_scale: bool = False,
+                        max_err1: float = 9.0, max_err2: float = 9.0, min_matches: int = 0, num_matches=None, prior=None):
+        """xfh_sim3_solve_host: the whole rule on one host thread, no ctx.  matched [n1] or [B][n1]; T1w [12] shared or [B][12]; draws [max_iters][3]
+        shared or [B][max_iters][3] -> dict(header, floats, inliers, Tcw, Ow), each with a leading B"""
+        B, n1, M, pts, p1, m, t1, t2, tb, d, out = Context._sim3_solve_arrays(points, point1, matched, T1w, T2w, iters_of_N, draws, prior)
+        max_iters = d.shape[-2]
+        ws = np.zeros(lib().xfh_sim3_solve_workspace_bytes(n1, M, B) + 16, np.uint8)
+        wp = (ws.ctypes.data + 15) & ~15
+        nm = None if num_matches is None else np.array([num_matches], np.int32)
+        check(lib().xfh_sim3_solve_host(B, n1, M, pts.ctypes.data, p1.ctypes.data, m.ctypes.data, t1.ctypes.data, 0 if t1.shape[0] == 1 else 12, t2.ctypes.data,
+                                        C.byref(cam1), C.byref(cam2), float(max_err1), float(max_err2), int(bool(fix_scale)), int(min_inliers), int(min_matches),
+                                        None if nm is None else nm.ctypes.data, tb.ctypes.data, max_iters, d.ctypes.data, 0 if d.ndim == 2 else max_iters * 3, rand_max,
+                                        wp, *[out[k].ctypes.data for k in Context.SIM3_SOLVE_OUT]))
+        return out
+
+    def sim3_solve(self, cam1, cam2, points, point1, matched, T1w, T2w, iters_of_N, draws, rand_max: int, min_inliers: int = 15, fix_scale: bool = False,
+                   max_err1: float = 9.0, max_err2: float = 9.0, prior=None):
+        """xfh_sim3_solve (host pointers, one problem) -> the dict of sim3_solve_host with B = 1"""
+        B, n1, M, pts, p1, m, t1, t2, tb, d, out = self._sim3_solve_arrays(points, point1, matched, T1w, T2w, iters_of_N, draws, prior)
+        assert B == 1 and d.ndim == 2
+        check(lib().xfh_sim3_solve(self.h, n1, M, pts.ctypes.data, p1.ctypes.data, m.ctypes.data, t1.ctypes.data, t2.ctypes.data, C.byref(cam1), C.byref(cam2),
+                                   float(max_err1), float(max_err2), int(bool(fix_scale)), int(min_inliers), tb.ctypes.data, d.shape[0], d.ctypes.data, rand_max,
+                                   *[out[k].ctypes.data for k in self.SIM3_SOLVE_OUT]), self.h)
+        return out
+
+    @staticmethod
+    def sim3_solve_set(draws3, rand_max: int, N: int):
+        d, s = np.ascontiguousarray(draws3, np.int32), np.zeros(3, np.int32)
+        check(lib().xfh_sim3_solve_set(d.ctypes.data, rand_max, N, s.ctypes.data))
+        return s
+
+    @staticmethod
+    def sim3_solve_horn(P1, P2, fix_scale: bool = False):
+        """two point triples [3][3] (point j in row j) -> hyp [40]: T12 [12], R [9], t [3], s, T21 [12], zeros"""
+        a, b, h = np.ascontiguousarray(P1, np.float32), np.ascontiguousarray(P2, np.float32), np.zeros(capi.SIM3_SOLVE_HYP_FLOATS, np.float32)
+        check(lib().xfh_sim3_solve_horn(a.ctypes.data, b.ctypes.data, int(bool(fix_scale)), h.ctypes.data))
+        return h
+
+    @staticmethod
+    def sim3_solve_check(T12, T21, cam1, cam2, X1, X2, max_err1: float = 9.0, max_err2: float = 9.0):
+        """-> (err [2], inlier) of one correspondence"""
+        a, b, x1, x2 = [np.ascontiguousarray(v, np.float32) for v in (T12, T21, X1, X2)]
+        err, inl = np.zeros(2, np.float32), C.c_int(0)
+        check(lib().xfh_sim3_solve_check(a.ctypes.data, b.ctypes.data, C.byref(cam1), C.byref(cam2), x1.ctypes.data, x2.ctypes.data, float(max_err1), float(max_err2),
+                                         err.ctypes.data, C.byref(inl)))
+        return err, inl.value
+
+    @staticmethod
+    def _sim3_merge_arrays(match12, point2):
+        m, p2 = np.ascontiguousarray(match12, np.int32), np.ascontiguousarray(point2, np.int32)
+        assert m.ndim == 2 and p2.ndim == 2 and m.shape[0] == p2.shape[0]
+        n1 = m.shape[1]
+        return m.shape[0], n1, p2.shape[1], m, p2, np.zeros(n1, np.int32), np.zeros(n1, np.int32), np.zeros(1, np.int32)
+
+    @staticmethod
+    def sim3_merge_matches_host(match12, point2, M: int):
+        """xfh_sim3_merge_matches_host: match12 [J][n1], point2 [J][n2] -> (matched [n1], matched_kf [n1], numBoWMatches)"""
+        J, n1, n2, m, p2, o0, o1, o2 = Context._sim3_merge_arrays(match12, point2)
+        ws = np.zeros(M + 4, np.int32)
+        wp = (ws.ctypes.data + 15) & ~15
+        check(lib().xfh_sim3_merge_matches_host(J, n1, n2, M, m.ctypes.data, p2.ctypes.data, wp, o0.ctypes.data, o1.ctypes.data, o2.ctypes.data))
+        return o0, o1, int(o2[0])
+
+    def sim3_merge_matches(self, match12, point2, M: int):
+        """xfh_sim3_merge_matches (host pointers) -> as sim3_merge_matches_host"""
+        J, n1, n2, m, p2, o0, o1, o2 = self._sim3_merge_arrays(match12, point2)
+        check(lib().xfh_sim3_merge_matches(self.h, J, n1, n2, M, m.ctypes.data, p2.ctypes.data, o0.ctypes.data, o1.ctypes.data, o2.ctypes.data), self.h)
+        return o0, o1, int(o2[0])
+
+    def sim3_merge_matches_device(self, J: int, n1: int, n2: int, M: int, d_match12, d_point2, d_workspace, d_matched, d_matched_kf, d_num_matches):
+        check(lib().xfh_sim3_merge_matches_device(self.h, J, n1, n2, M, d_match12, d_point2, d_workspace, d_matched, d_matched_kf, d_num_matches), self.h)
+
     def timing_enable(self, kernel_id: int, layer_mask: int = 0):
         check(lib().xfh_timing_enable(self.h, kernel_id, layer_mask), self.h)
 
