@@ -1617,6 +1617,126 @@ int xfh_sim3_merge_matches(xfh_ctx* ctx, int J, int n1, int n2, int M, const int
 int xfh_sim3_merge_matches_host(int J, int n1, int n2, int M, const int* match12, const int* point2, void* workspace, int* matched, int* matched_kf,
                                 int* num_matches);
 
+/* ---- MLPnPsolver (src/MLPnPsolver.cpp) as Tracking::Relocalization drives it (src/Tracking.cc:3678-3773) ------------------------------------------
+ * The step between xfh_bow_search_device (shared = 2: the current frame against the B relocalisation candidates) and xfh_pose_optimize_device:
+ * the PnP RANSAC over 6-point sets.  B problems per call, one candidate keyframe each; inputs as xfh_pose_optimize_device takes them: d_xy_un
+ * [n][2] (mvKeysUn, shared by all problems), d_assigned [B][n] (row b of the BoW search's d_assigned2: keypoint -> index into problem b's point
+ * block; anything outside 0 .. nq - 1 is "none"), d_points [B][nq][3] world positions, d_point_valid_or_null [B][nq] bytes (pMP && !pMP->isBad();
+ * NULL = all valid), cam (only the Pinhole model: fx, fy, cx, cy).  max_err = mvLevelSigma2[0] * th2 evaluated in float by the caller (every
+ * XFeat keypoint has octave 0).  The rule, written once in xfeatslam_amd/csrc/mlpnp_math.h and compiled for the kernels and for the host entry
+ * points below; IEEE double in the order written unless a float is named (the library is built without contraction):
+ *   1. Correspondences (:55-97).  The compact list in keypoint order over the keypoints with a valid point (ordered scan, no atomic counter);
+ *      N entries.  Bearing vector ((x - cx) / fx, (y - cy) / fy, 1) in float, then widened; it is NOT normalised (cv_br /= cv_br.z is a no-op,
+ *      the reference's comment at :77 notwithstanding).  The point stays float and is widened where a double is needed.
+ *   2. Parameters (:225-260).  min_inliers_eff = max((int)(N * eps), min_inliers, min_set) and the iteration count need the reference's float
+ *      arithmetic and host libm, so the caller passes two tables of n + 1 entries filled by xfh_mlpnp_iterations_table: for each N the
+ *      reference's lines :237-255 as written (int nMinInliers = N * eps in float; the float epsilon update; ceil(log(1 - p) / log(1 - pow(eps,
+ *      3))); max(1, min(nIterations, max_its)); max_its where the double is not finite or does not fit an int).  min_set is 6 and nothing else.
+ *      The count read from the table is clamped into 1 .. max_iters, the number of iterations d_draws holds (1 .. XFH_MLPNP_MAX_ITERS).
+ *   3. Too few: N < min_inliers_eff (:106), N < 6 (the set generation is undefined there) or d_n_matches_or_null[b] < min_matches (nmatches <
+ *      15, Tracking.cc:3708) -> status TOO_FEW.  The header is written (N, status, -1 for the winner and the best, zeros), d_assigned_out is set
+ *      to -1 (the optimiser behind this call must not see another problem's matches) and NOTHING else.
+ *   4. The loop of iterate(chunk, ..) (:100-223): `while (mnIterations < its || nCurrent < chunk)`.  A call that starts at iteration k0 =
+ *      d_start_iter_or_null[b] (NULL or negative: 0) runs the iterations k0 .. end - 1, end = min(max(its, k0 + chunk), max_iters), unless it
+ *      returns earlier.  Iteration k reads the draws 6k .. 6k + 5 of d_draws + b * draws_problem_stride whether or not it qualifies: draw j
+ *      indexes the shrinking vector of size N - j as step 4 of xfh_sim3_solve_device has it, six draws instead of three.
+ *   5. computePose (:356-658) on the 6 points of a set, or on the flagged inliers (Refine); m points, point i with bearing f_i, basis r_i, s_i:
+ *      (a) null-space basis: n = sqrt((x*x + y*y) + 1), sg = x >= 0 ? n : -n, v = (x + sg, y, 1), vv = (v0*v0 + v1*v1) + v2*v2, r = e_2 -
+ *          (2 v1 / vv) v, s = e_3 - (2 v2 / vv) v: columns 2 and 3 of the Householder reflection that maps f onto -sg e_1.  STATED DEVIATION: the
+ *          reference takes JacobiSVD<.., HouseholderQRPreconditioner> of the 1 x 3 matrix.  A^T A, J^T J and J^T r do not depend on the choice of
+ *          basis in exact arithmetic; only the stop test max |J dx| < 1e-5 does.
+ *      (b) planar test: S = sum p p^T (uncentred, as the reference has it; six sums).  rank(S) by a full-pivot Householder QR: at step k the
+ *          entry of largest magnitude of the remaining corner is swapped to (k, k) (the first in row-major order among equals); the loop ends
+ *          when that magnitude is <= 3 DBL_EPSILON times the first step's; the pivot is sqrt(sum of squares of column k from row k down); the
+ *          reflector is applied to the remaining columns; a pivot counts when it is > 3 DBL_EPSILON times the largest pivot.  rank == 2: the
+ *          eigenvectors of S in increasing eigenvalue order from the Jacobi of (d) (STATED DEVIATION from SelfAdjointEigenSolver), as the rows of
+ *          eigenRot; the design matrix uses eigenRot p and has 9 columns (r12 r13 r22 r23 r32 r33 t1 t2 t3), otherwise 12 (r11 .. r33 t1 t2 t3).
+ *      (c) A^T A is accumulated directly, entry (i, j), i <= j: the sum over the points of a_i a_j + b_i b_j, where a / b are the point's two
+ *          rows of the design matrix (basis vector r / s).  Sums over the 6 points of a set start at 0.0 and add in index order.  Sums over the
+ *          inliers of a Refine are the 256-lane fold of xfh_two_view_device: lane l adds the terms of the inlier correspondences l, l + 256, ..
+ *          (correspondence index, non-inliers skipped) to 0.0, then s[l] += s[l + h] for h = 128 .. 1.  Every sum of (b) and (g) likewise.
+ *      (d) the eigenvector of the smallest eigenvalue of A^T A: one-sided cyclic Jacobi in fp64 on the columns (pairs p < q in lexicographic
+ *          order, the rotation of xfh_triangulate_device's step 4, at most 30 sweeps); the column of least norm, the LAST among equals, as
+ *          matrixV().col(colsA - 1) does.  STATED DEVIATION from JacobiSVD<MatrixXd>.  Everything after it is invariant to the vector's sign.
+ *      (e) non-planar: scale = 1 / cbrt(|n0 n1 n2|) of the column norms (STATED DEVIATION: the reference writes pow(x, 1.0 / 3.0)); the nearest
+ *          rotation U V^T = (u0 v0^T + u1 v1^T) + u2 v2^T from the same Jacobi on the 3 x 3 (columns by norm, descending, u = column / norm),
+ *          negated when det < 0; tout = R (scale t); the two candidates [R | +-tout] are inverted as rigid motions (R^T, -R^T t: STATED DEVIATION
+ *          from the general Matrix4d::inverse()) and the one with the smaller sum of 1 - v.f over the FIRST six points wins (error[0] <
+ *          error[1], else the second); R = R^T.  Planar: :532-593 as written, four candidates, the first minimum wins.
+ *      (f) rot2rodrigues (acos, sin) and rodrigues2rot (sin, cos) as written.
+ *      (g) mlpnp_gn (:694-758), at most 5 rounds.  Residuals r = (r_i . u, s_i . u), u = (R X + T) / |R X + T|.  STATED DEVIATION: the reference's
+ *          machine-generated Jacobian is replaced by the same derivative in closed form: g = (n - (n . u) u) / |v|, J[3..5] = g, J[0..2] = -P^T
+ *          ((R^T g) x X) with P = (w w^T + (R^T - I)[w]x) / |w|^2; like the reference's it is 0 / 0 at w = 0.  J^T J (21 entries) and J^T r by
+ *          the sums of (c); the 6 x 6 system by the unpivoted LDL^T of xfh_pose_optimize_device (STATED DEVIATION from the pivoted Eigen::LDLT; a
+ *          pivot that is not > 0 ends the rounds without an update).  Then :744 (any |dx| > 5, or all |dx| > 1: end without update), :748 (stop
+ *          after the update when every |J dx| < 1e-5; a NaN is not below) and x -= dx.
+ *   6. CheckInliers (:262-293): xc = (float)(((R00 * (double)X + R01 * Y) + R02 * Z) + t0), likewise yc, zc; Pinhole::project in float; there is
+ *      NO depth test (a point behind the camera can be an inlier, as in the reference); inlier iff error2 < max_err; a NaN never passes.
+ *   7. The decision, order-free.  k ascending from 0; the state (best_count, best_iteration) is carried through the iterations < k0 too, without
+ *      returning there.  An iteration qualifies when count_k >= min_inliers_eff and becomes the new best when count_k > best_count.  At every
+ *      qualifying k >= k0, Refine (:295-353) runs on the CURRENT best's flags: step 5 on those inliers, step 6, success iff refined_count >
+ *      min_inliers_eff.  Refine depends only on the best's flags, so it is evaluated once per distinct best; the winner is the first
+ *      qualifying k >= k0 whose best refines.  REFINED: the refined pose and flags.  BEST: the loop ran out and best_count >= min_inliers_eff:
+ *      the best iteration's pose and flags.  NONE otherwise.  The pose is [R|t] rounded to float once.
+ *      STATED DEVIATION, and the one that changes results beyond last bits: the reference's Refine() as written (:325-334) calls computePose(..,
+ *      result) and then CheckInliers(), but never copies `result` into mRi / mti, which only iterate() writes (:152-164).  So the reference counts
+ *      and reports the pose of the ITERATION THAT CALLED Refine: it returns at the first qualifying k whose own count_k > min_inliers_eff, with
+ *      iteration k's pose and flags, and the re-solve on the best's inliers is discarded.  The rule stores the re-solved pose, as the function's
+ *      name, its members (mRefinedTcw, mvbRefinedInliers) and the caller (Tracking.cc:3744-3773) intend: REFINED reports another pose, and can
+ *      report other flags, another nInliers, another winning iteration and another consumed count than the reference as written does
+ *      (tests/test_mlpnp_forms.py pins both: the rule equals the literal form with that one copy added, and the literal form as written equals
+ *      the prediction above made from the rule's own iterations; profiles/mlpnp.md has how often they differ).
+ *      Resuming is stateless: mnBestInliers and mvbBestInliers are changed only by the loop, never by Refine, so a second iterate(chunk) on the
+ *      same solver is the SAME call with d_start_iter[b] = the previous header's consumed count.
+ * Outputs per problem.  d_header [B][16] ints: N, status (XFH_MLPNP_*), its, min_inliers_eff, the winning iteration (-1), nInliers, the best
+ * iteration (-1), the best count, the iterations consumed (winner + 1, or end), the number of Refine evaluations the sequential loop would have
+ * made on distinct bests, the planar flag of the reported solve, zeros.  d_Tcw [B][12]: written for REFINED and BEST only.  d_inliers [B][n]
+ * bytes by keypoint (vbInliers), d_assigned_out [B][n]: d_assigned where the keypoint is an inlier, -1 elsewhere (mCurrentFrame.mvpMapPoints
+ * after Tracking.cc:3762-3771: what xfh_pose_optimize_device takes with d_Tcw beside it); both all 0 / all -1 for NONE; for TOO_FEW d_assigned_out is all -1 and d_inliers untouched.
+ *
+ *   xfh_mlpnp_workspace_bytes  bytes of d_workspace; 0 for sizes the calls refuse.
+ *   xfh_mlpnp_solve_device  everything in device memory; asynchronous on the ctx stream, no allocation, no host synchronisation, no global
+ *                         atomics; SIX launches whatever the data (the Refine launch is max_iters x B workgroups, one per possible distinct
+ *                         best, of which all but the few that exist leave at once: keep max_iters at the draws the caller really holds).  XFH_ERR_INVALID_ARG before anything is queued: B outside 1 .. 65535, n
+ *                         outside 1 .. XFH_GRID_MAX_N, nq outside 1 .. 2^24, max_iters outside 1 .. XFH_MLPNP_MAX_ITERS, chunk < 0, max_err not
+ *                         finite, rand_max < 1, a draw stride that is neither 0 nor >= 6 * max_iters with B > 1, a NULL pointer (but the
+ *                         _or_null ones), a pointer that is not 4-byte (d_workspace: 16-byte) aligned.  Points, keypoints and the camera may
+ *                         hold anything, NaN and Inf included, and d_assigned, d_draws, d_start_iter and both tables any int: no load or store
+ *                         leaves the buffers, and every loop is bounded (Jacobi sweeps <= 30, GN rounds <= 5).
+ *   xfh_mlpnp_solve       host-pointer form for one problem through the ctx staging arena.
+ *   xfh_mlpnp_solve_host  the whole rule on ONE host thread over host pointers (workspace included): no ctx, no GPU.  Stateless and
+ *                         thread-safe, as are the ones below, each one piece of the rule:
+ *   xfh_mlpnp_iterations_table  step 2 for N = 0 .. n
+ *   xfh_mlpnp_set         the six indices of one iteration from its six draws and N >= 6
+ *   xfh_mlpnp_nullspace   step 5 (a) of one bearing vector -> rs [6]: r then s
+ *   xfh_mlpnp_compute_pose  step 5 of the points in use among m >= 6 correspondences (f [m][3], p [m][3] floats; use_or_null [m] bytes, NULL = all;
+ *                         at least six in use) -> Rt [12] doubles, row-major [R|t], and the planar flag; fold = 0: the sums in index order (a
+ *                         minimal set), 1: the 256-lane fold over the correspondence index (Refine)
+ *   xfh_mlpnp_check       step 6 of one correspondence -> error2 and the flag
+ * Out of scope: covariance input (use_cov; the reference never sets it); the KannalaBrandt8 model; octaves other than 0; min_set != 6. */
+enum { XFH_MLPNP_TOO_FEW = 0, XFH_MLPNP_NONE = 1, XFH_MLPNP_BEST = 2, XFH_MLPNP_REFINED = 3 };
+#define XFH_MLPNP_HEADER_INTS 16
+#define XFH_MLPNP_MAX_ITERS 1024
+size_t xfh_mlpnp_workspace_bytes(int n, int nq, int B, int max_iters);
+int xfh_mlpnp_solve_device(xfh_ctx* ctx, int B, int n, int nq, const float* d_xy_un, const int* d_assigned, const float* d_points,
+                           const uint8_t* d_point_valid_or_null, const xfh_camera* cam, float max_err, int min_matches, const int* d_n_matches_or_null,
+                           const int* d_iters_of_N, const int* d_min_inliers_of_N, int chunk, const int* d_start_iter_or_null, int max_iters,
+                           const int* d_draws, size_t draws_problem_stride, int rand_max, void* d_workspace, int* d_header, float* d_Tcw,
+                           uint8_t* d_inliers, int* d_assigned_out);
+int xfh_mlpnp_solve(xfh_ctx* ctx, int n, int nq, const float* xy_un, const int* assigned, const float* points, const uint8_t* point_valid_or_null,
+                    const xfh_camera* cam, float max_err, const int* iters_of_N, const int* min_inliers_of_N, int chunk, int start_iter, int max_iters,
+                    const int* draws, int rand_max, int* header, float* Tcw, uint8_t* inliers, int* assigned_out);
+int xfh_mlpnp_solve_host(int B, int n, int nq, const float* xy_un, const int* assigned, const float* points, const uint8_t* point_valid_or_null,
+                         const xfh_camera* cam, float max_err, int min_matches, const int* n_matches_or_null, const int* iters_of_N,
+                         const int* min_inliers_of_N, int chunk, const int* start_iter_or_null, int max_iters, const int* draws,
+                         size_t draws_problem_stride, int rand_max, void* workspace, int* header, float* Tcw, uint8_t* inliers, int* assigned_out);
+int xfh_mlpnp_iterations_table(double prob, int min_inliers, int max_its, int min_set, float eps, int n, int* iters_of_N /* n + 1 */,
+                               int* min_inliers_of_N /* n + 1 */);
+int xfh_mlpnp_set(const int* draws6, int rand_max, int N, int* set6);
+int xfh_mlpnp_nullspace(const double* f, double* rs);
+int xfh_mlpnp_compute_pose(int m, const float* f, const float* p, const uint8_t* use_or_null, int fold, double* Rt, int* planar);
+int xfh_mlpnp_check(const double* Rt, const xfh_camera* cam, const float* X, const float* xy, float max_err, float* error2, int* inlier);
+
 /* MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:329-403), batched over map points: group g observes the
  * descriptor rows indices[offsets[g] .. offsets[g+1]) of `table` (n_rows x 64).  Pairwise DescriptorDistance inside
  * the group (diagonal 0), per row the median sorted[(N-1)/2], and the FIRST row with the least median wins:

@@ -83,7 +83,8 @@ const char* xfh_kernel_name(int id) {
                                          "k_init_candidates", "k_init_resolve", "k_init_final", "?", "k_vocab_descend", "k_vocab_finish", "k_bowdb_score", "k_bowdb_select",
                                          "k_pose_optimize", "k_triangulate_pairs", "k_triangulate_winner", "k_triangulate_finish",
                                          "k_twoview_prepare", "k_twoview_fit", "k_twoview_score", "k_twoview_select", "k_twoview_check_rt", "k_twoview_final",
-                                         "k_sim3solve_prepare", "k_sim3solve_fit", "k_sim3solve_count", "k_sim3solve_decide", "k_sim3merge"};
+                                         "k_sim3solve_prepare", "k_sim3solve_fit", "k_sim3solve_count", "k_sim3solve_decide", "k_sim3merge",
+                                         "k_mlpnp_prepare", "k_mlpnp_fit", "k_mlpnp_count", "k_mlpnp_records", "k_mlpnp_refine", "k_mlpnp_decide"};
     return (id >= 0 && id < XFH_K_COUNT) ? n[id] : "?";
 }
 

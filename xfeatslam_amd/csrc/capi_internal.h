@@ -1,4 +1,4 @@
-// capi_internal.h -- what the entry-point files (capi.cpp, capi_search.cpp, capi_fuse.cpp, capi_triangulation.cpp, capi_bow.cpp, capi_vocab.cpp, capi_bowdb.cpp, capi_loop.cpp, capi_init.cpp, capi_poseopt.cpp, capi_triangulate.cpp, capi_twoview.cpp, capi_sim3solve.cpp, capi_bench.cpp) share.
+// capi_internal.h -- what the entry-point files (capi.cpp, capi_search.cpp, capi_fuse.cpp, capi_triangulation.cpp, capi_bow.cpp, capi_vocab.cpp, capi_bowdb.cpp, capi_loop.cpp, capi_init.cpp, capi_poseopt.cpp, capi_triangulate.cpp, capi_twoview.cpp, capi_sim3solve.cpp, capi_mlpnp.cpp, capi_bench.cpp) share.
 #pragma once
 #include "ctx.h"
 #include "window_layout.h"

@@ -232,6 +232,8 @@ struct S3Args;
 hipError_t launch_sim3_solve(xfh_ctx* c, const S3Args& a);                              // sim3solve.hip.h
 struct S3MergeArgs;
 hipError_t launch_sim3_merge(xfh_ctx* c, const S3MergeArgs& a);
+struct MlArgs;
+hipError_t launch_mlpnp_solve(xfh_ctx* c, const MlArgs& a);                              // mlpnp.hip.h
 struct VocabArgs;
 hipError_t launch_bow_transform(xfh_ctx* c, const VocabArgs& a, int B);             // vocab_transform.hip.h
 struct BowDbArgs;

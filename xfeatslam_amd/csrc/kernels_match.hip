@@ -45,6 +45,7 @@
 //   k_sim3solve_prepare / _fit / _count / _decide, k_sim3merge_* : Sim3Solver under LoopClosing's iterate(20) loop for B candidates per call (compact
 //                   correspondences, one lane per Horn hypothesis, one wave per hypothesis for its inlier count, the decision and the composed
 //                   pose) and the merge of the per-covisible BoW match lists in front of it (sim3solve.hip.h, sim3solve_math.h).
+//   (the kernels of the MLPnP solver, k_mlpnp_*, are in kernels_mlpnp.hip: two of them use scratch, which no kernel of this file may)
 //   k_distinctive_csr : MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:329-403), one wave per map point.
 // Shared by k_best2_csr and every *_search.hip.h kernel: search_common.hip.h (keys, descriptor_distance, top-two and K-list with their wave merges, wave
 // minimum / sum), window_search.hip.h (the grid walk), nodes_clamp.h (node blobs), resolve_rounds.hip.h (the rounds of k_proj_resolve / k_init_resolve: the argument, the cut, the advance of lo).

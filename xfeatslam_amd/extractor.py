@@ -1269,6 +1269,119 @@ class Context:
     def sim3_merge_matches_device(self, J: int, n1: int, n2: int, M: int, d_match12, d_point2, d_workspace, d_matched, d_matched_kf, d_num_matches):
         check(lib().xfh_sim3_merge_matches_device(self.h, J, n1, n2, M, d_match12, d_point2, d_workspace, d_matched, d_matched_kf, d_num_matches), self.h)
 
+    # -- Tracking::Relocalization: MLPnPsolver between SearchByBoW and PoseOptimization (xfh_mlpnp_*) ------------------------------------------------------
+    MLPNP_HEADER = ("N", "status", "its", "min_inliers", "winner", "n_inliers", "best", "best_count", "consumed", "refines", "planar")
+    MLPNP_OUT = ("header", "Tcw", "inliers", "assigned_out")
+    MLPNP_STATUS = ("TOO_FEW", "NONE", "BEST", "REFINED")
+
+    @staticmethod
+    def mlpnp_iterations_table(n: int, prob: float = 0.99, min_inliers: int = 10, max_its: int = 300, min_set: int = 6, eps: float = 0.5):
+        """xfh_mlpnp_iterations_table -> (iters_of_N [n + 1], min_inliers_of_N [n + 1]): SetRansacParameters for every N"""
+        t, m = np.zeros(n + 1, np.int32), np.zeros(n + 1, np.int32)
+        check(lib().xfh_mlpnp_iterations_table(float(prob), int(min_inliers), int(max_its), int(min_set), float(eps), int(n), t.ctypes.data, m.ctypes.data))
+        return t, m
+
+    @staticmethod
+    def mlpnp_layout(B: int, n: int, guard: int = 0):
+        """byte offsets of the outputs of mlpnp_solve_device inside one buffer (and its size under "bytes"); guard as in fuse_search_layout"""
+        al = lambda x: (x + 255) & ~255
+        o, off = {}, al(guard)
+        for name, nbytes in (("header", 4 * capi.MLPNP_HEADER_INTS * B), ("Tcw", 48 * B), ("inliers", B * n), ("assigned_out", 4 * B * n)):
+            o[name] = off; o[name + "_bytes"] = nbytes; off += al(nbytes) + al(guard)
+        o["bytes"] = off
+        return o
+
+    @staticmethod
+    def mlpnp_parse(raw: np.ndarray, lay, B: int, n: int):
+        cut = lambda k, dt: raw[lay[k]:lay[k] + lay[k + "_bytes"]].view(dt).copy()
+        return dict(header=cut("header", np.int32).reshape(B, -1), Tcw=cut("Tcw", np.float32).reshape(B, 12), inliers=cut("inliers", np.uint8).reshape(B, n),
+                    assigned_out=cut("assigned_out", np.int32).reshape(B, n))
+
+    def mlpnp_solve_device(self, B: int, n: int, nq: int, d_xy_un, d_assigned, d_points, d_point_valid, cam, max_err: float, d_iters_of_N, d_min_inliers_of_N,
+                           chunk: int, d_start_iter, max_iters: int, d_draws, draws_stride: int, rand_max: int, d_workspace, d_out, min_matches: int = 0,
+                           d_n_matches=None, guard: int = 0):
+        """xfh_mlpnp_solve_device on device pointers; asynchronous.  d_out: the outputs laid out as mlpnp_layout(B, n, guard) says; d_workspace:
+        xfh_mlpnp_workspace_bytes(n, nq, B, max_iters) bytes"""
+        o = self.mlpnp_layout(B, n, guard)
+        check(lib().xfh_mlpnp_solve_device(self.h, B, n, nq, d_xy_un, d_assigned, d_points, d_point_valid, C.byref(cam), float(max_err), int(min_matches), d_n_matches,
+                                           d_iters_of_N, d_min_inliers_of_N, int(chunk), d_start_iter, max_iters, d_draws, draws_stride, rand_max, d_workspace,
+                                           *[d_out + o[k] for k in self.MLPNP_OUT]), self.h)
+
+    @staticmethod
+    def _mlpnp_arrays(xy_un, assigned, points, point_valid, tables, draws, prior=None):
+        xy = np.ascontiguousarray(xy_un, np.float32).reshape(-1, 2)
+        a = np.ascontiguousarray(assigned, np.int32)
+        B, n = (1 if a.ndim == 1 else a.shape[0]), a.shape[-1]
+        pts = np.ascontiguousarray(points, np.float32).reshape(B, -1, 3)
+        nq = pts.shape[1]
+        va = None if point_valid is None else np.ascontiguousarray(point_valid, np.uint8).reshape(B, nq)
+        ti, tm = np.ascontiguousarray(tables[0], np.int32), np.ascontiguousarray(tables[1], np.int32)
+        d = np.ascontiguousarray(draws, np.int32)
+        assert len(xy) == n and len(ti) == n + 1 and len(tm) == n + 1 and d.shape[-1] == 6
+        out = dict(header=np.zeros((B, capi.MLPNP_HEADER_INTS), np.int32), Tcw=np.zeros((B, 12), np.float32), inliers=np.zeros((B, n), np.uint8),
+                   assigned_out=np.zeros((B, n), np.int32))
+        if prior is not None:
+            for k, v in prior.items():
+                out[k] = np.ascontiguousarray(v, out[k].dtype).reshape(out[k].shape).copy()
+        return B, n, nq, xy, a, pts, va, ti, tm, d, out
+
+    @staticmethod
+    def mlpnp_solve_host(cam, xy_un, assigned, points, tables, draws, rand_max: int, max_err: float = 5.991, chunk: int = 5, start_iter=None, point_valid=None,
+                         min_matches: int = 0, n_matches=None, prior=None):
+        """xfh_mlpnp_solve_host: the whole rule on one host thread, no ctx.  assigned [n] or [B][n]; points [B][nq][3]; tables = (iters_of_N, min_inliers_of_N);
+        draws [max_iters][6] shared or [B][max_iters][6]; start_iter None or [B] -> dict(header, Tcw, inliers, assigned_out), each with a leading B"""
+        B, n, nq, xy, a, pts, va, ti, tm, d, out = Context._mlpnp_arrays(xy_un, assigned, points, point_valid, tables, draws, prior)
+        max_iters = d.shape[-2]
+        ws = np.zeros(lib().xfh_mlpnp_workspace_bytes(n, nq, B, max_iters) + 16, np.uint8)
+        wp = (ws.ctypes.data + 15) & ~15
+        nm = None if n_matches is None else np.ascontiguousarray(n_matches, np.int32).reshape(B)
+        st = None if start_iter is None else np.ascontiguousarray(start_iter, np.int32).reshape(B)
+        check(lib().xfh_mlpnp_solve_host(B, n, nq, xy.ctypes.data, a.ctypes.data, pts.ctypes.data, None if va is None else va.ctypes.data, C.byref(cam), float(max_err),
+                                         int(min_matches), None if nm is None else nm.ctypes.data, ti.ctypes.data, tm.ctypes.data, int(chunk),
+                                         None if st is None else st.ctypes.data, max_iters, d.ctypes.data, 0 if d.ndim == 2 else max_iters * 6, rand_max, wp,
+                                         *[out[k].ctypes.data for k in Context.MLPNP_OUT]))
+        return out
+
+    def mlpnp_solve(self, cam, xy_un, assigned, points, tables, draws, rand_max: int, max_err: float = 5.991, chunk: int = 5, start_iter: int = 0, point_valid=None,
+                    prior=None):
+        """xfh_mlpnp_solve (host pointers, one problem) -> the dict of mlpnp_solve_host with B = 1"""
+        B, n, nq, xy, a, pts, va, ti, tm, d, out = self._mlpnp_arrays(xy_un, assigned, points, point_valid, tables, draws, prior)
+        assert B == 1 and d.ndim == 2
+        check(lib().xfh_mlpnp_solve(self.h, n, nq, xy.ctypes.data, a.ctypes.data, pts.ctypes.data, None if va is None else va.ctypes.data, C.byref(cam), float(max_err),
+                                    ti.ctypes.data, tm.ctypes.data, int(chunk), int(start_iter), d.shape[0], d.ctypes.data, rand_max,
+                                    *[out[k].ctypes.data for k in self.MLPNP_OUT]), self.h)
+        return out
+
+    @staticmethod
+    def mlpnp_set(draws6, rand_max: int, N: int):
+        d, s = np.ascontiguousarray(draws6, np.int32), np.zeros(6, np.int32)
+        check(lib().xfh_mlpnp_set(d.ctypes.data, rand_max, N, s.ctypes.data))
+        return s
+
+    @staticmethod
+    def mlpnp_nullspace(f):
+        """bearing vector [3] (doubles) -> (r [3], s [3])"""
+        a, rs = np.ascontiguousarray(f, np.float64), np.zeros(6, np.float64)
+        check(lib().xfh_mlpnp_nullspace(a.ctypes.data, rs.ctypes.data))
+        return rs[:3].copy(), rs[3:].copy()
+
+    @staticmethod
+    def mlpnp_compute_pose(f, p, use=None, fold: bool = False):
+        """bearing vectors [m][3] and points [m][3] (floats), use [m] bytes or None -> (Rt [3][4] doubles, planar)"""
+        a, b = np.ascontiguousarray(f, np.float32), np.ascontiguousarray(p, np.float32)
+        u = None if use is None else np.ascontiguousarray(use, np.uint8)
+        Rt, planar = np.zeros(12, np.float64), C.c_int(0)
+        check(lib().xfh_mlpnp_compute_pose(len(a), a.ctypes.data, b.ctypes.data, None if u is None else u.ctypes.data, int(bool(fold)), Rt.ctypes.data, C.byref(planar)))
+        return Rt.reshape(3, 4), planar.value
+
+    @staticmethod
+    def mlpnp_check(Rt, cam, X, xy, max_err: float = 5.991):
+        """-> (error2, inlier) of one correspondence under Rt [3][4] (doubles)"""
+        T, x, k = np.ascontiguousarray(Rt, np.float64), np.ascontiguousarray(X, np.float32), np.ascontiguousarray(xy, np.float32)
+        e, inl = C.c_float(0.0), C.c_int(0)
+        check(lib().xfh_mlpnp_check(T.ctypes.data, C.byref(cam), x.ctypes.data, k.ctypes.data, float(max_err), C.byref(e), C.byref(inl)))
+        return np.float32(e.value), inl.value
+
     def timing_enable(self, kernel_id: int, layer_mask: int = 0):
         check(lib().xfh_timing_enable(self.h, kernel_id, layer_mask), self.h)
 
