@@ -23,7 +23,7 @@ static void run(const Problem& p, std::vector<int>& header, std::vector<float>& 
     unsigned char* wp = (unsigned char*)(((uintptr_t)ws.data() + 15) & ~(uintptr_t)15);
     MlArgs a = {};
     a.B = 1; a.n = p.n; a.nq = p.nq; a.max_iters = p.max_iters; a.rand_max = p.rand_max; a.chunk = p.chunk; a.draws_stride = 0;
-    a.cam = TvCam{p.cam[0], p.cam[1], p.cam[2], p.cam[3]}; a.max_err = p.max_err; a.xy_un = p.xy.data(); a.points = p.points.data(); a.assigned = p.assigned.data();
+    a.cam = GeoCam{p.cam[0], p.cam[1], p.cam[2], p.cam[3]}; a.max_err = p.max_err; a.xy_un = p.xy.data(); a.points = p.points.data(); a.assigned = p.assigned.data();
     a.iters_of_N = p.iters.data(); a.min_of_N = p.mins.data(); a.start_iter = &p.start_iter; a.draws = p.draws.data(); a.valid = p.valid.empty() ? nullptr : p.valid.data();
     a.ws = wp; a.header = header.data(); a.Tcw = Tcw.data(); a.inliers = inliers.data(); a.assigned_out = aout.data();
     std::vector<unsigned char> flag((size_t)p.n);
@@ -61,7 +61,7 @@ static int hostile() {
     double rs[6]; const double f0[3] = {0.0, 0.0, 1.0}, fn[3] = {NAN, 1.0, 1.0};
     ml_nullspace(f0, rs); ml_nullspace(fn, rs);
     int set[6]; const int d[6] = {INT_MIN, INT_MAX, -1, 0, 5, 1 << 30};
-    ml_set(d, 1, 6, set);
+    geo_set<ML_MIN_SET>(d, 1, 6, set);
     for (int k = 0; k < 6; ++k) if (set[k] < 0 || set[k] >= 6) return 2;
     const double z6[6] = {0, 0, 0, 0, 0, 0}, n6[6] = {NAN, 1, 2, INFINITY, 0, 1};
     if (ml_rank3(z6) != 0) return 3;

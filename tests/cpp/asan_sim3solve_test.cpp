@@ -26,7 +26,7 @@ static Outputs run(const Problem& p) {
     std::vector<unsigned char> ws(s3_workspace_bytes(p.n1, p.M, 1));        // exactly the documented size: the sanitizer sees any byte past it
     S3Args a = {};
     a.B = 1; a.n1 = p.n1; a.M = p.M; a.max_iters = p.max_iters; a.rand_max = p.rand_max; a.min_inliers = p.min_inliers; a.fix_scale = p.fix_scale;
-    a.cam1 = TvCam{p.cam[0], p.cam[1], p.cam[2], p.cam[3]}; a.cam2 = TvCam{p.cam[4], p.cam[5], p.cam[6], p.cam[7]};
+    a.cam1 = GeoCam{p.cam[0], p.cam[1], p.cam[2], p.cam[3]}; a.cam2 = GeoCam{p.cam[4], p.cam[5], p.cam[6], p.cam[7]};
     a.max_err1 = p.max_err[0]; a.max_err2 = p.max_err[1];
     a.points = p.points.data(); a.T1w = p.T1w.data(); a.T2w = p.T2w.data(); a.point1 = p.point1.data(); a.matched = p.matched.data();
     a.iters_of_N = p.table.data(); a.draws = p.draws.data(); a.ws = ws.data();

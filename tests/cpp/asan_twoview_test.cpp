@@ -32,7 +32,7 @@ static void run(Problem& p) {
     p.inl_h.assign(p.n1, 0); p.inl_f.assign(p.n1, 0); p.tri.assign(p.n1, 0); p.p3d.assign((size_t)p.n1 * 3, 0.0f); p.matches_out = p.m12;
     TvArgs a = {};
     a.B = 1; a.n1 = p.n1; a.n2 = p.n2; a.iters = p.iters; a.rand_max = p.rand_max; a.min_tri = p.min_tri; a.draws_stride = 0;
-    a.cam = TvCam{p.cam[0], p.cam[1], p.cam[2], p.cam[3]}; a.sigma = p.sigma; a.min_parallax_cos = p.mpc;
+    a.cam = GeoCam{p.cam[0], p.cam[1], p.cam[2], p.cam[3]}; a.sigma = p.sigma; a.min_parallax_cos = p.mpc;
     a.xy1 = p.xy1.data(); a.xy2 = p.xy2.data(); a.match12 = p.m12.data(); a.draws = p.draws.data(); a.ws = (unsigned char*)ws.data();
     a.header = p.header.data(); a.fout = p.floats.data(); a.inl_h = p.inl_h.data(); a.inl_f = p.inl_f.data(); a.tri = p.tri.data();
     a.p3d = p.p3d.data(); a.matches_out = p.matches_out.data();
@@ -82,7 +82,7 @@ static int hostile() {
         for (int k = 0; k < 50; ++k) {
             int d[8], s[8];
             for (int j = 0; j < 8; ++j) { const unsigned r = lcg(seed); d[j] = k == 0 ? 0 : k == 1 ? 32767 : k == 2 ? 40000 : k == 3 ? -5 : (int)(r % 32768u); }
-            tv_set(d, 32767, N, s);
+            geo_set<TV_MIN_SET>(d, 32767, N, s);
             for (int j = 0; j < 8; ++j) {
                 if (s[j] < 0 || s[j] >= N) { printf("set index %d outside 0 .. %d\n", s[j], N - 1); return 1; }
                 for (int i = 0; i < j; ++i) if (s[i] == s[j]) { printf("set repeats %d\n", s[j]); return 1; }

@@ -456,3 +456,50 @@ def test_search_kernel_register_contract():
     for name in ("k_proj_resolve<false>", "k_proj_resolve<true>", "k_init_resolve"):
         k = [k for k in rows if k.split("(")[0] == name][0]
         assert rows[k][0] + rows[k][1] <= 128, (name, rows[k])
+
+
+# The solver kernels of kernels_match.hip and kernels_mlpnp.hip at the commit before their shared pieces moved into geom_common.h and
+# block_common.hip.h: (VGPRs, occupancy in waves per SIMD, scratch bytes per lane) as tools/kres.sh printed them for that commit with
+# clang 22 / ROCm 7.2.  k_mlpnp_fit also held 256 AGPRs, k_mlpnp_refine 8.
+GEOMETRY_KERNELS_BEFORE = {
+    "k_triangulate_pairs": (118, 4, 0), "k_triangulate_finish": (46, 8, 0),
+    "k_twoview_prepare": (18, 8, 0), "k_twoview_fit": (183, 1, 0), "k_twoview_score": (63, 8, 0), "k_twoview_select": (90, 5, 0),
+    "k_twoview_check_rt": (134, 3, 0), "k_twoview_final": (21, 8, 0),
+    "k_sim3solve_prepare": (46, 8, 0), "k_sim3solve_fit": (108, 4, 0), "k_sim3solve_count": (54, 8, 0), "k_sim3solve_decide": (55, 8, 0),
+    "k_mlpnp_prepare": (42, 8, 0), "k_mlpnp_fit": (256, 1, 1020), "k_mlpnp_count": (52, 8, 0), "k_mlpnp_records": (4, 8, 0),
+    "k_mlpnp_refine": (256, 1, 320), "k_mlpnp_decide": (36, 8, 0),
+}
+
+
+def test_geometry_kernel_register_contract():
+    """The geometry solvers share their math (geom_common.h) and their workgroup primitives (block_common.hip.h), so one edit there moves the
+    register allocation of every solver kernel at once -- and k_mlpnp_fit already sits at 256 VGPRs + 256 AGPRs with 1020 bytes of scratch per
+    lane.  No solver kernel may run at a lower occupancy than it did before the pieces were shared, none may gain scratch where it had none,
+    and k_mlpnp_fit / k_mlpnp_refine may use no more scratch than they did (GEOMETRY_KERNELS_BEFORE).  tools/kres.sh reads clang's
+    kernel-resource-usage remarks (no GPU needed)."""
+    import shutil
+    import subprocess
+    if not shutil.which("c++filt") or not os.path.exists("/opt/rocm/bin/hipcc"):
+        pytest.skip("needs hipcc and c++filt")
+    rows = {}
+    for src in ("kernels_match.hip", "kernels_mlpnp.hip"):
+        out = subprocess.run(["bash", os.path.join(ROOT, "tools", "kres.sh"), src], capture_output=True, text=True, timeout=600).stdout
+        rows.update(_kres_rows(out))
+    for name, (_, occ_before, scratch_before) in GEOMETRY_KERNELS_BEFORE.items():
+        hit = [k for k in rows if k.split("(")[0] == name]
+        assert len(hit) == 1, (name, sorted(rows))
+        vgpr, agpr, scratch, occ = rows[hit[0]]
+        print(f"{name}: vgpr {vgpr} agpr {agpr} scratch {scratch} occ {occ}   before: {GEOMETRY_KERNELS_BEFORE[name]}")
+        assert occ >= occ_before, (name, rows[hit[0]], GEOMETRY_KERNELS_BEFORE[name])
+        assert scratch <= scratch_before, (name, rows[hit[0]], GEOMETRY_KERNELS_BEFORE[name])
+
+
+def test_geometry_shared_pieces_under_sanitizers(tmp_path):
+    """tests/cpp/geom_common_test.cpp, a stand-alone program built from geom_common.h alone with AddressSanitizer + UBSan: the K-set against the
+    std::vector swap-remove, the cached and the run-time-rows Jacobi against each other by bits, the tie rules.  Nothing of the library is
+    linked, nothing runs on a GPU, nothing is loaded into Python."""
+    exe = str(tmp_path / "geom_common_test")
+    subprocess.check_call(["/opt/rocm/lib/llvm/bin/clang++", "-std=c++17", "-O1", "-g", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                           "-I" + os.path.join(ROOT, "xfeatslam_amd", "csrc"), os.path.join(ROOT, "tests", "cpp", "geom_common_test.cpp"), "-o", exe])
+    r = subprocess.run([exe], capture_output=True, text=True, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0"))
+    assert r.returncode == 0 and "geom_common_test ok" in r.stdout, (r.stdout[-1000:], r.stderr[-3000:])

@@ -18,7 +18,7 @@ static MlArgs ml_args(int B, int n, int nq, const float* xy_un, const int* assig
                       const int* draws, size_t draws_stride, int rand_max, void* ws, int* header, float* Tcw, uint8_t* inliers, int* assigned_out) {
     MlArgs a = {};
     a.B = B; a.n = n; a.nq = nq; a.max_iters = max_iters; a.rand_max = rand_max; a.min_matches = min_matches; a.chunk = chunk; a.draws_stride = draws_stride;
-    a.cam = TvCam{cam->fx, cam->fy, cam->cx, cam->cy}; a.max_err = max_err; a.xy_un = xy_un; a.points = points; a.assigned = assigned; a.n_matches = n_matches;
+    a.cam = GeoCam{cam->fx, cam->fy, cam->cx, cam->cy}; a.max_err = max_err; a.xy_un = xy_un; a.points = points; a.assigned = assigned; a.n_matches = n_matches;
     a.iters_of_N = iters_of_N; a.min_of_N = min_of_N; a.start_iter = start_iter; a.draws = draws; a.valid = valid; a.ws = (unsigned char*)ws; a.header = header;
     a.Tcw = Tcw; a.inliers = inliers; a.assigned_out = assigned_out;
     return a;
@@ -39,7 +39,7 @@ int xfh_mlpnp_iterations_table(double prob, int min_inliers, int max_its, int mi
 
 int xfh_mlpnp_set(const int* draws6, int rand_max, int N, int* set6) {
     if (!draws6 || !set6 || rand_max < 1 || N < ML_MIN_SET) return XFH_ERR_INVALID_ARG;
-    ml_set(draws6, rand_max, N, set6);
+    geo_set<ML_MIN_SET>(draws6, rand_max, N, set6);
     return XFH_OK;
 }
 
@@ -61,7 +61,7 @@ int xfh_mlpnp_compute_pose(int m, const float* f, const float* p, const uint8_t*
 
 int xfh_mlpnp_check(const double* Rt, const xfh_camera* cam, const float* X, const float* xy, float max_err, float* error2, int* inlier) {
     if (!Rt || !cam || !X || !xy || !error2 || !inlier) return XFH_ERR_INVALID_ARG;
-    *inlier = ml_check(Rt, TvCam{cam->fx, cam->fy, cam->cx, cam->cy}, X, xy, max_err, error2);
+    *inlier = ml_check(Rt, GeoCam{cam->fx, cam->fy, cam->cx, cam->cy}, X, xy, max_err, error2);
     return XFH_OK;
 }
 

@@ -18,7 +18,7 @@ static bool s3_strides_ok(int B, int max_iters, size_t draws_stride, size_t T1w_
 static bool s3_merge_dims_ok(int J, int n1, int n2, int M) {
     return J >= 1 && J <= 65535 && n1 >= 1 && n1 <= XFH_GRID_MAX_N && n2 >= 1 && n2 <= XFH_GRID_MAX_N && M >= 1 && M <= S3_MAX_POINTS;
 }
-static TvCam s3_cam(const xfh_camera* c) { return TvCam{c->fx, c->fy, c->cx, c->cy}; }
+static GeoCam s3_cam(const xfh_camera* c) { return GeoCam{c->fx, c->fy, c->cx, c->cy}; }
 
 static S3Args s3_args(int B, int n1, int M, const float* points, const int* point1, const int* matched, const float* T1w, size_t T1w_stride, const float* T2w,
                       const xfh_camera* cam1, const xfh_camera* cam2, float max_err1, float max_err2, int fix_scale, int min_inliers, int min_matches,
@@ -49,7 +49,7 @@ int xfh_sim3_solve_iterations_table(double prob, int min_inliers, int max_its, i
 
 int xfh_sim3_solve_set(const int* draws3, int rand_max, int N, int* set3) {
     if (!draws3 || !set3 || rand_max < 1 || N < 3) return XFH_ERR_INVALID_ARG;
-    s3_set(draws3, rand_max, N, set3);
+    geo_set<3>(draws3, rand_max, N, set3);
     return XFH_OK;
 }
 
@@ -63,7 +63,7 @@ int xfh_sim3_solve_check(const float* T12, const float* T21, const xfh_camera* c
                          float max_err2, float* err, int* inlier) {
     if (!T12 || !T21 || !cam1 || !cam2 || !X1 || !X2 || !err || !inlier) return XFH_ERR_INVALID_ARG;
     float p1[2], p2[2];
-    const TvCam k1 = s3_cam(cam1), k2 = s3_cam(cam2);
+    const GeoCam k1 = s3_cam(cam1), k2 = s3_cam(cam2);
     s3_project(k1, X1, p1); s3_project(k2, X2, p2);
     *inlier = s3_check(T12, T21, k1, k2, X1, X2, p1, p2, max_err1, max_err2, err);
     return XFH_OK;
@@ -146,7 +146,7 @@ int xfh_sim3_merge_matches_device(xfh_ctx* c, int J, int n1, int n2, int M, cons
 int xfh_sim3_merge_matches(xfh_ctx* c, int J, int n1, int n2, int M, const int* match12, const int* point2, int* matched, int* matched_kf, int* num_matches) {
     if (!c || !s3_merge_dims_ok(J, n1, n2, M) || !match12 || !point2 || !matched || !matched_kf || !num_matches) return XFH_ERR_INVALID_ARG;
     HostStage s{c};
-    auto m = s.in<int>(match12, (size_t)J * n1 * 4); auto p2 = s.in<int>(point2, (size_t)J * n2 * 4); auto ws = s.tmp<unsigned char>(tv_al16((size_t)M * 4));
+    auto m = s.in<int>(match12, (size_t)J * n1 * 4); auto p2 = s.in<int>(point2, (size_t)J * n2 * 4); auto ws = s.tmp<unsigned char>(geo_al16((size_t)M * 4));
     auto o0 = s.out<int>(matched, (size_t)n1 * 4); auto o1 = s.out<int>(matched_kf, (size_t)n1 * 4); auto o2 = s.out<int>(num_matches, 4);
     if (const int rc = s.upload(); rc != XFH_OK) return rc;
     const int rc = xfh_sim3_merge_matches_device(c, J, n1, n2, M, m, p2, (unsigned char*)ws, o0, o1, o2);

@@ -20,7 +20,7 @@ static TvArgs tv_args(int B, int n1, int n2, const float* xy1, const float* xy2,
                       uint8_t* inl_h, uint8_t* inl_f, uint8_t* tri, float* p3d, int* matches_out) {
     TvArgs a = {};
     a.B = B; a.n1 = n1; a.n2 = n2; a.iters = iters; a.rand_max = rand_max; a.min_tri = min_triangulated; a.draws_stride = stride;
-    a.cam = TvCam{cam->fx, cam->fy, cam->cx, cam->cy}; a.sigma = sigma; a.min_parallax_cos = min_parallax_cos;
+    a.cam = GeoCam{cam->fx, cam->fy, cam->cx, cam->cy}; a.sigma = sigma; a.min_parallax_cos = min_parallax_cos;
     a.xy1 = xy1; a.xy2 = xy2; a.match12 = matches12; a.draws = draws; a.ws = (unsigned char*)ws;
     a.header = header; a.fout = floats; a.inl_h = inl_h; a.inl_f = inl_f; a.tri = tri; a.p3d = p3d; a.matches_out = matches_out;
     return a;
@@ -35,14 +35,14 @@ size_t xfh_two_view_workspace_bytes(int n1, int n2, int iters, int B) {
 
 int xfh_two_view_set(const int* draws8, int rand_max, int N, int* set8) {
     if (!draws8 || !set8 || rand_max < 1 || N < 8) return XFH_ERR_INVALID_ARG;
-    tv_set(draws8, rand_max, N, set8);
+    geo_set<TV_MIN_SET>(draws8, rand_max, N, set8);
     return XFH_OK;
 }
 
 int xfh_two_view_fit(int model, const float* xy1n, const float* xy2n, float* M) {
     if (!tv_model_ok(model) || !xy1n || !xy2n || !M) return XFH_ERR_INVALID_ARG;
     double u[144], v[81];
-    const TvMat U{u, 1}, V{v, 1};
+    const GeoMat U{u, 1}, V{v, 1};
     if (model == TV_MODEL_H) tv_fit_h(xy1n, xy2n, U, V, M); else tv_fit_f(xy1n, xy2n, U, V, M);
     return XFH_OK;
 }
@@ -56,7 +56,7 @@ int xfh_two_view_score(int model, const float* M, float sigma, const float* xy1,
 int xfh_two_view_check_rt(const xfh_camera* cam, const float* T21, float sigma, const float* xy1, const float* xy2, int* verdict, float* cos_parallax,
                           float* p3d) {
     if (!cam || !T21 || !xy1 || !xy2 || !verdict || !cos_parallax || !p3d || !isfinite(sigma) || !(sigma > 0.0f)) return XFH_ERR_INVALID_ARG;
-    *verdict = tv_check_rt_pair(TvCam{cam->fx, cam->fy, cam->cx, cam->cy}, T21, tv_th2(sigma), xy1[0], xy1[1], xy2[0], xy2[1], cos_parallax, p3d);
+    *verdict = tv_check_rt_pair(GeoCam{cam->fx, cam->fy, cam->cx, cam->cy}, T21, tv_th2(sigma), xy1[0], xy1[1], xy2[0], xy2[1], cos_parallax, p3d);
     return XFH_OK;
 }
 

@@ -15,28 +15,24 @@
 // No global atomics, no waiting between workgroups; every loop is bounded (Jacobi sweeps <= 30, Gauss-Newton rounds <= 5).
 #pragma once
 #include "mlpnp_math.h"
+#include "block_common.hip.h"
 
-#define XFH_ML_THREADS TV_LANES
+#define XFH_ML_THREADS GEO_LANES
 #define XFH_ML_FIT_LANES 16
 
 __global__ __launch_bounds__(XFH_ML_THREADS)
 void k_mlpnp_prepare(MlArgs a) {
     __shared__ int s_cnt[4];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, b = blockIdx.x, n = a.n;
+    const int tid = threadIdx.x, b = blockIdx.x, n = a.n;
     const MlWs w = ml_ws(a, b);
     int base = 0;
     for (int i0 = 0; i0 < n; i0 += XFH_ML_THREADS) {
         const int i = i0 + tid;
         float pt[3];
         const bool ok = i < n && ml_corr_of(a, b, i, pt);
-        const unsigned long long bal = __ballot(ok);
-        __syncthreads();
-        if (lane == 0) s_cnt[wave] = __popcll(bal);
-        __syncthreads();
-        int before = 0;
-        for (int wv = 0; wv < wave; ++wv) before += s_cnt[wv];
+        __syncthreads();                                                   // s_cnt is free
+        const size_t c = (size_t)block_compact_step(ok, s_cnt, base);      // c < n
         if (ok) {
-            const size_t c = (size_t)(base + before + __popcll(bal & ((1ull << lane) - 1ull)));         // c < n
             w.cm[c] = i;
             for (int k = 0; k < 3; ++k) w.pt[3 * c + k] = pt[k];
             const float x = a.xy_un[2 * (size_t)i], y = a.xy_un[2 * (size_t)i + 1];
@@ -49,7 +45,6 @@ void k_mlpnp_prepare(MlArgs a) {
             for (int k = 0; k < 3; ++k) w.f[3 * c + k] = f[k];
             for (int k = 0; k < 6; ++k) w.rs[6 * c + k] = rs[k];
         }
-        base += ((s_cnt[0] + s_cnt[1]) + s_cnt[2]) + s_cnt[3];
     }
     if (tid == 0) ml_select(a, b, base, w.sel);                            // base <= n
 }
@@ -60,7 +55,7 @@ void k_mlpnp_fit(MlArgs a) {
     const int tid = threadIdx.x, it = blockIdx.x * XFH_ML_FIT_LANES + tid, b = blockIdx.y;
     const MlWs w = ml_ws(a, b);
     if (it >= w.sel[ML_S_END]) return;                                     // (no barrier below; end <= max_iters, so the draws are inside the caller's list)
-    const TvMat U{s_m + tid, XFH_ML_FIT_LANES}, V{s_m + 144 * XFH_ML_FIT_LANES + tid, XFH_ML_FIT_LANES};
+    const GeoMat U{s_m + tid, XFH_ML_FIT_LANES}, V{s_m + 144 * XFH_ML_FIT_LANES + tid, XFH_ML_FIT_LANES};
     double h[ML_HYP];
     ml_fit_iteration(a, b, w, it, U, V, h);
     double* dst = w.hyp + (size_t)it * ML_HYP;
@@ -76,13 +71,7 @@ void k_mlpnp_count(MlArgs a) {
     if (it >= w.sel[ML_S_END]) return;                                     // (the whole wave; no barrier below)
     double Rt[12];
     ml_hyp_Rt(w.hyp + (size_t)it * ML_HYP, Rt);
-    int count = 0;
-    for (int k0 = 0; k0 < N; k0 += 64) {
-        const int k = k0 + lane;
-        float e;
-        const bool in = k < N && ml_check(Rt, a.cam, w.pt + 3 * (size_t)k, w.xy + 2 * (size_t)k, a.max_err, &e);
-        count += __popcll(__ballot(in));
-    }
+    const int count = wave_count(N, [&](int k) { float e; return ml_check(Rt, a.cam, w.pt + 3 * (size_t)k, w.xy + 2 * (size_t)k, a.max_err, &e) != 0; });
     if (lane == 0) w.cnt[it] = count;
 }
 
@@ -114,19 +103,7 @@ struct MlBlock {
 #pragma unroll
                 for (int k = 0; k < K; ++k) part[k] = part[k] + t[k];
             }
-        __syncthreads();                                                   // s_fold is free
-#pragma unroll
-        for (int k = 0; k < K; ++k) s_fold[k * XFH_ML_THREADS + tid] = part[k];
-        __syncthreads();
-        for (int h = XFH_ML_THREADS / 2; h >= 1; h >>= 1) {
-            if (tid < h) {
-#pragma unroll
-                for (int k = 0; k < K; ++k) s_fold[k * XFH_ML_THREADS + tid] = s_fold[k * XFH_ML_THREADS + tid] + s_fold[k * XFH_ML_THREADS + tid + h];
-            }
-            __syncthreads();
-        }
-#pragma unroll
-        for (int k = 0; k < K; ++k) out[k] = s_fold[k * XFH_ML_THREADS];
+        block_tree_fold<double, K>(s_fold, part, out);
     }
 };
 
@@ -136,7 +113,7 @@ void k_mlpnp_refine(MlArgs a) {
     __shared__ double s_m[288];
     __shared__ MlShared s_sh;
     __shared__ int s_first[6], s_cnt[4];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = blockIdx.x, b = blockIdx.y;
+    const int tid = threadIdx.x, r = blockIdx.x, b = blockIdx.y;
     const MlWs w = ml_ws(a, b);
     if (w.sel[ML_S_ITS] == 0 || r >= w.sel[ML_S_NREC]) return;             // (the whole workgroup)
     double* rec = w.rec + (size_t)r * ML_HYP;
@@ -154,15 +131,9 @@ void k_mlpnp_refine(MlArgs a) {
         float e;
         const bool in = c < N && ml_check(Rt, a.cam, w.pt + 3 * (size_t)c, w.xy + 2 * (size_t)c, a.max_err, &e);
         if (in) mask |= 1ull << j;
-        const unsigned long long bal = __ballot(in);
-        __syncthreads();
-        if (lane == 0) s_cnt[wave] = __popcll(bal);
-        __syncthreads();
-        int before = 0;
-        for (int wv = 0; wv < wave; ++wv) before += s_cnt[wv];
-        const int pos = base + before + __popcll(bal & ((1ull << lane) - 1ull));
+        __syncthreads();                                                   // s_cnt is free
+        const int pos = block_compact_step(in, s_cnt, base);
         if (in && pos < 6) s_first[pos] = c;
-        base += ((s_cnt[0] + s_cnt[1]) + s_cnt[2]) + s_cnt[3];
     }
     __syncthreads();
     if (base < 6) {                                                         // (cannot happen: a record's count is >= min_inliers_eff >= 6; the whole workgroup)
@@ -171,16 +142,13 @@ void k_mlpnp_refine(MlArgs a) {
     }
     MlBlock cx{w, N, mask, s_fold, s_first};
     double Rr[12]; int planar;
-    ml_compute_pose(cx, TvMat{s_m, 1}, TvMat{s_m + 144, 1}, &s_sh, Rr, &planar);
+    ml_compute_pose(cx, GeoMat{s_m, 1}, GeoMat{s_m + 144, 1}, &s_sh, Rr, &planar);
     int count = 0;
     for (int c = tid; c < N; c += XFH_ML_THREADS) { float e; count += ml_check(Rr, a.cam, w.pt + 3 * (size_t)c, w.xy + 2 * (size_t)c, a.max_err, &e); }
-    count = wave_sum_i32(count);
-    __syncthreads();
-    if (lane == 0) s_cnt[wave] = count;
-    __syncthreads();
+    count = block_sum_i32(s_cnt, count);
     if (tid != 0) return;
     for (int rr = 0; rr < 3; ++rr) { for (int cc = 0; cc < 3; ++cc) rec[ML_P_R + 3 * rr + cc] = Rr[4 * rr + cc]; rec[ML_P_T + rr] = Rr[4 * rr + 3]; }
-    rec[ML_P_PLANAR] = (double)planar; rec[ML_P_COUNT] = (double)(((s_cnt[0] + s_cnt[1]) + s_cnt[2]) + s_cnt[3]); rec[14] = 0.0; rec[15] = 0.0;
+    rec[ML_P_PLANAR] = (double)planar; rec[ML_P_COUNT] = (double)count; rec[14] = 0.0; rec[15] = 0.0;
 }
 
 __global__ __launch_bounds__(XFH_ML_THREADS)

@@ -6,9 +6,7 @@
 // single-thread form of the whole rule, xfh_mlpnp_solve_host, included) and tests/cpp/asan_mlpnp_test.cpp compile these very lines.
 // All arithmetic is fp64 in the order written (the library is built with -ffp-contract=off) except where a float is spelled out.
 #pragma once
-#include "hd.h"
-#include "twoview_math.h"
-#include "poseopt_math.h"
+#include "geom_common.h"
 #include <math.h>
 #include <float.h>
 #include <stdint.h>
@@ -32,24 +30,8 @@ XFH_HD double ml_norm3(const double* a) { return sqrt((a[0] * a[0] + a[1] * a[1]
 // M v of a row-major 3 x 3; Mt v of its transpose
 XFH_HD void ml_mv(const double* M, const double* v, double* o) { for (int r = 0; r < 3; ++r) o[r] = (M[3 * r] * v[0] + M[3 * r + 1] * v[1]) + M[3 * r + 2] * v[2]; }
 XFH_HD void ml_mtv(const double* M, const double* v, double* o) { for (int c = 0; c < 3; ++c) o[c] = (M[c] * v[0] + M[3 + c] * v[1]) + M[6 + c] * v[2]; }
-XFH_HD double ml_det3(const double* A) {
-    return (A[0] * (A[4] * A[8] - A[5] * A[7]) - A[1] * (A[3] * A[8] - A[5] * A[6])) + A[2] * (A[3] * A[7] - A[4] * A[6]);
-}
 
-// ---- step 4: the minimal set of one iteration (:128-140): six draws on the shrinking vAvailableIndices, s3_set's rule for six.  N >= 6. ------------------
-XFH_HD void ml_set(const int* draws6, int rand_max, int N, int* set6) {
-    int pos[ML_MIN_SET], val[ML_MIN_SET], nd = 0;
-    for (int j = 0; j < ML_MIN_SET; ++j) {
-        const int size = N - j, r = tv_draw_index(draws6[j], rand_max, size), last = size - 1;
-        int idx = r, back = last, at = -1;
-        for (int k = 0; k < nd; ++k) {
-            if (pos[k] == r) { idx = val[k]; at = k; }
-            if (pos[k] == last) back = val[k];
-        }
-        set6[j] = idx;
-        if (at >= 0) val[at] = back; else { pos[nd] = r; val[nd] = back; ++nd; }
-    }
-}
+// ---- step 4: the minimal set of one iteration (:128-140): six draws on the shrinking vAvailableIndices, geo_set<ML_MIN_SET>.  N >= 6. ---------------------
 
 // ---- step 2: SetRansacParameters (:225-260) for one N: host libm, so both values are tables the caller fills on the host ------------------------------
 inline void ml_params(double prob, int min_inliers, int max_its, int min_set, float eps, int N, int* its, int* min_eff) {
@@ -71,7 +53,7 @@ inline void ml_params(double prob, int min_inliers, int max_its, int min_set, fl
 }
 
 // ---- step 1: the bearing vector of one keypoint, float: Pinhole::unproject, then `/= z` with z == 1 --------------------------------------------------
-XFH_HD void ml_bearing(const TvCam& k, float x, float y, float* f) { f[0] = (x - k.cx) / k.fx; f[1] = (y - k.cy) / k.fy; f[2] = 1.0f; }
+XFH_HD void ml_bearing(const GeoCam& k, float x, float y, float* f) { f[0] = (x - k.cx) / k.fx; f[1] = (y - k.cy) / k.fy; f[2] = 1.0f; }
 // ---- step 5 (a): columns 2 and 3 of the Householder reflection that maps f = (x, y, 1) onto -sg |f| e_1 ------------------------------------------------
 XFH_HD void ml_nullspace(const double* f, double* rs) {
     const double n = sqrt((f[0] * f[0] + f[1] * f[1]) + f[2] * f[2]), sg = f[0] >= 0.0 ? n : -n;
@@ -82,13 +64,14 @@ XFH_HD void ml_nullspace(const double* f, double* rs) {
     rs[3] = -(c2 * v[0]); rs[4] = -(c2 * v[1]); rs[5] = 1.0 - c2 * v[2];
 }
 
-// ---- the fp64 one-sided Jacobi of twoview_math.h for a square matrix of run-time size n (3, 9 or 12) in caller-given storage ---------------------------
-// U (n x n, row-major) <- U V with orthogonal columns; V accumulates from the identity.  For a symmetric U the columns of V are its eigenvectors
-// and the column norms of U the magnitudes of its eigenvalues.
-XFH_HD void ml_jacobi(const TvMat& U, const TvMat& V, int n) {
+// ---- the fp64 one-sided Jacobi for a square matrix of run-time size n (3, 9 or 12) in caller-given storage, with its column helpers ---------------------
+// geo_jacobi<0>, geo_col_dot and geo_order3 of geom_common.h term by term, but written out here: k_mlpnp_fit sits at 256 VGPRs + 256 AGPRs with 1020
+// bytes of scratch, and with the shared forms inlined the same registers and scratch are allocated differently and it runs 2.4 - 3 % slower
+// (profiles/geometry_common.md).  U (n x n, row-major) <- U V with orthogonal columns; V accumulates from the identity.
+XFH_HD void ml_jacobi(const GeoMat& U, const GeoMat& V, int n) {
     for (int r = 0; r < n; ++r)
         for (int c = 0; c < n; ++c) V(r * n + c) = r == c ? 1.0 : 0.0;
-    for (int sweep = 0; sweep < TRIANG_MAX_SWEEPS; ++sweep) {
+    for (int sweep = 0; sweep < GEO_JACOBI_MAX_SWEEPS; ++sweep) {
         int rot = 0;
         for (int p = 0; p < n - 1; ++p)
             for (int q = p + 1; q < n; ++q) {
@@ -98,7 +81,7 @@ XFH_HD void ml_jacobi(const TvMat& U, const TvMat& V, int n) {
                     alpha = alpha + up * up; beta = beta + uq * uq; gamma = gamma + up * uq;
                 }
                 double c, s;
-                if (!triang_jacobi_rotation(alpha, beta, gamma, &c, &s)) continue;
+                if (!geo_jacobi_rotation(alpha, beta, gamma, &c, &s)) continue;
                 for (int r = 0; r < n; ++r) {
                     const double up = U(r * n + p), uq = U(r * n + q), vp = V(r * n + p), vq = V(r * n + q);
                     U(r * n + p) = c * up - s * uq; U(r * n + q) = s * up + c * uq;
@@ -109,27 +92,20 @@ XFH_HD void ml_jacobi(const TvMat& U, const TvMat& V, int n) {
         if (rot == 0) break;
     }
 }
-XFH_HD double ml_col_norm2(const TvMat& U, int n, int c) {
+XFH_HD double ml_col_norm2(const GeoMat& U, int n, int c) {
     double s = U(c) * U(c);
     for (int r = 1; r < n; ++r) s = s + U(r * n + c) * U(r * n + c);
     return s;
 }
-// the column of least squared norm, the LAST on a tie (a NaN never wins)
-XFH_HD int ml_min_col_last(const TvMat& U, int n) {
-    int best = 0;
-    double bn = ml_col_norm2(U, n, 0);
-    for (int c = 1; c < n; ++c) { const double v = ml_col_norm2(U, n, c); if (v <= bn) { bn = v; best = c; } }
-    return best;
-}
 // the three columns of a 3 x 3 by squared norm: o[0..2] descending, stable
-XFH_HD void ml_order3(const TvMat& U, int* o) {
+XFH_HD void ml_order3(const GeoMat& U, int* o) {
     double n2[3];
     for (int c = 0; c < 3; ++c) { n2[c] = ml_col_norm2(U, 3, c); o[c] = c; }
     for (int a = 1; a < 3; ++a)
         for (int b = a; b > 0 && n2[o[b]] > n2[o[b - 1]]; --b) { const int t = o[b]; o[b] = o[b - 1]; o[b - 1] = t; }
 }
 // U V^T of the SVD of A (row-major 3 x 3): (u0 v0^T + u1 v1^T) + u2 v2^T, columns by norm descending, u = column / norm
-XFH_HD void ml_nearest_rotation(const double* A, const TvMat& U, const TvMat& V, double* R) {
+XFH_HD void ml_nearest_rotation(const double* A, const GeoMat& U, const GeoMat& V, double* R) {
     for (int k = 0; k < 9; ++k) U(k) = A[k];
     ml_jacobi(U, V, 3);
     int o[3]; double w[3];
@@ -177,15 +153,13 @@ XFH_HD int ml_rank3(const double* S6) {
     return rank;
 }
 // eigenRot: the eigenvectors of S as ROWS, increasing eigenvalue (column norm of the Jacobi's U), stable
-XFH_HD void ml_eigen_rot(const double* S6, const TvMat& U, const TvMat& V, double* E) {
+XFH_HD void ml_eigen_rot(const double* S6, const GeoMat& U, const GeoMat& V, double* E) {
     const double A[9] = {S6[0], S6[1], S6[2], S6[1], S6[3], S6[4], S6[2], S6[4], S6[5]};
     for (int k = 0; k < 9; ++k) U(k) = A[k];
     ml_jacobi(U, V, 3);
-    int o[3];
-    ml_order3(U, o);                                                        // descending, stable; read from the back with equal norms kept in column order
     double n2[3];
     for (int c = 0; c < 3; ++c) n2[c] = ml_col_norm2(U, 3, c);
-    int inc[3] = {0, 1, 2};
+    int inc[3] = {0, 1, 2};                                                 // ascending, stable: equal norms keep their column order
     for (int a = 1; a < 3; ++a)
         for (int b = a; b > 0 && n2[inc[b]] < n2[inc[b - 1]]; --b) { const int t = inc[b]; inc[b] = inc[b - 1]; inc[b - 1] = t; }
     for (int r = 0; r < 3; ++r)
@@ -299,10 +273,10 @@ XFH_HD int ml_gn_not_below(const double* J, const double* dx) {
 
 // ---- step 5 (d), (e): from the finished A^T A in U (cols x cols, symmetric) to the linear estimate x = (w, T) -------------------------------------------
 // f6, p6: the FIRST six correspondences (bearing vector, point), [6][3]
-XFH_HD void ml_linear(const TvMat& U, const TvMat& V, bool planar, const double* E, const double* f6, const double* p6, double* x) {
+XFH_HD void ml_linear(const GeoMat& U, const GeoMat& V, bool planar, const double* E, const double* f6, const double* p6, double* x) {
     const int cols = planar ? 9 : 12;
     ml_jacobi(U, V, cols);
-    const int col = ml_min_col_last(U, cols);
+    const int col = geo_min_col(U, cols, cols, true);
     double res[12];
     for (int k = 0; k < 12; ++k) res[k] = k < cols ? V(k * cols + col) : 0.0;
     double Rout[9], tout[3];
@@ -314,11 +288,11 @@ XFH_HD void ml_linear(const TvMat& U, const TvMat& V, bool planar, const double*
         const double scale = 1.0 / sqrt(fabs(ml_norm3(k1) * ml_norm3(k2)));
         double R1[9], Rb[9];
         ml_nearest_rotation(tmp, U, V, R1);
-        if (ml_det3(R1) < 0.0) for (int k = 0; k < 9; ++k) R1[k] = R1[k] * -1.0;
+        if (geo_det3(R1) < 0.0) for (int k = 0; k < 9; ++k) R1[k] = R1[k] * -1.0;
         for (int i = 0; i < 3; ++i)                                             // eigenRot^T R1, then transposed and negated
             for (int j = 0; j < 3; ++j) Rb[3 * j + i] = ((E[i] * R1[j] + E[3 + i] * R1[3 + j]) + E[6 + i] * R1[6 + j]) * -1.0;
         const double t[3] = {scale * res[6], scale * res[7], scale * res[8]};
-        if (ml_det3(Rb) < 0.0) { Rb[2] = Rb[2] * -1.0; Rb[5] = Rb[5] * -1.0; Rb[8] = Rb[8] * -1.0; }
+        if (geo_det3(Rb) < 0.0) { Rb[2] = Rb[2] * -1.0; Rb[5] = Rb[5] * -1.0; Rb[8] = Rb[8] * -1.0; }
         double best = 0.0; int bi = 0;
         for (int i = 0; i < 4; ++i) {
             const double sr = i >= 2 ? -1.0 : 1.0, st = (i & 1) ? -1.0 : 1.0;
@@ -340,7 +314,7 @@ XFH_HD void ml_linear(const TvMat& U, const TvMat& V, bool planar, const double*
         const double scale = 1.0 / cbrt(fabs((ml_norm3(k0) * ml_norm3(k1)) * ml_norm3(k2)));
         double R[9];
         ml_nearest_rotation(tmp, U, V, R);
-        if (ml_det3(R) < 0.0) for (int k = 0; k < 9; ++k) R[k] = R[k] * -1.0;
+        if (geo_det3(R) < 0.0) for (int k = 0; k < 9; ++k) R[k] = R[k] * -1.0;
         const double ts[3] = {scale * res[9], scale * res[10], scale * res[11]};
         double t0[3], ti[3];
         ml_mv(R, ts, t0);
@@ -374,7 +348,7 @@ XFH_HD void ml_linear(const TvMat& U, const TvMat& V, bool planar, const double*
 //   leader() / sync()          one thread runs the serial parts on the shared state (U, V, *w), the others wait
 struct MlShared { double E[9], x[6], dx[6], s6[6]; int planar, stop; };
 template <class Cx>
-XFH_HD void ml_compute_pose(Cx& cx, const TvMat& U, const TvMat& V, MlShared* w, double* Rt, int* planar_out) {
+XFH_HD void ml_compute_pose(Cx& cx, const GeoMat& U, const GeoMat& V, MlShared* w, double* Rt, int* planar_out) {
     double t[ML_CHUNK];
     cx.template sum<6>([&](int c, double* o) {
         double f[3], p[3], r[3], s[3];
@@ -482,7 +456,7 @@ struct MlSet6 {
 };
 
 // ---- step 6: CheckInliers of one correspondence; a NaN never passes ---------------------------------------------------------------------------------------
-XFH_HD int ml_check(const double* Rt, const TvCam& k, const float* X, const float* xy, float max_err, float* error2) {
+XFH_HD int ml_check(const double* Rt, const GeoCam& k, const float* X, const float* xy, float max_err, float* error2) {
     const float xc = (float)(((Rt[0] * (double)X[0] + Rt[1] * (double)X[1]) + Rt[2] * (double)X[2]) + Rt[3]);
     const float yc = (float)(((Rt[4] * (double)X[0] + Rt[5] * (double)X[1]) + Rt[6] * (double)X[2]) + Rt[7]);
     const float zc = (float)(((Rt[8] * (double)X[0] + Rt[9] * (double)X[1]) + Rt[10] * (double)X[2]) + Rt[11]);
@@ -518,7 +492,6 @@ XFH_HD int ml_winner(const int* rec_use, const double* rec, int nrec, int min_ef
 XFH_HD void ml_too_few_header(int* hdr, int N) {
     for (int k = 0; k < ML_HEADER_INTS; ++k) hdr[k] = k == ML_H_N ? N : (k == ML_H_WINNER || k == ML_H_BEST ? -1 : 0);
 }
-XFH_HD int ml_clamp_its(int v, int max_iters) { return v < 1 ? 1 : (v > max_iters ? max_iters : v); }
 // end of the loop of a call that starts at k0 (overflow-free: chunk and k0 are clamped to max_iters first)
 XFH_HD int ml_end(int its, int k0, int chunk, int max_iters) {
     const int c = chunk > max_iters ? max_iters : chunk, s = k0 > max_iters ? max_iters : k0;
@@ -530,18 +503,18 @@ XFH_HD int ml_end(int its, int k0, int chunk, int max_iters) {
 struct MlLayout { size_t cm, pt, xy, f, rs, sel, hyp, cnt, rec_it, rec_use, rec, per_problem; };
 XFH_HD MlLayout ml_layout(int n, int max_iters) {
     MlLayout L; size_t o = 0;
-    L.cm = o; o += tv_al16((size_t)n * 4);                   // int: the keypoint of correspondence c
-    L.pt = o; o += tv_al16((size_t)n * 12);                  // float [n][3]: its point
-    L.xy = o; o += tv_al16((size_t)n * 8);                   // float [n][2]: its keypoint position
-    L.f = o; o += tv_al16((size_t)n * 12);                   // float [n][3]: its bearing vector
-    L.rs = o; o += tv_al16((size_t)n * 48);                  // double [n][6]: its basis
+    L.cm = o; o += geo_al16((size_t)n * 4);                   // int: the keypoint of correspondence c
+    L.pt = o; o += geo_al16((size_t)n * 12);                  // float [n][3]: its point
+    L.xy = o; o += geo_al16((size_t)n * 8);                   // float [n][2]: its keypoint position
+    L.f = o; o += geo_al16((size_t)n * 12);                   // float [n][3]: its bearing vector
+    L.rs = o; o += geo_al16((size_t)n * 48);                  // double [n][6]: its basis
     L.sel = o; o += 32;                                      // int [8]: ML_S_*
     L.hyp = o; o += (size_t)max_iters * ML_HYP * 8;          // double [max_iters][16]
-    L.cnt = o; o += tv_al16((size_t)max_iters * 4);
-    L.rec_it = o; o += tv_al16((size_t)max_iters * 4);
-    L.rec_use = o; o += tv_al16((size_t)max_iters * 4);
+    L.cnt = o; o += geo_al16((size_t)max_iters * 4);
+    L.rec_it = o; o += geo_al16((size_t)max_iters * 4);
+    L.rec_use = o; o += geo_al16((size_t)max_iters * 4);
     L.rec = o; o += (size_t)max_iters * ML_HYP * 8;          // double [max_iters][16]: the Refine of record r
-    L.per_problem = tv_al16(o);
+    L.per_problem = geo_al16(o);
     return L;
 }
 
@@ -549,7 +522,7 @@ XFH_HD MlLayout ml_layout(int n, int max_iters) {
 struct MlArgs {
     int B, n, nq, max_iters, rand_max, min_matches, chunk;
     size_t draws_stride;
-    TvCam cam;
+    GeoCam cam;
     float max_err;
     const float *xy_un, *points;
     const int *assigned, *n_matches, *iters_of_N, *min_of_N, *start_iter, *draws;
@@ -581,16 +554,16 @@ XFH_HD void ml_select(const MlArgs& a, int b, int N, int* sel) {
     int min_eff = a.min_of_N[N];                                            // N <= n: inside the tables of n + 1 entries
     if (min_eff < ML_MIN_SET) min_eff = ML_MIN_SET;                         // (max(.., min_set) of step 2, whatever the table holds)
     const bool few = N < min_eff || N < ML_MIN_SET || (a.n_matches && a.n_matches[b] < a.min_matches);
-    const int its = few ? 0 : ml_clamp_its(a.iters_of_N[N], a.max_iters);
+    const int its = few ? 0 : geo_clamp_its(a.iters_of_N[N], a.max_iters);
     int k0 = a.start_iter ? a.start_iter[b] : 0;
     if (k0 < 0) k0 = 0;
     sel[ML_S_N] = N; sel[ML_S_ITS] = its; sel[ML_S_MIN] = min_eff; sel[ML_S_END] = few ? 0 : ml_end(its, k0, a.chunk, a.max_iters); sel[ML_S_K0] = k0;
     sel[ML_S_BEST_COUNT] = 0; sel[ML_S_BEST] = -1; sel[ML_S_NREC] = 0;
 }
 // one hypothesis: the set of iteration `it`, step 5 on its six points -> hyp [ML_HYP]
-XFH_HD void ml_fit_iteration(const MlArgs& a, int b, const MlWs& w, int it, const TvMat& U, const TvMat& V, double* hyp) {
+XFH_HD void ml_fit_iteration(const MlArgs& a, int b, const MlWs& w, int it, const GeoMat& U, const GeoMat& V, double* hyp) {
     int set[ML_MIN_SET];
-    ml_set(a.draws + (size_t)b * a.draws_stride + (size_t)ML_MIN_SET * it, a.rand_max, w.sel[ML_S_N], set);
+    geo_set<ML_MIN_SET>(a.draws + (size_t)b * a.draws_stride + (size_t)ML_MIN_SET * it, a.rand_max, w.sel[ML_S_N], set);
     MlSet6 cx;
     for (int j = 0; j < ML_MIN_SET; ++j) {
         const size_t c = (size_t)set[j];
@@ -642,13 +615,10 @@ struct MlHostFold {
             for (int c = 0; c < N; ++c) if (!flag || flag[c]) { term(c, t); for (int k = 0; k < K; ++k) out[k] = out[k] + t[k]; }
             return;
         }
-        double s[K][TV_LANES];
-        for (int k = 0; k < K; ++k) for (int l = 0; l < TV_LANES; ++l) s[k][l] = 0.0;
-        for (int c = 0; c < N; ++c) if (!flag || flag[c]) { term(c, t); for (int k = 0; k < K; ++k) s[k][c % TV_LANES] = s[k][c % TV_LANES] + t[k]; }
-        for (int k = 0; k < K; ++k) {
-            for (int h = TV_LANES / 2; h >= 1; h >>= 1) for (int l = 0; l < h; ++l) s[k][l] = s[k][l] + s[k][l + h];
-            out[k] = s[k][0];
-        }
+        double s[K][GEO_LANES];
+        for (int k = 0; k < K; ++k) for (int l = 0; l < GEO_LANES; ++l) s[k][l] = 0.0;
+        for (int c = 0; c < N; ++c) if (!flag || flag[c]) { term(c, t); for (int k = 0; k < K; ++k) s[k][c % GEO_LANES] = s[k][c % GEO_LANES] + t[k]; }
+        for (int k = 0; k < K; ++k) out[k] = geo_tree_fold(s[k]);
     }
 };
 // step 5 of the flagged correspondences (at least six flagged); false when fewer than six are
@@ -659,7 +629,7 @@ inline bool ml_host_pose(int N, const float* f, const float* pt, const double* r
     if (nf < 6) return false;
     double Um[144], Vm[144];
     MlShared sh;
-    ml_compute_pose(cx, TvMat{Um, 1}, TvMat{Vm, 1}, &sh, Rt, planar);
+    ml_compute_pose(cx, GeoMat{Um, 1}, GeoMat{Vm, 1}, &sh, Rt, planar);
     return true;
 }
 
@@ -690,7 +660,7 @@ inline void ml_host_problem(const MlArgs& a, int b, unsigned char* flag /* n byt
     double Um[144], Vm[144];
     for (int it = 0; it < end; ++it) {
         double* h = w.hyp + (size_t)it * ML_HYP;
-        ml_fit_iteration(a, b, w, it, TvMat{Um, 1}, TvMat{Vm, 1}, h);
+        ml_fit_iteration(a, b, w, it, GeoMat{Um, 1}, GeoMat{Vm, 1}, h);
         double Rt[12];
         ml_hyp_Rt(h, Rt);
         int c = 0;

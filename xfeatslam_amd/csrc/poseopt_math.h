@@ -5,7 +5,7 @@
 // (optimization_algorithm_levenberg.cpp:61-194) as a state machine that one lane or one host thread drives.  IEEE double throughout, every
 // product and sum in the order written here (the library is built without contraction); tests/ref_poseopt.py restates these lines.
 #pragma once
-#include "hd.h"
+#include "geom_common.h"
 #include <math.h>
 #include <float.h>
 
@@ -206,40 +206,7 @@ XFH_HD void pose_accumulate(double* acc, const double* J, const double* e, bool 
     }
 }
 
-// (H + lambda I) x = b by an unpivoted LDL^T in place of Eigen's pivoting LDLT + isPositive(): false, with x untouched, as soon as a pivot is not > 0
-// (a NaN pivot included).  H is the 21 upper entries.
-XFH_HD bool pose_ldlt_solve(const double* H, double lambda, const double* b, double* x) {
-    double A[6][6], d[6], y[6];
-    int n = 0;
-    _Pragma("unroll")
-    for (int i = 0; i < 6; ++i)
-        _Pragma("unroll")
-        for (int j = i; j < 6; ++j, ++n) { A[i][j] = H[n]; A[j][i] = H[n]; }
-    _Pragma("unroll")
-    for (int i = 0; i < 6; ++i) A[i][i] = A[i][i] + lambda;
-    _Pragma("unroll")
-    for (int j = 0; j < 6; ++j) {                                           // the strict lower triangle of A becomes L
-        double dj = A[j][j];
-        _Pragma("unroll")
-        for (int k = 0; k < j; ++k) dj = dj - A[j][k] * A[j][k] * d[k];
-        if (!(dj > 0.0)) return false;
-        d[j] = dj;
-        _Pragma("unroll")
-        for (int i = j + 1; i < 6; ++i) {
-            double s = A[i][j];
-            _Pragma("unroll")
-            for (int k = 0; k < j; ++k) s = s - A[i][k] * A[j][k] * d[k];
-            A[i][j] = s / dj;
-        }
-    }
-    _Pragma("unroll")
-    for (int i = 0; i < 6; ++i) { double s = b[i]; for (int k = 0; k < i; ++k) s = s - A[i][k] * y[k]; y[i] = s; }
-    _Pragma("unroll")
-    for (int i = 0; i < 6; ++i) y[i] = y[i] / d[i];
-    _Pragma("unroll")
-    for (int i = 5; i >= 0; --i) { double s = y[i]; for (int k = i + 1; k < 6; ++k) s = s - A[k][i] * x[k]; x[i] = s; }
-    return true;
-}
+// (H + lambda I) x = b of the Levenberg step: pose_ldlt_solve of geom_common.h, the unpivoted 6 x 6 LDL^T that MLPnP's Gauss-Newton shares.
 
 // ---- the four rounds of optimize(10) as a state machine.  The driver runs the pass an action asks for over every edge at S.est and hands the folded
 // sums back: BUILD wants all XFH_POSE_NSUM (computeActiveErrors + activeRobustChi2 + buildSystem), TRIAL only the robust chi2 (sums[27]), CLASSIFY the

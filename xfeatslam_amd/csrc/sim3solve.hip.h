@@ -15,6 +15,7 @@
 // and the owner count (an integer atomicAdd per workgroup) do not depend on the order of arrival: two runs give identical bytes.
 #pragma once
 #include "sim3solve_math.h"
+#include "block_common.hip.h"
 
 #define XFH_S3_THREADS 256
 #define XFH_S3_FIT_LANES 64
@@ -32,31 +33,25 @@ __device__ __forceinline__ S3Ws s3_ws(const S3Args& a, int b) {
 __global__ __launch_bounds__(XFH_S3_THREADS)
 void k_sim3solve_prepare(S3Args a) {
     __shared__ int s_cnt[4];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, b = blockIdx.x, n1 = a.n1;
+    const int tid = threadIdx.x, b = blockIdx.x, n1 = a.n1;
     const S3Ws w = s3_ws(a, b);
     int base = 0;
     for (int i0 = 0; i0 < n1; i0 += XFH_S3_THREADS) {
         const int i = i0 + tid;
         float X1[3], X2[3], p1[2], p2[2];
         const bool ok = i < n1 && s3_corr(a, b, i, X1, X2, p1, p2);
-        const unsigned long long bal = __ballot(ok);
-        __syncthreads();
-        if (lane == 0) s_cnt[wave] = __popcll(bal);
-        __syncthreads();
-        int before = 0;
-        for (int wv = 0; wv < wave; ++wv) before += s_cnt[wv];
+        __syncthreads();                                                   // s_cnt is free
+        const size_t pos = (size_t)block_compact_step(ok, s_cnt, base);    // pos < n1
         if (ok) {
-            const size_t pos = (size_t)(base + before + __popcll(bal & ((1ull << lane) - 1ull)));       // pos < n1
             w.cm[pos] = i;
             for (int c = 0; c < 3; ++c) { w.X1[3 * pos + c] = X1[c]; w.X2[3 * pos + c] = X2[c]; }
             w.P1[2 * pos] = p1[0]; w.P1[2 * pos + 1] = p1[1]; w.P2[2 * pos] = p2[0]; w.P2[2 * pos + 1] = p2[1];
         }
-        base += ((s_cnt[0] + s_cnt[1]) + s_cnt[2]) + s_cnt[3];
     }
     if (tid == 0) {
         const int N = base;                                                // N <= n1: inside the table of n1 + 1 entries
         const bool few = N < 3 || N < a.min_inliers || (a.num_matches && *a.num_matches < a.min_matches);
-        w.sel[0] = N; w.sel[1] = few ? 0 : s3_clamp_its(a.iters_of_N[N], a.max_iters);
+        w.sel[0] = N; w.sel[1] = few ? 0 : geo_clamp_its(a.iters_of_N[N], a.max_iters);
     }
 }
 
@@ -67,7 +62,7 @@ void k_sim3solve_fit(S3Args a) {
     const int N = w.sel[0], its = w.sel[1];
     if (it >= its) return;                                                 // (no barrier below; its <= max_iters, so the draws are inside the caller's list)
     int set[3];
-    s3_set(a.draws + (size_t)b * a.draws_stride + 3 * (size_t)it, a.rand_max, N, set);
+    geo_set<3>(a.draws + (size_t)b * a.draws_stride + 3 * (size_t)it, a.rand_max, N, set);
     float p1[9], p2[9], h[S3_HYP];
 #pragma unroll
     for (int j = 0; j < 3; ++j)
@@ -88,14 +83,10 @@ void k_sim3solve_count(S3Args a) {
     float T12[12], T21[12];
 #pragma unroll
     for (int k = 0; k < 12; ++k) { T12[k] = w.hyp[(size_t)it * S3_HYP + S3_F_T12 + k]; T21[k] = w.hyp[(size_t)it * S3_HYP + S3_F_T21 + k]; }
-    int count = 0;
-    for (int k0 = 0; k0 < N; k0 += 64) {
-        const int k = k0 + lane;
+    const int count = wave_count(N, [&](int k) {
         float err[2];
-        const bool in = k < N && s3_check(T12, T21, a.cam1, a.cam2, w.X1 + 3 * (size_t)k, w.X2 + 3 * (size_t)k, w.P1 + 2 * (size_t)k, w.P2 + 2 * (size_t)k, a.max_err1,
-                                          a.max_err2, err);
-        count += __popcll(__ballot(in));
-    }
+        return s3_check(T12, T21, a.cam1, a.cam2, w.X1 + 3 * (size_t)k, w.X2 + 3 * (size_t)k, w.P1 + 2 * (size_t)k, w.P2 + 2 * (size_t)k, a.max_err1, a.max_err2, err) != 0;
+    });
     if (lane == 0) w.cnt[it] = count;
 }
 

@@ -6,8 +6,7 @@
 // single-thread form of the whole rule, xfh_sim3_solve_host, included) and tests/cpp/asan_sim3solve_test.cpp compile these very lines.
 // All arithmetic is fp32 in the order written (the library is built with -ffp-contract=off) except where a double is spelled out.
 #pragma once
-#include "hd.h"
-#include "twoview_math.h"
+#include "geom_common.h"
 #include <math.h>
 #include <stdint.h>
 #include <stddef.h>
@@ -27,22 +26,9 @@ XFH_HD void s3_transform(const float* T, const float* p, float* X) {
     for (int r = 0; r < 3; ++r) X[r] = ((T[4 * r] * p[0] + T[4 * r + 1] * p[1]) + T[4 * r + 2] * p[2]) + T[4 * r + 3];
 }
 // Pinhole::project (src/CameraModels/Pinhole.cpp:43-49)
-XFH_HD void s3_project(const TvCam& k, const float* X, float* uv) { uv[0] = k.fx * X[0] / X[2] + k.cx; uv[1] = k.fy * X[1] / X[2] + k.cy; }
+XFH_HD void s3_project(const GeoCam& k, const float* X, float* uv) { uv[0] = k.fx * X[0] / X[2] + k.cx; uv[1] = k.fy * X[1] / X[2] + k.cy; }
 
-// ---- the minimal set of one iteration (:245-259): three draws on the shrinking vAvailableIndices, tv_set's rule for three.  N >= 3. -----------------
-XFH_HD void s3_set(const int* draws3, int rand_max, int N, int* set3) {
-    int pos[3], val[3], nd = 0;
-    for (int j = 0; j < 3; ++j) {
-        const int size = N - j, r = tv_draw_index(draws3[j], rand_max, size), last = size - 1;
-        int idx = r, back = last, at = -1;
-        for (int k = 0; k < nd; ++k) {
-            if (pos[k] == r) { idx = val[k]; at = k; }
-            if (pos[k] == last) back = val[k];
-        }
-        set3[j] = idx;
-        if (at >= 0) val[at] = back; else { pos[nd] = r; val[nd] = back; ++nd; }
-    }
-}
+// ---- the minimal set of one iteration (:245-259): three draws on the shrinking vAvailableIndices, geo_set<3>.  N >= 3. ----------------------------------
 
 // ---- SetRansacParameters (:123-147): host libm, so the count is a table the caller fills on the host ---------------------------------------------------
 inline int s3_iterations(double prob, int min_inliers, int max_its, int N) {
@@ -156,7 +142,7 @@ XFH_HD void s3_horn(const float* P1, const float* P2, bool fix_scale, float* hyp
 }
 
 // ---- CheckInliers (:415-439) of one correspondence: err[0] against image 1, err[1] against image 2; a NaN never passes ------------------------------
-XFH_HD int s3_check(const float* T12, const float* T21, const TvCam& k1, const TvCam& k2, const float* X1, const float* X2, const float* p1, const float* p2,
+XFH_HD int s3_check(const float* T12, const float* T21, const GeoCam& k1, const GeoCam& k2, const float* X1, const float* X2, const float* p1, const float* p2,
                     float max_err1, float max_err2, float* err) {
     float q[3], uv[2];
     s3_transform(T12, X2, q); s3_project(k1, q, uv);
@@ -188,25 +174,24 @@ XFH_HD void s3_compose(const float* hyp, const float* T2w, float* Tcw, float* Ow
 // ---- the decision (:240-293 under `while(!bConverge && !bNoMore) iterate(20, ..)`) from the counts of its iterations, order-free ---------------------
 // winner = the first k with count > min_inliers; best = the last k whose count is the largest (count * 4096 + k is its key)
 XFH_HD int s3_best_key(int count, int k) { return count * S3_MAX_ITERS + k; }
-XFH_HD int s3_clamp_its(int v, int max_iters) { return v < 1 ? 1 : (v > max_iters ? max_iters : v); }
 
 // ---- the workspace of one call (device memory, B problems): offsets in bytes, every piece 16-byte aligned ----------------------------------------
 struct S3Layout { size_t cm, X1, X2, P1, P2, sel, hyp, cnt, per_problem; };
 XFH_HD S3Layout s3_layout(int n1) {
     S3Layout L; size_t o = 0;
-    L.cm = o; o += tv_al16((size_t)n1 * 4);                  // int i1 of correspondence k
-    L.X1 = o; o += tv_al16((size_t)n1 * 12);                 // float [n1][3] mvX3Dc1
-    L.X2 = o; o += tv_al16((size_t)n1 * 12);
-    L.P1 = o; o += tv_al16((size_t)n1 * 8);                  // float [n1][2] mvP1im1
-    L.P2 = o; o += tv_al16((size_t)n1 * 8);
+    L.cm = o; o += geo_al16((size_t)n1 * 4);                  // int i1 of correspondence k
+    L.X1 = o; o += geo_al16((size_t)n1 * 12);                 // float [n1][3] mvX3Dc1
+    L.X2 = o; o += geo_al16((size_t)n1 * 12);
+    L.P1 = o; o += geo_al16((size_t)n1 * 8);                  // float [n1][2] mvP1im1
+    L.P2 = o; o += geo_al16((size_t)n1 * 8);
     L.sel = o; o += 32;                                      // int N, its (0: TOO_FEW)
     L.hyp = o; o += (size_t)S3_MAX_ITERS * S3_HYP * 4;       // float [4096][40]
     L.cnt = o; o += (size_t)S3_MAX_ITERS * 4;                // int [4096]
-    L.per_problem = tv_al16(o);
+    L.per_problem = geo_al16(o);
     return L;
 }
 XFH_HD size_t s3_workspace_bytes(int n1, int M, int B) {
-    const size_t solve = s3_layout(n1).per_problem * (size_t)B, merge = tv_al16((size_t)M * 4);       // the merge's owner table lies over the solver's part
+    const size_t solve = s3_layout(n1).per_problem * (size_t)B, merge = geo_al16((size_t)M * 4);       // the merge's owner table lies over the solver's part
     return solve > merge ? solve : merge;
 }
 
@@ -214,7 +199,7 @@ XFH_HD size_t s3_workspace_bytes(int n1, int M, int B) {
 struct S3Args {
     int B, n1, M, max_iters, rand_max, min_inliers, min_matches, fix_scale;
     size_t draws_stride, T1w_stride;
-    TvCam cam1, cam2;
+    GeoCam cam1, cam2;
     float max_err1, max_err2;
     const float *points, *T1w, *T2w;
     const int *point1, *matched, *num_matches, *iters_of_N, *draws;
@@ -246,14 +231,14 @@ inline void s3_host_problem(const S3Args& a, int b) {
     for (int i = 0; i < n1; ++i)
         if (s3_corr(a, b, i, X1 + 3 * (size_t)N, X2 + 3 * (size_t)N, P1 + 2 * (size_t)N, P2 + 2 * (size_t)N)) cm[N++] = i;
     const bool few = N < 3 || N < a.min_inliers || (a.num_matches && *a.num_matches < a.min_matches);
-    sel[0] = N; sel[1] = few ? 0 : s3_clamp_its(a.iters_of_N[N], a.max_iters);
+    sel[0] = N; sel[1] = few ? 0 : geo_clamp_its(a.iters_of_N[N], a.max_iters);
     if (few) { s3_too_few_header(hdr, N); return; }
     const int its = sel[1];
     const int* draws = a.draws + (size_t)b * a.draws_stride;
     int winner = -1, best_key = -1;
     for (int it = 0; it < its; ++it) {
         int set[3]; float p1[9], p2[9];
-        s3_set(draws + 3 * (size_t)it, a.rand_max, N, set);
+        geo_set<3>(draws + 3 * (size_t)it, a.rand_max, N, set);
         for (int j = 0; j < 3; ++j)
             for (int c = 0; c < 3; ++c) { p1[3 * j + c] = X1[3 * (size_t)set[j] + c]; p2[3 * j + c] = X2[3 * (size_t)set[j] + c]; }
         float* h = hyp + (size_t)it * S3_HYP;

@@ -13,6 +13,7 @@
 //                         -1 / 0 tail.  Two runs give identical bytes.
 #pragma once
 #include "triangulate_math.h"
+#include "block_common.hip.h"
 
 #define XFH_TRIANG_THREADS 256
 
@@ -77,14 +78,8 @@ void k_triangulate_finish(TriangArgs a) {
     for (int i0 = 0; i0 < n1; i0 += XFH_TRIANG_THREADS) {
         const int i = i0 + tid;
         const bool mine = i < n1 && a.winner[i] == b;
-        const unsigned long long bal = __ballot(mine);
-        if (lane == 0) s_cnt[wave][0] = __popcll(bal);
-        __syncthreads();
-        int before = 0;
-        for (int wv = 0; wv < wave; ++wv) before += s_cnt[wv][0];
-        const int chunk = ((s_cnt[0][0] + s_cnt[1][0]) + s_cnt[2][0]) + s_cnt[3][0];
+        const int pos = block_compact_step(mine, s_cnt[0], base);         // < n1: one entry per keypoint of KF1 at most; the four ints lie in row 0
         if (mine) {
-            const int pos = base + before + __popcll(bal & ((1ull << lane) - 1ull));      // < n1: one entry per keypoint of KF1 at most
             const size_t kg = (size_t)b * n1 + i;
             const float X[3] = {a.xyz[3 * kg], a.xyz[3 * kg + 1], a.xyz[3 * kg + 2]};
             float nrm[3], dst[3];
@@ -93,8 +88,7 @@ void k_triangulate_finish(TriangArgs a) {
 #pragma unroll
             for (int k = 0; k < 3; ++k) { a.new_xyz[3 * pos + k] = X[k]; a.new_normal[3 * pos + k] = nrm[k]; a.new_dist[3 * pos + k] = dst[k]; }
         }
-        base += chunk;
-        __syncthreads();
+        __syncthreads();                                                   // s_cnt is free for the next step
     }
     if (b == 0) {
         const int n_new = tot[8];

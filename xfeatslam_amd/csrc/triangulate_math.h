@@ -5,13 +5,11 @@
 // (triangulate.hip.h), xfh_triangulate_pair (capi_triangulate.cpp) and tests/cpp/asan_triangulate_test.cpp compile these very lines.
 // All arithmetic is fp32 in the order written (the library is built with -ffp-contract=off) except where a double is spelled out.
 #pragma once
-#include "hd.h"
+#include "geom_common.h"
 #include <math.h>
 
 enum { TRIANG_NO_MATCH = 0, TRIANG_LOW_PARALLAX = 1, TRIANG_STEREO_NO_DEPTH = 2, TRIANG_DEGENERATE = 3, TRIANG_BEHIND1 = 4, TRIANG_BEHIND2 = 5,
        TRIANG_REPROJ1 = 6, TRIANG_REPROJ2 = 7, TRIANG_ZERO_DIST = 8, TRIANG_FAR = 9, TRIANG_SCALE = 10, TRIANG_ACCEPTED = 11, TRIANG_SUPERSEDED = 12 };
-#define TRIANG_MAX_SWEEPS 30
-#define TRIANG_JACOBI_TOL 1e-15
 
 struct TriangParams {
     float fx, fy, cx, cy, invfx, invfy, bf, mb;        // invfx = 1.0f / fx (Frame.cc), mb = bf / fx
@@ -30,24 +28,14 @@ XFH_HD float triang_cos_stereo(float mb, float depth) {
     return (float)((z * z - h * h) / (z * z + h * h));
 }
 
-// the rotation of one column pair from alpha = |U_p|^2, beta = |U_q|^2, gamma = U_p . U_q; false: the pair is orthogonal enough (or a NaN) and
-// does not rotate.  Shared by the 4 x 4 instance below and the M x N one of twoview_math.h.
-XFH_HD bool triang_jacobi_rotation(double alpha, double beta, double gamma, double* c, double* s) {
-    if (!(fabs(gamma) > TRIANG_JACOBI_TOL * sqrt(alpha * beta))) return false;
-    const double zeta = (beta - alpha) / (2.0 * gamma);
-    const double t = (zeta < 0.0 ? -1.0 : 1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
-    *c = 1.0 / sqrt(1.0 + t * t); *s = *c * t;
-    return true;
-}
-
-// one rotation of the one-sided Jacobi iteration on columns P < Q of U (V accumulates); returns 1 when it rotated
+// one rotation (geo_jacobi_rotation) of the one-sided Jacobi iteration on columns P < Q of U (V accumulates); returns 1 when it rotated
 template <int P, int Q>
 XFH_HD int triang_jacobi_pair(double (&U)[4][4], double (&V)[4][4]) {
     const double alpha = ((U[0][P] * U[0][P] + U[1][P] * U[1][P]) + U[2][P] * U[2][P]) + U[3][P] * U[3][P];
     const double beta = ((U[0][Q] * U[0][Q] + U[1][Q] * U[1][Q]) + U[2][Q] * U[2][Q]) + U[3][Q] * U[3][Q];
     const double gamma = ((U[0][P] * U[0][Q] + U[1][P] * U[1][Q]) + U[2][P] * U[2][Q]) + U[3][P] * U[3][Q];
     double c, s;
-    if (!triang_jacobi_rotation(alpha, beta, gamma, &c, &s)) return 0;         // (a NaN does not rotate)
+    if (!geo_jacobi_rotation(alpha, beta, gamma, &c, &s)) return 0;         // (a NaN does not rotate)
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
         const double up = U[r][P], uq = U[r][Q], vp = V[r][P], vq = V[r][Q];
@@ -58,14 +46,14 @@ XFH_HD int triang_jacobi_pair(double (&U)[4][4], double (&V)[4][4]) {
 }
 
 // the right singular vector of the smallest singular value of the float 4x4 A, in fp64: cyclic sweeps (0,1) (0,2) (0,3) (1,2) (1,3) (2,3) until a
-// sweep rotates nothing, at most TRIANG_MAX_SWEEPS; the column of V whose column of U has the least norm, the first such on a tie
+// sweep rotates nothing, at most GEO_JACOBI_MAX_SWEEPS; the column of V whose column of U has the least norm, the first such on a tie
 XFH_HD void triang_null_vector(const float (&A)[4][4], double* x) {
     double U[4][4], V[4][4];
 #pragma unroll
     for (int r = 0; r < 4; ++r)
 #pragma unroll
         for (int c = 0; c < 4; ++c) { U[r][c] = (double)A[r][c]; V[r][c] = r == c ? 1.0 : 0.0; }
-    for (int sweep = 0; sweep < TRIANG_MAX_SWEEPS; ++sweep) {
+    for (int sweep = 0; sweep < GEO_JACOBI_MAX_SWEEPS; ++sweep) {
         int rot = triang_jacobi_pair<0, 1>(U, V);
         rot += triang_jacobi_pair<0, 2>(U, V);
         rot += triang_jacobi_pair<0, 3>(U, V);

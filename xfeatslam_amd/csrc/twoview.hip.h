@@ -13,11 +13,12 @@
 //   k_twoview_check_rt one workgroup per (problem, motion hypothesis): CheckRT of every inlier pair, nGood, and the cosine at sorted index
 //                      min(50, nGood - 1) by a radix select over the float keys (32 counting passes; only the value matters, so ties are harmless).
 //   k_twoview_final    one workgroup per problem: the decision (tv_decide, the same integers on every lane) and the outputs.
-// No global atomics, no waiting between workgroups; every float sum has the order of tv_tree_fold.  Two runs give identical bytes.
+// No global atomics, no waiting between workgroups; every float sum has the order of geo_tree_fold.  Two runs give identical bytes.
 #pragma once
 #include "twoview_math.h"
+#include "block_common.hip.h"
 
-#define XFH_TV_THREADS TV_LANES
+#define XFH_TV_THREADS GEO_LANES
 #define XFH_TV_FIT_LANES 32
 
 struct TvWs {
@@ -34,31 +35,18 @@ __device__ __forceinline__ TvWs tv_ws(const TvArgs& a, int b) {
     w.verdict = p + L.verdict; w.cosv = (float*)(p + L.cosv); w.p3d = (float*)(p + L.p3d);
     return w;
 }
-// the fold of tv_tree_fold by 256 lanes; every lane returns s[0]
+// one float sum of the rule: the fold of geo_tree_fold by 256 lanes, on every lane
 __device__ __forceinline__ float tv_block_fold(float* s, float mine) {
-    const int tid = threadIdx.x;
-    __syncthreads();                                                       // s is free
-    s[tid] = mine;
-    __syncthreads();
-    for (int h = TV_LANES / 2; h >= 1; h >>= 1) {
-        if (tid < h) s[tid] = s[tid] + s[tid + h];
-        __syncthreads();
-    }
-    return s[0];
-}
-__device__ __forceinline__ int tv_block_sum_i32(int* s4, int mine) {
-    const int v = wave_sum_i32(mine);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) s4[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return ((s4[0] + s4[1]) + s4[2]) + s4[3];
+    float out;
+    block_tree_fold<float, 1>(s, &mine, &out);
+    return out;
 }
 
 __global__ __launch_bounds__(XFH_TV_THREADS)
 void k_twoview_prepare(TvArgs a) {
-    __shared__ float s_f[TV_LANES];
+    __shared__ float s_f[GEO_LANES];
     __shared__ int s_cnt[4];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, b = blockIdx.x, n1 = a.n1, n2 = a.n2;
+    const int tid = threadIdx.x, b = blockIdx.x, n1 = a.n1, n2 = a.n2;
     const TvWs w = tv_ws(a, b);
     const int* m12 = a.match12 + (size_t)b * n1;
     int base = 0;
@@ -66,14 +54,9 @@ void k_twoview_prepare(TvArgs a) {
         const int i = i0 + tid;
         const int m = i < n1 ? m12[i] : -1;
         const bool ok = i < n1 && tv_match_ok(m, n2);
-        const unsigned long long bal = __ballot(ok);
-        __syncthreads();
-        if (lane == 0) s_cnt[wave] = __popcll(bal);
-        __syncthreads();
-        int before = 0;
-        for (int wv = 0; wv < wave; ++wv) before += s_cnt[wv];
-        if (ok) { const int pos = base + before + __popcll(bal & ((1ull << lane) - 1ull)); w.cm1[pos] = i; w.cm2[pos] = m; }      // pos < n1
-        base += ((s_cnt[0] + s_cnt[1]) + s_cnt[2]) + s_cnt[3];
+        __syncthreads();                                                   // s_cnt is free
+        const int pos = block_compact_step(ok, s_cnt, base);
+        if (ok) { w.cm1[pos] = i; w.cm2[pos] = m; }                        // pos < n1
     }
     if (tid == 0) w.sel[TV_S_N] = base;
     for (int f = 0; f < 2; ++f) {
@@ -82,10 +65,10 @@ void k_twoview_prepare(TvArgs a) {
         float mean[2], inv[2];
         for (int d = 0; d < 2; ++d) {
             float acc = 0.0f;
-            for (int i = tid; i < n; i += TV_LANES) acc = acc + xy[2 * (size_t)i + d];
+            for (int i = tid; i < n; i += GEO_LANES) acc = acc + xy[2 * (size_t)i + d];
             mean[d] = tv_mean(tv_block_fold(s_f, acc), n);
             acc = 0.0f;
-            for (int i = tid; i < n; i += TV_LANES) acc = acc + fabsf(xy[2 * (size_t)i + d] - mean[d]);
+            for (int i = tid; i < n; i += GEO_LANES) acc = acc + fabsf(xy[2 * (size_t)i + d] - mean[d]);
             inv[d] = tv_inv_dev(tv_block_fold(s_f, acc), n);
         }
         if (tid == 0) { w.nrm[4 * f] = mean[0]; w.nrm[4 * f + 1] = mean[1]; w.nrm[4 * f + 2] = inv[0]; w.nrm[4 * f + 3] = inv[1]; }
@@ -100,7 +83,7 @@ void k_twoview_fit(TvArgs a) {
     const int N = w.sel[TV_S_N];
     if (it >= a.iters || N < 8) return;                                    // (no barrier below)
     int set[8];
-    tv_set(a.draws + (size_t)b * a.draws_stride + (size_t)it * 8, a.rand_max, N, set);
+    geo_set<TV_MIN_SET>(a.draws + (size_t)b * a.draws_stride + (size_t)it * 8, a.rand_max, N, set);
     float p1[16], p2[16];
     const float* xy1 = a.xy1 + (size_t)b * a.n1 * 2;
     const float* xy2 = a.xy2 + (size_t)b * a.n2 * 2;
@@ -110,7 +93,7 @@ void k_twoview_fit(TvArgs a) {
         tv_normalized(w.nrm, xy1[2 * (size_t)i1], xy1[2 * (size_t)i1 + 1], p1 + 2 * j);
         tv_normalized(w.nrm + 4, xy2[2 * (size_t)i2], xy2[2 * (size_t)i2 + 1], p2 + 2 * j);
     }
-    const TvMat U{s_m + tid, XFH_TV_FIT_LANES}, V{s_m + 144 * XFH_TV_FIT_LANES + tid, XFH_TV_FIT_LANES};
+    const GeoMat U{s_m + tid, XFH_TV_FIT_LANES}, V{s_m + 144 * XFH_TV_FIT_LANES + tid, XFH_TV_FIT_LANES};
     float M[9], out[18];
     if (model == TV_MODEL_H) { tv_fit_h(p1, p2, U, V, M); tv_compose_h(M, w.nrm, w.nrm + 4, out); }
     else { tv_fit_f(p1, p2, U, V, M); tv_compose_f(M, w.nrm, w.nrm + 4, out); }
@@ -121,7 +104,7 @@ void k_twoview_fit(TvArgs a) {
 
 __global__ __launch_bounds__(XFH_TV_THREADS)
 void k_twoview_score(TvArgs a) {
-    __shared__ float s_f[TV_LANES];
+    __shared__ float s_f[GEO_LANES];
     __shared__ float s_M[18];
     const int tid = threadIdx.x, it = blockIdx.x, model = blockIdx.y ? TV_MODEL_F : TV_MODEL_H, b = blockIdx.z;
     const TvWs w = tv_ws(a, b);
@@ -136,7 +119,7 @@ void k_twoview_score(TvArgs a) {
     const float* xy2 = a.xy2 + (size_t)b * a.n2 * 2;
     const float inv_s2 = tv_inv_sigma2(a.sigma);
     float acc = 0.0f;
-    for (int k = tid; k < N; k += TV_LANES) {
+    for (int k = tid; k < N; k += GEO_LANES) {
         const int i1 = w.cm1[k], i2 = w.cm2[k];
         float chi[2]; int in;
         acc = acc + tv_score(model, M, inv_s2, xy1[2 * (size_t)i1], xy1[2 * (size_t)i1 + 1], xy2[2 * (size_t)i2], xy2[2 * (size_t)i2 + 1], chi, &in);
@@ -190,8 +173,8 @@ void k_twoview_select(TvArgs a) {
         a.inl_h[(size_t)b * n1 + i] = (unsigned char)inH; a.inl_f[(size_t)b * n1 + i] = (unsigned char)inF;
         cH += inH; cF += inF;
     }
-    cH = tv_block_sum_i32(s_cnt, cH);
-    cF = tv_block_sum_i32(s_cnt, cF);
+    cH = block_sum_i32(s_cnt, cH);
+    cF = block_sum_i32(s_cnt, cF);
     if (tid != 0) return;
     float* fo = a.fout + (size_t)b * TV_FLOATS;
     for (int k = 0; k < TV_FLOATS; ++k) fo[k] = 0.0f;
@@ -202,7 +185,7 @@ void k_twoview_select(TvArgs a) {
         const float RH = SH / (SH + SF);
         fo[TV_F_RH] = RH;
         model = (double)RH > 0.50 ? TV_MODEL_H : TV_MODEL_F;
-        const TvMat U{s_m, 1}, V{s_m + 9, 1};
+        const GeoMat U{s_m, 1}, V{s_m + 9, 1};
         if (model == TV_MODEL_H) { hdeg = !tv_motions_h(MH, a.cam, U, V, w.motion); nhyp = hdeg ? 0 : 8; }
         else { tv_motions_f(MF, a.cam, U, V, w.motion); nhyp = 4; }
     }
@@ -243,7 +226,7 @@ void k_twoview_check_rt(TvArgs a) {
         p3d[3 * (size_t)i] = p[0]; p3d[3 * (size_t)i + 1] = p[1]; p3d[3 * (size_t)i + 2] = p[2];
         cnt += v != 0;
     }
-    const int nGood = tv_block_sum_i32(s_cnt, cnt);                        // (its barriers also publish verdict / cosv to the workgroup)
+    const int nGood = block_sum_i32(s_cnt, cnt);                        // (its barriers also publish verdict / cosv to the workgroup)
     float ck = 1.0f;
     if (nGood > 0) {
         int k = nGood - 1 < 50 ? nGood - 1 : 50;
@@ -255,7 +238,7 @@ void k_twoview_check_rt(TvArgs a) {
                 const uint32_t key = tv_float_key(cosv[i]);
                 c0 += verdict[i] != 0 && (key & mask) == prefix && !(key & bb);
             }
-            c0 = tv_block_sum_i32(s_cnt, c0);
+            c0 = block_sum_i32(s_cnt, c0);
             if (k >= c0) { k -= c0; prefix |= bb; }
             mask |= bb;
         }
@@ -293,7 +276,7 @@ void k_twoview_final(TvArgs a) {
         a.matches_out[kg] = chosen >= 0 && tv_match_ok(m, a.n2) && v != 2 ? -1 : m;
         ntri += v == 2;
     }
-    ntri = tv_block_sum_i32(s_cnt, ntri);
+    ntri = block_sum_i32(s_cnt, ntri);
     if (tid != 0) return;
     int* hdr = a.header + (size_t)b * TV_HEADER_INTS;
     float* fo = a.fout + (size_t)b * TV_FLOATS;

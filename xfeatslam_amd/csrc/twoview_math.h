@@ -5,7 +5,7 @@
 // single-thread form of the whole rule, xfh_two_view_host, included) and tests/cpp/asan_twoview_test.cpp compile these very lines.
 // All arithmetic is fp32 in the order written (the library is built with -ffp-contract=off) except where a double is spelled out.
 #pragma once
-#include "hd.h"
+#include "geom_common.h"
 #include "triangulate_math.h"
 #include <math.h>
 #include <stdint.h>
@@ -16,43 +16,8 @@ enum { TV_MODEL_NONE = 0, TV_MODEL_H = 1, TV_MODEL_F = 2 };
 enum { TV_H_N = 0, TV_H_STATUS = 1, TV_H_MODEL = 2, TV_H_WIN_H = 3, TV_H_WIN_F = 4, TV_H_NGOOD = 5, TV_H_CHOSEN = 13, TV_H_INL_H = 14, TV_H_INL_F = 15,
        TV_H_NTRI = 16, TV_H_NHYP = 17, TV_H_NMATCHES = 18, TV_HEADER_INTS = 24 };
 enum { TV_F_SH = 0, TV_F_SF = 1, TV_F_RH = 2, TV_F_H21 = 3, TV_F_F21 = 12, TV_F_T21 = 21, TV_F_COS = 33, TV_FLOATS = 48 };
-#define TV_LANES 256                  // the width of every float reduction of the rule (tv_tree_fold), whatever runs it
 #define TV_MAX_ITERS 4096
-
-struct TvCam { float fx, fy, cx, cy; };
-
-// ---- the minimal set of one iteration -------------------------------------------------------------------------------------------------------
-// DUtils::Random::RandomInt(0, d - 1) of one raw draw: int(((double)draw / ((double)rand_max + 1.0)) * d).  A draw outside 0 .. rand_max (the
-// reference cannot produce one) is clamped into the vector: index 0 .. d - 1 always.
-XFH_HD int tv_draw_index(int draw, int rand_max, int d) {
-    const double v = ((double)draw / ((double)rand_max + 1.0)) * (double)d;
-    return !(v >= 0.0) ? 0 : (v >= (double)d ? d - 1 : (int)v);
-}
-// the shrinking vAvailableIndices with swap-remove, without the vector: only the (at most eight) positions a removal has overwritten are kept.
-// N >= 8.
-XFH_HD void tv_set(const int* draws8, int rand_max, int N, int* set8) {
-    int pos[8], val[8], nd = 0;
-    for (int j = 0; j < 8; ++j) {
-        const int size = N - j, r = tv_draw_index(draws8[j], rand_max, size), last = size - 1;
-        int idx = r, back = last, at = -1;
-        for (int k = 0; k < nd; ++k) {
-            if (pos[k] == r) { idx = val[k]; at = k; }
-            if (pos[k] == last) back = val[k];
-        }
-        set8[j] = idx;
-        if (at >= 0) val[at] = back; else { pos[nd] = r; val[nd] = back; ++nd; }
-    }
-}
-
-// ---- reductions ---------------------------------------------------------------------------------------------------------------------------------
-// Every float sum of the rule over n terms: lane l of TV_LANES adds the terms l, l + 256, l + 512, ... in that order to 0.0f, then the 256
-// partial sums are folded s[l] += s[l + h] for h = 128, 64, .. 1.  tv_tree_fold is the fold as one thread does it (the kernels do the same
-// adds with a barrier between the steps).
-XFH_HD float tv_tree_fold(float* s) {
-    for (int h = TV_LANES / 2; h >= 1; h >>= 1)
-        for (int l = 0; l < h; ++l) s[l] = s[l] + s[l + h];
-    return s[0];
-}
+#define TV_MIN_SET 8                  // the minimal set of one iteration: geo_set on eight raw draws.  N >= 8.
 
 // Normalize (:737-784) of one frame from its two passes: mean = sum / n, s = 1 / (sum |x - mean| / n)
 XFH_HD float tv_mean(float sum, int n) { return sum / (float)n; }
@@ -60,66 +25,14 @@ XFH_HD float tv_inv_dev(float sum_dev, int n) { const float md = sum_dev / (floa
 // nrm = (meanX, meanY, sX, sY)
 XFH_HD void tv_normalized(const float* nrm, float x, float y, float* o) { o[0] = (x - nrm[0]) * nrm[2]; o[1] = (y - nrm[1]) * nrm[3]; }
 
-// ---- the fp64 one-sided Jacobi of triang_null_vector for an M x N matrix in caller-given storage ---------------------------------------------------
-// element k of a matrix lives at p[k * stride]: stride 1 on the host, the block width in LDS (one matrix per lane, bank-conflict free)
-struct TvMat { double* p; int stride; XFH_HD double& operator()(int k) const { return p[(size_t)k * stride]; } };
-
-XFH_HD double tv_col_dot(const TvMat& U, int M, int N, int a, int b) {
-    double s = U(a) * U(b);
-    for (int r = 1; r < M; ++r) s = s + U(r * N + a) * U(r * N + b);
-    return s;
-}
-// U (M x N, row-major) <- U V with orthogonal columns; V (N x N) accumulates from the identity.  Cyclic sweeps over the pairs p < q in
-// lexicographic order, the rotation of triang_jacobi_rotation, until a sweep rotates nothing, at most TRIANG_MAX_SWEEPS.  M is a template
-// argument so that the two columns of a pair are read ONCE into registers (2 M doubles) for the three dot products and the rotation: the sums
-// are the ones tv_col_dot writes, term by term.
-template <int M>
-XFH_HD void tv_jacobi_m(const TvMat& U, const TvMat& V, int N) {
-    for (int r = 0; r < N; ++r)
-        for (int c = 0; c < N; ++c) V(r * N + c) = r == c ? 1.0 : 0.0;
-    for (int sweep = 0; sweep < TRIANG_MAX_SWEEPS; ++sweep) {
-        int rot = 0;
-        for (int p = 0; p < N - 1; ++p)
-            for (int q = p + 1; q < N; ++q) {
-                double up[M], uq[M];
-#pragma unroll
-                for (int r = 0; r < M; ++r) { up[r] = U(r * N + p); uq[r] = U(r * N + q); }
-                double alpha = up[0] * up[0], beta = uq[0] * uq[0], gamma = up[0] * uq[0];
-#pragma unroll
-                for (int r = 1; r < M; ++r) { alpha = alpha + up[r] * up[r]; beta = beta + uq[r] * uq[r]; gamma = gamma + up[r] * uq[r]; }
-                double c, s;
-                if (!triang_jacobi_rotation(alpha, beta, gamma, &c, &s)) continue;
-#pragma unroll
-                for (int r = 0; r < M; ++r) { U(r * N + p) = c * up[r] - s * uq[r]; U(r * N + q) = s * up[r] + c * uq[r]; }
-                for (int r = 0; r < N; ++r) {
-                    const double vp = V(r * N + p), vq = V(r * N + q);
-                    V(r * N + p) = c * vp - s * vq; V(r * N + q) = s * vp + c * vq;
-                }
-                ++rot;
-            }
-        if (rot == 0) break;
-    }
-}
-XFH_HD void tv_jacobi(const TvMat& U, const TvMat& V, int M, int N) {
-    if (M == 16) tv_jacobi_m<16>(U, V, N); else if (M == 8) tv_jacobi_m<8>(U, V, N); else tv_jacobi_m<3>(U, V, N);     // the three instances of the rule
-}
-// the column of least squared norm, the first on a tie
-XFH_HD int tv_min_col(const TvMat& U, int M, int N) {
-    int best = 0;
-    double bn = tv_col_dot(U, M, N, 0, 0);
-    for (int c = 1; c < N; ++c) { const double n = tv_col_dot(U, M, N, c, c); if (n < bn) { bn = n; best = c; } }
-    return best;
-}
-// the three columns by squared norm, descending, stable (the earlier column first on a tie; a NaN stays where it is)
-XFH_HD void tv_order3(const TvMat& U, int* o, double* n2) {
-    for (int c = 0; c < 3; ++c) { n2[c] = tv_col_dot(U, 3, 3, c, c); o[c] = c; }
-    for (int a = 1; a < 3; ++a)
-        for (int b = a; b > 0 && n2[o[b]] > n2[o[b - 1]]; --b) { const int t = o[b]; o[b] = o[b - 1]; o[b - 1] = t; }
+// ---- the fp64 one-sided Jacobi (geo_jacobi) for the M x N matrices of the rule, rows cached: a column pair is read from LDS once ---------------------
+XFH_HD void tv_jacobi(const GeoMat& U, const GeoMat& V, int M, int N) {
+    if (M == 16) geo_jacobi<16>(U, V, N); else if (M == 8) geo_jacobi<8>(U, V, N); else geo_jacobi<3>(U, V, N);     // the three instances of the rule
 }
 
 // ---- the two fits of eight normalised point pairs (p1, p2: [8][2]); U has room for 16 x 9 doubles, V for 9 x 9 -------------------------------------
 // ComputeH21 (:232-272): V's column of the least singular value of the 16 x 9 A, row-major 3 x 3, rounded to float once
-XFH_HD void tv_fit_h(const float* p1, const float* p2, const TvMat& U, const TvMat& V, float* Hn) {
+XFH_HD void tv_fit_h(const float* p1, const float* p2, const GeoMat& U, const GeoMat& V, float* Hn) {
     for (int i = 0; i < 8; ++i) {
         const float u1 = p1[2 * i], v1 = p1[2 * i + 1], u2 = p2[2 * i], v2 = p2[2 * i + 1];
         const float r0[9] = {0.0f, 0.0f, 0.0f, -u1, -v1, -1.0f, v2 * u1, v2 * v1, v2};
@@ -127,25 +40,25 @@ XFH_HD void tv_fit_h(const float* p1, const float* p2, const TvMat& U, const TvM
         for (int c = 0; c < 9; ++c) { U((2 * i) * 9 + c) = (double)r0[c]; U((2 * i + 1) * 9 + c) = (double)r1[c]; }
     }
     tv_jacobi(U, V, 16, 9);
-    const int k = tv_min_col(U, 16, 9);
+    const int k = geo_min_col(U, 16, 9, false);
     for (int c = 0; c < 9; ++c) Hn[c] = (float)V(c * 9 + k);
 }
 // ComputeF21 (:274-308): the null vector of the 8 x 9 A as above, then the rank-2 projection: the 3 x 3 Jacobi of Fpre gives the columns
 // a_i = sigma_i u_i of Fpre V; Fn = a_i0 v_i0^T + a_i1 v_i1^T over the two columns of largest norm, in double, rounded to float once
-XFH_HD void tv_fit_f(const float* p1, const float* p2, const TvMat& U, const TvMat& V, float* Fn) {
+XFH_HD void tv_fit_f(const float* p1, const float* p2, const GeoMat& U, const GeoMat& V, float* Fn) {
     for (int i = 0; i < 8; ++i) {
         const float u1 = p1[2 * i], v1 = p1[2 * i + 1], u2 = p2[2 * i], v2 = p2[2 * i + 1];
         const float r0[9] = {u2 * u1, u2 * v1, u2, v2 * u1, v2 * v1, v2, u1, v1, 1.0f};
         for (int c = 0; c < 9; ++c) U(i * 9 + c) = (double)r0[c];
     }
     tv_jacobi(U, V, 8, 9);
-    const int k = tv_min_col(U, 8, 9);
+    const int k = geo_min_col(U, 8, 9, false);
     float f[9];
     for (int c = 0; c < 9; ++c) f[c] = (float)V(c * 9 + k);
     for (int c = 0; c < 9; ++c) U(c) = (double)f[c];
     tv_jacobi(U, V, 3, 3);
     int o[3]; double n2[3];
-    tv_order3(U, o, n2);
+    geo_order3(U, o, n2);
     for (int r = 0; r < 3; ++r)
         for (int c = 0; c < 3; ++c) Fn[r * 3 + c] = (float)(U(r * 3 + o[0]) * V(c * 3 + o[0]) + U(r * 3 + o[1]) * V(c * 3 + o[1]));
 }
@@ -158,11 +71,8 @@ XFH_HD void tv_times_T(const float* X, const float* nrm, float* M) {
         M[r * 3 + 2] = (X[r * 3] * tx + X[r * 3 + 1] * ty) + X[r * 3 + 2];
     }
 }
-XFH_HD float tv_det3(const float* A) {
-    return (A[0] * (A[4] * A[8] - A[5] * A[7]) - A[1] * (A[3] * A[8] - A[5] * A[6])) + A[2] * (A[3] * A[7] - A[4] * A[6]);
-}
 XFH_HD void tv_inv3(const float* A, float* I) {
-    const float id = 1.0f / tv_det3(A);
+    const float id = 1.0f / geo_det3(A);
     I[0] = (A[4] * A[8] - A[5] * A[7]) * id; I[1] = (A[2] * A[7] - A[1] * A[8]) * id; I[2] = (A[1] * A[5] - A[2] * A[4]) * id;
     I[3] = (A[5] * A[6] - A[3] * A[8]) * id; I[4] = (A[0] * A[8] - A[2] * A[6]) * id; I[5] = (A[2] * A[3] - A[0] * A[5]) * id;
     I[6] = (A[3] * A[7] - A[4] * A[6]) * id; I[7] = (A[1] * A[6] - A[0] * A[7]) * id; I[8] = (A[0] * A[4] - A[1] * A[3]) * id;
@@ -232,11 +142,11 @@ XFH_HD int tv_argmax(const float* score, int iters, float* best) {
 // A = U diag(w) V^T from the Jacobi: the columns by norm, descending; w_i = sqrt |a_i|^2, u_i = a_i / w_i in double.  rank2 (DecomposeE): u_2 is
 // not a_2 / w_2 (w_2 is 0 up to rounding) but the cross product u_0 x u_1.  U, V (row-major, columns in the sorted order), w rounded to float once.
 struct TvSvd3 { float U[9], V[9], w[3]; };
-XFH_HD void tv_svd3(const float* A, bool rank2, const TvMat& U, const TvMat& V, TvSvd3* o) {
+XFH_HD void tv_svd3(const float* A, bool rank2, const GeoMat& U, const GeoMat& V, TvSvd3* o) {
     for (int k = 0; k < 9; ++k) U(k) = (double)A[k];
     tv_jacobi(U, V, 3, 3);
     int ord[3]; double n2[3], u[9];
-    tv_order3(U, ord, n2);
+    geo_order3(U, ord, n2);
     for (int k = 0; k < 3; ++k) {
         const double w = sqrt(n2[ord[k]]);
         o->w[k] = (float)w;
@@ -249,7 +159,7 @@ XFH_HD void tv_svd3(const float* A, bool rank2, const TvMat& U, const TvMat& V, 
     }
     for (int k = 0; k < 9; ++k) o->U[k] = (float)u[k];
 }
-XFH_HD void tv_times_K(const float* X, const TvCam& k, float* G) {
+XFH_HD void tv_times_K(const float* X, const GeoCam& k, float* G) {
     for (int r = 0; r < 3; ++r) {
         G[r * 3] = X[r * 3] * k.fx; G[r * 3 + 1] = X[r * 3 + 1] * k.fy; G[r * 3 + 2] = (X[r * 3] * k.cx + X[r * 3 + 1] * k.cy) + X[r * 3 + 2];
     }
@@ -259,7 +169,7 @@ XFH_HD void tv_unit3(const float* t, float* o) {
     o[0] = t[0] / n; o[1] = t[1] / n; o[2] = t[2] / n;
 }
 // ReconstructF's four hypotheses (:483-503, DecomposeE :903-927): E = K^T F K, (R1, t) (R2, t) (R1, -t) (R2, -t) as rows [R|t] of Rt[4][12]
-XFH_HD void tv_motions_f(const float* F, const TvCam& k, const TvMat& U, const TvMat& V, float* Rt) {
+XFH_HD void tv_motions_f(const float* F, const GeoCam& k, const GeoMat& U, const GeoMat& V, float* Rt) {
     float G[9], E[9];
     tv_times_K(F, k, G);
     for (int c = 0; c < 3; ++c) { E[c] = k.fx * G[c]; E[3 + c] = k.fy * G[3 + c]; E[6 + c] = (k.cx * G[c] + k.cy * G[3 + c]) + G[6 + c]; }
@@ -273,7 +183,7 @@ XFH_HD void tv_motions_f(const float* F, const TvCam& k, const TvMat& U, const T
             R1[r * 3 + c] = (s.U[r * 3 + 1] * s.V[c * 3] - s.U[r * 3] * s.V[c * 3 + 1]) + s.U[r * 3 + 2] * s.V[c * 3 + 2];
             R2[r * 3 + c] = (s.U[r * 3] * s.V[c * 3 + 1] - s.U[r * 3 + 1] * s.V[c * 3]) + s.U[r * 3 + 2] * s.V[c * 3 + 2];
         }
-    const bool n1 = tv_det3(R1) < 0.0f, n2 = tv_det3(R2) < 0.0f;
+    const bool n1 = geo_det3(R1) < 0.0f, n2 = geo_det3(R2) < 0.0f;
     for (int h = 0; h < 4; ++h) {
         const float* R = (h & 1) ? R2 : R1;
         const bool neg = (h & 1) ? n2 : n1;
@@ -285,7 +195,7 @@ XFH_HD void tv_motions_f(const float* F, const TvCam& k, const TvMat& U, const T
 }
 // ReconstructH's eight hypotheses (:582-690): A = K^-1 H K with K^-1 = [1/fx 0 -cx/fx; 0 1/fy -cy/fy; 0 0 1] written out.  false: d1/d2 or
 // d2/d3 < 1.00001 (nothing is written).
-XFH_HD bool tv_motions_h(const float* H, const TvCam& k, const TvMat& Um, const TvMat& Vm, float* Rt) {
+XFH_HD bool tv_motions_h(const float* H, const GeoCam& k, const GeoMat& Um, const GeoMat& Vm, float* Rt) {
     float G[9], A[9];
     tv_times_K(H, k, G);
     const float ifx = 1.0f / k.fx, ify = 1.0f / k.fy, icx = -k.cx * ifx, icy = -k.cy * ify;
@@ -293,7 +203,7 @@ XFH_HD bool tv_motions_h(const float* H, const TvCam& k, const TvMat& Um, const 
     TvSvd3 sv;
     tv_svd3(A, false, Um, Vm, &sv);
     const float* U = sv.U; const float* V = sv.V;
-    const float s = tv_det3(U) * tv_det3(V);
+    const float s = geo_det3(U) * geo_det3(V);
     const float d1 = sv.w[0], d2 = sv.w[1], d3 = sv.w[2];
     if ((double)(d1 / d2) < 1.00001 || (double)(d2 / d3) < 1.00001) return false;
     const float aux1 = sqrtf((d1 * d1 - d2 * d2) / (d1 * d1 - d3 * d3)), aux3 = sqrtf((d2 * d2 - d3 * d3) / (d1 * d1 - d3 * d3));
@@ -325,7 +235,7 @@ XFH_HD bool tv_motions_h(const float* H, const TvCam& k, const TvMat& Um, const 
 
 // ---- CheckRT (:786-901) for one inlier pair: 0 = not counted, 1 = counted (nGood, vCosParallax, vP3D), 2 = counted and vbGood -------------------
 XFH_HD float tv_th2(float sigma) { return (float)(4.0 * (double)(sigma * sigma)); }
-XFH_HD int tv_check_rt_pair(const TvCam& k, const float* Rt, float th2, float x1, float y1, float x2, float y2, float* cosp, float* p) {
+XFH_HD int tv_check_rt_pair(const GeoCam& k, const float* Rt, float th2, float x1, float y1, float x2, float y2, float* cosp, float* p) {
     float A[4][4], P2[3][4];
     for (int c = 0; c < 4; ++c) {
         P2[0][c] = k.fx * Rt[c] + k.cx * Rt[8 + c]; P2[1][c] = k.fy * Rt[4 + c] + k.cy * Rt[8 + c]; P2[2][c] = Rt[8 + c];
@@ -401,22 +311,21 @@ XFH_HD int tv_decide(int model, bool h_degenerate, const int* nGood, const float
 
 // ---- the workspace of one call (device memory, B problems): offsets in bytes, every piece 16-byte aligned ----------------------------------------
 struct TvLayout { size_t cm1, cm2, nrm, sel, hyp, score, motion, ngood, cosk, verdict, cosv, p3d, per_problem; };
-XFH_HD size_t tv_al16(size_t x) { return (x + 15) & ~(size_t)15; }
 XFH_HD TvLayout tv_layout(int n1, int iters) {
     TvLayout L; size_t o = 0;
-    L.cm1 = o; o += tv_al16((size_t)n1 * 4);                 // int idx1 of compact match k
-    L.cm2 = o; o += tv_al16((size_t)n1 * 4);                 // int idx2
+    L.cm1 = o; o += geo_al16((size_t)n1 * 4);                 // int idx1 of compact match k
+    L.cm2 = o; o += geo_al16((size_t)n1 * 4);                 // int idx2
     L.nrm = o; o += 32;                                      // float (meanX, meanY, sX, sY) of frame 1, of frame 2
     L.sel = o; o += 32;                                      // int N, winH, winF, model, inliers of the model, h_degenerate, nhyp, 0
     L.hyp = o; o += (size_t)2 * iters * 18 * 4;              // float [2][iters][18]
-    L.score = o; o += tv_al16((size_t)2 * iters * 4);        // float [2][iters]
+    L.score = o; o += geo_al16((size_t)2 * iters * 4);        // float [2][iters]
     L.motion = o; o += 8 * 12 * 4;                           // float [8][12]
     L.ngood = o; o += 32;                                    // int [8]
     L.cosk = o; o += 32;                                     // float [8]
-    L.verdict = o; o += tv_al16((size_t)8 * n1);             // u8 [8][n1]
-    L.cosv = o; o += tv_al16((size_t)8 * n1 * 4);            // float [8][n1]
-    L.p3d = o; o += tv_al16((size_t)8 * n1 * 12);            // float [8][n1][3]
-    L.per_problem = tv_al16(o);
+    L.verdict = o; o += geo_al16((size_t)8 * n1);             // u8 [8][n1]
+    L.cosv = o; o += geo_al16((size_t)8 * n1 * 4);            // float [8][n1]
+    L.p3d = o; o += geo_al16((size_t)8 * n1 * 12);            // float [8][n1][3]
+    L.per_problem = geo_al16(o);
     return L;
 }
 enum { TV_S_N = 0, TV_S_WIN_H = 1, TV_S_WIN_F = 2, TV_S_MODEL = 3, TV_S_NINL = 4, TV_S_HDEG = 5, TV_S_NHYP = 6 };
@@ -425,7 +334,7 @@ enum { TV_S_N = 0, TV_S_WIN_H = 1, TV_S_WIN_F = 2, TV_S_MODEL = 3, TV_S_NINL = 4
 struct TvArgs {
     int B, n1, n2, iters, rand_max, min_tri;
     size_t draws_stride;
-    TvCam cam;
+    GeoCam cam;
     float sigma;
     double min_parallax_cos;
     const float *xy1, *xy2;
@@ -440,9 +349,9 @@ XFH_HD bool tv_match_ok(int m, int n2) { return m >= 0 && m < n2; }
 // ---- the whole rule for problem b on ONE host thread, over host pointers in the same argument block and workspace layout as the kernels ------------
 // (xfh_two_view_host and tests/cpp/asan_twoview_test.cpp; the kernels of twoview.hip.h do these steps with 256 lanes)
 inline float tv_host_sum(const float* term, int n) {
-    float s[TV_LANES];
-    for (int l = 0; l < TV_LANES; ++l) { float acc = 0.0f; for (int i = l; i < n; i += TV_LANES) acc = acc + term[i]; s[l] = acc; }
-    return tv_tree_fold(s);
+    float s[GEO_LANES];
+    for (int l = 0; l < GEO_LANES; ++l) { float acc = 0.0f; for (int i = l; i < n; i += GEO_LANES) acc = acc + term[i]; s[l] = acc; }
+    return geo_tree_fold(s);
 }
 inline void tv_host_problem(const TvArgs& a, int b, float* scratch /* max(n1, n2) floats */) {
     const TvLayout L = tv_layout(a.n1, a.iters);
@@ -475,11 +384,11 @@ inline void tv_host_problem(const TvArgs& a, int b, float* scratch /* max(n1, n2
     }
     const float inv_s2 = tv_inv_sigma2(a.sigma);
     double um[144], vm[81];
-    const TvMat U{um, 1}, V{vm, 1};
+    const GeoMat U{um, 1}, V{vm, 1};
     for (int model = TV_MODEL_H; model <= TV_MODEL_F; ++model)
         for (int it = 0; it < a.iters; ++it) {
             int set[8]; float p1[16], p2[16], M[9];
-            tv_set(a.draws + (size_t)b * a.draws_stride + (size_t)it * 8, a.rand_max, N, set);
+            geo_set<TV_MIN_SET>(a.draws + (size_t)b * a.draws_stride + (size_t)it * 8, a.rand_max, N, set);
             for (int j = 0; j < 8; ++j) {
                 const int i1 = cm1[set[j]], i2 = cm2[set[j]];
                 tv_normalized(nrm, xy1[2 * (size_t)i1], xy1[2 * (size_t)i1 + 1], p1 + 2 * j);
