@@ -7,7 +7,9 @@
  * of keypoint k, or anything outside [0, nq) for none), the world points the search projected, and the pose.  It returns the reference's int
  * (nInitialCorrespondences - nBad) and leaves the new pose and the mvbOutlier flags in device memory, where the next search reads them; the
  * pose also comes back to the host, as pFrame->SetPose would want it.  This is not a graph optimiser: one SE3 vertex, unary edges, nothing else
- * (include/xfeat_hip.h has the contract line by line).  Header only; needs nothing but xfeat_hip.h.
+ * (include/xfeat_hip.h has the contract line by line).  XFoptimizer::OptimizeSim3 is Optimizer::OptimizeSim3 (:2100-2381) in the same way: one
+ * Sim3 vertex, two projection edges per correspondence, as one call of xfh_sim3_optimize_device between the two Sim3 projection searches of loop
+ * detection.  Header only; needs nothing but xfeat_hip.h.
  */
 #ifndef XFEAT_OPTIMIZER_XFEAT_H
 #define XFEAT_OPTIMIZER_XFEAT_H
@@ -23,7 +25,7 @@ namespace ORB_SLAM3 {
 class XFoptimizer {
 public:
     explicit XFoptimizer(xfh_ctx* c) : ctx(c) {}
-    ~XFoptimizer() { if (d_buf) xfh_dev_free(d_buf); }
+    ~XFoptimizer() { if (d_buf) xfh_dev_free(d_buf); if (d_s3) xfh_dev_free(d_s3); }
     XFoptimizer(const XFoptimizer&) = delete;
     XFoptimizer& operator=(const XFoptimizer&) = delete;
 
@@ -72,6 +74,79 @@ public:
         out.assign((size_t)n, 0.0f);
         if (n > 0 && xfh_memcpy_d2h(out.data(), d_chi2, (size_t)n * 4) != XFH_OK) throw std::runtime_error("XFoptimizer::chi2: download failed");
     }
+    // ---- Optimizer::OptimizeSim3 (reference src/Optimizer.cc:2100-2381) as LoopClosing calls it between its two Sim3 projection searches: one call of
+    // xfh_sim3_optimize_device.  The arrays of both keyframes are in device memory as the calls around it leave them (include/xfeat_hip.h, the
+    // OptimizeSim3 section, names them one by one); d_Tmw, the pose of pMostBoWMatchesKF, may be nullptr (then no composed pose is written).
+    struct Sim3Input {
+        int n1, M1, nq, n2;
+        const float* d_T1w; const float* d_keysUn1; const int* d_point1; const float* d_points1;
+        const int* d_assigned; const float* d_points2; const unsigned char* d_flags2; const int* d_index2; const float* d_keysUn2; const float* d_T2w;
+        const float* d_Tmw;
+    };
+    // S12: g2oS12 as 13 floats (R row-major 9, t 3, s), replaced by the optimised similarity.  Returns the reference's int (nIn, or 0 when fewer
+    // than 10 correspondences survive the first classification).  vpMatches1 with its NULLs (deviceMatches()), the composed pose and camera centre
+    // for the next search (deviceScw(), deviceOw()) and the similarity (deviceS12()) stay on the device.  Blocks until S12 and the counts are on the host.
+    int OptimizeSim3(const Sim3Input& in, float S12[13], const xfh_camera& cam1, const xfh_camera& cam2, float th2, bool bFixScale, bool bAllPoints,
+                     float invSigma2_1 = 1.0f, float invSigma2_2 = 1.0f) {
+        const size_t ws = xfh_sim3_optimize_workspace_bytes(in.n1, 1);
+        if (ws == 0) throw std::runtime_error("XFoptimizer::OptimizeSim3: sizes out of range");
+        auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+        const size_t N = (size_t)in.n1, bw = al(ws), ba = al(N * 4), bs = al(N), bc = al(N * 8);
+        const size_t need = bw + ba + bs + bc + 5 * 256;
+        if (need > s3_bytes) {
+            if (d_s3) { xfh_synchronize(ctx); xfh_dev_free(d_s3); d_s3 = nullptr; s3_bytes = 0; }
+            if (xfh_dev_alloc(&d_s3, need) != XFH_OK) throw std::runtime_error("XFoptimizer::OptimizeSim3: out of device memory");
+            s3_bytes = need;
+        }
+        char* p = (char*)d_s3;
+        void* dws = p; p += bw;
+        d_matches = (int*)p; p += ba;
+        d_status = (unsigned char*)p; p += bs;
+        d_chi2_pairs = (float*)p; p += bc;
+        d_S12 = (float*)p; p += 256;
+        d_Scw = in.d_Tmw ? (float*)p : nullptr; d_Ow = in.d_Tmw ? (float*)(p + 64) : nullptr; p += 256;     // no composed pose without d_Tmw
+        double* dst = (double*)p; double* dfc = (double*)(p + 64); p += 256;
+        int* dh = (int*)p;
+        n_pairs = in.n1;
+        int rc = xfh_synchronize(ctx);
+        if (rc == XFH_OK) rc = xfh_memcpy_h2d(d_S12, S12, XFH_SIM3_OPT_S12_FLOATS * 4);
+        if (rc == XFH_OK) rc = xfh_sim3_optimize_device(ctx, 1, in.n1, in.M1, in.nq, in.n2, 0, in.d_T1w, in.d_keysUn1, in.d_point1, in.d_points1, in.d_assigned,
+                                                        in.d_points2, in.d_flags2, in.d_index2, in.d_keysUn2, in.d_T2w, d_S12, XFH_SIM3_OPT_S12_FLOATS, in.d_Tmw,
+                                                        &cam1, &cam2, th2, bFixScale ? 1 : 0, bAllPoints ? 1 : 0, invSigma2_1, invSigma2_2, dws, d_matches, d_status,
+                                                        d_chi2_pairs, dst, d_S12, XFH_SIM3_OPT_S12_FLOATS, d_Scw, d_Ow,
+                                                        dh, dfc);
+        if (rc == XFH_OK) rc = xfh_synchronize(ctx);
+        if (rc == XFH_OK) rc = xfh_memcpy_d2h(S12, d_S12, XFH_SIM3_OPT_S12_FLOATS * 4);
+        if (rc == XFH_OK) rc = xfh_memcpy_d2h(sim3State, dst, 64);
+        if (rc == XFH_OK) rc = xfh_memcpy_d2h(sim3Header, dh, XFH_SIM3_OPT_HEADER_INTS * 4);
+        if (rc == XFH_OK) rc = xfh_memcpy_d2h(&sim3FinalChi2, dfc, 8);
+        if (rc != XFH_OK) throw std::runtime_error(std::string("XFoptimizer::OptimizeSim3: ") + xfh_strerror(rc));
+        return sim3Header[6];
+    }
+    // of the last OptimizeSim3: vpMatches1 (d_assigned with -1 where the match was removed), the composed [R | t / s] and camera centre the fine
+    // xfh_map_projection_search_device takes (both nullptr when the call had no d_Tmw: nothing was composed), the similarity; the pair status and the
+    // two chi2 per keypoint on request
+    const int* deviceMatches() const { return d_matches; }
+    const float* deviceScw() const { return d_Scw; }
+    const float* deviceOw() const { return d_Ow; }
+    const float* deviceS12() const { return d_S12; }
+    void matches(std::vector<int>& out) const {
+        out.assign((size_t)n_pairs, -1);
+        if (n_pairs > 0 && xfh_memcpy_d2h(out.data(), d_matches, (size_t)n_pairs * 4) != XFH_OK) throw std::runtime_error("XFoptimizer::matches: download failed");
+    }
+    void pairStatus(std::vector<unsigned char>& out) const {
+        out.assign((size_t)n_pairs, 0);
+        if (n_pairs > 0 && xfh_memcpy_d2h(out.data(), d_status, (size_t)n_pairs) != XFH_OK) throw std::runtime_error("XFoptimizer::pairStatus: download failed");
+    }
+    void pairChi2(std::vector<float>& out) const {
+        out.assign((size_t)n_pairs * 2, 0.0f);
+        if (n_pairs > 0 && xfh_memcpy_d2h(out.data(), d_chi2_pairs, (size_t)n_pairs * 8) != XFH_OK) throw std::runtime_error("XFoptimizer::pairChi2: download failed");
+    }
+    // n_corr, n_in_kf2, n_out_kf2, n_bad, n_bad_out_kf2, n_more, the return value, classifications run, iterations, trials, rejected, failures, zeros
+    int sim3Header[XFH_SIM3_OPT_HEADER_INTS] = {};
+    double sim3State[8] = {};                                // quaternion (x, y, z, w), t, s of g2oS12 on return
+    double sim3FinalChi2 = 0.0;
+
     int nInitialCorrespondences() const { return header[0]; }
     int nBad() const { return header[1]; }
     // n_initial, n_bad, the return value, rounds run, Levenberg iterations, trials, rejected trials, factorisation failures
@@ -83,6 +158,9 @@ private:
     void* d_buf = nullptr; size_t bytes = 0;
     float* d_pose = nullptr; unsigned char* d_outlier = nullptr; float* d_chi2 = nullptr;
     int n = 0;
+    void* d_s3 = nullptr; size_t s3_bytes = 0;                       // OptimizeSim3's own buffer
+    int* d_matches = nullptr; unsigned char* d_status = nullptr; float* d_chi2_pairs = nullptr; float* d_S12 = nullptr; float* d_Scw = nullptr; float* d_Ow = nullptr;
+    int n_pairs = 0;
 };
 
 }  // namespace ORB_SLAM3

@@ -1584,7 +1584,7 @@ int xfh_two_view_check_rt(const xfh_camera* cam, const float* T21, float sigma, 
  *   xfh_sim3_solve_check  step 6 of one correspondence (X1, X2 in their camera frames) -> err [2] and the flag
  *   xfh_sim3_merge_matches_device / xfh_sim3_merge_matches / xfh_sim3_merge_matches_host   the merge: three launches; J in 1 .. 65535, n1, n2 in
  *                         1 .. XFH_GRID_MAX_N; the host form takes M ints of workspace.
- * Out of scope: Optimizer::OptimizeSim3; the KannalaBrandt8 project; per-keypoint octaves other than 0; the 4-argument iterate / find as
+ * Optimizer::OptimizeSim3 behind this call is xfh_sim3_optimize_device below.  Out of scope: the KannalaBrandt8 project; per-keypoint octaves other than 0; the 4-argument iterate / find as
  * separate entry points (the same rule gives them: find() is iterate(mRansacMaxIts), one chunk, and the chunk length does not enter the rule;
  * the 4-argument iterate differs from the 5-argument one only in what it returns without convergence). */
 enum { XFH_SIM3_SOLVE_TOO_FEW = 0, XFH_SIM3_SOLVE_NO_MORE = 1, XFH_SIM3_SOLVE_CONVERGED = 2 };
@@ -1616,6 +1616,115 @@ int xfh_sim3_merge_matches_device(xfh_ctx* ctx, int J, int n1, int n2, int M, co
 int xfh_sim3_merge_matches(xfh_ctx* ctx, int J, int n1, int n2, int M, const int* match12, const int* point2, int* matched, int* matched_kf, int* num_matches);
 int xfh_sim3_merge_matches_host(int J, int n1, int n2, int M, const int* match12, const int* point2, void* workspace, int* matched, int* matched_kf,
                                 int* num_matches);
+
+/* ---- OptimizeSim3: the similarity refinement between the two Sim3 projection searches of loop detection, device resident --------------------
+ * Optimizer::OptimizeSim3(pKF1, pKF2, vpMatches1, g2oS12, th2, bFixScale, mAcumHessian, bAllPoints) (src/Optimizer.cc:2100-2381) as
+ * LoopClosing::DetectCommonRegionsFromBoW (src/LoopClosing.cc:767) and DetectAndReffineSim3FromLastKF (:556) call it, Pinhole cameras.  Not a graph
+ * optimiser: the one fixed problem that function sets up -- one Sim3 vertex of 7 unknowns, two mono edges per correspondence, fixed points,
+ * Levenberg on a dense 7x7 system -- for B problems per call.  It reads what xfh_sim3_solve_device (d_floats + 12 with stride
+ * XFH_SIM3_SOLVE_FLOATS is d_S12) and the coarse xfh_map_projection_search_device (d_assigned) leave in device memory, and writes what the fine
+ * xfh_map_projection_search_device reads (d_Tcw, d_Ow).  The rule is written once in xfeatslam_amd/csrc/optsim3_math.h and compiled for the
+ * kernel, the host form and the piece functions below; IEEE double in the order written there unless a float is named.
+ *
+ * Side 1 is the current keyframe: d_T1w [12] row-major [R|t], d_xy_un1 [n1][2] (mvKeysUn), d_point1 [n1] = the row of the keyframe's own map point
+ *   in d_points1 [M1][3] (world positions); an entry outside 0 .. M1 - 1 is NULL or isBad(), which both leave the loop without an edge (:2183-2227;
+ *   only counters nobody reads tell them apart).  With side1_shared = 1 every problem reads problem 0's arrays, with 0 its own block.
+ * Side 2, per problem: d_assigned [B][n1] = exactly the d_assigned of the coarse search, assigned[i] = q the row of vpMatches1[i] in d_points2
+ *   [B][nq][3], anything outside 0 .. nq - 1 is NULL; d_flags2 [B][nq] bytes, bit 0 = !pMP2->isBad() (the search's XFH_MAPPROJ_FLAG_ACTIVE array
+ *   can be passed as it is); d_index2 [B][nq] ints = get<0>(GetIndexInKeyFrame(pKF2)), negative = not in KF2 (STATED: an index >= n2, which the
+ *   reference cannot produce, is "not in KF2" too); d_xy_un2 [B][n2][2]; d_T2w [B][12].
+ * d_S12 + b * S12_problem_stride: 13 floats, R row-major 9, t 3, s.  d_Tmw_or_null [B][12]: the pose of pMostBoWMatchesKF for the composed output.
+ * Host scalars: cam1, cam2 (fx, fy, cx, cy are read), th2, fix_scale, all_points, inv_sigma2_1, inv_sigma2_2 (mvInvLevelSigma2[octave]: every
+ *   XFeat keypoint has octave 0, and the cv::KeyPoint(Point2f, mnTrackScaleLevel) of :2280 passes the level as the SIZE, so its octave is 0 too).
+ *
+ * Edges (:2167-2304).  Keypoint i has the edge pair iff assigned[i] is valid, bit 0 of its flag byte is set, point1[i] is valid, index2 >= 0 ||
+ *   all_points, and !(P3D2c.z < 0) (a NaN z passes, as there).  P3D1c = R1w X1 + t1w and P3D2c = R2w X2 + t2w in FLOAT, each row ((a*x + b*y) +
+ *   c*z) + t (no bit claim against Eigen's product), then widened.  e12 (EdgeSim3ProjectXYZ): error = obs1 - project1(S12.map(P3D2c)), obs1 =
+ *   xy_un1[i].  e21 (EdgeInverseSim3ProjectXYZ): error = obs2 - project2(S12.inverse().map(P3D1c)); obs2 = xy_un2[index2] when the point is in
+ *   KF2, otherwise the NORMALISED coordinates the reference writes at :2275-2279 (invz = 1 / z, x * invz, y * invz in float) -- not pixels,
+ *   although the edge projects to pixels; such a pair normally leaves in the first classification, and that behaviour is kept, not repaired.
+ *   project = f * x / z + c in double (Pinhole.cpp:35-41).  Information = inv_sigma2 * I, chi2 = e0 * (w * e0) + e1 * (w * e1), Huber delta =
+ *   (float)sqrt(th2) (:2157).  n_corr = the number of pairs; n_in_kf2 / n_out_kf2 split them by index2.
+ * State (thirdparty/g2o/g2o/types/sim3.h).  Quaternion (x, y, z, w), t, s, doubles.  The quaternion comes from R by the matrix-to-quaternion rule
+ *   of the PoseOptimization section and is NOT normalised afterwards (Sim3(R, t, s) does not, neither does operator*).  map(X) = s * (r * X) + t,
+ *   r * X by Eigen's quaternion-vector formula; inverse() = (r*, r* * ((-1 / s) * t), 1 / s).  An update u = (omega, upsilon, sigma) is applied as
+ *   Sim3(u) * estimate (OptimizableTypes.h:158-167) with u[6] = 0 first under fix_scale; Sim3(u) is the exponential of sim3.h:70-142 with all four
+ *   branches of (|sigma| < 1e-5, theta < 1e-5), through the matrix-to-quaternion rule again.  No bit claim against Eigen / libm.
+ * Jacobian.  The reference defines no linearizeOplus for these edges (OptimizableTypes.h:192, 213), so g2o differentiates numerically
+ *   (base_binary_edge.hpp:130-205): column d = (e(exp(+delta e_d) (+) est) - e(exp(-delta e_d) (+) est)) * (1 / (2 delta)), delta = 1e-9; the
+ *   points are fixed, so only the 2 x 7 block of the Sim3 vertex exists.  The rule IS that central difference: its rounding noise, about 1e-7
+ *   relative in an entry, is part of the path the reference takes.  The 14 perturbed similarities and their 14 inverses are the same for every
+ *   edge and are computed once per linearisation.  With fix_scale column 6 is exactly zero and H_66 is lambda alone.
+ * System and Levenberg (:2306-2380).  An edge adds B^T (rho[1] w) B to H and subtracts rho[1] B^T (w e) from b (base_binary_edge.hpp:56-120).
+ *   The Levenberg loop is the one the PoseOptimization section describes -- lambda init, trial loop, rho, stop rules, the unpivoted LDL^T that
+ *   fails at a pivot that is not > 0, x kept after a failure, the NaN behaviour -- with 7 unknowns.
+ *   Round 1: optimize(5), all pairs, Huber; it runs whenever n_corr >= 1.  Classification 1: a pair is bad iff chi2_12 > (double)th2 || chi2_21 >
+ *   (double)th2, each chi2 read from _error as the last computeActiveErrors() left it -- after a rejected last trial the error at the REJECTED
+ *   estimate.  n_bad, n_bad_out_kf2 (bad pairs not in KF2); the survivors lose their kernel.  n_more = n_bad > 0 ? 10 : 5.  n_corr - n_bad < 10:
+ *   the function returns 0, the estimate stays the INPUT (the reference returns before :2378) and the bad matches are already removed.
+ *   Round 2: optimize(n_more) CONTINUES from round 1's estimate, survivors only, no kernel, lambda afresh.  Final classification: fresh errors at
+ *   the final estimate, the same test; a failing pair loses its match, the others count into n_in, the return value.  mAcumHessian is zeroed at
+ *   :2356 and never filled: not an output.  At most (5 + 10) x 10 trials run whatever the data.
+ * Sums.  The upper triangle of H (28), b (7) and the robust chi2 are folded as in xfh_pose_optimize_device: lane l of 256 adds its keypoints l,
+ *   l + 256, .. in that order, e12 before e21; 64 lanes fold by the xor butterfly 32 .. 1; the four waves in order.  Two runs give identical
+ *   bytes, and a problem's result does not depend on B or on its neighbours.
+ *
+ *   xfh_sim3_state_from / _to   13 floats <-> state8 = (qx, qy, qz, qw, tx, ty, tz, s); host, stateless, thread-safe, no ctx, the kernel's own
+ *                         lines, as are:  xfh_sim3_oplus (update7, fix_scale), xfh_sim3_map, xfh_sim3_inverse_map (inverse() then map),
+ *                         xfh_sim3_solve7 (H28 = the upper triangle row by row; 1, or 0 with x untouched when a pivot is not > 0),
+ *                         xfh_sim3_edge: one pair (its two camera-frame points and observations) at one state -> error4 (e12, e21), chi2_2,
+ *                         jacobian28 (the 2 x 7 numeric Jacobian of e12 row-major, then e21's) and rho[1] of each Huber kernel (1 when robust
+ *                         == 0); any output may be NULL.
+ *   xfh_sim3_optimize_workspace_bytes   bytes of d_workspace for B problems of n1 keypoints (0 for arguments the call would refuse).  For n1 <=
+ *                         1024 the kernel keeps every pair in registers and does not touch it.
+ *   xfh_sim3_optimize_device   B problems, ONE launch, one workgroup each, asynchronous on the ctx stream: no host synchronisation, no allocation.
+ *                         Outputs, every one always written: d_assigned_out [B][n1] = the input with -1 where vpMatches1 was set NULL (may be
+ *                         d_assigned); d_pair_status [B][n1] bytes XFH_SIM3_OPT_NO_EDGE / _BAD_FIRST / _BAD_FINAL / _INLIER (INLIER = the pair
+ *                         kept its match: after the early return that is every survivor of classification 1); d_chi2 [B][n1][2] floats, the
+ *                         two values the pair's last classification read, 0 without an edge; d_state [B][8] doubles, the estimate g2oS12 holds
+ *                         on return; d_S12_out + b * S12_out_problem_stride, 13 floats in the input layout, the matrix taken from the
+ *                         quaternion (may be d_S12 when the strides agree); d_Tcw [B][12], d_Ow [B][3], written (and required) only with d_Tmw:
+ *                         gScw = gS12 * Sim3(Rmw, tmw, 1), Tcw = [R | t / s], Ow = -R^T (t / s) in double, rounded once
+ *                         (LoopClosing.cc:771-773, ORBmatcher.cc:621-622); d_header [B][XFH_SIM3_OPT_HEADER_INTS] ints: n_corr, n_in_kf2,
+ *                         n_out_kf2, n_bad, n_bad_out_kf2, n_more, the return value, classifications run (1 or 2), Levenberg iterations,
+ *                         trials, rejected trials, factorisation failures, zeros; d_final_chi2 [B] doubles, currentChi of the last iteration
+ *                         that ran (0 if none).
+ *                         XFH_ERR_INVALID_ARG before any launch: B outside 1 .. 65535; n1, M1, nq or n2 outside 1 .. XFH_GRID_MAX_N; a NULL
+ *                         required pointer; a misaligned pointer (16 bytes for the workspace, 8 for d_state and d_final_chi2, 4 for floats
+ *                         and ints); th2 or an inv_sigma2 that is not finite or not > 0; side1_shared, fix_scale or all_points outside 0 .. 1;
+ *                         a stride below 13 floats.  Every array may hold anything, NaN, Inf and any int included: no load or store leaves the
+ *                         named buffers, and the call terminates.
+ *   xfh_sim3_optimize     host-pointer form for ONE problem through the ctx staging arena (S12 and S12_out are 13 floats).
+ *   xfh_sim3_optimize_host   the whole rule on ONE host thread over host pointers (workspace included): no ctx, no GPU.
+ * Out of scope: KannalaBrandt8, octaves other than 0, OptimizeEssentialGraph and the other graph optimisers. */
+enum { XFH_SIM3_OPT_NO_EDGE = 0, XFH_SIM3_OPT_BAD_FIRST = 1, XFH_SIM3_OPT_BAD_FINAL = 2, XFH_SIM3_OPT_INLIER = 3 };
+#define XFH_SIM3_OPT_HEADER_INTS 16
+#define XFH_SIM3_OPT_S12_FLOATS 13
+int xfh_sim3_state_from(const float* S13, double* state8);
+int xfh_sim3_state_to(const double* state8, float* S13);
+int xfh_sim3_oplus(const double* state8, const double* update7, int fix_scale, double* state8_out);
+int xfh_sim3_map(const double* state8, const double* point3, double* out3);
+int xfh_sim3_inverse_map(const double* state8, const double* point3, double* out3);
+int xfh_sim3_solve7(const double* H28, double lambda, const double* b7, double* x7);
+int xfh_sim3_edge(const double* state8, const xfh_camera* cam1, const xfh_camera* cam2, const float* P3D1c, const float* P3D2c, const float* obs1, const float* obs2,
+                  float inv_sigma2_1, float inv_sigma2_2, float th2, int fix_scale, int robust, double* error4, double* chi2_2, double* jacobian28, double* rho1_2);
+size_t xfh_sim3_optimize_workspace_bytes(int n1, int B);
+int xfh_sim3_optimize_device(xfh_ctx* ctx, int B, int n1, int M1, int nq, int n2, int side1_shared, const float* d_T1w, const float* d_xy_un1, const int* d_point1,
+                             const float* d_points1, const int* d_assigned, const float* d_points2, const uint8_t* d_flags2, const int* d_index2,
+                             const float* d_xy_un2, const float* d_T2w, const float* d_S12, size_t S12_problem_stride, const float* d_Tmw_or_null,
+                             const xfh_camera* cam1, const xfh_camera* cam2, float th2, int fix_scale, int all_points, float inv_sigma2_1, float inv_sigma2_2,
+                             void* d_workspace, int* d_assigned_out, uint8_t* d_pair_status, float* d_chi2, double* d_state, float* d_S12_out,
+                             size_t S12_out_problem_stride, float* d_Tcw, float* d_Ow, int* d_header, double* d_final_chi2);
+int xfh_sim3_optimize(xfh_ctx* ctx, int n1, int M1, int nq, int n2, const float* T1w, const float* xy_un1, const int* point1, const float* points1,
+                      const int* assigned, const float* points2, const uint8_t* flags2, const int* index2, const float* xy_un2, const float* T2w, const float* S12,
+                      const float* Tmw_or_null, const xfh_camera* cam1, const xfh_camera* cam2, float th2, int fix_scale, int all_points, float inv_sigma2_1,
+                      float inv_sigma2_2, int* assigned_out, uint8_t* pair_status, float* chi2, double* state, float* S12_out, float* Tcw, float* Ow, int* header,
+                      double* final_chi2);
+int xfh_sim3_optimize_host(int B, int n1, int M1, int nq, int n2, int side1_shared, const float* T1w, const float* xy_un1, const int* point1, const float* points1,
+                           const int* assigned, const float* points2, const uint8_t* flags2, const int* index2, const float* xy_un2, const float* T2w,
+                           const float* S12, size_t S12_problem_stride, const float* Tmw_or_null, const xfh_camera* cam1, const xfh_camera* cam2, float th2,
+                           int fix_scale, int all_points, float inv_sigma2_1, float inv_sigma2_2, void* workspace, int* assigned_out, uint8_t* pair_status,
+                           float* chi2, double* state, float* S12_out, size_t S12_out_problem_stride, float* Tcw, float* Ow, int* header, double* final_chi2);
 
 /* ---- MLPnPsolver (src/MLPnPsolver.cpp) as Tracking::Relocalization drives it (src/Tracking.cc:3678-3773) ------------------------------------------
  * The step between xfh_bow_search_device (shared = 2: the current frame against the B relocalisation candidates) and xfh_pose_optimize_device:

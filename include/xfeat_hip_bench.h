@@ -32,7 +32,8 @@ enum {
     XFH_K_TWOVIEW_FINAL = 44,
     XFH_K_SIM3SOLVE_PREPARE = 45, XFH_K_SIM3SOLVE_FIT = 46, XFH_K_SIM3SOLVE_COUNT = 47, XFH_K_SIM3SOLVE_DECIDE = 48, XFH_K_SIM3SOLVE_MERGE = 49,
     XFH_K_MLPNP_PREPARE = 50, XFH_K_MLPNP_FIT = 51, XFH_K_MLPNP_COUNT = 52, XFH_K_MLPNP_RECORDS = 53, XFH_K_MLPNP_REFINE = 54, XFH_K_MLPNP_DECIDE = 55,
-    XFH_K_COUNT = 56
+    XFH_K_SIM3_OPTIMIZE = 56,
+    XFH_K_COUNT = 57
 };
 /* layer_mask selects conv layers for XFH_K_CONV_*: 0 = every layer, else bit i = BasicLayer i
  * (0..22 in XFeatModel order) and bit 23 = block_fusion.2 */

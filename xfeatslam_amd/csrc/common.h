@@ -224,6 +224,8 @@ struct InitArgs;
 hipError_t launch_init_search(xfh_ctx* c, const InitArgs& a, int B);                  // init_search.hip.h
 struct PoseArgs;
 hipError_t launch_pose_optimize(xfh_ctx* c, const PoseArgs& a, int B);              // poseopt.hip.h
+struct Os3Args;
+hipError_t launch_sim3_optimize(xfh_ctx* c, const Os3Args& a, int B);               // optsim3.hip.h
 struct TriangArgs;
 hipError_t launch_triangulate(xfh_ctx* c, const TriangArgs& a);                        // triangulate.hip.h
 struct TvArgs;

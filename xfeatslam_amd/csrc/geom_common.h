@@ -1,6 +1,6 @@
 // geom_common.h -- what every geometry solver (triangulate_math.h, twoview_math.h, sim3solve_math.h, mlpnp_math.h, poseopt_math.h) needs of the
 // others, written ONCE for host and device (XFH_HD): the pinhole camera and the strided matrix view, the minimal set from raw draws, the
-// rotation of a column pair and the fp64 one-sided Jacobi built on it with its column helpers, the 3 x 3 determinant, the 6 x 6 LDL^T solve
+// rotation of a column pair and the fp64 one-sided Jacobi built on it with its column helpers, the 3 x 3 determinant, the unpivoted LDL^T solve
 // and two one-liners.  Plain C++; tests/cpp/geom_common_test.cpp runs these very lines against the obvious forms.
 // Every product and sum is in the order written (the library is built with -ffp-contract=off).
 #pragma once
@@ -147,25 +147,27 @@ XFH_HD T geo_det3(const T* A) {
 }
 
 // (H + lambda I) x = b by an unpivoted LDL^T in place of Eigen's pivoting LDLT + isPositive(): false, with x untouched, as soon as a pivot is not > 0
-// (a NaN pivot included).  H is the 21 upper entries of the 6 x 6 (row-major, i <= j).  PoseOptimization's Levenberg step and MLPnP's Gauss-Newton.
-XFH_HD bool pose_ldlt_solve(const double* H, double lambda, const double* b, double* x) {
-    double A[6][6], d[6], y[6];
+// (a NaN pivot included).  H is the N (N + 1) / 2 upper entries of the N x N (row-major, i <= j).  N = 6: PoseOptimization's Levenberg step and MLPnP's
+// Gauss-Newton (pose_ldlt_solve); N = 7: OptimizeSim3's Levenberg step.
+template <int N>
+XFH_HD bool geo_ldlt_solve(const double* H, double lambda, const double* b, double* x) {
+    double A[N][N], d[N], y[N];
     int n = 0;
     _Pragma("unroll")
-    for (int i = 0; i < 6; ++i)
+    for (int i = 0; i < N; ++i)
         _Pragma("unroll")
-        for (int j = i; j < 6; ++j, ++n) { A[i][j] = H[n]; A[j][i] = H[n]; }
+        for (int j = i; j < N; ++j, ++n) { A[i][j] = H[n]; A[j][i] = H[n]; }
     _Pragma("unroll")
-    for (int i = 0; i < 6; ++i) A[i][i] = A[i][i] + lambda;
+    for (int i = 0; i < N; ++i) A[i][i] = A[i][i] + lambda;
     _Pragma("unroll")
-    for (int j = 0; j < 6; ++j) {                                           // the strict lower triangle of A becomes L
+    for (int j = 0; j < N; ++j) {                                           // the strict lower triangle of A becomes L
         double dj = A[j][j];
         _Pragma("unroll")
         for (int k = 0; k < j; ++k) dj = dj - A[j][k] * A[j][k] * d[k];
         if (!(dj > 0.0)) return false;
         d[j] = dj;
         _Pragma("unroll")
-        for (int i = j + 1; i < 6; ++i) {
+        for (int i = j + 1; i < N; ++i) {
             double s = A[i][j];
             _Pragma("unroll")
             for (int k = 0; k < j; ++k) s = s - A[i][k] * A[j][k] * d[k];
@@ -173,10 +175,11 @@ XFH_HD bool pose_ldlt_solve(const double* H, double lambda, const double* b, dou
         }
     }
     _Pragma("unroll")
-    for (int i = 0; i < 6; ++i) { double s = b[i]; for (int k = 0; k < i; ++k) s = s - A[i][k] * y[k]; y[i] = s; }
+    for (int i = 0; i < N; ++i) { double s = b[i]; for (int k = 0; k < i; ++k) s = s - A[i][k] * y[k]; y[i] = s; }
     _Pragma("unroll")
-    for (int i = 0; i < 6; ++i) y[i] = y[i] / d[i];
+    for (int i = 0; i < N; ++i) y[i] = y[i] / d[i];
     _Pragma("unroll")
-    for (int i = 5; i >= 0; --i) { double s = y[i]; for (int k = i + 1; k < 6; ++k) s = s - A[k][i] * x[k]; x[i] = s; }
+    for (int i = N - 1; i >= 0; --i) { double s = y[i]; for (int k = i + 1; k < N; ++k) s = s - A[k][i] * x[k]; x[i] = s; }
     return true;
 }
+XFH_HD bool pose_ldlt_solve(const double* H, double lambda, const double* b, double* x) { return geo_ldlt_solve<6>(H, lambda, b, x); }

@@ -36,6 +36,9 @@
 //                   every query's turn against the final chains (init_search.hip.h).
 //   k_pose_optimize : Optimizer::PoseOptimization for B frames in one launch, one workgroup per frame: the edges in registers, H, b and the chi2 sums
 //                   folded in a fixed order, the Levenberg state machine on one lane (poseopt.hip.h, poseopt_math.h).
+//   k_sim3_optimize : Optimizer::OptimizeSim3 between the two Sim3 projection searches of loop detection, B problems in one launch, one workgroup each:
+//                   two edges per correspondence with g2o's numeric Jacobian (its 14 + 14 perturbed similarities built once per linearisation in
+//                   LDS), the same fold, a Levenberg state machine of 7 unknowns on one lane (optsim3.hip.h, optsim3_math.h).
 //   k_triangulate_pairs / k_triangulate_winner / k_triangulate_finish : the triangulation half of LocalMapping::CreateNewMapPoints for B neighbours per call:
 //                   one lane per matched pair (parallax, fp64 null vector or stereo unprojection, the gates), then the least accepted neighbour per
 //                   keypoint, then per neighbour the header and the ordered compact list (triangulate.hip.h, triangulate_math.h).
@@ -112,6 +115,7 @@ hipError_t launch_best2(xfh_ctx* c, const float* q, int nq, const float* tg, con
 #include "sim3_search.hip.h"
 #include "init_search.hip.h"
 #include "poseopt.hip.h"
+#include "optsim3.hip.h"
 #include "triangulate.hip.h"
 #include "twoview.hip.h"
 #include "sim3solve.hip.h"

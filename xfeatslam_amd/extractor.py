@@ -942,6 +942,44 @@ class Context:
                                       p.ctypes.data, float(inv_sigma2), To.ctypes.data, ol.ctypes.data, c2.ctypes.data, hd.ctypes.data, fc.ctypes.data), self.h)
         return dict(ret=int(hd[2]), Tcw=To.reshape(3, 4), outlier=ol, chi2=c2, header=dict(zip(self.POSE_HEADER, hd.tolist())), final_chi2=float(fc[0]))
 
+    # -- OptimizeSim3 between the two Sim3 projection searches of loop detection (xfh_sim3_optimize*) ---------------------------
+    SIM3_OPT_HEADER = ("n_corr", "n_in_kf2", "n_out_kf2", "n_bad", "n_bad_out_kf2", "n_more", "ret", "rounds", "iterations", "trials", "rejected", "ldlt_failures")
+
+    @staticmethod
+    def sim3_optimize_workspace_bytes(n1: int, B: int = 1) -> int:
+        return int(lib().xfh_sim3_optimize_workspace_bytes(n1, B))
+
+    def sim3_optimize_device(self, B: int, n1: int, M1: int, nq: int, n2: int, side1_shared: bool, side1, side2, d_S12, S12_stride: int, d_Tmw, cam1, cam2,
+                             d_workspace, d_assigned_out, d_pair_status, d_chi2, d_state, d_S12_out, S12_out_stride: int, d_Tcw, d_Ow, d_header, d_final_chi2,
+                             th2: float = 10.0, fix_scale: bool = False, all_points: bool = False, inv_sigma2_1: float = 1.0, inv_sigma2_2: float = 1.0):
+        """xfh_sim3_optimize_device on device pointers; asynchronous.  side1: (d_T1w, d_xy_un1, d_point1, d_points1); side2: (d_assigned, d_points2,
+        d_flags2, d_index2, d_xy_un2, d_T2w).  d_S12 with stride XFH_SIM3_SOLVE_FLOATS is xfh_sim3_solve_device's d_floats + 12; d_assigned_out may
+        be d_assigned, d_S12_out may be d_S12; d_Tmw (and with it d_Tcw, d_Ow) may be None"""
+        check(lib().xfh_sim3_optimize_device(self.h, B, n1, M1, nq, n2, 1 if side1_shared else 0, *side1, *side2, d_S12, S12_stride, d_Tmw, C.byref(cam1),
+                                             C.byref(cam2), float(th2), 1 if fix_scale else 0, 1 if all_points else 0, float(inv_sigma2_1), float(inv_sigma2_2),
+                                             d_workspace, d_assigned_out, d_pair_status, d_chi2, d_state, d_S12_out, S12_out_stride, d_Tcw, d_Ow, d_header,
+                                             d_final_chi2), self.h)
+
+    def sim3_optimize(self, T1w, xy_un1, point1, points1, assigned, points2, flags2, index2, xy_un2, T2w, S12, cam1, cam2, Tmw=None, th2: float = 10.0,
+                      fix_scale: bool = False, all_points: bool = False, inv_sigma2_1: float = 1.0, inv_sigma2_2: float = 1.0):
+        """xfh_sim3_optimize (host pointers, one problem) -> dict(ret, assigned, status, chi2, state, S12, Tcw, Ow, header, final_chi2); ret is the
+        reference's return value, assigned is vpMatches1 with -1 where a match was removed"""
+        f32 = lambda a, shape: np.ascontiguousarray(a, np.float32).reshape(shape)
+        i32 = lambda a: np.ascontiguousarray(a, np.int32).reshape(-1)
+        ins = [f32(T1w, 12), f32(xy_un1, (-1, 2)), i32(point1), f32(points1, (-1, 3)), i32(assigned), f32(points2, (-1, 3)),
+               np.ascontiguousarray(flags2, np.uint8).reshape(-1), i32(index2), f32(xy_un2, (-1, 2)), f32(T2w, 12), f32(S12, 13)]
+        n1, M1, nq, n2 = len(ins[4]), len(ins[3]), len(ins[5]), len(ins[8])
+        assert len(ins[1]) == n1 and len(ins[2]) == n1 and len(ins[6]) == nq and len(ins[7]) == nq
+        tm = None if Tmw is None else f32(Tmw, 12)
+        ao, st, c2, sv, so = np.zeros(n1, np.int32), np.zeros(n1, np.uint8), np.zeros((n1, 2), np.float32), np.zeros(8, np.float64), np.zeros(13, np.float32)
+        To, Ow, hd, fc = np.zeros(12, np.float32), np.zeros(3, np.float32), np.zeros(16, np.int32), np.zeros(1, np.float64)
+        check(lib().xfh_sim3_optimize(self.h, n1, M1, nq, n2, *[a.ctypes.data for a in ins], None if tm is None else tm.ctypes.data, C.byref(cam1), C.byref(cam2),
+                                      float(th2), 1 if fix_scale else 0, 1 if all_points else 0, float(inv_sigma2_1), float(inv_sigma2_2), ao.ctypes.data,
+                                      st.ctypes.data, c2.ctypes.data, sv.ctypes.data, so.ctypes.data, None if tm is None else To.ctypes.data,
+                                      None if tm is None else Ow.ctypes.data, hd.ctypes.data, fc.ctypes.data), self.h)
+        return dict(ret=int(hd[6]), assigned=ao, status=st, chi2=c2, state=sv, S12=so, Tcw=None if tm is None else To.reshape(3, 4), Ow=None if tm is None else Ow,
+                    header=dict(zip(self.SIM3_OPT_HEADER, hd.tolist())), final_chi2=float(fc[0]))
+
     # -- CreateNewMapPoints: triangulation of the matched pairs (xfh_triangulate*) ----------------------------------------------
     TRIANG_HEADER = ("matched", "tri_attempts", "stereo_attempts", "accepted", "new", "new_stereo", "superseded", "reserved")
     TRIANG_CLAIM_OUT = ("winner", "new_idx1", "new_b", "new_idx2", "new_xyz", "new_normal", "new_dist", "n_new")
