@@ -494,6 +494,33 @@ def test_geometry_kernel_register_contract():
         assert scratch <= scratch_before, (name, rows[hit[0]], GEOMETRY_KERNELS_BEFORE[name])
 
 
+# The two Levenberg kernels of kernels_match.hip at the commit before their state machine moved into geom_common.h and their quaternion product into one
+# place in poseopt_math.h: (VGPRs, AGPRs, occupancy in waves per SIMD) as tools/kres.sh printed them for that commit
+# with clang 22 / ROCm 7.2.  Every instance was at scratch 0; the AGPRs are spill space, and k_sim3_optimize<4> is 40 of them from scratch.
+LEVENBERG_KERNELS_BEFORE = {
+    "k_pose_optimize<4>": (256, 0, 2), "k_pose_optimize<16>": (256, 224, 1), "k_pose_optimize<0>": (236, 0, 2),
+    "k_sim3_optimize<4>": (256, 216, 1), "k_sim3_optimize<0>": (256, 150, 1),
+}
+
+
+def test_levenberg_kernel_register_contract():
+    """k_pose_optimize and k_sim3_optimize share the Levenberg machine (geom_common.h) and the quaternion product (poseopt_math.h) and sit at the
+    register limit: every instance is there exactly once, none uses scratch and none runs at a lower occupancy than before the pieces were shared
+    (LEVENBERG_KERNELS_BEFORE; a fold-and-dispatch helper shared by the two kernels cost k_pose_optimize<0> its second wave per SIMD,
+    profiles/levenberg_common.md).  tools/kres.sh reads clang's kernel-resource-usage remarks (no GPU needed)."""
+    import shutil
+    if not shutil.which("c++filt") or not os.path.exists("/opt/rocm/bin/hipcc"):
+        pytest.skip("needs hipcc and c++filt")
+    out = subprocess.run(["bash", os.path.join(ROOT, "tools", "kres.sh"), "kernels_match.hip"], capture_output=True, text=True, timeout=600).stdout
+    rows = _kres_rows(out)
+    for name, (_, _, occ_before) in LEVENBERG_KERNELS_BEFORE.items():
+        hit = [k for k in rows if k.split("(")[0] == name]
+        assert len(hit) == 1, (name, sorted(rows))
+        vgpr, agpr, scratch, occ = rows[hit[0]]
+        print(f"{name}: vgpr {vgpr} agpr {agpr} scratch {scratch} occ {occ}   before: {LEVENBERG_KERNELS_BEFORE[name]}")
+        assert scratch == 0 and occ >= occ_before, (name, rows[hit[0]], LEVENBERG_KERNELS_BEFORE[name])
+
+
 def test_geometry_shared_pieces_under_sanitizers(tmp_path):
     """tests/cpp/geom_common_test.cpp, a stand-alone program built from geom_common.h alone with AddressSanitizer + UBSan: the K-set against the
     std::vector swap-remove, the cached and the run-time-rows Jacobi against each other by bits, the tie rules.  Nothing of the library is

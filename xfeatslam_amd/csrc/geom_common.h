@@ -1,11 +1,13 @@
 // geom_common.h -- what every geometry solver (triangulate_math.h, twoview_math.h, sim3solve_math.h, mlpnp_math.h, poseopt_math.h) needs of the
 // others, written ONCE for host and device (XFH_HD): the pinhole camera and the strided matrix view, the minimal set from raw draws, the
-// rotation of a column pair and the fp64 one-sided Jacobi built on it with its column helpers, the 3 x 3 determinant, the unpivoted LDL^T solve
-// and two one-liners.  Plain C++; tests/cpp/geom_common_test.cpp runs these very lines against the obvious forms.
+// rotation of a column pair and the fp64 one-sided Jacobi built on it with its column helpers, the 3 x 3 determinant, the unpivoted LDL^T solve,
+// the Levenberg step of the two optimisers (poseopt_math.h, optsim3_math.h) on top of it and two one-liners.  Plain C++;
+// tests/cpp/geom_common_test.cpp runs these very lines against the obvious forms, asan_poseopt_test.cpp and asan_optsim3_test.cpp the Levenberg step.
 // Every product and sum is in the order written (the library is built with -ffp-contract=off).
 #pragma once
 #include "hd.h"
 #include <math.h>
+#include <float.h>
 #include <stddef.h>
 
 struct GeoCam { float fx, fy, cx, cy; };
@@ -183,3 +185,70 @@ XFH_HD bool geo_ldlt_solve(const double* H, double lambda, const double* b, doub
     return true;
 }
 XFH_HD bool pose_ldlt_solve(const double* H, double lambda, const double* b, double* x) { return geo_ldlt_solve<6>(H, lambda, b, x); }
+
+// ---- the Levenberg step ------------------------------------------------------------------------------------------------------------------------
+// g2o's optimize() loop (optimization_algorithm_levenberg.cpp:61-194) as a state machine that one lane or one host thread drives, written ONCE for
+// PoseOptimization (PoseLM of poseopt_math.h, 6 unknowns) and OptimizeSim3 (Os3LM of optsim3_math.h, 7).  The driver runs the pass an action asks for
+// over every edge at S.est and hands the folded sums back: BUILD wants the N (N + 1) / 2 upper entries of H, the N of b and the robust chi2
+// (computeActiveErrors + activeRobustChi2 + buildSystem), TRIAL the robust chi2 alone, CLASSIFY is the optimiser's own step between two optimize() calls.
+// LM is a flat struct with the fields est, backup, H, b, x, lambda, ni, currentChi, iniChi, iter, qmax, nbad_lm, solved and hdr, and the statics
+//   N              the number of unknowns
+//   H_ITERATIONS   where hdr counts the iterations; the trials, the rejected trials and the LDL^T failures follow it in that order
+//   iterations(S)  the argument of the optimize() call that is running
+//   oplus(S)       oplusImpl: the estimate S.est updated by S.x
+enum { GEO_LM_BUILD = 0, GEO_LM_TRIAL = 1, GEO_LM_CLASSIFY = 2, GEO_LM_DONE = 3 };
+#define GEO_LM_MAX_TRIALS 10              /* _maxTrialsAfterFailure */
+
+template <class LM>
+XFH_HD int geo_lm_trial(LM& S) {                                            // push(); setLambda; solve(); update(x)
+    S.backup = S.est;
+    S.solved = geo_ldlt_solve<LM::N>(S.H, S.lambda, S.b, S.x) ? 1 : 0;
+    S.est = LM::oplus(S);
+    ++S.hdr[LM::H_ITERATIONS + 1];
+    if (!S.solved) ++S.hdr[LM::H_ITERATIONS + 3];
+    return GEO_LM_TRIAL;
+}
+template <class LM>
+XFH_HD int geo_lm_after_build(LM& S, const double* sums) {
+    constexpr int N = LM::N, NH = N * (N + 1) / 2;
+    _Pragma("unroll")
+    for (int k = 0; k < NH; ++k) S.H[k] = sums[k];
+    _Pragma("unroll")
+    for (int k = 0; k < N; ++k) S.b[k] = sums[NH + k];
+    S.currentChi = sums[NH + N]; S.iniChi = S.currentChi;
+    if (S.iter == 0) {                                                      // computeLambdaInit: std::max(fabs(H_jj), maxDiagonal), a NaN first argument wins
+        double m = 0.0;
+        _Pragma("unroll")
+        for (int j = 0, n = 0; j < N; n += N - j, ++j) { const double a = fabs(S.H[n]); m = (a < m) ? m : a; }
+        S.lambda = 1e-5 * m; S.ni = 2.0; S.nbad_lm = 0;
+    }
+    S.qmax = 0;
+    ++S.hdr[LM::H_ITERATIONS];
+    return geo_lm_trial(S);
+}
+template <class LM>
+XFH_HD int geo_lm_after_trial(LM& S, double chi) {
+    const double tempChi = S.solved ? chi : DBL_MAX;
+    double rho = S.currentChi - tempChi, scale = 0.0;
+    _Pragma("unroll")
+    for (int j = 0; j < LM::N; ++j) scale += S.x[j] * (S.lambda * S.x[j] + S.b[j]);
+    scale += 1e-3;
+    rho /= scale;
+    if (rho > 0.0 && isfinite(tempChi)) {
+        const double t = 2.0 * rho - 1.0;
+        double alpha = 1.0 - t * t * t;
+        alpha = (2.0 / 3.0 < alpha) ? 2.0 / 3.0 : alpha;                    // std::min(alpha, _goodStepUpperScale)
+        const double f = (1.0 / 3.0 < alpha) ? alpha : 1.0 / 3.0;           // std::max(_goodStepLowerScale, alpha)
+        S.lambda *= f; S.ni = 2.0; S.currentChi = tempChi;
+    } else {
+        S.lambda *= S.ni; S.ni *= 2.0;
+        S.est = S.backup;                                                   // pop(): the edges keep the errors of the rejected estimate
+        ++S.hdr[LM::H_ITERATIONS + 2];
+    }
+    ++S.qmax;
+    if (rho < 0.0 && S.qmax < GEO_LM_MAX_TRIALS) return geo_lm_trial(S);
+    if (S.qmax == GEO_LM_MAX_TRIALS || rho == 0.0) return GEO_LM_CLASSIFY;
+    if ((S.iniChi - S.currentChi) * 1e3 < S.iniChi) ++S.nbad_lm; else S.nbad_lm = 0;
+    if (S.nbad_lm >= 3) return GEO_LM_CLASSIFY;
+    return ++S.iter < LM::iterations(S) ? GEO_LM_BUILD : GEO_LM_CLASSIFY;
+}

@@ -35,10 +35,10 @@
 //                   its window, then the reference's retraction order resolved per problem with the acceptors of every keypoint chained in LDS, then
 //                   every query's turn against the final chains (init_search.hip.h).
 //   k_pose_optimize : Optimizer::PoseOptimization for B frames in one launch, one workgroup per frame: the edges in registers, H, b and the chi2 sums
-//                   folded in a fixed order, the Levenberg state machine on one lane (poseopt.hip.h, poseopt_math.h).
+//                   folded in a fixed order, the Levenberg state machine of geom_common.h on one lane (poseopt.hip.h, poseopt_math.h).
 //   k_sim3_optimize : Optimizer::OptimizeSim3 between the two Sim3 projection searches of loop detection, B problems in one launch, one workgroup each:
 //                   two edges per correspondence with g2o's numeric Jacobian (its 14 + 14 perturbed similarities built once per linearisation in
-//                   LDS), the same fold, a Levenberg state machine of 7 unknowns on one lane (optsim3.hip.h, optsim3_math.h).
+//                   LDS), the same fold, the same Levenberg state machine with 7 unknowns on one lane (optsim3.hip.h, optsim3_math.h).
 //   k_triangulate_pairs / k_triangulate_winner / k_triangulate_finish : the triangulation half of LocalMapping::CreateNewMapPoints for B neighbours per call:
 //                   one lane per matched pair (parallax, fp64 null vector or stereo unprojection, the gates), then the least accepted neighbour per
 //                   keypoint, then per neighbour the header and the ordered compact list (triangulate.hip.h, triangulate_math.h).
@@ -51,7 +51,7 @@
 //   (the kernels of the MLPnP solver, k_mlpnp_*, are in kernels_mlpnp.hip: two of them use scratch, which no kernel of this file may)
 //   k_distinctive_csr : MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:329-403), one wave per map point.
 // Shared by k_best2_csr and every *_search.hip.h kernel: search_common.hip.h (keys, descriptor_distance, top-two and K-list with their wave merges, wave
-// minimum / sum), window_search.hip.h (the grid walk), nodes_clamp.h (node blobs), resolve_rounds.hip.h (the rounds of k_proj_resolve / k_init_resolve: the argument, the cut, the advance of lo).
+// minimum / sum, the fp64 wave sum of the two optimisers), window_search.hip.h (the grid walk), nodes_clamp.h (node blobs), resolve_rounds.hip.h (the rounds of k_proj_resolve / k_init_resolve: the argument, the cut, the advance of lo).
 //
 // Numerics: normalised rows and the 64-term dot products are bit-identical to the oracle
 // (fp64 sum of squares -> fp32 sqrt/max/div; one fp32 fma chain in k order, which is what

@@ -5,13 +5,14 @@
 // two camera-frame points, its two observations, its state word and the two chi2 its last computeActiveErrors left stay in registers through both
 // rounds.  For larger n1 (EPT = 0) the state word and the two chi2 live in the caller's workspace and the points and observations are computed
 // again in every pass (float arithmetic on the same inputs: the same bits).  No instance uses scratch.  The workgroup runs the state machine of
-// optsim3_math.h: lane 0 holds it in LDS and names the next pass (BUILD / TRIAL / CLASSIFY); lanes 0 .. 14 then write the similarities of the pass
+// geom_common.h (Os3LM of optsim3_math.h): lane 0 holds it in LDS and names the next pass (BUILD / TRIAL / CLASSIFY); lanes 0 .. 14 then write the similarities of the pass
 // into LDS -- the estimate's inverse, and for BUILD the 14 perturbed similarities of the numeric Jacobian with their inverses, once per
 // linearisation -- and every lane runs the pass over its slots, adding its shares of H, b and the robust chi2 in slot order, e12 before e21.  The
 // fold is k_pose_optimize's: the xor butterfly 32, 16, .. 1 inside a wave, then waves 0 .. 3 in order on lane 0.  Nothing depends on timing, so two
 // runs give identical bytes.  At most XFH_OS3_MAX_PASSES passes, whatever the data.
 #pragma once
 #include "optsim3_math.h"
+#include "search_common.hip.h"
 
 template <int EPT>
 __global__ __launch_bounds__(XFH_OS3_THREADS)
@@ -57,8 +58,8 @@ void k_sim3_optimize(Os3Args a) {
     for (int pass = 0; pass <= XFH_OS3_MAX_PASSES; ++pass) {
         __syncthreads();                                                   // lane 0's action and estimate are in LDS; s_red and s_cnt are free again
         const int act = s_act;
-        if (act == XFH_OS3_DONE) break;
-        if (tid < 15 && (tid == 14 || act == XFH_OS3_BUILD)) {
+        if (act == GEO_LM_DONE) break;
+        if (tid < 15 && (tid == 14 || act == GEO_LM_BUILD)) {
             const Os3Sim E = S.est;
             os3_sims_piece(E, a.fix_scale, tid, &sims);
         }
@@ -82,10 +83,10 @@ void k_sim3_optimize(Os3Args a) {
                 ws_st[k] = s; ws_last[2 * k] = c12; ws_last[2 * k + 1] = c21;
             }
         }
-        if (act == XFH_OS3_BUILD) {
+        if (act == GEO_LM_BUILD) {
 #pragma unroll
             for (int n = 0; n < XFH_OS3_NSUM; ++n) { const double s = wave_sum_f64(acc[n]); if (lane == 0) s_red[wave][n] = s; }
-        } else if (act == XFH_OS3_TRIAL) {
+        } else if (act == GEO_LM_TRIAL) {
             const double s = wave_sum_f64(acc[35]);
             if (lane == 0) s_red[wave][35] = s;
         } else {
@@ -94,13 +95,13 @@ void k_sim3_optimize(Os3Args a) {
         }
         __syncthreads();
         if (tid == 0) {
-            if (act == XFH_OS3_BUILD) {
+            if (act == GEO_LM_BUILD) {
                 double sums[XFH_OS3_NSUM];
 #pragma unroll
                 for (int n = 0; n < XFH_OS3_NSUM; ++n) sums[n] = ((s_red[0][n] + s_red[1][n]) + s_red[2][n]) + s_red[3][n];
-                s_act = os3_lm_after_build(S, sums);
-            } else if (act == XFH_OS3_TRIAL) {
-                s_act = os3_lm_after_trial(S, ((s_red[0][35] + s_red[1][35]) + s_red[2][35]) + s_red[3][35]);
+                s_act = geo_lm_after_build(S, sums);
+            } else if (act == GEO_LM_TRIAL) {
+                s_act = geo_lm_after_trial(S, ((s_red[0][35] + s_red[1][35]) + s_red[2][35]) + s_red[3][35]);
             } else {
                 s_act = os3_lm_after_classify(S, ((s_cnt[0] + s_cnt[1]) + s_cnt[2]) + s_cnt[3]);
             }

@@ -2,12 +2,10 @@
 // searches, written ONCE for k_sim3_optimize (optsim3.hip.h), the host form xfh_sim3_optimize_host, the single-piece entry points of
 // capi_optsim3.cpp and the sanitizer program tests/cpp/asan_optsim3_test.cpp: the g2o::Sim3 state (thirdparty/g2o/g2o/types/sim3.h) with its
 // exponential, product and inverse, the two projection edges of OptimizableTypes.h:175-215 with g2o's NUMERIC Jacobian
-// (base_binary_edge.hpp:130-205), one edge's share of H and b, and the two rounds of Levenberg as a state machine that one lane or one host thread
-// drives.  The quaternion rules, the rotation of a vector and the Huber kernel are poseopt_math.h's.  IEEE double throughout, every product and sum
-// in the order written here (the library is built without contraction); tests/ref_optsim3.py restates these lines.
-//
-// The Levenberg state machine is a second copy of poseopt_math.h's with 7 unknowns, two rounds that continue from each other and a Huber switch per
-// round: sharing one templated machine would have moved PoseOptimization's code, whose host outputs are pinned by bytes and whose kernel by registers.
+// (base_binary_edge.hpp:130-205), one edge's share of H and b, and the two rounds around the Levenberg machine of geom_common.h, which one lane or
+// one host thread drives.  The quaternion rules, the quaternion product, the rotation of a vector and the Huber kernel are
+// poseopt_math.h's.  IEEE double throughout, every product and sum in the order written here (the library is built without contraction);
+// tests/ref_optsim3.py restates these lines.
 #pragma once
 #include "poseopt_math.h"
 
@@ -16,9 +14,8 @@
 #define XFH_OS3_ITERS_FIRST 5             /* optimize(5) */
 #define XFH_OS3_ITERS_MORE 5              /* nMoreIterations without a bad pair, */
 #define XFH_OS3_ITERS_MORE_BAD 10         /* and with one */
-#define XFH_OS3_MAX_TRIALS 10             /* _maxTrialsAfterFailure */
 #define XFH_OS3_MIN_PAIRS 10              /* `if (nCorrespondences - nBad < 10) return 0` */
-#define XFH_OS3_MAX_PASSES ((XFH_OS3_ITERS_FIRST + XFH_OS3_ITERS_MORE_BAD) * (1 + XFH_OS3_MAX_TRIALS) + 2)
+#define XFH_OS3_MAX_PASSES ((XFH_OS3_ITERS_FIRST + XFH_OS3_ITERS_MORE_BAD) * (1 + GEO_LM_MAX_TRIALS) + 2)
 #define XFH_OS3_DELTA 1e-9                /* base_binary_edge.hpp:147 */
 #define XFH_OS3_HEADER_INTS 16
 #define XFH_OS3_S12_FLOATS 13
@@ -26,7 +23,6 @@
 // a pair's state word: bit 0 it has its two edges, bit 1 its point is in KF2, bit 2 bad in the first classification, bit 3 bad in the final one
 enum { OS3_EDGE = 1, OS3_IN_KF2 = 2, OS3_BAD_FIRST = 4, OS3_BAD_FINAL = 8 };
 enum { XFH_OS3_NO_EDGE = 0, XFH_OS3_BAD_FIRST = 1, XFH_OS3_BAD_FINAL = 2, XFH_OS3_INLIER = 3 };
-enum { XFH_OS3_BUILD = 0, XFH_OS3_TRIAL = 1, XFH_OS3_CLASSIFY = 2, XFH_OS3_DONE = 3 };
 enum { XFH_OS3_H_CORR = 0, XFH_OS3_H_IN_KF2 = 1, XFH_OS3_H_OUT_KF2 = 2, XFH_OS3_H_BAD = 3, XFH_OS3_H_BAD_OUT_KF2 = 4, XFH_OS3_H_MORE = 5, XFH_OS3_H_RETURN = 6,
        XFH_OS3_H_ROUNDS = 7, XFH_OS3_H_ITERATIONS = 8, XFH_OS3_H_TRIALS = 9, XFH_OS3_H_REJECTED = 10, XFH_OS3_H_LDLT_FAILURES = 11 };
 
@@ -80,13 +76,9 @@ XFH_HD void os3_inverse(const Os3Sim& S, Os3Sim* o) {
 }
 // operator*: r = a.r * b.r, t = a.s * (a.r * b.t) + a.t, s = a.s * b.s; nothing is normalised
 XFH_HD void os3_mul(const Os3Sim& A, const Os3Sim& B, Os3Sim* o) {
-    const double *a = A.q, *b = B.q;
     double rt[3];
     pose_rotate(A.q, B.t, rt);
-    o->q[3] = ((a[3] * b[3] - a[0] * b[0]) - a[1] * b[1]) - a[2] * b[2];
-    o->q[0] = ((a[3] * b[0] + a[0] * b[3]) + a[1] * b[2]) - a[2] * b[1];
-    o->q[1] = ((a[3] * b[1] + a[1] * b[3]) + a[2] * b[0]) - a[0] * b[2];
-    o->q[2] = ((a[3] * b[2] + a[2] * b[3]) + a[0] * b[1]) - a[1] * b[0];
+    pose_quat_mul(A.q, B.q, o->q);
     o->t[0] = A.s * rt[0] + A.t[0]; o->t[1] = A.s * rt[1] + A.t[1]; o->t[2] = A.s * rt[2] + A.t[2];
     o->s = A.s * B.s;
 }
@@ -239,7 +231,7 @@ XFH_HD void os3_pair_pass(int act, bool robust, bool final, const Os3Sims& S, co
     const double X1[3] = {(double)p.P1[0], (double)p.P1[1], (double)p.P1[2]}, X2[3] = {(double)p.P2[0], (double)p.P2[1], (double)p.P2[2]};
     const double o1[2] = {(double)p.o1[0], (double)p.o1[1]}, o2[2] = {(double)p.o2[0], (double)p.o2[1]};
     double e[2];
-    if (act == XFH_OS3_CLASSIFY) {
+    if (act == GEO_LM_CLASSIFY) {
         if (final) {
             const Os3Sim T = S.est, Ti = S.inv;
             l12 = os3_edge_error(T, a.cam1, X2, o1, a.w1, e);
@@ -256,7 +248,7 @@ XFH_HD void os3_pair_pass(int act, bool robust, bool final, const Os3Sims& S, co
         double r0 = c, r1 = 1.0;
         if (robust) pose_huber(c, a.delta, &r0, &r1);
         acc[35] += r0;
-        if (act == XFH_OS3_BUILD) {
+        if (act == GEO_LM_BUILD) {
             double J[14];
             os3_edge_jacobian(S.pert, a.cam1, X2, o1, J);
             os3_accumulate(acc, J, e, a.w1, r1);
@@ -269,7 +261,7 @@ XFH_HD void os3_pair_pass(int act, bool robust, bool final, const Os3Sims& S, co
         double r0 = c, r1 = 1.0;
         if (robust) pose_huber(c, a.delta, &r0, &r1);
         acc[35] += r0;
-        if (act == XFH_OS3_BUILD) {
+        if (act == GEO_LM_BUILD) {
             double J[14];
             os3_edge_jacobian(S.pinv, a.cam2, X1, o2, J);
             os3_accumulate(acc, J, e, a.w2, r1);
@@ -286,15 +278,19 @@ XFH_HD void os3_pair_store(const Os3Args& a, int pb, int i, int st, double l12, 
     a.chi2[kg * 2] = (st & OS3_EDGE) ? (float)l12 : 0.0f; a.chi2[kg * 2 + 1] = (st & OS3_EDGE) ? (float)l21 : 0.0f;
 }
 
-// ---- optimize(5), the classification, optimize(5 or 10), the final classification as a state machine.  The driver runs the pass an action asks for
-// over every pair with S.est's similarities and hands the folded sums back: BUILD wants all XFH_OS3_NSUM, TRIAL the robust chi2 (sums[35]), CLASSIFY
-// the packed count of bad pairs.  The Huber kernel is on in round 0; round 1's classification computes fresh errors.
+// ---- optimize(5), the classification, optimize(5 or 10), the final classification: the Levenberg machine of geom_common.h (geo_lm_after_build /
+// geo_lm_after_trial) with 7 unknowns, and around it what is OptimizeSim3's own: round 1 continues from round 0's estimate with its own iteration
+// cap, CLASSIFY hands back the packed count of bad pairs, the Huber kernel is on in round 0, round 1's classification computes fresh errors.  The
+// driver runs a pass over every pair with S.est's similarities.  sums: XFH_OS3_NSUM, the robust chi2 last.
 struct Os3LM {
     Os3Sim input, est, backup;
     double H[28], b[7], x[7];
     double lambda, ni, currentChi, iniChi;
     int round, iter, iters, qmax, nbad_lm, solved, fix_scale;
     int hdr[XFH_OS3_HEADER_INTS];
+    static constexpr int N = 7, H_ITERATIONS = XFH_OS3_H_ITERATIONS;
+    static XFH_HD int iterations(const Os3LM& S) { return S.iters; }
+    static XFH_HD Os3Sim oplus(const Os3LM& S) { Os3Sim n; os3_oplus(S.x, S.est, S.fix_scale, &n); return n; }
 };
 XFH_HD bool os3_lm_robust(const Os3LM& S) { return S.round == 0; }
 XFH_HD bool os3_lm_final(const Os3LM& S) { return S.round == 1; }
@@ -306,71 +302,25 @@ XFH_HD int os3_lm_begin(Os3LM& S, const Os3Sim& input, int fix_scale, int n_corr
     _Pragma("unroll")
     for (int k = 0; k < XFH_OS3_HEADER_INTS; ++k) S.hdr[k] = 0;
     S.hdr[XFH_OS3_H_CORR] = n_corr; S.hdr[XFH_OS3_H_OUT_KF2] = n_out_kf2; S.hdr[XFH_OS3_H_IN_KF2] = n_corr - n_out_kf2;
-    return n_corr > 0 ? XFH_OS3_BUILD : XFH_OS3_CLASSIFY;                   // no edge: optimize() returns at once
+    return n_corr > 0 ? GEO_LM_BUILD : GEO_LM_CLASSIFY;                     // no edge: optimize() returns at once
 }
-XFH_HD int os3_lm_trial(Os3LM& S) {                                         // push(); setLambda; solve(); update(x)
-    S.backup = S.est;
-    S.solved = geo_ldlt_solve<7>(S.H, S.lambda, S.b, S.x) ? 1 : 0;
-    Os3Sim n;
-    os3_oplus(S.x, S.est, S.fix_scale, &n);
-    S.est = n;
-    ++S.hdr[XFH_OS3_H_TRIALS];
-    if (!S.solved) ++S.hdr[XFH_OS3_H_LDLT_FAILURES];
-    return XFH_OS3_TRIAL;
-}
-XFH_HD int os3_lm_after_build(Os3LM& S, const double* sums) {
-    _Pragma("unroll")
-    for (int k = 0; k < 28; ++k) S.H[k] = sums[k];
-    _Pragma("unroll")
-    for (int k = 0; k < 7; ++k) S.b[k] = sums[28 + k];
-    S.currentChi = sums[35]; S.iniChi = S.currentChi;
-    if (S.iter == 0) {                                                      // computeLambdaInit: std::max(fabs(H_jj), maxDiagonal), a NaN first argument wins
-        double m = 0.0;
-        _Pragma("unroll")
-        for (int j = 0, n = 0; j < 7; n += 7 - j, ++j) { const double a = fabs(S.H[n]); m = (a < m) ? m : a; }
-        S.lambda = 1e-5 * m; S.ni = 2.0; S.nbad_lm = 0;
-    }
-    S.qmax = 0;
-    ++S.hdr[XFH_OS3_H_ITERATIONS];
-    return os3_lm_trial(S);
-}
-XFH_HD int os3_lm_after_trial(Os3LM& S, double chi) {
-    const double tempChi = S.solved ? chi : DBL_MAX;
-    double rho = S.currentChi - tempChi, scale = 0.0;
-    _Pragma("unroll")
-    for (int j = 0; j < 7; ++j) scale += S.x[j] * (S.lambda * S.x[j] + S.b[j]);
-    scale += 1e-3;
-    rho /= scale;
-    if (rho > 0.0 && isfinite(tempChi)) {
-        const double t = 2.0 * rho - 1.0;
-        double alpha = 1.0 - t * t * t;
-        alpha = (2.0 / 3.0 < alpha) ? 2.0 / 3.0 : alpha;                    // std::min(alpha, _goodStepUpperScale)
-        const double f = (1.0 / 3.0 < alpha) ? alpha : 1.0 / 3.0;           // std::max(_goodStepLowerScale, alpha)
-        S.lambda *= f; S.ni = 2.0; S.currentChi = tempChi;
-    } else {
-        S.lambda *= S.ni; S.ni *= 2.0;
-        S.est = S.backup;                                                   // pop(): the edges keep the errors of the rejected estimate
-        ++S.hdr[XFH_OS3_H_REJECTED];
-    }
-    ++S.qmax;
-    if (rho < 0.0 && S.qmax < XFH_OS3_MAX_TRIALS) return os3_lm_trial(S);
-    if (S.qmax == XFH_OS3_MAX_TRIALS || rho == 0.0) return XFH_OS3_CLASSIFY;
-    if ((S.iniChi - S.currentChi) * 1e3 < S.iniChi) ++S.nbad_lm; else S.nbad_lm = 0;
-    if (S.nbad_lm >= 3) return XFH_OS3_CLASSIFY;
-    return ++S.iter < S.iters ? XFH_OS3_BUILD : XFH_OS3_CLASSIFY;
-}
+// The names under which tests/cpp/asan_optsim3_test.cpp drives the machine.  That program is the independent statement the library is compared with
+// and stays as it was written before the machine was shared, so that it holds this build without having been touched: nothing else uses these.
+enum { XFH_OS3_BUILD = GEO_LM_BUILD, XFH_OS3_TRIAL = GEO_LM_TRIAL, XFH_OS3_CLASSIFY = GEO_LM_CLASSIFY, XFH_OS3_DONE = GEO_LM_DONE };
+XFH_HD int os3_lm_after_build(Os3LM& S, const double* sums) { return geo_lm_after_build(S, sums); }
+XFH_HD int os3_lm_after_trial(Os3LM& S, double chi) { return geo_lm_after_trial(S, chi); }
 XFH_HD int os3_lm_after_classify(Os3LM& S, int bad_packed) {
     const int n_bad = bad_packed & 0xFFFF, n_bad_out = bad_packed >> 16;
     ++S.hdr[XFH_OS3_H_ROUNDS];
     if (S.round == 0) {
         S.hdr[XFH_OS3_H_BAD] = n_bad; S.hdr[XFH_OS3_H_BAD_OUT_KF2] = n_bad_out;
         S.hdr[XFH_OS3_H_MORE] = n_bad > 0 ? XFH_OS3_ITERS_MORE_BAD : XFH_OS3_ITERS_MORE;
-        if (S.hdr[XFH_OS3_H_CORR] - n_bad < XFH_OS3_MIN_PAIRS) { S.est = S.input; return XFH_OS3_DONE; }   // return 0 before :2378: g2oS12 stays the input
+        if (S.hdr[XFH_OS3_H_CORR] - n_bad < XFH_OS3_MIN_PAIRS) { S.est = S.input; return GEO_LM_DONE; }    // return 0 before :2378: g2oS12 stays the input
         S.round = 1; S.iter = 0; S.iters = S.hdr[XFH_OS3_H_MORE];
-        return XFH_OS3_BUILD;                                               // continues from round 0's estimate; lambda afresh (iter == 0)
+        return GEO_LM_BUILD;                                                // continues from round 0's estimate; lambda afresh (iter == 0)
     }
     S.hdr[XFH_OS3_H_RETURN] = (S.hdr[XFH_OS3_H_CORR] - S.hdr[XFH_OS3_H_BAD]) - n_bad;
-    return XFH_OS3_DONE;
+    return GEO_LM_DONE;
 }
 
 // what lane 0 writes at the end: the state, S12_out, the composed pose for the next search (LoopClosing.cc:771-773, ORBmatcher.cc:621-622), the header
@@ -430,9 +380,9 @@ inline void os3_host_problem(const Os3Args& a, int pb) {
     os3_from_floats(a.S12 + (size_t)pb * a.S12_stride, &in);
     int act = os3_lm_begin(S, in, a.fix_scale, n_corr, n_out);
     static thread_local double part[XFH_OS3_THREADS][XFH_OS3_NSUM];
-    for (int pass = 0; pass <= XFH_OS3_MAX_PASSES && act != XFH_OS3_DONE; ++pass) {
+    for (int pass = 0; pass <= XFH_OS3_MAX_PASSES && act != GEO_LM_DONE; ++pass) {
         Os3Sims sims;
-        for (int j = act == XFH_OS3_BUILD ? 0 : 14; j < 15; ++j) os3_sims_piece(S.est, a.fix_scale, j, &sims);
+        for (int j = act == GEO_LM_BUILD ? 0 : 14; j < 15; ++j) os3_sims_piece(S.est, a.fix_scale, j, &sims);
         for (int l = 0; l < XFH_OS3_THREADS; ++l)
             for (int n = 0; n < XFH_OS3_NSUM; ++n) part[l][n] = 0.0;
         int bad = 0;
@@ -441,11 +391,11 @@ inline void os3_host_problem(const Os3Args& a, int pb) {
             os3_pair_load(a, pb, i, &p);
             os3_pair_pass(act, os3_lm_robust(S), os3_lm_final(S), sims, a, p, st[i], last[2 * i], last[2 * i + 1], part[i % XFH_OS3_THREADS], bad);
         }
-        if (act == XFH_OS3_BUILD) {
+        if (act == GEO_LM_BUILD) {
             double sums[XFH_OS3_NSUM];
             for (int n = 0; n < XFH_OS3_NSUM; ++n) sums[n] = os3_host_fold(part, n);
-            act = os3_lm_after_build(S, sums);
-        } else if (act == XFH_OS3_TRIAL) act = os3_lm_after_trial(S, os3_host_fold(part, 35));
+            act = geo_lm_after_build(S, sums);
+        } else if (act == GEO_LM_TRIAL) act = geo_lm_after_trial(S, os3_host_fold(part, 35));
         else act = os3_lm_after_classify(S, bad);
     }
     for (int i = 0; i < a.n1; ++i) os3_pair_store(a, pb, i, st[i], last[2 * i], last[2 * i + 1]);

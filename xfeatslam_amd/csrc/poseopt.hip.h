@@ -4,23 +4,18 @@
 // Lane l owns the keypoints l, l + 256, ...  For nt <= 4096 they are EPT slots, a template parameter (4 or 16), so that the slot loop unrolls and an
 // edge's world point, observation, state and the chi2 its last computeActiveErrors left stay in registers through all four rounds.  For larger nt
 // (EPT = 0) that state does not fit the register file: the state word and the chi2 live in the caller's workspace and the point and the observation
-// are read again in every pass.  No instance uses scratch.  The workgroup runs the state machine of poseopt_math.h: lane 0 holds it in LDS and names
+// are read again in every pass.  No instance uses scratch.  The workgroup runs the state machine of geom_common.h (PoseLM of poseopt_math.h): lane 0 holds it in LDS and names
 // the next pass (BUILD / TRIAL / CLASSIFY) and its pose, every lane reads both after a barrier, runs the pass over its slots and adds its shares of
 // H, b and the robust chi2 in slot order.  The fold is fixed: the xor butterfly 32, 16, .. 1 inside a wave (a + b is commutative, so all lanes hold
 // the same bits), then waves 0 .. 3 in order on lane 0.  Nothing depends on timing, so two runs give identical bytes.  At most
 // XFH_POSE_MAX_PASSES passes, whatever the data.
 #pragma once
 #include "poseopt_math.h"
+#include "search_common.hip.h"
 
 #define XFH_POSE_THREADS 256
-#define XFH_POSE_MAX_PASSES (XFH_POSE_ROUNDS * (XFH_POSE_ITERATIONS * (1 + XFH_POSE_MAX_TRIALS) + 1))
+#define XFH_POSE_MAX_PASSES (XFH_POSE_ROUNDS * (XFH_POSE_ITERATIONS * (1 + GEO_LM_MAX_TRIALS) + 1))
 enum { POSE_EDGE = 1, POSE_STEREO = 2, POSE_OUTLIER = 4 };
-
-__device__ __forceinline__ double wave_sum_f64(double x) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) x += __shfl_xor(x, m);
-    return x;
-}
 
 // keypoint k of problem pb: has it an edge, and of which kind; the point and the observation when it has
 __device__ __forceinline__ int pose_slot_load(const PoseArgs& a, int pb, int k, float* X, float* ob) {
@@ -38,10 +33,10 @@ __device__ __forceinline__ int pose_slot_load(const PoseArgs& a, int pb, int k, 
 __device__ __forceinline__ void pose_slot_pass(int act, const PosePose& P, bool robust, const PoseArgs& a, size_t kg, int& st, double& last, const float* X,
                                                const float* ob, double (&acc)[XFH_POSE_NSUM], int& bad) {
     const bool stereo = (st & POSE_STEREO) != 0, out = (st & POSE_OUTLIER) != 0;
-    if (act != XFH_POSE_CLASSIFY && out) return;                           // level 1: not in _activeEdges
+    if (act != GEO_LM_CLASSIFY && out) return;                             // level 1: not in _activeEdges
     const double Xd[3] = {(double)X[0], (double)X[1], (double)X[2]}, od[3] = {(double)ob[0], (double)ob[1], (double)ob[2]};
     double pc[3], e[3];
-    if (act == XFH_POSE_CLASSIFY) {
+    if (act == GEO_LM_CLASSIFY) {
         // an outlier's error is computed afresh at the round's estimate (:1021-1024); an inlier's is what computeActiveErrors left
         const double c = out ? pose_edge_error(P, a.cam, Xd, od, stereo, a.w, pc, e) : last;
         const float cf = (float)c;
@@ -56,7 +51,7 @@ __device__ __forceinline__ void pose_slot_pass(int act, const PosePose& P, bool 
     double r0 = c, r1 = 1.0;
     if (robust) pose_huber(c, pose_delta(stereo), &r0, &r1);
     acc[27] += r0;
-    if (act == XFH_POSE_BUILD) {
+    if (act == GEO_LM_BUILD) {
         double J[18];
         pose_edge_jacobian(a.cam, pc, stereo, J);
         pose_accumulate(acc, J, e, stereo, a.w, r1);
@@ -117,7 +112,7 @@ void k_pose_optimize(PoseArgs a) {
     for (int pass = 0; pass <= XFH_POSE_MAX_PASSES; ++pass) {
         __syncthreads();                                                   // lane 0's action and pose are in LDS; s_red and s_cnt are free again
         const int act = s_act;
-        if (act == XFH_POSE_DONE) break;
+        if (act == GEO_LM_DONE) break;
         const PosePose P = S.est;
         const bool robust = pose_lm_robust(S);
         double acc[XFH_POSE_NSUM];
@@ -138,10 +133,10 @@ void k_pose_optimize(PoseArgs a) {
                 ws_st[k] = s; ws_last[k] = l;
             }
         }
-        if (act == XFH_POSE_BUILD) {
+        if (act == GEO_LM_BUILD) {
 #pragma unroll
             for (int n = 0; n < XFH_POSE_NSUM; ++n) { const double s = wave_sum_f64(acc[n]); if (lane == 0) s_red[wave][n] = s; }
-        } else if (act == XFH_POSE_TRIAL) {
+        } else if (act == GEO_LM_TRIAL) {
             const double s = wave_sum_f64(acc[27]);
             if (lane == 0) s_red[wave][27] = s;
         } else {
@@ -150,13 +145,13 @@ void k_pose_optimize(PoseArgs a) {
         }
         __syncthreads();
         if (tid == 0) {
-            if (act == XFH_POSE_BUILD) {
+            if (act == GEO_LM_BUILD) {
                 double sums[XFH_POSE_NSUM];
 #pragma unroll
                 for (int n = 0; n < XFH_POSE_NSUM; ++n) sums[n] = ((s_red[0][n] + s_red[1][n]) + s_red[2][n]) + s_red[3][n];
-                s_act = pose_lm_after_build(S, sums);
-            } else if (act == XFH_POSE_TRIAL) {
-                s_act = pose_lm_after_trial(S, ((s_red[0][27] + s_red[1][27]) + s_red[2][27]) + s_red[3][27]);
+                s_act = geo_lm_after_build(S, sums);
+            } else if (act == GEO_LM_TRIAL) {
+                s_act = geo_lm_after_trial(S, ((s_red[0][27] + s_red[1][27]) + s_red[2][27]) + s_red[3][27]);
             } else {
                 s_act = pose_lm_after_classify(S, ((s_cnt[0] + s_cnt[1]) + s_cnt[2]) + s_cnt[3]);
             }

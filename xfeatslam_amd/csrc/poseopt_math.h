@@ -1,19 +1,17 @@
 // poseopt_math.h -- the arithmetic of Optimizer::PoseOptimization (src/Optimizer.cc:814-1114, the conventional-camera branch), written ONCE for
 // k_pose_optimize (poseopt.hip.h) and the host entry point xfh_pose_edge (capi_poseopt.cpp): the SE3Quat pose (types/se3quat.h), the mono edge
 // EdgeSE3ProjectXYZOnlyPose with Pinhole::project / projectJac and the stereo edge EdgeStereoSE3ProjectXYZOnlyPose (types_six_dof_expmap.cpp),
-// the Huber kernel, one edge's share of H and b (base_unary_edge.hpp:43-72), the 6x6 LDL^T solve and the Levenberg step
-// (optimization_algorithm_levenberg.cpp:61-194) as a state machine that one lane or one host thread drives.  IEEE double throughout, every
-// product and sum in the order written here (the library is built without contraction); tests/ref_poseopt.py restates these lines.
+// the Huber kernel, one edge's share of H and b (base_unary_edge.hpp:43-72) and the four rounds around the Levenberg machine of geom_common.h.  The
+// quaternion product is written here for OptimizeSim3 (optsim3_math.h) too.  IEEE double throughout, every product and
+// sum in the order written here (the library is built without contraction); tests/ref_poseopt.py restates these lines.
 #pragma once
 #include "geom_common.h"
 #include <math.h>
-#include <float.h>
 
 #define XFH_POSE_CHI2_MONO 5.991f
 #define XFH_POSE_CHI2_STEREO 7.815f
 #define XFH_POSE_ROUNDS 4
 #define XFH_POSE_ITERATIONS 10            /* optimize(its[it]) */
-#define XFH_POSE_MAX_TRIALS 10            /* _maxTrialsAfterFailure */
 #define XFH_POSE_NSUM 28                  /* 21 upper entries of H (row-major, i <= j), 6 of b, the robust chi2 */
 
 struct PosePose { double q[4]; double t[3]; };          // SE3Quat: unit quaternion (x, y, z, w) and translation
@@ -98,6 +96,14 @@ XFH_HD void pose_rotate(const double* q, const double* v, double* o) {
     o[2] = (v[2] + q[3] * uz) + (q[0] * uy - q[1] * ux);
 }
 
+// Quaterniond * Quaterniond, the Hamilton product a b of two (x, y, z, w); o is neither a nor b
+XFH_HD void pose_quat_mul(const double* a, const double* b, double* o) {
+    o[3] = ((a[3] * b[3] - a[0] * b[0]) - a[1] * b[1]) - a[2] * b[2];
+    o[0] = ((a[3] * b[0] + a[0] * b[3]) + a[1] * b[2]) - a[2] * b[1];
+    o[1] = ((a[3] * b[1] + a[1] * b[3]) + a[2] * b[0]) - a[0] * b[2];
+    o[2] = ((a[3] * b[2] + a[2] * b[3]) + a[0] * b[1]) - a[1] * b[0];
+}
+
 // VertexSE3Expmap::oplusImpl: SE3Quat::exp(u) * est, u = (omega, upsilon)
 XFH_HD void pose_oplus(const double* u, const PosePose& est, PosePose* out) {
     const double wx = u[0], wy = u[1], wz = u[2];
@@ -128,11 +134,7 @@ XFH_HD void pose_oplus(const double* u, const PosePose& est, PosePose* out) {
     pose_normalize(e.q);                                                   // SE3Quat(q, t)
     double rt[3];
     pose_rotate(e.q, est.t, rt);                                           // operator*: t = e.t + e.r * est.t;  r = e.r * est.r;  normalizeRotation
-    const double *a = e.q, *b = est.q;
-    out->q[3] = ((a[3] * b[3] - a[0] * b[0]) - a[1] * b[1]) - a[2] * b[2];
-    out->q[0] = ((a[3] * b[0] + a[0] * b[3]) + a[1] * b[2]) - a[2] * b[1];
-    out->q[1] = ((a[3] * b[1] + a[1] * b[3]) + a[2] * b[0]) - a[0] * b[2];
-    out->q[2] = ((a[3] * b[2] + a[2] * b[3]) + a[0] * b[1]) - a[1] * b[0];
+    pose_quat_mul(e.q, est.q, out->q);
     out->t[0] = e.t[0] + rt[0]; out->t[1] = e.t[1] + rt[1]; out->t[2] = e.t[2] + rt[2];
     pose_normalize(out->q);
 }
@@ -206,12 +208,9 @@ XFH_HD void pose_accumulate(double* acc, const double* J, const double* e, bool 
     }
 }
 
-// (H + lambda I) x = b of the Levenberg step: pose_ldlt_solve of geom_common.h, the unpivoted 6 x 6 LDL^T that MLPnP's Gauss-Newton shares.
-
-// ---- the four rounds of optimize(10) as a state machine.  The driver runs the pass an action asks for over every edge at S.est and hands the folded
-// sums back: BUILD wants all XFH_POSE_NSUM (computeActiveErrors + activeRobustChi2 + buildSystem), TRIAL only the robust chi2 (sums[27]), CLASSIFY the
-// number of edges over their threshold.  The Huber kernel is on in a pass iff pose_lm_robust(S).
-enum { XFH_POSE_BUILD = 0, XFH_POSE_TRIAL = 1, XFH_POSE_CLASSIFY = 2, XFH_POSE_DONE = 3 };
+// ---- the four rounds of optimize(10): the Levenberg machine of geom_common.h (geo_lm_after_build / geo_lm_after_trial, the LDL^T that MLPnP's
+// Gauss-Newton shares) with 6 unknowns, and around it what is PoseOptimization's own: every round starts from the input pose, CLASSIFY hands back the
+// number of edges over their threshold, the Huber kernel is on in a pass iff pose_lm_robust(S).  sums: XFH_POSE_NSUM, the robust chi2 last.
 enum { XFH_POSE_H_INITIAL = 0, XFH_POSE_H_BAD = 1, XFH_POSE_H_RETURN = 2, XFH_POSE_H_ROUNDS = 3, XFH_POSE_H_ITERATIONS = 4, XFH_POSE_H_TRIALS = 5,
        XFH_POSE_H_REJECTED = 6, XFH_POSE_H_LDLT_FAILURES = 7 };
 struct PoseLM {
@@ -220,12 +219,15 @@ struct PoseLM {
     double lambda, ni, currentChi, iniChi;
     int round, iter, qmax, nbad_lm, solved;
     int hdr[8];
+    static constexpr int N = 6, H_ITERATIONS = XFH_POSE_H_ITERATIONS;
+    static XFH_HD int iterations(const PoseLM&) { return XFH_POSE_ITERATIONS; }
+    static XFH_HD PosePose oplus(const PoseLM& S) { PosePose n; pose_oplus(S.x, S.est, &n); return n; }
 };
 XFH_HD bool pose_lm_robust(const PoseLM& S) { return S.round < 3; }        // `if (it == 2) e->setRobustKernel(0)`
 
 XFH_HD int pose_lm_round(PoseLM& S) {                                       // setEstimate(pFrame->GetPose()); initializeOptimization(0); optimize(10)
     S.est = S.input; S.iter = 0;
-    return S.hdr[XFH_POSE_H_INITIAL] - S.hdr[XFH_POSE_H_BAD] > 0 ? XFH_POSE_BUILD : XFH_POSE_CLASSIFY;   // no level-0 edge: optimize() returns at once
+    return S.hdr[XFH_POSE_H_INITIAL] - S.hdr[XFH_POSE_H_BAD] > 0 ? GEO_LM_BUILD : GEO_LM_CLASSIFY;       // no level-0 edge: optimize() returns at once
 }
 XFH_HD int pose_lm_begin(PoseLM& S, const PosePose& input, int n_initial) {
     S.input = input; S.round = 0; S.currentChi = 0.0;
@@ -236,62 +238,17 @@ XFH_HD int pose_lm_begin(PoseLM& S, const PosePose& input, int n_initial) {
     S.hdr[XFH_POSE_H_INITIAL] = n_initial;
     return pose_lm_round(S);
 }
-XFH_HD int pose_lm_trial(PoseLM& S) {                                       // push(); setLambda; solve(); update(x)
-    S.backup = S.est;
-    S.solved = pose_ldlt_solve(S.H, S.lambda, S.b, S.x) ? 1 : 0;
-    PosePose n;
-    pose_oplus(S.x, S.est, &n);
-    S.est = n;
-    ++S.hdr[XFH_POSE_H_TRIALS];
-    if (!S.solved) ++S.hdr[XFH_POSE_H_LDLT_FAILURES];
-    return XFH_POSE_TRIAL;
-}
-XFH_HD int pose_lm_after_build(PoseLM& S, const double* sums) {
-    _Pragma("unroll")
-    for (int k = 0; k < 21; ++k) S.H[k] = sums[k];
-    _Pragma("unroll")
-    for (int k = 0; k < 6; ++k) S.b[k] = sums[21 + k];
-    S.currentChi = sums[27]; S.iniChi = S.currentChi;
-    if (S.iter == 0) {                                                      // computeLambdaInit: std::max(fabs(H_jj), maxDiagonal), a NaN first argument wins
-        double m = 0.0;
-        _Pragma("unroll")
-        for (int j = 0, n = 0; j < 6; n += 6 - j, ++j) { const double a = fabs(S.H[n]); m = (a < m) ? m : a; }
-        S.lambda = 1e-5 * m; S.ni = 2.0; S.nbad_lm = 0;
-    }
-    S.qmax = 0;
-    ++S.hdr[XFH_POSE_H_ITERATIONS];
-    return pose_lm_trial(S);
-}
-XFH_HD int pose_lm_after_trial(PoseLM& S, double chi) {
-    const double tempChi = S.solved ? chi : DBL_MAX;
-    double rho = S.currentChi - tempChi, scale = 0.0;
-    _Pragma("unroll")
-    for (int j = 0; j < 6; ++j) scale += S.x[j] * (S.lambda * S.x[j] + S.b[j]);
-    scale += 1e-3;
-    rho /= scale;
-    if (rho > 0.0 && isfinite(tempChi)) {
-        const double t = 2.0 * rho - 1.0;
-        double alpha = 1.0 - t * t * t;
-        alpha = (2.0 / 3.0 < alpha) ? 2.0 / 3.0 : alpha;                    // std::min(alpha, _goodStepUpperScale)
-        const double f = (1.0 / 3.0 < alpha) ? alpha : 1.0 / 3.0;           // std::max(_goodStepLowerScale, alpha)
-        S.lambda *= f; S.ni = 2.0; S.currentChi = tempChi;
-    } else {
-        S.lambda *= S.ni; S.ni *= 2.0;
-        S.est = S.backup;                                                   // pop(): the edges keep the errors of the rejected estimate
-        ++S.hdr[XFH_POSE_H_REJECTED];
-    }
-    ++S.qmax;
-    if (rho < 0.0 && S.qmax < XFH_POSE_MAX_TRIALS) return pose_lm_trial(S);
-    if (S.qmax == XFH_POSE_MAX_TRIALS || rho == 0.0) return XFH_POSE_CLASSIFY;
-    if ((S.iniChi - S.currentChi) * 1e3 < S.iniChi) ++S.nbad_lm; else S.nbad_lm = 0;
-    if (S.nbad_lm >= 3) return XFH_POSE_CLASSIFY;
-    return ++S.iter < XFH_POSE_ITERATIONS ? XFH_POSE_BUILD : XFH_POSE_CLASSIFY;
-}
 XFH_HD int pose_lm_after_classify(PoseLM& S, int n_bad) {
     S.hdr[XFH_POSE_H_BAD] = n_bad;
     S.hdr[XFH_POSE_H_RETURN] = S.hdr[XFH_POSE_H_INITIAL] - n_bad;
     ++S.hdr[XFH_POSE_H_ROUNDS];
-    if (S.hdr[XFH_POSE_H_INITIAL] < 10) return XFH_POSE_DONE;               // `if (optimizer.edges().size() < 10) break`
-    if (++S.round == XFH_POSE_ROUNDS) return XFH_POSE_DONE;
+    if (S.hdr[XFH_POSE_H_INITIAL] < 10) return GEO_LM_DONE;                 // `if (optimizer.edges().size() < 10) break`
+    if (++S.round == XFH_POSE_ROUNDS) return GEO_LM_DONE;
     return pose_lm_round(S);
 }
+
+// The names under which tests/cpp/asan_poseopt_test.cpp drives the machine.  That program is the independent statement the library is compared with
+// and stays as it was written before the machine was shared, so that it holds this build without having been touched: nothing else uses these.
+enum { XFH_POSE_BUILD = GEO_LM_BUILD, XFH_POSE_TRIAL = GEO_LM_TRIAL, XFH_POSE_CLASSIFY = GEO_LM_CLASSIFY, XFH_POSE_DONE = GEO_LM_DONE };
+XFH_HD int pose_lm_after_build(PoseLM& S, const double* sums) { return geo_lm_after_build(S, sums); }
+XFH_HD int pose_lm_after_trial(PoseLM& S, double chi) { return geo_lm_after_trial(S, chi); }

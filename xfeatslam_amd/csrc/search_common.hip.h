@@ -1,5 +1,5 @@
 // search_common.hip.h -- what a wave does in every device-side ORBmatcher search (k_best2_csr and the *_search.hip.h kernels), written once: the
-// keys, DescriptorDistance, a lane's two / K smallest keys with their wave-wide merges, the wave minimum and sum, one lane's double for all.  The lane-local pieces are plain
+// keys, DescriptorDistance, a lane's two / K smallest keys with their wave-wide merges, the wave minimum and sums (integer, and fp64 for the two optimisers), one lane's double for all.  The lane-local pieces are plain
 // C++ (XFH_HD): tests/cpp/search_common_test.cpp runs these very lines on the host against the obvious form.
 #pragma once
 #include <math.h>
@@ -62,6 +62,12 @@ __device__ __forceinline__ u64 wave_min_u64(u64 x) {
     return x;
 }
 __device__ __forceinline__ int wave_sum_i32(int x) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) x += __shfl_xor(x, m);
+    return x;
+}
+// a + b is commutative, so after the xor butterfly every lane holds the same bits
+__device__ __forceinline__ double wave_sum_f64(double x) {
 #pragma unroll
     for (int m = 32; m >= 1; m >>= 1) x += __shfl_xor(x, m);
     return x;
