@@ -16,6 +16,7 @@ import struct
 
 import numpy as np
 
+import guarded
 import ref_bow as RB
 import triangulation_rig as TR
 from xfeatslam_amd import capi
@@ -194,29 +195,15 @@ class BowRig:
             bufs.append(b)
             return b.ptr
 
-        wsb = Context.bow_search_workspace_bytes(n1, n2, B)
-        ws = capi.DeviceBuffer(wsb + 2 * GUARD).upload(np.full(wsb + 2 * GUARD, 0xA5, np.uint8))
-        out = capi.DeviceBuffer(lay["bytes"]).upload(np.full(lay["bytes"], 0xA5, np.uint8))
+        ws = guarded.Guarded(Context.bow_search_workspace_bytes(n1, n2, B), GUARD)
+        out = guarded.outputs(lay)
         d1 = [dev(s1[k]) for k in ("blob", "flag", "desc")]; d2 = [dev(s2[k]) for k in ("blob", "flag", "desc")]
-        ctx.bow_search_device(B, n1, n2, shared, *d1, s1["stride"], *d2, s2["stride"], ws.ptr + GUARD, out.ptr, strict_low=strict, init_dist=init_dist,
+        ctx.bow_search_device(B, n1, n2, shared, *d1, s1["stride"], *d2, s2["stride"], ws.ptr, out.ptr, strict_low=strict, init_dist=init_dist,
                               th_low=th_low, nn_ratio=nn_ratio, guard=GUARD)
         ctx.synchronize()
-        raw = out.download(np.uint8, lay["bytes"])
-        wraw = ws.download(np.uint8, wsb + 2 * GUARD)
-        assert np.all(wraw[:GUARD] == 0xA5) and np.all(wraw[GUARD + wsb:] == 0xA5), "a guard byte around the workspace was written"
-        counters = wraw[GUARD:GUARD + 16 * B].view(np.int32).reshape(B, 4).copy()
-        res = []
-        for p in range(B):
-            o = {k: raw[lay[k] + 4 * p * n1: lay[k] + 4 * (p + 1) * n1].view(np.int32) for k in Context.BOW_OUT_INT}
-            o["assigned2"] = raw[lay["assigned2"] + 4 * p * n2: lay["assigned2"] + 4 * (p + 1) * n2].view(np.int32)
-            o["n_matches"] = int(raw[lay["n_matches"] + 4 * p: lay["n_matches"] + 4 * p + 4].view(np.int32)[0])
-            o["status"] = raw[lay["status"] + p * n1: lay["status"] + (p + 1) * n1]
-            res.append(o)
-        used = np.zeros(lay["bytes"], bool)
-        for k, n in [(k, 4 * B * n1) for k in Context.BOW_OUT_INT] + [("assigned2", 4 * B * n2), ("n_matches", 4 * B), ("status", B * n1)]:
-            used[lay[k]:lay[k] + n] = True
-            assert not used[lay[k] - GUARD:lay[k]].any() and not used[lay[k] + n:lay[k] + n + GUARD].any() and lay[k] + n + GUARD <= lay["bytes"]
-        assert np.all(raw[~used] == 0xA5), "a guard byte around the outputs was written"
+        raw = guarded.download(out, lay)
+        counters = ws.download()[:16 * B].view(np.int32).reshape(B, 4)
+        res = guarded.problems(lay.parse(raw), B)
         out.free(); ws.free()
         for b in bufs:
             b.free()

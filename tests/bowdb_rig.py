@@ -268,6 +268,7 @@ class DeviceRig:
     def run(self, name, c, form, queries, states):
         """B = len(queries) problems against the case's database in one call; states: float32 [B][n], the state each problem starts from.
         Guard bytes round every output, the workspace and the state are checked.  -> (results per problem, raw output bytes, states after)"""
+        import guarded
         from xfeatslam_amd import capi
         from xfeatslam_amd.extractor import Context
         ctx = self.ctx
@@ -283,32 +284,21 @@ class DeviceRig:
         up = lambda a: capi.DeviceBuffer(a.nbytes + 16).upload(a)
         dqi, dqv, dqn = up(qi), up(qv), up(qn)
         dex = up(ex) if ex.any() else None                                                   # no exclusion at all: the NULL form
-        st = np.full(2 * GUARD + 4 * B * n, 0xA5, np.uint8)
-        st[GUARD:GUARD + 4 * B * n] = np.ascontiguousarray(states, F).view(np.uint8).ravel()
-        dst = capi.DeviceBuffer(st.nbytes).upload(st)
-        wsb = Context.bowdb_query_workspace_bytes(n, B)
-        ws = capi.DeviceBuffer(wsb + 2 * GUARD).upload(np.full(wsb + 2 * GUARD, 0xA5, np.uint8))
+        dst = guarded.Guarded(4 * B * n, GUARD, inner=np.ascontiguousarray(states, F), what="the state")
+        ws = guarded.Guarded(Context.bowdb_query_workspace_bytes(n, B), GUARD)
         lay = Context.bowdb_query_layout(B, n, GUARD)
-        out = capi.DeviceBuffer(lay["bytes"]).upload(np.full(lay["bytes"], 0xA5, np.uint8))
+        out = guarded.outputs(lay)
         nn = c["db"]["neigh"].shape[1]
         ctx.bowdb_query_device(B, n, form, dqi.ptr, dqv.ptr, dqn.ptr, qs, d["ids"].ptr, d["vals"].ptr, d["nw"].ptr, stride, d["seq"].ptr if d["seq"] else None,
-                               d["neigh"].ptr if d["neigh"] else None, nn, dex.ptr if dex else None, dst.ptr + GUARD, ws.ptr + GUARD, out.ptr, guard=GUARD)
+                               d["neigh"].ptr if d["neigh"] else None, nn, dex.ptr if dex else None, dst.ptr, ws.ptr, out.ptr, guard=GUARD)
         ctx.synchronize()
-        raw = out.download(np.uint8, lay["bytes"])
-        wraw, sraw = ws.download(np.uint8, wsb + 2 * GUARD), dst.download(np.uint8, st.nbytes)
-        assert np.all(wraw[:GUARD] == 0xA5) and np.all(wraw[GUARD + wsb:] == 0xA5), "a guard byte around the workspace was written"
-        assert np.all(sraw[:GUARD] == 0xA5) and np.all(sraw[GUARD + 4 * B * n:] == 0xA5), "a guard byte around the state was written"
-        sizes = {k: np.dtype(dt).itemsize * B * n for k, dt in Context.BOWDB_OUT}
-        sizes.update(header=4 * capi.BOWDB_HEADER_INTS * B, best_acc=4 * B)
-        used = np.zeros(lay["bytes"], bool)
-        for k, sz in sizes.items():
-            used[lay[k]:lay[k] + sz] = True
-            assert not used[lay[k] - GUARD:lay[k]].any() and not used[lay[k] + sz:lay[k] + sz + GUARD].any() and lay[k] + sz + GUARD <= lay["bytes"]
-        assert np.all(raw[~used] == 0xA5), "a guard byte around the outputs was written"
+        raw = guarded.download(out, lay)
+        ws.download()
+        after = dst.download().view(F).reshape(B, n)
         for x in (dqi, dqv, dqn, dex, dst, ws, out):
             if x is not None:
                 x.free()
-        return Context.bowdb_query_parse(raw, lay, B, n), raw, sraw[GUARD:GUARD + 4 * B * n].view(F).reshape(B, n).copy()
+        return Context.bowdb_query_parse(raw, lay, B, n), raw, after
 
     def chain(self, name, form):
         """the case's queries one after the other (B = 1) on one state array, each checked against the rule; -> the raw output bytes"""

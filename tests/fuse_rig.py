@@ -6,6 +6,7 @@ from (every query has its keypoint nearby), problems 1 .. 3 are that frame moved
 for every problem would answer for the wrong query; with stride 0 there is the one unrotated block.  No test lives here."""
 import numpy as np
 
+import guarded
 import ref_fuse as RU
 import ref_projection as RP
 from projection_rig import GUARD, SHIFTS, TUM1, F, Rig, cam_struct
@@ -52,25 +53,14 @@ class FuseRig:
         pts, nr, dd, fl, qd = (np.concatenate([b[k] for b in blocks]) for k in ("xyz", "normals", "dist", "flags", "qdesc"))
         T = pick(poses, self.poses)[first:first + B].astype(F); O = pick(Ow, self.Ow)[first:first + B].astype(F)
         lay = Context.fuse_search_layout(B, nf, GUARD)
-        out = capi.DeviceBuffer(lay["bytes"]).upload(np.full(lay["bytes"], 0xA5, np.uint8))
+        out = guarded.outputs(lay)
         d = [self.dev(a) for a in (pts, nr, dd, qd, fl, T, O)]
         ctx.fuse_search_device(B, nf, 0 if stride0 else nf, d[0].ptr, d[1].ptr, d[2].ptr, d[3].ptr, d[4].ptr, d[5].ptr, d[6].ptr, cam_struct(TUM1), self.bounds, th,
                                self.sf, self.rmax, r.fin[3].ptr + first * ctx.grid_bytes(nf), r.rec.ptr + first * ctx.rec_bytes + ctx.desc_off, ctx.rec_bytes, nf,
                                out.ptr, d_uright=r.fin[1].ptr + 4 * nf * first if uright else None, chi2=chi2, init_dist=init, th_low=th_low, guard=GUARD)
         ctx.synchronize()
-        raw = out.download(np.uint8, lay["bytes"])
-        res = []
-        for p in range(B):
-            o = {k: raw[lay[k] + 4 * p * nf: lay[k] + 4 * (p + 1) * nf].view(np.int32) for k in OUT_INT}
-            o["proj"] = raw[lay["proj"] + 12 * p * nf: lay["proj"] + 12 * (p + 1) * nf].view(F).reshape(nf, 3)
-            o["n_fused"] = int(raw[lay["n_fused"] + 4 * p: lay["n_fused"] + 4 * p + 4].view(np.int32)[0])
-            o["status"] = raw[lay["status"] + p * nf: lay["status"] + (p + 1) * nf]
-            res.append(o)
-        used = np.zeros(lay["bytes"], bool)
-        for k, n in [(k, 4 * B * nf) for k in OUT_INT] + [("proj", 12 * B * nf), ("n_fused", 4 * B), ("status", B * nf)]:
-            used[lay[k]:lay[k] + n] = True
-            assert not used[lay[k] - GUARD:lay[k]].any() and not used[lay[k] + n:lay[k] + n + GUARD].any() and lay[k] + n + GUARD <= lay["bytes"]
-        assert np.all(raw[~used] == 0xA5), "a guard byte around the outputs was written"
+        raw = guarded.download(out, lay)
+        res = guarded.problems(lay.parse(raw), B)
         out.free()
         for b in self.bufs:
             b.free()

@@ -8,6 +8,7 @@ block is another problem, not the same answers rotated); all problems search fra
 whose conditions tests/test_init_ref.py asserts.  No test lives here."""
 import numpy as np
 
+import guarded
 import ref_frame as RF
 import ref_init as RI
 import ref_window as RW
@@ -60,41 +61,32 @@ class InitRig:
         dq = self.dev(np.ascontiguousarray(np.concatenate([b[0] for b in blocks]), F))
         pmh = np.ascontiguousarray(np.concatenate([b[1] for b in blocks]), F)
         # (the in-place run: the centres sit in a buffer of their own with guard bytes around them)
-        dpm = self.dev(np.concatenate([np.full(GUARD, 0xA5, np.uint8), pmh.view(np.uint8).reshape(-1), np.full(GUARD, 0xA5, np.uint8)]))
+        dpm = guarded.Guarded(pmh.nbytes, GUARD, inner=pmh, what="prev_matched")
         dfl = self.dev(np.ascontiguousarray(np.concatenate([np.roll(flags, (first + p) * ROLL) for p in range(B)]), np.uint8)) if flags is not None else None
         dtg = self.dev(np.ascontiguousarray(tg, F)) if tg is not None else self.dtg
         lay = Context.init_search_layout(B, nf, nf, GUARD)
-        out = capi.DeviceBuffer(lay["bytes"]).upload(np.full(lay["bytes"], 0xA5, np.uint8))
+        out = guarded.outputs(lay)
         wsb = Context.init_search_workspace_bytes(nf, nf, B)
-        ws = capi.DeviceBuffer(wsb)
-        if fill is not None:
-            ws.upload(np.full(wsb, fill, np.uint8))
+        ws = guarded.Guarded(wsb, GUARD, inner=fill)
         # every problem searches frame 1: its grid blob B times over, one set of rows (stride 0) and of coordinates per problem
         g = self.fin[3].download(np.uint8, ctx.grid_bytes(nf), ctx.grid_bytes(nf))
         dg = self.dev(np.tile(g, B))
         dxy = self.dev(np.tile(self.xy[1].reshape(-1), B)) if prev_out else None
-        ctx.init_search_device(B, nf, dq.ptr, dpm.ptr + GUARD, dg.ptr, dtg.ptr, 0, nf, ws.ptr, out.ptr, window=window, d_query_flags=dfl.ptr if dfl else None,
-                               d_target_xy=dxy.ptr if dxy else None, d_prev_out=dpm.ptr + GUARD if in_place else None, th_low=th_low, nn_ratio=ratio, guard=GUARD)
+        ctx.init_search_device(B, nf, dq.ptr, dpm.ptr, dg.ptr, dtg.ptr, 0, nf, ws.ptr, out.ptr, window=window, d_query_flags=dfl.ptr if dfl else None,
+                               d_target_xy=dxy.ptr if dxy else None, d_prev_out=dpm.ptr if in_place else None, th_low=th_low, nn_ratio=ratio, guard=GUARD)
         ctx.synchronize()
-        raw = out.download(np.uint8, lay["bytes"])
-        pmr = dpm.download(np.uint8, 2 * GUARD + pmh.nbytes)
-        assert np.all(pmr[:GUARD] == 0xA5) and np.all(pmr[GUARD + pmh.nbytes:] == 0xA5), "a guard byte around prev_matched was written"
-        res = []
-        for p in range(B):
-            o = {k: raw[lay[k] + 4 * p * nf: lay[k] + 4 * (p + 1) * nf].view(np.int32) for k in OUT_Q + OUT_T}
-            o["n_matches"] = int(raw[lay["n_matches"] + 4 * p: lay["n_matches"] + 4 * p + 4].view(np.int32)[0])
-            o["status"] = raw[lay["status"] + p * nf: lay["status"] + (p + 1) * nf]
-            if in_place:
-                o["prev_out"] = pmr[GUARD + 8 * p * nf: GUARD + 8 * (p + 1) * nf].view(F).reshape(nf, 2)
-            elif prev_out:
-                o["prev_out"] = raw[lay["prev_out"] + 8 * p * nf: lay["prev_out"] + 8 * (p + 1) * nf].view(F).reshape(nf, 2)
-            res.append(o)
-        if not in_place:
-            assert pmr[GUARD:GUARD + pmh.nbytes].tobytes() == pmh.tobytes(), "prev_matched was written"
-        sizes = [(k, 4 * B * nf) for k in OUT_Q + OUT_T] + [("n_matches", 4 * B), ("status", B * nf)] + ([("prev_out", 8 * B * nf)] if prev_out and not in_place else [])
-        check_guards(raw, lay, sizes)
-        hdr = np.stack([ws.download(np.int32, 4, p * (wsb // B)) for p in range(B)])
-        out.free(); ws.free()
+        own = prev_out and not in_place                                # prev_out is written into the layout's own array
+        raw = guarded.download(out, lay, skip=() if own else ("prev_out",))
+        pmr = dpm.download()
+        a = lay.parse(raw)
+        if in_place:
+            a["prev_out"] = pmr.view(F).reshape(B, nf, 2)
+        else:
+            assert pmr.tobytes() == pmh.tobytes(), "prev_matched was written"
+        res = guarded.problems(a, B, [k for k in a if k != "prev_out" or prev_out or in_place])
+        wraw = ws.download()
+        hdr = np.stack([wraw[p * (wsb // B):p * (wsb // B) + 16].view(np.int32) for p in range(B)])
+        out.free(); ws.free(); dpm.free()
         for b in self.bufs:
             b.free()
         self.bufs = []
@@ -115,16 +107,6 @@ class InitRig:
         for x in (self.din, self.rec, self.dtg) + tuple(b for b in self.fin if b is not None):
             x.free()
         self.ctx.close()
-
-
-def check_guards(raw, lay, sizes):
-    """at least GUARD bytes before and after every output array, and they still hold the fill"""
-    used = np.zeros(lay["bytes"], bool)
-    for k, n in sizes:
-        used[lay[k]:lay[k] + n] = True
-    for k, n in sizes:
-        assert not used[lay[k] - GUARD:lay[k]].any() and not used[lay[k] + n:lay[k] + n + GUARD].any() and lay[k] + n + GUARD <= lay["bytes"], k
-    assert np.all(raw[~used] == 0xA5), "a guard byte around the outputs was written"
 
 
 def cpu_frames(O, blob_weights, nf, seed):

@@ -9,6 +9,7 @@ SearchBySim3: side 1 is frame 0, side 2 of problem p is frame p, each problem wi
 with side1_shared every problem reads problem 0's side 1.  No test lives here."""
 import numpy as np
 
+import guarded
 import ref_fuse as RU
 import ref_loop as RL
 import ref_projection as RP
@@ -79,26 +80,18 @@ class LoopRig:
         d = [self.dev(a) for a in (cat("xyz", F), cat("normals", F), cat("dist", F), cat("qdesc", F), cat("flags", np.uint8), T, Ow)]
         dtk = self.dev(cat("taken", np.uint8)) if taken else None
         lay = Context.map_projection_search_layout(B, nf, nf, GUARD)
-        out = capi.DeviceBuffer(lay["bytes"]).upload(np.full(lay["bytes"], 0xA5, np.uint8))
-        wsb = Context.map_projection_search_workspace_bytes(nf, nf, B)
-        ws = capi.DeviceBuffer(wsb)
+        out = guarded.outputs(lay)
+        ws = guarded.Guarded(Context.map_projection_search_workspace_bytes(nf, nf, B), GUARD)
         f0 = 0 if shared else first
         ctx.map_projection_search_device(form, B, nf, d[0].ptr, d[1].ptr, d[2].ptr, d[3].ptr, d[4].ptr, d[5].ptr, d[6].ptr, cam_struct(TUM1), self.bounds, th,
                                          self.sf, self.rmax, r.fin[3].ptr + f0 * ctx.grid_bytes(nf), r.rec.ptr + f0 * ctx.rec_bytes + ctx.desc_off, ctx.rec_bytes,
                                          1 if shared else 0, nf, ws.ptr, out.ptr, d_taken=dtk.ptr if dtk else None, accept_max=accept, guard=GUARD)
         ctx.synchronize()
-        raw = out.download(np.uint8, lay["bytes"])
-        res = []
-        for p in range(B):
-            o = {k: raw[lay[k] + 4 * p * nf: lay[k] + 4 * (p + 1) * nf].view(np.int32) for k in MAP_INT + ("assigned",)}
-            o["proj"] = raw[lay["proj"] + 12 * p * nf: lay["proj"] + 12 * (p + 1) * nf].view(F).reshape(nf, 3)
-            o["n_matches"] = int(raw[lay["n_matches"] + 4 * p: lay["n_matches"] + 4 * p + 4].view(np.int32)[0])
-            o["status"] = raw[lay["status"] + p * nf: lay["status"] + (p + 1) * nf]
-            res.append(o)
-        sizes = [(k, 4 * B * nf) for k in MAP_INT + ("assigned",)] + [("proj", 12 * B * nf), ("n_matches", 4 * B), ("status", B * nf)]
-        check_guards(raw, lay, sizes)
+        raw = guarded.download(out, lay)
+        res = guarded.problems(lay.parse(raw), B)
         per = Context.search_projection_workspace_bytes(nf, nf, 1)
-        hdr = np.stack([ws.download(np.int32, 4, p * per) for p in range(B)])
+        wraw = ws.download()
+        hdr = np.stack([wraw[p * per:p * per + 16].view(np.int32) for p in range(B)])
         out.free(); ws.free(); self.free()
         return res, raw, hdr
 
@@ -129,7 +122,7 @@ class LoopRig:
         nf, ctx, r = self.nf, self.ctx, self.rig
         pr = [self.problem(first + p, shared, **over) for p in range(B)]
         lay = Context.sim3_search_layout(B, nf, nf, GUARD)
-        out = capi.DeviceBuffer(lay["bytes"]).upload(np.full(lay["bytes"], 0xA5, np.uint8))
+        out = guarded.outputs(lay)
         types = dict(points=F, dist=F, mp_desc=F, flags=np.uint8)
         n1 = 1 if shared else B
         d1 = {k: self.dev(np.ascontiguousarray(np.concatenate([pr[p][0][k] for p in range(n1)]), types[k])) for k in SIDE_IN}
@@ -144,19 +137,8 @@ class LoopRig:
         ctx.sim3_search_device(B, 1 if shared else 0, side1, side2, dM21.ptr, dM12.ptr, cam_struct(TUM1), self.bounds, th, self.sf, self.rmax,
                                out.ptr + lay["match12"], out.ptr + lay["n_found"], th_high=th_high)
         ctx.synchronize()
-        raw = out.download(np.uint8, lay["bytes"])
-        res = []
-        for p in range(B):
-            o = {}
-            for s in "12":
-                o.update({k + s: raw[lay[k + s] + 4 * p * nf: lay[k + s] + 4 * (p + 1) * nf].view(np.int32) for k in SIM3_INT})
-                o["proj" + s] = raw[lay["proj" + s] + 12 * p * nf: lay["proj" + s] + 12 * (p + 1) * nf].view(F).reshape(nf, 3)
-                o["status" + s] = raw[lay["status" + s] + p * nf: lay["status" + s] + (p + 1) * nf]
-            o["match12"] = raw[lay["match12"] + 4 * p * nf: lay["match12"] + 4 * (p + 1) * nf].view(np.int32)
-            o["n_found"] = int(raw[lay["n_found"] + 4 * p: lay["n_found"] + 4 * p + 4].view(np.int32)[0])
-            res.append(o)
-        sizes = [(k + s, 4 * B * nf) for k in SIM3_INT for s in "12"] + [("proj" + s, 12 * B * nf) for s in "12"] + [("status" + s, B * nf) for s in "12"]
-        check_guards(raw, lay, sizes + [("match12", 4 * B * nf), ("n_found", 4 * B)])
+        raw = guarded.download(out, lay)
+        res = guarded.problems(lay.parse(raw), B)
         out.free(); self.free()
         return res, raw
 
@@ -174,13 +156,3 @@ class LoopRig:
         for b in self.grid0.values():
             b.free()
         self.rig.close()
-
-
-def check_guards(raw, lay, sizes):
-    """at least GUARD bytes before and after every output array, and they still hold the fill"""
-    used = np.zeros(lay["bytes"], bool)
-    for k, n in sizes:
-        used[lay[k]:lay[k] + n] = True
-    for k, n in sizes:
-        assert not used[lay[k] - GUARD:lay[k]].any() and not used[lay[k] + n:lay[k] + n + GUARD].any() and lay[k] + n + GUARD <= lay["bytes"], k
-    assert np.all(raw[~used] == 0xA5), "a guard byte around the outputs was written"

@@ -219,6 +219,7 @@ class MlpnpRig:
 
     def run(self, s, draws=None, start_iter=None, n_matches=None, min_matches=0, tables=None, chunk=None, valid=True):
         """a scene (B = its number of candidates; draws [max_iters][6] = shared, stride 0) -> (parsed outputs, raw bytes)"""
+        import guarded
         from xfeatslam_amd import capi
         from xfeatslam_amd.extractor import Context
         assigned = np.ascontiguousarray(s["assigned"], np.int32)
@@ -233,22 +234,16 @@ class MlpnpRig:
         lay = Context.mlpnp_layout(B, n, GUARD)
         wsb = self.L.xfh_mlpnp_workspace_bytes(n, nq, B, max_iters)
         assert wsb > 0
-        ws = capi.DeviceBuffer(wsb + 2 * GUARD).upload(np.full(wsb + 2 * GUARD, 0xA5, np.uint8))
-        out = capi.DeviceBuffer(lay["bytes"]).upload(np.full(lay["bytes"], 0xA5, np.uint8))
+        ws, out = guarded.Guarded(wsb, GUARD), guarded.outputs(lay)
         try:
             self.ctx.mlpnp_solve_device(B, n, nq, bufs[0].ptr, bufs[1].ptr, bufs[2].ptr, bufs[3].ptr if valid else None, camera(s["cam"]), s["max_err"], bufs[4].ptr,
                                         bufs[5].ptr, s["chunk"] if chunk is None else chunk, None if start_iter is None else bufs[7].ptr, max_iters, bufs[6].ptr,
-                                        0 if draws.ndim == 2 else max_iters * 6, RAND_MAX, ws.ptr + GUARD, out.ptr, min_matches=min_matches,
+                                        0 if draws.ndim == 2 else max_iters * 6, RAND_MAX, ws.ptr, out.ptr, min_matches=min_matches,
                                         d_n_matches=None if n_matches is None else bufs[8].ptr, guard=GUARD)
             self.ctx.synchronize()
-            raw = out.download(np.uint8, lay["bytes"])
-            wraw = ws.download(np.uint8, wsb + 2 * GUARD)
+            raw = guarded.download(out, lay)
+            ws.download()
         finally:
             for b in bufs + [ws, out]:
                 b.free()
-        used = np.zeros(lay["bytes"], bool)
-        for k in Context.MLPNP_OUT:
-            used[lay[k]:lay[k] + lay[k + "_bytes"]] = True
-        assert np.all(raw[~used] == 0xA5), "a byte outside the outputs was written"
-        assert np.all(wraw[:GUARD] == 0xA5) and np.all(wraw[GUARD + wsb:] == 0xA5), "a byte outside the workspace was written"
-        return Context.mlpnp_parse(raw, lay, B, n), raw
+        return lay.parse(raw), raw

@@ -7,10 +7,12 @@ import functools
 
 import numpy as np
 
+import guarded
 import ref_optsim3 as R
 import ref_optsim3_literal as RL
 import ref_poseopt as RP
 from xfeatslam_amd import capi
+from xfeatslam_amd.extractor import Context
 
 F, D = np.float32, np.float64
 CAM = (517.3, 516.5, 318.6, 255.3)                                      # fx, fy, cx, cy (TUM1-like)
@@ -208,8 +210,6 @@ def cam_struct(cam=CAM):
 
 SIDE1 = (("T1w", F), ("xy_un1", F), ("point1", np.int32), ("points1", F))
 SIDE2 = (("assigned", np.int32), ("points2", F), ("flags2", np.uint8), ("index2", np.int32), ("xy_un2", F), ("T2w", F))
-OUTS = (("assigned_out", np.int32, "n1", 1), ("status", np.uint8, "n1", 1), ("chi2", F, "n1", 2), ("state", D, None, 8), ("S12_out", F, None, 13),
-        ("Tcw", F, None, 12), ("Ow", F, None, 3), ("header", np.int32, None, 16), ("final_chi2", D, None, 1))
 
 
 def _inputs(problems, side1_shared):
@@ -226,17 +226,9 @@ def _inputs(problems, side1_shared):
     return dims, arrays, s12, tmw
 
 
-def _split(B, n1, get, has_tmw):
-    res = [dict() for _ in range(B)]
-    for name, dt, per, width in OUTS:
-        if name in ("Tcw", "Ow") and not has_tmw:
-            continue
-        n = (n1 if per else 1) * width
-        a = get(name)
-        for b in range(B):
-            v = a[b * n:(b + 1) * n].copy()
-            res[b][name] = float(v[0]) if name == "final_chi2" else (v.reshape(n1, 2) if name == "chi2" else v)
-    return res
+def _split(B, arrays, has_tmw):
+    """dict of output arrays with a leading B -> one dict per problem (Tcw and Ow only where the call had a Tmw)"""
+    return guarded.problems(arrays, B, [k for k in arrays if has_tmw or k not in ("Tcw", "Ow")])
 
 
 def run_host(problems, side1_shared=False, L=None):
@@ -245,7 +237,7 @@ def run_host(problems, side1_shared=False, L=None):
     B = len(problems)
     (n1, M1, nq, n2), arrays, s12, tmw = _inputs(problems, side1_shared)
     p0 = problems[0]
-    outs = {name: np.zeros(B * (n1 if per else 1) * width, dt) for name, dt, per, width in OUTS}
+    outs = Context.sim3_optimize_layout(B, n1).zeros()
     ws = np.zeros(int(L.xfh_sim3_optimize_workspace_bytes(n1, B)) + 16, np.uint8)
     wsp = (ws.ctypes.data + 15) & ~15
     c1, c2 = cam_struct(p0["cam1"]), cam_struct(p0["cam2"])
@@ -256,7 +248,7 @@ def run_host(problems, side1_shared=False, L=None):
                                   None if tmw is None else outs["Tcw"].ctypes.data, None if tmw is None else outs["Ow"].ctypes.data,
                                   outs["header"].ctypes.data, outs["final_chi2"].ctypes.data)
     assert rc == 0, rc
-    return _split(B, n1, lambda k: outs[k], tmw is not None)
+    return _split(B, outs, tmw is not None)
 
 
 class Sim3OptRig:
@@ -264,14 +256,13 @@ class Sim3OptRig:
     the last run left it"""
 
     def __init__(self, L):
-        from xfeatslam_amd.extractor import Context
         self.L = L
         self.ctx = Context(nfeatures=1, max_height=32, max_width=32)
 
     def close(self):
         self.ctx.close()
 
-    def run(self, problems, side1_shared=False, fill=0xA5, in_place=False, ws_fill=0x3C, s12_stride=13):
+    def run(self, problems, side1_shared=False, fill=guarded.FILL, in_place=False, ws_fill=0x3C, s12_stride=13):
         """fill: the byte around and under the outputs and around the workspace; ws_fill: the byte the workspace holds before the call.  in_place:
         d_assigned_out = d_assigned and d_S12_out = d_S12."""
         L, B = self.L, len(problems)
@@ -282,47 +273,31 @@ class Sim3OptRig:
             wide[:, :13] = s12
             s12 = wide
         dev = [capi.DeviceBuffer(a.nbytes).upload(a) for a in arrays + [s12] + ([tmw] if tmw is not None else [])]
-        al = lambda x: (x + 255) & ~255
-        off, pos = {}, GUARD
-        for name, dt, per, width in OUTS:
-            off[name] = pos
-            pos = al(pos + B * (n1 if per else 1) * width * np.dtype(dt).itemsize + GUARD)
-        out = capi.DeviceBuffer(pos).upload(np.full(pos, fill, np.uint8))
+        lay = Context.sim3_optimize_layout(B, n1, GUARD)
+        out = guarded.outputs(lay, fill)
         ws_bytes = int(L.xfh_sim3_optimize_workspace_bytes(n1, B))
         assert ws_bytes > 0 and ws_bytes % 16 == 0
-        ws_host = np.full(GUARD + ws_bytes + GUARD, fill, np.uint8)
-        ws_host[GUARD:GUARD + ws_bytes] = ws_fill
-        ws = capi.DeviceBuffer(ws_host.nbytes).upload(ws_host)
+        ws = guarded.Guarded(ws_bytes, GUARD, fill, inner=ws_fill)
         c1, c2 = cam_struct(p0["cam1"]), cam_struct(p0["cam2"])
-        ptr = lambda k: out.ptr + off[k]
+        ptr = lambda k: out.ptr + lay[k]
         a_out = dev[4].ptr if in_place else ptr("assigned_out")
         s_out, s_out_stride = (dev[10].ptr, s12_stride) if in_place else (ptr("S12_out"), 13)
         rc = L.xfh_sim3_optimize_device(self.ctx.h, B, n1, M1, nq, n2, int(side1_shared), *[d.ptr for d in dev[:10]], dev[10].ptr, s12_stride,
                                         dev[11].ptr if tmw is not None else None, C.byref(c1), C.byref(c2), p0["th2"], p0["fix_scale"], p0["all_points"],
-                                        p0["inv_sigma2_1"], p0["inv_sigma2_2"], ws.ptr + GUARD, a_out, ptr("status"), ptr("chi2"), ptr("state"), s_out,
+                                        p0["inv_sigma2_1"], p0["inv_sigma2_2"], ws.ptr, a_out, ptr("status"), ptr("chi2"), ptr("state"), s_out,
                                         s_out_stride, ptr("Tcw") if tmw is not None else None, ptr("Ow") if tmw is not None else None, ptr("header"),
                                         ptr("final_chi2"))
         assert rc == 0, rc
         self.ctx.synchronize()
-        raw = out.download(np.uint8, pos)
-        ws_after = ws.download(np.uint8, ws_host.nbytes)
-        assert np.all(ws_after[:GUARD] == fill) and np.all(ws_after[GUARD + ws_bytes:] == fill), "bytes outside the workspace were written"
-        self.workspace = ws_after[GUARD:GUARD + ws_bytes].copy()
-        written = np.zeros(pos, bool)
-
-        def get(name):
-            dt, per, width = next((d, p, w) for n, d, p, w in OUTS if n == name)
-            if in_place and name == "assigned_out":
-                return dev[4].download(np.int32, B * n1)
-            if in_place and name == "S12_out":
-                wide_after = dev[10].download(F, B * s12_stride).reshape(B, s12_stride)
-                assert np.all(np.isnan(wide_after[:, 13:])), "the rest of the solver's record was written"
-                return wide_after[:, :13].reshape(-1).copy()
-            size = B * (n1 if per else 1) * width * np.dtype(dt).itemsize
-            written[off[name]:off[name] + size] = True
-            return raw[off[name]:off[name] + size].view(dt)
-        res = _split(B, n1, get, tmw is not None)
-        assert np.all(raw[~written] == fill), "bytes outside the output arrays were written"
+        skip = (("assigned_out", "S12_out") if in_place else ()) + (() if tmw is not None else ("Tcw", "Ow"))
+        raw = guarded.download(out, lay, fill, skip)
+        self.workspace = ws.download()
+        a = lay.parse(raw)
+        if in_place:
+            a["assigned_out"] = dev[4].download(np.int32, B * n1).reshape(B, n1)
+            wide_after = dev[10].download(F, B * s12_stride).reshape(B, s12_stride)
+            assert np.all(np.isnan(wide_after[:, 13:])), "the rest of the solver's record was written"
+            a["S12_out"] = wide_after[:, :13].copy()
         for d in dev + [out, ws]:
             d.free()
-        return res, raw[written].copy()
+        return _split(B, a, tmw is not None), raw[lay.used(skip)]

@@ -6,6 +6,7 @@ import ctypes as C
 
 import numpy as np
 
+import guarded
 import ref_poseopt as RP
 from xfeatslam_amd import capi
 
@@ -162,9 +163,6 @@ def cam_struct():
     return c
 
 
-OUTS = (("Tcw_out", F, 12), ("outlier", np.uint8, None), ("chi2", F, None), ("header", np.int32, 8), ("final_chi2", D, 1))
-
-
 class PoseRig:
     """device buffers for B problems of (nt, nq); run() -> per problem dict of outputs, the raw output bytes, guards checked; .workspace is the
     workspace as the last run left it"""
@@ -178,7 +176,7 @@ class PoseRig:
     def close(self):
         self.ctx.close()
 
-    def run(self, scenes, fill=0xA5, uright=True, in_place=False, ws_fill=0x3C):
+    def run(self, scenes, fill=guarded.FILL, uright=True, in_place=False, ws_fill=0x3C):
         """fill: the byte around and under the outputs and around the workspace; ws_fill: the byte the workspace holds before the call.  Scenes
         whose uright is None (all of them, or none) give the call a null pointer."""
         L, B, nt, nq = self.L, len(scenes), scenes[0]["nt"], scenes[0]["nq"]
@@ -189,41 +187,23 @@ class PoseRig:
                np.stack([s["uright"] for s in scenes]).astype(F) if has_ur else None,
                np.stack([s["assigned"] for s in scenes]).astype(np.int32), np.stack([s["points"] for s in scenes]).astype(F)]
         dev = [None if a is None else capi.DeviceBuffer(a.nbytes).upload(a) for a in ins]
-        al = lambda x: (x + 255) & ~255
-        off, pos = {}, GUARD
-        for name, dt, per in OUTS:
-            off[name] = pos
-            pos = al(pos + B * (per or nt) * np.dtype(dt).itemsize + GUARD)
-        out = capi.DeviceBuffer(pos).upload(np.full(pos, fill, np.uint8))
+        lay = self.ctx.pose_optimize_layout(B, nt, GUARD)
+        out = guarded.outputs(lay, fill)
         ws_bytes = int(L.xfh_pose_optimize_workspace_bytes(nt, B))      # exactly what the call may use, between two guards
         assert ws_bytes > 0 and ws_bytes % 16 == 0
-        ws_host = np.full(GUARD + ws_bytes + GUARD, fill, np.uint8)
-        ws_host[GUARD:GUARD + ws_bytes] = ws_fill
-        ws = capi.DeviceBuffer(ws_host.nbytes).upload(ws_host)
-        tcw_out = dev[0].ptr if in_place else out.ptr + off["Tcw_out"]
+        ws = guarded.Guarded(ws_bytes, GUARD, fill, inner=ws_fill)
+        tcw_out = dev[0].ptr if in_place else out.ptr + lay["Tcw_out"]
         rc = L.xfh_pose_optimize_device(self.ctx.h, B, nt, nq, dev[0].ptr, C.byref(self.cam), dev[1].ptr, dev[2].ptr if has_ur else None, dev[3].ptr,
-                                        dev[4].ptr, INV_SIGMA2, ws.ptr + GUARD, tcw_out, out.ptr + off["outlier"], out.ptr + off["chi2"], out.ptr + off["header"],
-                                        out.ptr + off["final_chi2"])
+                                        dev[4].ptr, INV_SIGMA2, ws.ptr, tcw_out, *[out.ptr + lay[k] for k in lay.names[1:]])
         assert rc == 0, rc
         self.ctx.synchronize()
-        raw = out.download(np.uint8, pos)
-        ws_after = ws.download(np.uint8, ws_host.nbytes)
-        assert np.all(ws_after[:GUARD] == fill) and np.all(ws_after[GUARD + ws_bytes:] == fill), "bytes outside the workspace were written"
-        self.workspace = ws_after[GUARD:GUARD + ws_bytes].copy()        # as the call left it: B strides of xfh_pose_optimize_workspace_bytes(nt, 1)
-        written = np.zeros(pos, bool)
-        res = [dict() for _ in range(B)]
-        for name, dt, per in OUTS:
-            n = per or nt
-            size = B * n * np.dtype(dt).itemsize
-            if name == "Tcw_out" and in_place:
-                a = dev[0].download(F, B * 12)
-            else:
-                a = raw[off[name]:off[name] + size].view(dt)
-                written[off[name]:off[name] + size] = True
-            for b in range(B):
-                res[b][name] = a[b * n:(b + 1) * n].copy() if name != "final_chi2" else float(a[b])
-        assert np.all(raw[~written] == fill), "bytes outside the output arrays were written"
+        skip = ("Tcw_out",) if in_place else ()
+        raw = guarded.download(out, lay, fill, skip)
+        self.workspace = ws.download()                                  # as the call left it: B strides of xfh_pose_optimize_workspace_bytes(nt, 1)
+        a = lay.parse(raw)
+        if in_place:
+            a["Tcw_out"] = dev[0].download(F, B * 12).reshape(B, 12)
         for d in dev + [out, ws]:
             if d is not None:
                 d.free()
-        return res, raw[written].copy()
+        return guarded.problems(a, B), raw[lay.used(skip)]

@@ -3,6 +3,7 @@ frames extracted and finished on the device, world points and poses from tests/r
 xfh_search_projection_device.  No test lives here, and nothing but numpy and the package is imported."""
 import numpy as np
 
+import guarded
 import ref_frame as RF
 import ref_projection as RP
 import ref_window as RW
@@ -61,12 +62,10 @@ class Rig:
         bytes of the output buffer, proj [B][nq][3], workspace header ints [B][2])"""
         nf, ctx = self.nf, self.ctx
         lay = Context.search_projection_layout(B, nf, nf, GUARD)
-        out = capi.DeviceBuffer(lay["bytes"]).upload(np.full(lay["bytes"], 0xA5, np.uint8))
-        dproj = capi.DeviceBuffer(B * nf * 12 + 2 * GUARD).upload(np.full(B * nf * 12 + 2 * GUARD, 0xA5, np.uint8)) if proj else None
+        out = guarded.outputs(lay)
+        dproj = guarded.Guarded(B * nf * 12, GUARD, what="proj") if proj else None
         wsb = Context.search_projection_workspace_bytes(nf, nf, B)
-        ws = capi.DeviceBuffer(wsb)
-        if fill is not None:
-            ws.upload(np.full(wsb, fill, np.uint8))
+        ws = guarded.Guarded(wsb, GUARD, inner=fill)
         qd = self.dev(np.tile(self.recs[0][1], (B, 1)))
         dp = self.dev(np.ascontiguousarray(pts, F)); dfl = self.dev(np.ascontiguousarray(flags, np.uint8)); dT = self.dev(self.poses[:B])
         duq = self.dev(np.ascontiguousarray(ur_query, F)) if ur_query is not None else None
@@ -75,30 +74,16 @@ class Rig:
                                      ctx.rec_bytes, nf, ws.ptr, out.ptr, radius=radius, d_Tcw=dT.ptr, cam=cam_struct(TUM1), bounds=self.bounds,
                                      d_ur_query=duq.ptr if duq else None, d_skip=dsk.ptr if dsk else None,
                                      d_uright=self.fin[1].ptr + 4 * nf if uright else None, init_dist=init, th_high=th_high, nn_ratio=ratio,
-                                     d_proj_out=dproj.ptr + GUARD if dproj else None, guard=GUARD)
+                                     d_proj_out=dproj.ptr if dproj else None, guard=GUARD)
         ctx.synchronize()
-        raw = out.download(np.uint8, lay["bytes"])
-        res = []
-        for p in range(B):
-            r = {k: raw[lay[k] + 4 * p * nf: lay[k] + 4 * (p + 1) * nf].view(np.int32) for k in OUT_INT}
-            r["assigned"] = raw[lay["assigned"] + 4 * p * nf: lay["assigned"] + 4 * (p + 1) * nf].view(np.int32)
-            r["n_matches"] = int(raw[lay["n_matches"] + 4 * p: lay["n_matches"] + 4 * p + 4].view(np.int32)[0])
-            r["status"] = raw[lay["status"] + p * nf: lay["status"] + (p + 1) * nf]
-            res.append(r)
-        # guard words: at least GUARD bytes before and after every output array, and they still hold the fill
-        used = np.zeros(lay["bytes"], bool)
-        for k, n in (("match_idx", 4 * B * nf), ("best_dist", 4 * B * nf), ("second_dist", 4 * B * nf), ("n_candidates", 4 * B * nf),
-                     ("assigned", 4 * B * nf), ("n_matches", 4 * B), ("status", B * nf)):
-            used[lay[k]:lay[k] + n] = True
-            assert not used[lay[k] - GUARD:lay[k]].any() and not used[lay[k] + n:lay[k] + n + GUARD].any() and lay[k] + n + GUARD <= lay["bytes"]
-        assert np.all(raw[~used] == 0xA5), "a guard byte around the outputs was written"
+        raw = guarded.download(out, lay)
+        res = guarded.problems(lay.parse(raw), B)
         pj = None
         if dproj:
-            pr = dproj.download(np.uint8, B * nf * 12 + 2 * GUARD)
-            assert np.all(pr[:GUARD] == 0xA5) and np.all(pr[GUARD + B * nf * 12:] == 0xA5), "a guard byte around proj was written"
-            pj = pr[GUARD:GUARD + B * nf * 12].view(F).reshape(B, nf, 3)
+            pj = dproj.download().view(F).reshape(B, nf, 3)
             dproj.free()
-        hdr = np.stack([ws.download(np.int32, 2, p * (wsb // B)) for p in range(B)])
+        wraw = ws.download()
+        hdr = np.stack([wraw[p * (wsb // B):p * (wsb // B) + 8].view(np.int32) for p in range(B)])
         out.free(); ws.free()
         for b in self.bufs:
             b.free()

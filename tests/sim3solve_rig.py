@@ -241,6 +241,7 @@ class Sim3SolveRig:
 
     def run(self, s, draws=None, T1w=None, num_matches=None, min_matches=0):
         """a scene (B = its number of candidates; draws [max_iters][3] = shared, stride 0; T1w [12] shared or [B][12]) -> (parsed outputs, raw bytes)"""
+        import guarded
         from xfeatslam_amd import capi
         from xfeatslam_amd.extractor import Context
         matched = np.ascontiguousarray(s["matched"], np.int32)
@@ -253,49 +254,38 @@ class Sim3SolveRig:
         lay = Context.sim3_solve_layout(B, n1, GUARD)
         wsb = self.L.xfh_sim3_solve_workspace_bytes(n1, M, B)
         assert wsb > 0
-        ws = capi.DeviceBuffer(wsb + 2 * GUARD).upload(np.full(wsb + 2 * GUARD, 0xA5, np.uint8))
-        out = capi.DeviceBuffer(lay["bytes"]).upload(np.full(lay["bytes"], 0xA5, np.uint8))
+        ws, out = guarded.Guarded(wsb, GUARD), guarded.outputs(lay)
         try:
             self.ctx.sim3_solve_device(B, n1, M, bufs[0].ptr, bufs[1].ptr, bufs[2].ptr, bufs[3].ptr, 0 if T1w.ndim == 1 else 12, bufs[4].ptr, camera(s["cam1"]),
-                                       camera(s["cam2"]), bufs[5].ptr, max_iters, bufs[6].ptr, 0 if draws.ndim == 2 else max_iters * 3, RAND_MAX, ws.ptr + GUARD, out.ptr,
+                                       camera(s["cam2"]), bufs[5].ptr, max_iters, bufs[6].ptr, 0 if draws.ndim == 2 else max_iters * 3, RAND_MAX, ws.ptr, out.ptr,
                                        min_inliers=s["min_inliers"], fix_scale=s["fix_scale"], max_err1=s["max_err"], max_err2=s["max_err"], min_matches=min_matches,
                                        d_num_matches=bufs[7].ptr if num_matches is not None else None, guard=GUARD)
             self.ctx.synchronize()
-            raw = out.download(np.uint8, lay["bytes"])
-            wraw = ws.download(np.uint8, wsb + 2 * GUARD)
+            raw = guarded.download(out, lay)
+            ws.download()
         finally:
             for b in bufs + [ws, out]:
                 b.free()
-        used = np.zeros(lay["bytes"], bool)
-        for k in Context.SIM3_SOLVE_OUT:
-            used[lay[k]:lay[k] + lay[k + "_bytes"]] = True
-        assert np.all(raw[~used] == 0xA5), "a byte outside the outputs was written"
-        assert np.all(wraw[:GUARD] == 0xA5) and np.all(wraw[GUARD + wsb:] == 0xA5), "a byte outside the workspace was written"
-        return Context.sim3_solve_parse(raw, lay, B, n1), raw
+        return lay.parse(raw), raw
 
     def merge(self, match12, point2, M):
         """-> (matched, matched_kf, num, raw bytes of the three outputs with their guards)"""
+        import guarded
         from xfeatslam_amd import capi
+        from xfeatslam_amd.extractor import Context
         match12, point2 = np.ascontiguousarray(match12, np.int32), np.ascontiguousarray(point2, np.int32)
         J, n1 = match12.shape
         n2 = point2.shape[1]
-        al = lambda x: (x + 255) & ~255
-        o_m, o_k, o_n = GUARD, GUARD + al(4 * n1) + GUARD, GUARD + 2 * (al(4 * n1) + GUARD)
-        total = o_n + 256 + GUARD
-        wsb = self.L.xfh_sim3_solve_workspace_bytes(n1, M, 1)
+        lay = Context.sim3_merge_layout(n1, GUARD)
         bufs = [capi.DeviceBuffer(a.nbytes).upload(a) for a in (match12, point2)]
-        ws = capi.DeviceBuffer(wsb + 2 * GUARD).upload(np.full(wsb + 2 * GUARD, 0xA5, np.uint8))
-        out = capi.DeviceBuffer(total).upload(np.full(total, 0xA5, np.uint8))
+        ws, out = guarded.Guarded(self.L.xfh_sim3_solve_workspace_bytes(n1, M, 1), GUARD), guarded.outputs(lay)
         try:
-            self.ctx.sim3_merge_matches_device(J, n1, n2, M, bufs[0].ptr, bufs[1].ptr, ws.ptr + GUARD, out.ptr + o_m, out.ptr + o_k, out.ptr + o_n)
+            self.ctx.sim3_merge_matches_device(J, n1, n2, M, bufs[0].ptr, bufs[1].ptr, ws.ptr, *[out.ptr + lay[k] for k in lay.names])
             self.ctx.synchronize()
-            raw = out.download(np.uint8, total)
-            wraw = ws.download(np.uint8, wsb + 2 * GUARD)
+            raw = guarded.download(out, lay)
+            ws.download()
         finally:
             for b in bufs + [ws, out]:
                 b.free()
-        used = np.zeros(total, bool)
-        used[o_m:o_m + 4 * n1] = used[o_k:o_k + 4 * n1] = used[o_n:o_n + 4] = True
-        assert np.all(raw[~used] == 0xA5), "a byte outside the outputs was written"
-        assert np.all(wraw[:GUARD] == 0xA5) and np.all(wraw[GUARD + wsb:] == 0xA5), "a byte outside the workspace was written"
-        return raw[o_m:o_m + 4 * n1].view(np.int32).copy(), raw[o_k:o_k + 4 * n1].view(np.int32).copy(), int(raw[o_n:o_n + 4].view(np.int32)[0]), raw
+        a = lay.parse(raw)
+        return a["matched"], a["matched_kf"], int(a["num_matches"][0]), raw

@@ -7,9 +7,10 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import guarded
 import ref_init as RI
 import ref_window as RW
-from init_rig import InitRig, check_guards
+from init_rig import InitRig
 from projection_rig import F, GUARD
 from xfeatslam_amd import capi
 from xfeatslam_amd.extractor import Context
@@ -161,15 +162,11 @@ def test_16384_by_16384_runs_the_large_lds_path(rig, oracle_mod):
     txy = np.stack([kp["x"], kp["y"]], 1).astype(F)
     bufs = [capi.DeviceBuffer(a.nbytes).upload(a) for a in (q, pm, tg, txy)]
     lay = Context.init_search_layout(1, n, n, GUARD)
-    out = capi.DeviceBuffer(lay["bytes"]).upload(np.full(lay["bytes"], 0xA5, np.uint8))
+    out = guarded.outputs(lay)
     ws = capi.DeviceBuffer(Context.init_search_workspace_bytes(n, n, 1))
     ctx.init_search_device(1, n, bufs[0].ptr, bufs[1].ptr, dg.ptr, bufs[2].ptr, 0, n, ws.ptr, out.ptr, window=6.0, d_target_xy=bufs[3].ptr, guard=GUARD)
     ctx.synchronize()
-    raw = out.download(np.uint8, lay["bytes"])
-    res = {k: raw[lay[k]: lay[k] + 4 * n].view(np.int32) for k in Context.INIT_OUT_Q + Context.INIT_OUT_T}
-    res.update(n_matches=int(raw[lay["n_matches"]: lay["n_matches"] + 4].view(np.int32)[0]), status=raw[lay["status"]: lay["status"] + n],
-               prev_out=raw[lay["prev_out"]: lay["prev_out"] + 8 * n].view(F).reshape(n, 2))
-    check_guards(raw, lay, [(k, 4 * n) for k in Context.INIT_OUT_Q + Context.INIT_OUT_T] + [("n_matches", 4), ("status", n), ("prev_out", 8 * n)])
+    res = guarded.problems(lay.parse(guarded.download(out, lay)), 1)[0]
     hdr = ws.download(np.int32, 4)
     x, y = kp["x"].copy(), kp["y"].copy()
     m = RI.literal(oracle_mod, q, pm, 6.0, RW.build(x, y, bounds), x, y, bounds, tg, txy=txy)

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import bow_rig as BR
+import guarded
 import mlpnp_rig as G
 import poseopt_rig as PR
 import ref_mlpnp as R
@@ -63,52 +64,47 @@ def test_bow_search_then_mlpnp_then_pose_optimisation_on_one_stream(gpu_lib, ora
         lay_b = Context.bow_search_layout(B, n1, n2, GUARD)
         ws_b = dev(np.zeros(Context.bow_search_workspace_bytes(n1, n2, B), np.uint8))
         d1 = [dev(s1[k]).ptr for k in ("blob", "flag", "desc")]; d2 = [dev(s2["blob"]).ptr, None, dev(s2["desc"]).ptr]
-        lay_m = Context.mlpnp_layout(B, n2, GUARD)
+        lay_m, lay_p = Context.mlpnp_layout(B, n2, GUARD), Context.pose_optimize_layout(B, n2, GUARD)
         ws_m = dev(np.zeros(gpu_lib.xfh_mlpnp_workspace_bytes(n2, n1, B, max_iters), np.uint8))
         ins = [dev(a) for a in (xy, points, tables[0], tables[1], draws, np.tile(xy, (B, 1, 1)))]      # the optimiser takes d_xy_un [B][nt][2]: the frame's keypoints per candidate
         ws_p = dev(np.zeros(Context.pose_optimize_workspace_bytes(n2, B), np.uint8))
 
         def chain(host_copies):
             """the three calls; host_copies: every intermediate goes through the host and comes back in a fresh buffer"""
-            out_b = dev(np.full(lay_b["bytes"], 0xA5, np.uint8)); out_m = dev(np.full(lay_m["bytes"], 0xA5, np.uint8))
-            po = [dev(np.full(nb, 0xA5, np.uint8)) for nb in (48 * B, n2 * B, 4 * n2 * B, 32 * B, 8 * B)]       # Tcw_out, outlier, chi2, header, final_chi2
+            out_b, out_m, out_p = (guarded.outputs(lay, keep=bufs) for lay in (lay_b, lay_m, lay_p))
             ctx.bow_search_device(B, n1, n2, 2, *d1, s1["stride"], *d2, s2["stride"], ws_b.ptr, out_b.ptr, nn_ratio=0.75, guard=GUARD)
             d_assigned, d_nm = out_b.ptr + lay_b["assigned2"], out_b.ptr + lay_b["n_matches"]
             if host_copies:
                 ctx.synchronize()
-                raw = out_b.download(np.uint8, lay_b["bytes"])
-                d_assigned = dev(raw[lay_b["assigned2"]:lay_b["assigned2"] + 4 * B * n2].copy()).ptr
-                d_nm = dev(raw[lay_b["n_matches"]:lay_b["n_matches"] + 4 * B].copy()).ptr
+                a = lay_b.parse(out_b.download(np.uint8, lay_b["bytes"]))
+                d_assigned, d_nm = dev(a["assigned2"]).ptr, dev(a["n_matches"]).ptr
             ctx.mlpnp_solve_device(B, n2, n1, ins[0].ptr, d_assigned, ins[1].ptr, None, cam, G.MAX_ERR, ins[2].ptr, ins[3].ptr, 5, None, max_iters, ins[4].ptr, 0,
                                    G.RAND_MAX, ws_m.ptr, out_m.ptr, min_matches=min_matches, d_n_matches=d_nm, guard=GUARD)
             d_T, d_a = out_m.ptr + lay_m["Tcw"], out_m.ptr + lay_m["assigned_out"]
             if host_copies:
                 ctx.synchronize()
-                raw = out_m.download(np.uint8, lay_m["bytes"])
-                d_T = dev(raw[lay_m["Tcw"]:lay_m["Tcw"] + 48 * B].copy()).ptr
-                d_a = dev(raw[lay_m["assigned_out"]:lay_m["assigned_out"] + 4 * B * n2].copy()).ptr
-            ctx.pose_optimize_device(B, n2, n1, d_T, cam, ins[5].ptr, None, d_a, ins[1].ptr, ws_p.ptr, *[b.ptr for b in po], inv_sigma2=1.0)
+                a = lay_m.parse(out_m.download(np.uint8, lay_m["bytes"]))
+                d_T, d_a = dev(a["Tcw"]).ptr, dev(a["assigned_out"]).ptr
+            ctx.pose_optimize_device(B, n2, n1, d_T, cam, ins[5].ptr, None, d_a, ins[1].ptr, ws_p.ptr, *[out_p.ptr + lay_p[k] for k in lay_p.names], inv_sigma2=1.0)
             ctx.synchronize()                                               # the only wait of the device chain
-            return (out_b.download(np.uint8, lay_b["bytes"]), out_m.download(np.uint8, lay_m["bytes"]),
-                    [b.download(np.uint8, nb) for b, nb in zip(po, (48 * B, n2 * B, 4 * n2 * B, 32 * B, 8 * B))])
+            return guarded.download(out_b, lay_b), guarded.download(out_m, lay_m), guarded.download(out_p, lay_p)
         raw_b, raw_m, raw_p = chain(False)
         sep_b, sep_m, sep_p = chain(True)
     finally:
         for b in bufs:
             b.free()
         ctx.close()
-    assert np.array_equal(raw_b, sep_b) and np.array_equal(raw_m, sep_m) and all(np.array_equal(a, b) for a, b in zip(raw_p, sep_p))
-    got_a2 = raw_b[lay_b["assigned2"]:lay_b["assigned2"] + 4 * B * n2].view(np.int32).reshape(B, n2)
-    got_nm = raw_b[lay_b["n_matches"]:lay_b["n_matches"] + 4 * B].view(np.int32)
+    assert np.array_equal(raw_b, sep_b) and np.array_equal(raw_m, sep_m) and np.array_equal(raw_p, sep_p)
+    got_b = lay_b.parse(raw_b)
     for b in range(B):
-        assert np.array_equal(got_a2[b], want_bow[b]["assigned2"]) and got_nm[b] == nm[b]
-    got = Context.mlpnp_parse(raw_m, lay_m, B, n2)
+        assert np.array_equal(got_b["assigned2"][b], want_bow[b]["assigned2"]) and got_b["n_matches"][b] == nm[b]
+    got = lay_m.parse(raw_m)
     for b in range(B):
-        G.assert_equals_rule(got, rules[b], b, prior_byte=0xA5)
-    Tout, outl, chi2, hdr, fin = raw_p[0].view(F).reshape(B, 12), raw_p[1].reshape(B, n2), raw_p[2].view(F).reshape(B, n2), raw_p[3].view(np.int32).reshape(B, 8), raw_p[4].view(np.float64)
+        G.assert_equals_rule(got, rules[b], b, prior_byte=guarded.FILL)
+    got_p = lay_p.parse(raw_p)
+    Tout, hdr = got_p["Tcw_out"], got_p["header"]
     m = RPO.rule(got["Tcw"][0], CAM5, xy, None, got["assigned_out"][0], points[0], 1.0)     # the optimiser's rule on the solver's outputs (within a step of its rule's)
-    res = dict(Tcw_out=Tout[0], outlier=outl[0], chi2=chi2[0], header=hdr[0], final_chi2=float(fin[0]))
-    assert RPO.outputs_agree(res, m, PR.MONO_TOL) == [] and hdr[0, 2] > 50
+    assert RPO.outputs_agree(guarded.problems(got_p, B)[0], m, PR.MONO_TOL) == [] and hdr[0, 2] > 50
     for b in (1, 2):                                                        # no pose, every match -1: refused (fewer than three edges)
         assert np.all(got["assigned_out"][b] == -1) and hdr[b, 0] == 0 and hdr[b, 2] == 0, (b, hdr[b])
         m = RPO.rule(got["Tcw"][b], CAM5, xy, None, got["assigned_out"][b], points[b], 1.0)

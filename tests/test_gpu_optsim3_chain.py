@@ -14,6 +14,7 @@ not change when the pose it is fed moves by SIM3OPT_TOL in any direction tried (
 import numpy as np
 import pytest
 
+import guarded
 import optsim3_rig as OG
 import ref_fuse as RU
 import ref_loop as RL
@@ -99,19 +100,15 @@ def test_solve_search_optimise_search_on_one_set_of_device_buffers(lr):
     ins = [lr.dev(np.ascontiguousarray(a)) for a in (sc["points"], sc["point1"], sc["matched"], sc["T1w"], sc["T2w"], sc["table"], sc["draws"][0])]
     n1s, M = len(sc["point1"]), len(sc["points"])
     lay_s = Context.sim3_solve_layout(1, n1s, GUARD)
-    out_s = lr.dev(np.full(lay_s["bytes"], 0xA5, np.uint8))
+    out_s = guarded.outputs(lay_s, keep=lr.bufs)
     ws_s = lr.dev(np.zeros(capi.lib().xfh_sim3_solve_workspace_bytes(n1s, M, 1), np.uint8))
     lay = Context.map_projection_search_layout(1, nf, nf, GUARD)
-    out_c, out_f = lr.dev(np.full(lay["bytes"], 0xA5, np.uint8)), lr.dev(np.full(lay["bytes"], 0xA5, np.uint8))
+    out_c, out_f = guarded.outputs(lay, keep=lr.bufs), guarded.outputs(lay, keep=lr.bufs)
     ws = lr.dev(np.zeros(Context.map_projection_search_workspace_bytes(nf, nf, 1), np.uint8))
     side1 = [lr.dev(p[k]) for k in ("T1w",)] + [None] + [lr.dev(p[k]) for k in ("point1", "points1")]
     i2, xy2 = lr.dev(p["index2"]), lr.dev(p["xy_un2"])
-    al = lambda x: (x + 255) & ~255
-    off, pos = {}, GUARD
-    for name, nbytes in (("assigned_out", 4 * nf), ("status", nf), ("chi2", 8 * nf), ("state", 64), ("Tcw", 48), ("Ow", 12), ("header", 64), ("final_chi2", 8)):
-        off[name] = pos
-        pos = al(pos + nbytes + GUARD)
-    out_o = lr.dev(np.full(pos, 0xA5, np.uint8))
+    off = Context.sim3_optimize_layout(1, nf, GUARD)                        # (its S12_out stays unwritten: the optimiser rewrites the solver's record in place)
+    out_o = guarded.outputs(off, keep=lr.bufs)
     ws_o = lr.dev(np.zeros(ctx.sim3_optimize_workspace_bytes(nf, 1), np.uint8))
     cam, S12_ptr = cam_struct(TUM1), out_s.ptr + lay_s["floats"] + 48
     search = lambda Tp, Op, th, accept, o: ctx.map_projection_search_device(
@@ -128,18 +125,12 @@ def test_solve_search_optimise_search_on_one_set_of_device_buffers(lr):
                                  th2=TH2, fix_scale=False, all_points=True)
         search(out_o.ptr + off["Tcw"], out_o.ptr + off["Ow"], 5.0, acc_f, out_f)
         ctx.synchronize()                                                   # the only wait of the chain
-        raw_c, raw_f, raw_o = out_c.download(np.uint8, lay["bytes"]), out_f.download(np.uint8, lay["bytes"]), out_o.download(np.uint8, pos)
-        got_s = Context.sim3_solve_parse(out_s.download(np.uint8, lay_s["bytes"]), lay_s, 1, n1s)
+        raw_c, raw_f = guarded.download(out_c, lay), guarded.download(out_f, lay)
+        got_o = guarded.problems(off.parse(guarded.download(out_o, off, skip=("S12_out",))), 1)[0]
+        got_s = lay_s.parse(guarded.download(out_s, lay_s))
     finally:
         lr.free()
-    cut = lambda raw, k, dt, n: raw[off[k]:off[k] + n * np.dtype(dt).itemsize].view(dt).copy()
-    got_o = dict(assigned_out=cut(raw_o, "assigned_out", np.int32, nf), status=cut(raw_o, "status", np.uint8, nf), chi2=cut(raw_o, "chi2", F, 2 * nf).reshape(nf, 2),
-                 state=cut(raw_o, "state", D, 8), S12_out=got_s["floats"][0, 12:25].copy(), Tcw=cut(raw_o, "Tcw", F, 12), Ow=cut(raw_o, "Ow", F, 3),
-                 header=cut(raw_o, "header", np.int32, 16), final_chi2=float(cut(raw_o, "final_chi2", D, 1)[0]))
-    used = np.zeros(pos, bool)
-    for k, n in (("assigned_out", 4 * nf), ("status", nf), ("chi2", 8 * nf), ("state", 64), ("Tcw", 48), ("Ow", 12), ("header", 64), ("final_chi2", 8)):
-        used[off[k]:off[k] + n] = True
-    assert np.all(raw_o[~used] == 0xA5), "a guard byte around the optimiser's outputs was written"
+    got_o["S12_out"] = got_s["floats"][0, 12:25].copy()
     # the solver's record: everything but the 13 floats the optimiser rewrote in place is the solver's
     keep = np.r_[0:12, 25:capi.SIM3_SOLVE_FLOATS]
     assert np.array_equal(got_s["floats"][0, keep].view(np.int32), np.asarray(rule_s["floats"], F)[keep].view(np.int32))

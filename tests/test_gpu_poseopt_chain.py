@@ -8,6 +8,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import guarded
 import ref_poseopt as RPO
 import ref_projection as RP
 from projection_rig import BIG, F, GUARD, OUT_INT, TUM1, Rig, cam_struct
@@ -29,31 +30,24 @@ def rig(gpu_lib, weights_dense):
 def chain(rig, radius):
     """-> (search 1, pose optimisation, search 2) as dicts of host arrays"""
     nf, ctx, L = rig.nf, rig.ctx, rig.L
-    lay = Context.search_projection_layout(1, nf, nf, GUARD)
-    al = lambda x: (x + 255) & ~255
-    outs = [capi.DeviceBuffer(lay["bytes"]).upload(np.full(lay["bytes"], 0xA5, np.uint8)) for _ in range(2)]
-    ws = capi.DeviceBuffer(Context.search_projection_workspace_bytes(nf, nf, 1))
-    o_ol, o_c2, o_h, o_fc = 256, 256 + al(nf), 256 + al(nf) + al(4 * nf), 256 + al(nf) + al(4 * nf) + 256
-    po = capi.DeviceBuffer(o_fc + 256)
-    pws = capi.DeviceBuffer(int(L.xfh_pose_optimize_workspace_bytes(nf, 1)))
+    lay, play = Context.search_projection_layout(1, nf, nf, GUARD), Context.pose_optimize_layout(1, nf, GUARD)
+    outs, po = [guarded.outputs(lay) for _ in range(2)], guarded.outputs(play)
+    ws = guarded.Guarded(Context.search_projection_workspace_bytes(nf, nf, 1), GUARD)
+    pws = guarded.Guarded(int(L.xfh_pose_optimize_workspace_bytes(nf, 1)), GUARD)
     qd, dp, dfl, dT = rig.dev(rig.recs[0][1]), rig.dev(np.ascontiguousarray(rig.xyz, F)), rig.dev(np.ascontiguousarray(rig.flags, np.uint8)), rig.dev(rig.poses[0])
     cam = cam_struct(TUM1)
     grids, targets = rig.fin[3].ptr + ctx.grid_bytes(nf), rig.rec.ptr + ctx.rec_bytes + ctx.desc_off
     kw = dict(radius=radius, cam=cam, bounds=rig.bounds, init_dist=BIG, th_high=1000, nn_ratio=0.0, guard=GUARD)
     ctx.search_projection_device(capi.PROJ_POINTS, 1, nf, dp.ptr, qd.ptr, dfl.ptr, grids, targets, ctx.rec_bytes, nf, ws.ptr, outs[0].ptr, d_Tcw=dT.ptr, **kw)
     rc = L.xfh_pose_optimize_device(ctx.h, 1, nf, nf, dT.ptr, C.byref(cam), rig.fin[0].ptr + 8 * nf, rig.fin[1].ptr + 4 * nf, outs[0].ptr + lay["assigned"], dp.ptr, 1.0,
-                                    pws.ptr, po.ptr, po.ptr + o_ol, po.ptr + o_c2, po.ptr + o_h, po.ptr + o_fc)
+                                    pws.ptr, *[po.ptr + play[k] for k in play.names])
     assert rc == 0
-    ctx.search_projection_device(capi.PROJ_POINTS, 1, nf, dp.ptr, qd.ptr, dfl.ptr, grids, targets, ctx.rec_bytes, nf, ws.ptr, outs[1].ptr, d_Tcw=po.ptr, d_skip=po.ptr + o_ol, **kw)
+    ctx.search_projection_device(capi.PROJ_POINTS, 1, nf, dp.ptr, qd.ptr, dfl.ptr, grids, targets, ctx.rec_bytes, nf, ws.ptr, outs[1].ptr, d_Tcw=po.ptr + play["Tcw_out"],
+                                 d_skip=po.ptr + play["outlier"], **kw)
     ctx.synchronize()                                                     # the only one
-    res = []
-    for o in outs:
-        raw = o.download(np.uint8, lay["bytes"])
-        r = {k: raw[lay[k]:lay[k] + 4 * nf].view(np.int32) for k in OUT_INT + ("assigned",)}
-        r["status"], r["n_matches"] = raw[lay["status"]:lay["status"] + nf], int(raw[lay["n_matches"]:lay["n_matches"] + 4].view(np.int32)[0])
-        res.append(r)
-    pose = dict(Tcw_out=po.download(F, 12), outlier=po.download(np.uint8, nf, o_ol), chi2=po.download(F, nf, o_c2), header=po.download(np.int32, 8, o_h),
-                final_chi2=float(po.download(np.float64, 1, o_fc)[0]))
+    res = [guarded.problems(lay.parse(guarded.download(o, lay)), 1)[0] for o in outs]
+    pose = guarded.problems(play.parse(guarded.download(po, play)), 1)[0]
+    ws.download(); pws.download()
     for b in outs + [ws, po, pws] + rig.bufs:
         b.free()
     rig.bufs = []

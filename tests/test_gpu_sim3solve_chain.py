@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import bow_rig as BR
+import guarded
 import ref_loop as RL
 import ref_sim3solve as R
 import sim3solve_rig as G
@@ -61,28 +62,30 @@ def test_bow_search_then_merge_then_solve_on_one_set_of_device_buffers(gpu_lib, 
     try:
         s1, s2 = BR.BowRig.side([s.s1], "active"), BR.BowRig.side(s.s2, "has")
         lay_b = Context.bow_search_layout(J, n1, n2, GUARD)
-        out_b = dev(np.full(lay_b["bytes"], 0xA5, np.uint8))
+        out_b = guarded.outputs(lay_b, keep=bufs)
         ws_b = dev(np.zeros(Context.bow_search_workspace_bytes(n1, n2, J), np.uint8))
         d1 = [dev(s1[k]).ptr for k in ("blob", "flag", "desc")]; d2 = [dev(s2[k]).ptr for k in ("blob", "flag", "desc")]
         lay_s = Context.sim3_solve_layout(1, n1, GUARD)
-        out_s = dev(np.full(lay_s["bytes"], 0xA5, np.uint8))
+        out_s = guarded.outputs(lay_s, keep=bufs)
         ws_s = dev(np.zeros(gpu_lib.xfh_sim3_solve_workspace_bytes(n1, M, 1), np.uint8))
-        mid = dev(np.full(2 * n1 + 64, -7, np.int32))                                        # d_matched [n1], d_matched_kf [n1], the count
+        lay_mid = Context.sim3_merge_layout(n1, GUARD)                                       # d_matched [n1], d_matched_kf [n1], the count
+        mid = guarded.outputs(lay_mid, keep=bufs)
+        d_matched, d_kf, d_num = (mid.ptr + lay_mid[k] for k in lay_mid.names)
         ins = [dev(a) for a in (points, point1, point2, T1w, T2w, table, draws)]
         ctx.bow_search_device(J, n1, n2, 1, *d1, s1["stride"], *d2, s2["stride"], ws_b.ptr, out_b.ptr, strict_low=True, guard=GUARD)
-        ctx.sim3_merge_matches_device(J, n1, n2, M, out_b.ptr + lay_b["match12"], ins[2].ptr, ws_s.ptr, mid.ptr, mid.ptr + 4 * n1, mid.ptr + 8 * n1)
-        ctx.sim3_solve_device(1, n1, M, ins[0].ptr, ins[1].ptr, mid.ptr, ins[3].ptr, 0, ins[4].ptr, G.camera(G.CAM), G.camera(G.CAM2), ins[5].ptr, G.MAX_ITS, ins[6].ptr, 0,
-                              G.RAND_MAX, ws_s.ptr, out_s.ptr, min_inliers=15, min_matches=20, d_num_matches=mid.ptr + 8 * n1, guard=GUARD)
+        ctx.sim3_merge_matches_device(J, n1, n2, M, out_b.ptr + lay_b["match12"], ins[2].ptr, ws_s.ptr, d_matched, d_kf, d_num)
+        ctx.sim3_solve_device(1, n1, M, ins[0].ptr, ins[1].ptr, d_matched, ins[3].ptr, 0, ins[4].ptr, G.camera(G.CAM), G.camera(G.CAM2), ins[5].ptr, G.MAX_ITS, ins[6].ptr, 0,
+                              G.RAND_MAX, ws_s.ptr, out_s.ptr, min_inliers=15, min_matches=20, d_num_matches=d_num, guard=GUARD)
         ctx.synchronize()                                                   # the only wait of the chain
-        got_m12 = out_b.download(np.uint8, lay_b["bytes"])[lay_b["match12"]:lay_b["match12"] + 4 * J * n1].view(np.int32).reshape(J, n1)
-        got_mid = mid.download(np.int32, 2 * n1 + 1)
-        got = Context.sim3_solve_parse(out_s.download(np.uint8, lay_s["bytes"]), lay_s, 1, n1)
+        got_m12 = lay_b.parse(guarded.download(out_b, lay_b))["match12"]
+        got_mid = lay_mid.parse(guarded.download(mid, lay_mid))
+        got = lay_s.parse(guarded.download(out_s, lay_s))
     finally:
         for b in bufs:
             b.free()
         ctx.close()
     assert np.array_equal(got_m12, match12)
-    assert np.array_equal(got_mid[:n1], matched) and np.array_equal(got_mid[n1:2 * n1], kf) and got_mid[2 * n1] == num
+    assert np.array_equal(got_mid["matched"], matched) and np.array_equal(got_mid["matched_kf"], kf) and got_mid["num_matches"][0] == num
     G.assert_equals_rule(got, rule, 0)
     print("chain: BoW matches per covisible", [int((m >= 0).sum()) for m in match12], "numBoWMatches", num, dict(zip(R.HEADER, got["header"][0].tolist())))
 
@@ -106,10 +109,10 @@ def test_solve_then_map_projection_search_fed_the_device_pose(lr):
     d = [lr.dev(np.ascontiguousarray(blk[k], t)) for k, t in (("xyz", F), ("normals", F), ("dist", F), ("qdesc", F), ("flags", np.uint8), ("taken", np.uint8))]
     ins = [lr.dev(np.ascontiguousarray(a)) for a in (sc["points"], sc["point1"], sc["matched"], sc["T1w"], sc["T2w"], sc["table"], sc["draws"][0])]
     lay_s = Context.sim3_solve_layout(1, n1, GUARD)
-    out_s = lr.dev(np.full(lay_s["bytes"], 0xA5, np.uint8))
+    out_s = guarded.outputs(lay_s, keep=lr.bufs)
     ws_s = lr.dev(np.zeros(capi.lib().xfh_sim3_solve_workspace_bytes(n1, M, 1), np.uint8))
     lay = Context.map_projection_search_layout(1, nf, nf, GUARD)
-    out = lr.dev(np.full(lay["bytes"], 0xA5, np.uint8))
+    out = guarded.outputs(lay, keep=lr.bufs)
     ws = lr.dev(np.zeros(Context.map_projection_search_workspace_bytes(nf, nf, 1), np.uint8))
     try:
         ctx.sim3_solve_device(1, n1, M, ins[0].ptr, ins[1].ptr, ins[2].ptr, ins[3].ptr, 0, ins[4].ptr, G.camera(sc["cam1"]), G.camera(sc["cam2"]), ins[5].ptr,
@@ -118,8 +121,8 @@ def test_solve_then_map_projection_search_fed_the_device_pose(lr):
                                          lr.bounds, th, lr.sf, lr.rmax, r.fin[3].ptr, r.rec.ptr + ctx.desc_off, ctx.rec_bytes, 0, nf, ws.ptr, out.ptr, d_taken=d[5].ptr,
                                          accept_max=accept, guard=GUARD)
         ctx.synchronize()                                                   # nothing was read back between the two calls
-        raw = out.download(np.uint8, lay["bytes"])
-        got = Context.sim3_solve_parse(out_s.download(np.uint8, lay_s["bytes"]), lay_s, 1, n1)
+        raw = guarded.download(out, lay)
+        got = lay_s.parse(guarded.download(out_s, lay_s))
     finally:
         lr.free()
     G.assert_equals_rule(got, rule, 0)

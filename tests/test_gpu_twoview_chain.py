@@ -9,6 +9,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import guarded
 import ref_twoview as R
 import twoview_rig as G
 from init_rig import InitRig
@@ -33,13 +34,13 @@ def test_init_search_then_two_view_on_the_device(gpu_lib, weights_dense, oracle_
         dq, dpm = dev(np.ascontiguousarray(q, F)), dev(np.ascontiguousarray(pm, F))
         draws = G.draws_of(77, ITERS)
         dd = dev(draws)
-        out, ws = dev(np.full(lay["bytes"], 0xA5, np.uint8)), dev(np.zeros(Context.init_search_workspace_bytes(nf, nf, 1), np.uint8))
-        tout, tws = dev(np.full(tlay["bytes"], 0xA5, np.uint8)), dev(np.zeros(L.xfh_two_view_workspace_bytes(nf, nf, ITERS, 1), np.uint8))
+        out, ws = guarded.outputs(lay, keep=bufs), dev(np.zeros(Context.init_search_workspace_bytes(nf, nf, 1), np.uint8))
+        tout, tws = guarded.outputs(tlay, keep=bufs), dev(np.zeros(L.xfh_two_view_workspace_bytes(nf, nf, ITERS, 1), np.uint8))
         ctx.init_search_device(1, nf, dq.ptr, dpm.ptr, rig.dgrid, rig.dtg.ptr, 0, nf, ws.ptr, out.ptr, window=WINDOW, guard=256)
         ctx.two_view_device(1, nf, nf, cam, rig.fin[0].ptr, rig.dxy, out.ptr + lay["matches12"], dd.ptr, 0, ITERS, G.RAND_MAX, tws.ptr, tout.ptr, guard=256)
         ctx.synchronize()                                                   # the only one
-        m12 = out.download(np.int32, nf, lay["matches12"])
-        got = Context.two_view_parse(tout.download(np.uint8, tlay["bytes"]), tlay, 1, nf)
+        m12 = lay.parse(guarded.download(out, lay, skip=("prev_out",)))["matches12"][0]         # (no d_target_xy: prev_out is not written)
+        got = tlay.parse(guarded.download(tout, tlay))
         want = R.rule(rig.xy[0], rig.xy[1], m12, [F(TUM1[k]) for k in ("fx", "fy", "cx", "cy")], draws, G.RAND_MAX)
         print("chain: matches", int((m12 >= 0).sum()), "->", R.STATUS_NAMES[want["header"][1]], dict(zip(R.HEADER, want["header"].tolist())))
         assert (m12 >= 0).sum() >= 100 and want["header"][0] == (m12 >= 0).sum()
@@ -62,22 +63,22 @@ def test_two_view_then_pose_optimize_on_the_device(gpu_lib):
         dev = lambda a: bufs.append(capi.DeviceBuffer(max(np.ascontiguousarray(a).nbytes, 16)).upload(a)) or bufs[-1]
         tlay = Context.two_view_layout(1, n1, 256)
         dx1, dx2, dm, dd, dm21 = dev(s["xy1"]), dev(s["xy2"]), dev(s["m12"]), dev(s["draws"]), dev(m21)
-        tout, tws = dev(np.full(tlay["bytes"], 0xA5, np.uint8)), dev(np.zeros(L.xfh_two_view_workspace_bytes(n1, n2, iters, 1), np.uint8))
-        al = lambda x: (x + 255) & ~255
-        o_ol, o_c2, o_h, o_fc = 256, 256 + al(n2), 256 + al(n2) + al(4 * n2), 256 + al(n2) + al(4 * n2) + 256
-        po, pws = dev(np.zeros(o_fc + 256, np.uint8)), dev(np.zeros(int(L.xfh_pose_optimize_workspace_bytes(n2, 1)), np.uint8))
+        tout, tws = guarded.outputs(tlay, keep=bufs), dev(np.zeros(L.xfh_two_view_workspace_bytes(n1, n2, iters, 1), np.uint8))
+        play = Context.pose_optimize_layout(1, n2, 256)
+        po, pws = guarded.outputs(play, keep=bufs), dev(np.zeros(int(L.xfh_pose_optimize_workspace_bytes(n2, 1)), np.uint8))
         cam = G.camera()
         ctx.two_view_device(1, n1, n2, cam, dx1.ptr, dx2.ptr, dm.ptr, dd.ptr, 0, iters, G.RAND_MAX, tws.ptr, tout.ptr, guard=256)
         rc = L.xfh_pose_optimize_device(ctx.h, 1, n2, n1, tout.ptr + tlay["floats"] + 4 * R.F_T21, C.byref(cam), dx2.ptr, None, dm21.ptr, tout.ptr + tlay["p3d"], 1.0,
-                                        pws.ptr, po.ptr, po.ptr + o_ol, po.ptr + o_c2, po.ptr + o_h, po.ptr + o_fc)
+                                        pws.ptr, *[po.ptr + play[k] for k in play.names])
         assert rc == 0
         ctx.synchronize()                                                   # the only one
-        got = Context.two_view_parse(tout.download(np.uint8, tlay["bytes"]), tlay, 1, n1)
+        got = tlay.parse(guarded.download(tout, tlay))
+        pose = guarded.problems(play.parse(guarded.download(po, play)), 1)[0]
         want = G.rule_of(s)
         G.assert_equals_rule(got, want, 0)
         assert got["header"][0, 1] == R.OK_F
-        T0, T1 = got["floats"][0, R.F_T21:R.F_T21 + 12].reshape(3, 4), po.download(F, 12).reshape(3, 4)
-        hdr, outlier = po.download(np.int32, 8, o_h), po.download(np.uint8, n2, o_ol)
+        T0, T1 = got["floats"][0, R.F_T21:R.F_T21 + 12].reshape(3, 4), pose["Tcw_out"].reshape(3, 4)
+        hdr, outlier = pose["header"], pose["outlier"]
         tri2 = s["m12"][np.nonzero(got["tri"][0])[0]]                        # the current frame's keypoints whose points were triangulated
         print("pose optimisation on T21 and p3d:", dict(zip(Context.POSE_HEADER, hdr.tolist())), "triangulated", len(tri2), "of them outliers", int(outlier[tri2].sum()))
         # every triangulated point reprojects within 2 px into both frames under T21 (CheckRT), so the optimisation starts at a pose that fits them:

@@ -5,6 +5,7 @@ stereo keypoint and the camera centres.  small_scene() is a seeded keyframe with
 comparisons and the n1 = 65 case; planted() puts pairs with written-out causes into it.  No test lives here."""
 import numpy as np
 
+import guarded
 import ref_triangulate as RG
 import ref_triangulation as RT
 import triangulation_rig as TR
@@ -247,17 +248,13 @@ class TriangRig:
         B, n1, n2 = len(k2s), len(side1[0]["xy"]), len(k2s[0]["xy"])
         shared = len(side1) == 1
         lay = Context.triangulate_layout(B, n1, GUARD)
-        out = capi.DeviceBuffer(lay["bytes"]).upload(np.full(lay["bytes"], 0xA5, np.uint8))
+        out = guarded.outputs(lay)
         dm = d_match12 if d_match12 is not None else self.dev(np.ascontiguousarray(match12, np.int32))
         self.ctx.triangulate_device(B, n1, n2, shared, cam, self.side(side1), self.side(k2s), dm, out.ptr, sigma2=P["sigma2"], ratio_factor=P["ratio_factor"],
                                     scale_last=P["scale_last"], far_th=P["far_th"], inertial=P["inertial"], claim=claim, guard=GUARD)
         self.ctx.synchronize()
-        raw = out.download(np.uint8, lay["bytes"])
+        raw = guarded.download(out, lay, skip=() if claim else Context.TRIANG_CLAIM_OUT)
         out.free(); self.free()
-        used = np.zeros(lay["bytes"], bool)
-        for k in ("status", "kind", "xyz", "header") + (Context.TRIANG_CLAIM_OUT if claim else ()):
-            used[lay[k]:lay[k] + lay[k + "_bytes"]] = True
-        assert np.all(raw[~used] == 0xA5), "a byte outside the outputs was written"
         return Context.triangulate_parse(raw, lay, B, n1, claim), raw
 
 

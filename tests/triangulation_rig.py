@@ -10,6 +10,7 @@ import struct
 
 import numpy as np
 
+import guarded
 import ref_frame as RF
 import ref_triangulation as RT
 from xfeatslam_amd import capi
@@ -201,24 +202,14 @@ class TriRig:
             bufs.append(b)
             return b.ptr
 
-        out = capi.DeviceBuffer(lay["bytes"]).upload(np.full(lay["bytes"], 0xA5, np.uint8))
+        out = guarded.outputs(lay)
         d1 = [dev(s1[k]) for k in ("blob", "xy", "ur", "has", "desc")]; d2 = [dev(s2[k]) for k in ("blob", "xy", "ur", "has", "desc")]
         dF, de = dev(np.stack(F12).astype(F)), dev(np.stack(ep).astype(F))
         ctx.triangulation_search_device(B, n1, s2["n"], shared, *d1, s1["stride"], *d2, s2["stride"], dF, de, out.ptr, only_stereo=only_stereo, coarse=coarse,
                                         th_low=th_low, epipole_r2=r2, unc=unc, guard=GUARD)
         ctx.synchronize()
-        raw = out.download(np.uint8, lay["bytes"])
-        res = []
-        for p in range(B):
-            o = {k: raw[lay[k] + 4 * p * n1: lay[k] + 4 * (p + 1) * n1].view(np.int32) for k in Context.TRI_OUT_INT}
-            o["n_matches"] = int(raw[lay["n_matches"] + 4 * p: lay["n_matches"] + 4 * p + 4].view(np.int32)[0])
-            o["status"] = raw[lay["status"] + p * n1: lay["status"] + (p + 1) * n1]
-            res.append(o)
-        used = np.zeros(lay["bytes"], bool)
-        for k, n in [(k, 4 * B * n1) for k in Context.TRI_OUT_INT] + [("n_matches", 4 * B), ("status", B * n1)]:
-            used[lay[k]:lay[k] + n] = True
-            assert not used[lay[k] - GUARD:lay[k]].any() and not used[lay[k] + n:lay[k] + n + GUARD].any() and lay[k] + n + GUARD <= lay["bytes"]
-        assert np.all(raw[~used] == 0xA5), "a guard byte around the outputs was written"
+        raw = guarded.download(out, lay)
+        res = guarded.problems(lay.parse(raw), B)
         out.free()
         for b in bufs:
             b.free()

@@ -177,6 +177,7 @@ class TwoViewRig:
 
     def run(self, xy1, xy2, m12, draws, sigma=1.0, min_parallax_cos=None, min_tri=50, cam=None):
         """arrays with a leading B (draws [iters][8] = shared, stride 0) -> (parsed outputs, raw bytes)"""
+        import guarded
         from xfeatslam_amd import capi
         from xfeatslam_amd.extractor import Context
         xy1, xy2, m12 = np.ascontiguousarray(xy1, F), np.ascontiguousarray(xy2, F), np.ascontiguousarray(m12, np.int32)
@@ -187,20 +188,14 @@ class TwoViewRig:
         bufs = [capi.DeviceBuffer(max(a.nbytes, 16)).upload(a) for a in (xy1, xy2, m12, draws)]
         wsb = self.L.xfh_two_view_workspace_bytes(n1, n2, iters, B)
         assert wsb > 0
-        ws = capi.DeviceBuffer(wsb + 2 * GUARD).upload(np.full(wsb + 2 * GUARD, 0xA5, np.uint8))
-        out = capi.DeviceBuffer(lay["bytes"]).upload(np.full(lay["bytes"], 0xA5, np.uint8))
+        ws, out = guarded.Guarded(wsb, GUARD), guarded.outputs(lay)
         try:
-            self.ctx.two_view_device(B, n1, n2, camera(cam), bufs[0].ptr, bufs[1].ptr, bufs[2].ptr, bufs[3].ptr, stride, iters, RAND_MAX, ws.ptr + GUARD, out.ptr,
+            self.ctx.two_view_device(B, n1, n2, camera(cam), bufs[0].ptr, bufs[1].ptr, bufs[2].ptr, bufs[3].ptr, stride, iters, RAND_MAX, ws.ptr, out.ptr,
                                      sigma=sigma, min_parallax_cos=min_parallax_cos, min_triangulated=min_tri, guard=GUARD)
             self.ctx.synchronize()
-            raw = out.download(np.uint8, lay["bytes"])
-            wraw = ws.download(np.uint8, wsb + 2 * GUARD)
+            raw = guarded.download(out, lay)
+            ws.download()
         finally:
             for b in bufs + [ws, out]:
                 b.free()
-        used = np.zeros(lay["bytes"], bool)
-        for k in Context.TWO_VIEW_OUT:
-            used[lay[k]:lay[k] + lay[k + "_bytes"]] = True
-        assert np.all(raw[~used] == 0xA5), "a byte outside the outputs was written"
-        assert np.all(wraw[:GUARD] == 0xA5) and np.all(wraw[GUARD + wsb:] == 0xA5), "a byte outside the workspace was written"
-        return Context.two_view_parse(raw, lay, B, n1), raw
+        return lay.parse(raw), raw

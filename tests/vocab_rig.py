@@ -17,6 +17,7 @@ import functools
 
 import numpy as np
 
+import guarded
 import ref_vocab as RV
 from xfeatslam_amd import capi
 from xfeatslam_amd.extractor import Context
@@ -280,27 +281,12 @@ class VocabRig:
             host[b * stride + off: b * stride + off + n * 256] = np.ascontiguousarray(f, F).view(np.uint8).ravel()
         rows = capi.DeviceBuffer(host.nbytes).upload(host)
         lay = Context.bow_transform_layout(B, n, GUARD)
-        wsb = Context.bow_transform_workspace_bytes(n, B)
-        ws = capi.DeviceBuffer(wsb + 2 * GUARD).upload(np.full(wsb + 2 * GUARD, 0xA5, np.uint8))
-        out = capi.DeviceBuffer(lay["bytes"]).upload(np.full(lay["bytes"], 0xA5, np.uint8))
-        ctx.bow_transform_device(B, n, dv.ptr, nb, rows.ptr + off, stride, ws.ptr + GUARD, out.ptr, levelsup=levelsup, guard=GUARD)
+        ws = guarded.Guarded(Context.bow_transform_workspace_bytes(n, B), GUARD)
+        out = guarded.outputs(lay)
+        ctx.bow_transform_device(B, n, dv.ptr, nb, rows.ptr + off, stride, ws.ptr, out.ptr, levelsup=levelsup, guard=GUARD)
         ctx.synchronize()
-        raw = out.download(np.uint8, lay["bytes"])
-        wraw = ws.download(np.uint8, wsb + 2 * GUARD)
-        assert np.all(wraw[:GUARD] == 0xA5) and np.all(wraw[GUARD + wsb:] == 0xA5), "a guard byte around the workspace was written"
-        nbn = Context.nodes_bytes(n)
-        sizes = dict(word=4 * B * n, node_of=4 * B * n, weight=8 * B * n, nodes=B * nbn, bow_ids=4 * B * n, bow_vals=8 * B * n, n_words=4 * B)
-        used = np.zeros(lay["bytes"], bool)
-        for k, sz in sizes.items():
-            used[lay[k]:lay[k] + sz] = True
-            assert not used[lay[k] - GUARD:lay[k]].any() and not used[lay[k] + sz:lay[k] + sz + GUARD].any() and lay[k] + sz + GUARD <= lay["bytes"]
-        assert np.all(raw[~used] == 0xA5), "a guard byte around the outputs was written"
-        res = []
-        for b in range(B):
-            o = {k: raw[lay[k] + w * b * n: lay[k] + w * (b + 1) * n].view(dt) for k, dt, w in (("word", np.uint32, 4), ("node_of", np.uint32, 4),
-                 ("weight", np.float64, 8), ("bow_ids", np.uint32, 4), ("bow_vals", np.float64, 8))}
-            o["nodes"] = raw[lay["nodes"] + b * nbn: lay["nodes"] + (b + 1) * nbn]
-            o["n_words"] = int(raw[lay["n_words"] + 4 * b: lay["n_words"] + 4 * b + 4].view(np.int32)[0])
-            res.append(o)
+        raw = guarded.download(out, lay)
+        ws.download()
+        res = guarded.problems(lay.parse(raw), B)
         rows.free(); ws.free()
         return res, raw, out, lay

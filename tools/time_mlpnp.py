@@ -151,7 +151,7 @@ def main():
     ctx.synchronize()
     kt = kernel_times(ctx, solve, KERNELS, a)
     med, lo, hi = windows(ctx, solve, a)
-    got = Context.mlpnp_parse(out.download(np.uint8, lay["bytes"]), lay, B, N_KP)
+    got = lay.parse(out.download(np.uint8, lay["bytes"]))
     t0 = time.perf_counter()
     host = G.host_of(dict(s, draws=s["draws"][:1]))
     host_us = (time.perf_counter() - t0) * 1e6
@@ -217,7 +217,7 @@ def main():
     ctx.synchronize()
     kt = kernel_times(ctx, chain, CHAIN, a)
     med, lo, hi = windows(ctx, chain, a)
-    gm = Context.mlpnp_parse(out_m.download(np.uint8, lay["bytes"]), lay, B, N_KP)
+    gm = lay.parse(out_m.download(np.uint8, lay["bytes"]))
     ret = po[3].download(np.uint8, 32 * B).view(np.int32).reshape(B, 8)[:, 2]
     lines += [f"The chain `xfh_bow_search_device` (shared = 2) -> `xfh_mlpnp_solve_device` -> `xfh_pose_optimize_device` on one stream, nothing read back in between: "
               f"BoW matches {[int((r >= 0).sum()) for r in a2]}, MLPnP statuses {[R.STATUS[v] for v in gm['header'][:, 1]]}, PoseOptimization returns {ret.tolist()}.", "",

@@ -52,10 +52,9 @@ def gpu_part(a, lines):
         (n1, M1, nq, n2), arrays, s12, tmw = G._inputs(ps, False)
         dev = [capi.DeviceBuffer(x.nbytes).upload(x) for x in arrays + [s12, tmw]]
         ws = capi.DeviceBuffer(int(L.xfh_sim3_optimize_workspace_bytes(n1, B)))
-        out = capi.DeviceBuffer(B * (n1 * 16 + 4096))
-        o = out.ptr
-        outs = (o, o + B * n1 * 4, o + B * n1 * 8, o + B * n1 * 16, o + B * n1 * 16 + B * 256, o + B * n1 * 16 + B * 512, o + B * n1 * 16 + B * 768,
-                o + B * n1 * 16 + B * 1024, o + B * n1 * 16 + B * 1280)
+        lay = ctx.sim3_optimize_layout(B, n1)
+        out = capi.DeviceBuffer(lay["bytes"])
+        outs = [out.ptr + lay[k] for k in lay.names]
         cam = G.cam_struct()
 
         def call():

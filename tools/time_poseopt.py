@@ -54,17 +54,13 @@ def main():
             nt, nq = s["nt"], s["nq"]
             for B in (1, 8):
                 ins = [up(np.tile(np.ascontiguousarray(s[k]).reshape(1, -1), (B, 1))) for k in ("Tcw", "xy_un", "uright", "assigned", "points")]
-                al = lambda x: (x + 255) & ~255
-                o_T, o_ol = 0, al(48 * B)
-                o_c2 = o_ol + al(B * nt)
-                o_h = o_c2 + al(4 * B * nt)
-                o_fc = o_h + al(32 * B)
-                out = capi.DeviceBuffer(o_fc + al(8 * B))
+                lay = ctx.pose_optimize_layout(B, nt)
+                out = capi.DeviceBuffer(lay["bytes"])
                 ws = capi.DeviceBuffer(ctx.pose_optimize_workspace_bytes(nt, B))
 
                 def call():
-                    ctx.pose_optimize_device(B, nt, nq, ins[0].ptr, rig.cam, ins[1].ptr, ins[2].ptr, ins[3].ptr, ins[4].ptr, ws.ptr, out.ptr + o_T, out.ptr + o_ol,
-                                             out.ptr + o_c2, out.ptr + o_h, out.ptr + o_fc, R.INV_SIGMA2)
+                    ctx.pose_optimize_device(B, nt, nq, ins[0].ptr, rig.cam, ins[1].ptr, ins[2].ptr, ins[3].ptr, ins[4].ptr, ws.ptr, *[out.ptr + lay[k] for k in lay.names],
+                                             R.INV_SIGMA2)
 
                 for _ in range(a.warmup):
                     call()
@@ -81,7 +77,7 @@ def main():
                     call()
                 ctx.synchronize()
                 wall = (time.perf_counter() - t0) * 1e6 / a.iters
-                h = out.download(np.int32, 8, o_h)
+                h = out.download(np.int32, 8, lay["header"])
                 lines.append(f"| {n} | {nt} | {int(outl * 100)} % | {B} | {kus:.1f} | {wall:.1f} | {kus / B:.1f} | {h[3]} | {h[4]} | {h[5]} | {h[6]} | {h[1]} |")
                 print(lines[-1], flush=True)
                 for x in ins + [out, ws]:

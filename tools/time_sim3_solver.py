@@ -77,7 +77,7 @@ def gpu_part(a, lines):
             call()
         ctx.synchronize()
         wall = (time.perf_counter() - t0) * 1e6 / a.iters
-        r = Context.sim3_solve_parse(out.download(np.uint8, lay["bytes"]), lay, B, n1)
+        r = lay.parse(out.download(np.uint8, lay["bytes"]))
         lines.append(f"| {B} | {int(r['header'][0, 0])} | {R.STATUS_NAMES[r['header'][0, 1]]} after {int(r['header'][0, 7])} iterations | " + " | ".join(f"{k:.1f}" for k in kus)
                      + f" | {wall:.1f} |")
         print(lines[-1], flush=True)

@@ -81,7 +81,7 @@ def main():
             call()
         ctx.synchronize()
         wall = (time.perf_counter() - t0) * 1e6 / a.iters
-        r = Context.two_view_parse(out.download(np.uint8, lay["bytes"]), lay, B, n)
+        r = lay.parse(out.download(np.uint8, lay["bytes"]))
         lines.append(f"| {B} | {n} | {int(r['header'][0, 0])} | {R.STATUS_NAMES[r['header'][0, 1]]} | " + " | ".join(f"{k:.1f}" for k in kus) + f" | {wall:.1f} |")
         print(lines[-1], flush=True)
         for b in bufs + [out, ws]:

@@ -14,6 +14,31 @@ import numpy as np
 
 from . import capi
 from .capi import KP_DTYPE, Config, check, lib
+from .layout import Layout
+
+I32, U32, F32, F64, U8 = np.int32, np.uint32, np.float32, np.float64, np.uint8
+
+
+def _ptr(a):
+    """the address of a host array, None for an absent one"""
+    return None if a is None else a.ctypes.data
+
+
+def _opt(a, dt):
+    """an optional input as a contiguous array of dt, None when absent"""
+    return None if a is None else np.ascontiguousarray(a, dt)
+
+
+def _names(table, per=None):
+    """the names of a table's arrays in its order (per: only the int arrays shaped ("B", per), which the C calls take side by side)"""
+    return tuple(name for name, dt, shape in table if per is None or (dt is I32 and shape == ("B", per)))
+
+
+def _with_prior(out, prior):
+    """the zeroed outputs of a host form with the arrays of prior (what the caller's buffers held before the call) put over them"""
+    for k, v in (prior or {}).items():
+        out[k] = np.ascontiguousarray(v, out[k].dtype).reshape(out[k].shape).copy()
+    return out
 
 
 class Context:
@@ -233,13 +258,13 @@ class Context:
         k = np.ascontiguousarray(kps, KP_DTYPE); tg = np.ascontiguousarray(targets, np.float32)
         nq, nt = len(q), len(k)
         assert len(w) == nq and len(tg) == nt
-        sk = None if skip is None else np.ascontiguousarray(skip, np.uint8)
-        ur = None if uright is None else np.ascontiguousarray(uright, np.float32)
-        uq = None if ur_query is None else np.ascontiguousarray(ur_query, np.float32)
+        sk = _opt(skip, np.uint8)
+        ur = _opt(uright, np.float32)
+        uq = _opt(ur_query, np.float32)
         out = [np.zeros(max(nq, 1), np.int32) for _ in range(5)]
         check(lib().xfh_search_window(self.h, q.ctypes.data, w.ctypes.data, nq, k.ctypes.data, C.byref(capi.GridBounds(*bounds)), tg.ctypes.data, nt,
-                                      None if sk is None else sk.ctypes.data, None if ur is None else ur.ctypes.data,
-                                      None if uq is None else uq.ctypes.data, int(init_dist), *[o.ctypes.data for o in out]), self.h)
+                                      _ptr(sk), _ptr(ur),
+                                      _ptr(uq), int(init_dist), *[o.ctypes.data for o in out]), self.h)
         return tuple(o[:nq] for o in out)
 
     # -- finishing an RGB-D frame (xfh_undistort_points / xfh_camera_bounds / xfh_frame_finish*) ---------
@@ -285,7 +310,7 @@ class Context:
             img = np.ascontiguousarray(depth)
             dt = {np.dtype(np.float32): capi.DEPTH_F32, np.dtype(np.uint16): capi.DEPTH_U16}[img.dtype]
             pitch = img.strides[0]
-        check(lib().xfh_frame_finish(self.h, k.ctypes.data, n, C.byref(cam), None if img is None else img.ctypes.data, dt, pitch, float(depth_scale),
+        check(lib().xfh_frame_finish(self.h, k.ctypes.data, n, C.byref(cam), _ptr(img), dt, pitch, float(depth_scale),
                                      xy.ctypes.data, ur.ctypes.data, dz.ctypes.data), self.h)
         return xy[:n], ur[:n], dz[:n]
 
@@ -316,17 +341,14 @@ class Context:
                                                  d_workspace, d_out + o["status"], d_out + o["match_idx"], d_out + o["best_dist"], d_out + o["second_dist"],
                                                  d_out + o["n_candidates"], d_proj_out, d_out + o["assigned"], d_out + o["n_matches"]), self.h)
 
+    SEARCH_PROJECTION_TABLE = (("match_idx", I32, ("B", "nq")), ("best_dist", I32, ("B", "nq")), ("second_dist", I32, ("B", "nq")), ("n_candidates", I32, ("B", "nq")),
+                               ("assigned", I32, ("B", "nt")), ("n_matches", I32, ("B",)), ("status", U8, ("B", "nq")))
+
     @staticmethod
     def search_projection_layout(B: int, nq: int, nt: int, guard: int = 0):
         """byte offsets of the outputs of search_projection_device inside one buffer (and its size under "bytes"); guard > 0 leaves
         at least that many bytes the call never writes before the first array and after every array (for tests that fill them)"""
-        al = lambda x: (x + 255) & ~255
-        o, off = {}, al(guard)
-        for name, nbytes in (("match_idx", 4 * B * nq), ("best_dist", 4 * B * nq), ("second_dist", 4 * B * nq), ("n_candidates", 4 * B * nq),
-                             ("assigned", 4 * B * nt), ("n_matches", 4 * B), ("status", B * nq)):
-            o[name] = off; off += al(nbytes) + al(guard)
-        o["bytes"] = off
-        return o
+        return Layout.of(Context.SEARCH_PROJECTION_TABLE, guard, B=B, nq=nq, nt=nt)
 
     def search_projection(self, mode: int, points, query_desc, query_flags, kps, bounds, targets, radius: float = 0.0, Tcw=None, cam=None,
                           ur_query=None, skip=None, uright=None, init_dist: int = 256, th_high: int = 1000, nn_ratio: float = 0.0):
@@ -336,15 +358,14 @@ class Context:
         nq, nt = len(p), len(k)
         assert len(q) == nq and len(fl) == nq and len(tg) == nt
         T = None if Tcw is None else np.ascontiguousarray(Tcw, np.float32).reshape(12)
-        uq = None if ur_query is None else np.ascontiguousarray(ur_query, np.float32)
-        sk = None if skip is None else np.ascontiguousarray(skip, np.uint8)
-        ur = None if uright is None else np.ascontiguousarray(uright, np.float32)
-        ptr = lambda a: None if a is None else a.ctypes.data
+        uq = _opt(ur_query, np.float32)
+        sk = _opt(skip, np.uint8)
+        ur = _opt(uright, np.float32)
         st = np.zeros(nq, np.uint8); oi = [np.zeros(nq, np.int32) for _ in range(4)]; proj = np.zeros((nq, 3), np.float32)
         asg = np.zeros(nt, np.int32); nm = np.zeros(1, np.int32)
-        check(lib().xfh_search_projection(self.h, mode, nq, p.ctypes.data, ptr(uq), ptr(T), C.byref(cam) if cam is not None else None,
+        check(lib().xfh_search_projection(self.h, mode, nq, p.ctypes.data, _ptr(uq), _ptr(T), C.byref(cam) if cam is not None else None,
                                           C.byref(capi.GridBounds(*bounds)), float(radius), q.ctypes.data, fl.ctypes.data, k.ctypes.data, tg.ctypes.data, nt,
-                                          ptr(sk), ptr(ur), int(init_dist), int(th_high), float(nn_ratio), st.ctypes.data, *[o.ctypes.data for o in oi],
+                                          _ptr(sk), _ptr(ur), int(init_dist), int(th_high), float(nn_ratio), st.ctypes.data, *[o.ctypes.data for o in oi],
                                           proj.ctypes.data, asg.ctypes.data, nm.ctypes.data), self.h)
         return dict(status=st, match_idx=oi[0], best_dist=oi[1], second_dist=oi[2], n_candidates=oi[3], proj=proj, assigned=asg, n_matches=int(nm[0]))
 
@@ -380,19 +401,15 @@ class Context:
                                      len(sf), p.ctypes.data, nr.ctypes.data, d.ctypes.data, n, uvr.ctypes.data, ur.ctypes.data, lv.ctypes.data, st.ctypes.data))
         return uvr[:n], ur[:n], lv[:n], st[:n]
 
-    FUSE_OUT_INT = ("best_idx", "best_dist", "n_window", "n_tested", "level")
+    FUSE_TABLE = (("best_idx", I32, ("B", "nq")), ("best_dist", I32, ("B", "nq")), ("n_window", I32, ("B", "nq")), ("n_tested", I32, ("B", "nq")), ("level", I32, ("B", "nq")),
+                  ("proj", F32, ("B", "nq", 3)), ("n_fused", I32, ("B",)), ("status", U8, ("B", "nq")))
+    FUSE_OUT_INT = _names(FUSE_TABLE, "nq")
 
     @staticmethod
     def fuse_search_layout(B: int, nq: int, guard: int = 0):
         """byte offsets of the outputs of fuse_search_device inside one buffer (and its size under "bytes"); guard > 0 leaves at least
         that many bytes the call never writes before the first array and after every array (for tests that fill them)"""
-        al = lambda x: (x + 255) & ~255
-        o, off = {}, al(guard)
-        for name, nbytes in (("best_idx", 4 * B * nq), ("best_dist", 4 * B * nq), ("n_window", 4 * B * nq), ("n_tested", 4 * B * nq), ("level", 4 * B * nq),
-                             ("proj", 12 * B * nq), ("n_fused", 4 * B), ("status", B * nq)):
-            o[name] = off; off += al(nbytes) + al(guard)
-        o["bytes"] = off
-        return o
+        return Layout.of(Context.FUSE_TABLE, guard, B=B, nq=nq)
 
     def fuse_search_device(self, B: int, nq: int, query_stride: int, d_points, d_normals, d_distances, d_query_desc, d_query_flags, d_Tcw, d_Ow, cam, bounds,
                            th: float, scale_factors, ratio_max, d_grids, d_targets, target_stride: int, nt: int, d_out, d_uright=None, chi2: bool = True,
@@ -416,11 +433,11 @@ class Context:
         sf = np.ascontiguousarray(scale_factors, np.float32); rm = np.ascontiguousarray(ratio_max, np.float32)
         nq, nt = len(p), len(k)
         assert len(nr) == nq and len(d) == nq and len(q) == nq and len(fl) == nq and len(tg) == nt and len(rm) >= len(sf) - 1
-        ur = None if uright is None else np.ascontiguousarray(uright, np.float32)
+        ur = _opt(uright, np.float32)
         st = np.zeros(nq, np.uint8); oi = [np.zeros(nq, np.int32) for _ in range(5)]; proj = np.zeros((nq, 3), np.float32); nf = np.zeros(1, np.int32)
         check(lib().xfh_fuse_search(self.h, nq, p.ctypes.data, nr.ctypes.data, d.ctypes.data, q.ctypes.data, fl.ctypes.data, T.ctypes.data, O.ctypes.data,
                                     C.byref(cam), C.byref(capi.GridBounds(*bounds)), float(th), sf.ctypes.data, rm.ctypes.data, len(sf), k.ctypes.data,
-                                    tg.ctypes.data, nt, None if ur is None else ur.ctypes.data, capi.FUSE_CHI2 if chi2 else 0, int(init_dist), int(th_low),
+                                    tg.ctypes.data, nt, _ptr(ur), capi.FUSE_CHI2 if chi2 else 0, int(init_dist), int(th_low),
                                     st.ctypes.data, *[o.ctypes.data for o in oi], proj.ctypes.data, nf.ctypes.data), self.h)
         r = dict(zip(self.FUSE_OUT_INT, oi))
         r.update(status=st, proj=proj, n_fused=int(nf[0]))
@@ -453,27 +470,23 @@ class Context:
         """xfh_epipolar_gate (host): the gates of SearchForTriangulation for one keypoint of KF1 against n of KF2 -> capi.TRI_GATE_* per keypoint"""
         Fm = np.ascontiguousarray(F12, np.float32).reshape(9); e = np.ascontiguousarray(ep, np.float32).reshape(2)
         xy = np.ascontiguousarray(xy2, np.float32).reshape(-1, 2)
-        ur = None if uright2 is None else np.ascontiguousarray(uright2, np.float32)
+        ur = _opt(uright2, np.float32)
         n = len(xy)
         assert ur is None or len(ur) == n
         out = np.zeros(max(n, 1), np.uint8)
         check(lib().xfh_epipolar_gate(Fm.ctypes.data, e.ctypes.data, float(epipole_r2), float(unc), int(flags), float(x1), float(y1), int(bool(stereo1)),
-                                      xy.ctypes.data, None if ur is None else ur.ctypes.data, n, out.ctypes.data))
+                                      xy.ctypes.data, _ptr(ur), n, out.ctypes.data))
         return out[:n]
 
-    TRI_OUT_INT = ("match12", "best_dist", "n_candidates", "n_geom")
+    TRI_TABLE = (("match12", I32, ("B", "n1")), ("best_dist", I32, ("B", "n1")), ("n_candidates", I32, ("B", "n1")), ("n_geom", I32, ("B", "n1")), ("n_matches", I32, ("B",)),
+                 ("status", U8, ("B", "n1")))
+    TRI_OUT_INT = _names(TRI_TABLE, "n1")
 
     @staticmethod
     def triangulation_search_layout(B: int, n1: int, guard: int = 0):
         """byte offsets of the outputs of triangulation_search_device inside one buffer (and its size under "bytes"); guard as in
         fuse_search_layout"""
-        al = lambda x: (x + 255) & ~255
-        o, off = {}, al(guard)
-        for name, nbytes in (("match12", 4 * B * n1), ("best_dist", 4 * B * n1), ("n_candidates", 4 * B * n1), ("n_geom", 4 * B * n1), ("n_matches", 4 * B),
-                             ("status", B * n1)):
-            o[name] = off; off += al(nbytes) + al(guard)
-        o["bytes"] = off
-        return o
+        return Layout.of(Context.TRI_TABLE, guard, B=B, n1=n1)
 
     def triangulation_search_device(self, B: int, n1: int, n2: int, side1_shared: bool, d_nodes1, d_xy1, d_uright1, d_has1, d_desc1, desc1_stride: int,
                                     d_nodes2, d_xy2, d_uright2, d_has2, d_desc2, desc2_stride: int, d_F12, d_ep, d_out, only_stereo: bool = False,
@@ -501,15 +514,17 @@ class Context:
         st = np.zeros(n1, np.uint8); oi = [np.zeros(n1, np.int32) for _ in range(4)]; nm = np.zeros(1, np.int32)
         flags = (capi.TRI_ONLY_STEREO if only_stereo else 0) | (capi.TRI_COARSE if coarse else 0)
         check(lib().xfh_triangulation_search(self.h, n1, n2, flags, int(th_low), float(epipole_r2), float(unc), no1.ctypes.data, x1.ctypes.data,
-                                             None if u1 is None else u1.ctypes.data, h1.ctypes.data, d1.ctypes.data, no2.ctypes.data, x2.ctypes.data,
-                                             None if u2 is None else u2.ctypes.data, h2.ctypes.data, d2.ctypes.data, Fm.ctypes.data, e.ctypes.data,
+                                             _ptr(u1), h1.ctypes.data, d1.ctypes.data, no2.ctypes.data, x2.ctypes.data,
+                                             _ptr(u2), h2.ctypes.data, d2.ctypes.data, Fm.ctypes.data, e.ctypes.data,
                                              st.ctypes.data, *[o.ctypes.data for o in oi], nm.ctypes.data), self.h)
         r = dict(zip(self.TRI_OUT_INT, oi))
         r.update(status=st, n_matches=int(nm[0]))
         return r
 
     # -- SearchByBoW over feature-vector nodes (xfh_bow_accept / xfh_bow_search*) ---------------------------------------------
-    BOW_OUT_INT = ("match12", "best_dist", "second_dist", "n_candidates")
+    BOW_TABLE = (("match12", I32, ("B", "n1")), ("best_dist", I32, ("B", "n1")), ("second_dist", I32, ("B", "n1")), ("n_candidates", I32, ("B", "n1")),
+                 ("assigned2", I32, ("B", "n2")), ("n_matches", I32, ("B",)), ("status", U8, ("B", "n1")))
+    BOW_OUT_INT = _names(BOW_TABLE, "n1")
 
     @staticmethod
     def bow_accept(best_idx: int, best: int, second: int, th_low: int, nn_ratio: float, flags: int = 0) -> bool:
@@ -524,13 +539,7 @@ class Context:
     def bow_search_layout(B: int, n1: int, n2: int, guard: int = 0):
         """byte offsets of the outputs of bow_search_device inside one buffer (and its size under "bytes"); guard as in fuse_search_layout.
         The workspace is a buffer of its own (bow_search_workspace_bytes)."""
-        al = lambda x: (x + 255) & ~255
-        o, off = {}, al(guard)
-        for name, nbytes in (("match12", 4 * B * n1), ("best_dist", 4 * B * n1), ("second_dist", 4 * B * n1), ("n_candidates", 4 * B * n1),
-                             ("assigned2", 4 * B * n2), ("n_matches", 4 * B), ("status", B * n1)):
-            o[name] = off; off += al(nbytes) + al(guard)
-        o["bytes"] = off
-        return o
+        return Layout.of(Context.BOW_TABLE, guard, B=B, n1=n1, n2=n2)
 
     def bow_search_device(self, B: int, n1: int, n2: int, shared: int, d_nodes1, d_active1, d_desc1, desc1_stride: int, d_nodes2, d_eligible2, d_desc2,
                           desc2_stride: int, d_workspace, d_out, strict_low: bool = False, init_dist: int = 256, th_low: int = 100, nn_ratio: float = 0.6,
@@ -549,12 +558,12 @@ class Context:
         no1, no2 = np.ascontiguousarray(node_of1, np.uint32), np.ascontiguousarray(node_of2, np.uint32)
         d1, d2 = f32(desc1), f32(desc2)
         a1 = np.ascontiguousarray(active1, np.uint8)
-        e2 = None if eligible2 is None else np.ascontiguousarray(eligible2, np.uint8)
+        e2 = _opt(eligible2, np.uint8)
         n1, n2 = len(no1), len(no2)
         assert len(a1) == n1 and len(d1) == n1 and len(d2) == n2 and (e2 is None or len(e2) == n2)
         st = np.zeros(n1, np.uint8); oi = [np.zeros(n1, np.int32) for _ in range(4)]; as2 = np.zeros(n2, np.int32); nm = np.zeros(1, np.int32)
         check(lib().xfh_bow_search(self.h, n1, n2, capi.BOW_STRICT_LOW if strict_low else 0, int(init_dist), int(th_low), float(nn_ratio), no1.ctypes.data,
-                                   a1.ctypes.data, d1.ctypes.data, no2.ctypes.data, None if e2 is None else e2.ctypes.data, d2.ctypes.data, st.ctypes.data,
+                                   a1.ctypes.data, d1.ctypes.data, no2.ctypes.data, _ptr(e2), d2.ctypes.data, st.ctypes.data,
                                    *[o.ctypes.data for o in oi], as2.ctypes.data, nm.ctypes.data), self.h)
         r = dict(zip(self.BOW_OUT_INT, oi))
         r.update(status=st, assigned2=as2, n_matches=int(nm[0]))
@@ -608,17 +617,14 @@ class Context:
     def bow_transform_workspace_bytes(n: int, B: int = 1) -> int:
         return int(lib().xfh_bow_transform_workspace_bytes(n, B))
 
+    BOW_TRANSFORM_TABLE = (("word", U32, ("B", "n")), ("node_of", U32, ("B", "n")), ("weight", F64, ("B", "n")), ("nodes", U8, ("B", "nodes_bytes")),
+                           ("bow_ids", U32, ("B", "n")), ("bow_vals", F64, ("B", "n")), ("n_words", I32, ("B",)))
+
     @staticmethod
     def bow_transform_layout(B: int, n: int, guard: int = 0):
         """byte offsets of the outputs of bow_transform_device inside one buffer (and its size under "bytes"); guard as in fuse_search_layout.
         The workspace is a buffer of its own (bow_transform_workspace_bytes)."""
-        al = lambda x: (x + 255) & ~255
-        o, off = {}, al(guard)
-        for name, nbytes in (("word", 4 * B * n), ("node_of", 4 * B * n), ("weight", 8 * B * n), ("nodes", B * Context.nodes_bytes(n)), ("bow_ids", 4 * B * n),
-                             ("bow_vals", 8 * B * n), ("n_words", 4 * B)):
-            o[name] = off; off += al(nbytes) + al(guard)
-        o["bytes"] = off
-        return o
+        return Layout.of(Context.BOW_TRANSFORM_TABLE, guard, B=B, n=n, nodes_bytes=Context.nodes_bytes(n))
 
     def bow_transform_device(self, B: int, n: int, d_vocab, vocab_bytes: int, d_desc, desc_stride: int, d_workspace, d_out, levelsup: int = 4, guard: int = 0):
         """xfh_bow_transform_device on device pointers; asynchronous.  d_out: pointer to the outputs laid out as bow_transform_layout(B, n,
@@ -644,8 +650,10 @@ class Context:
         return dict(word=word, node_of=node_of, weight=wt, nodes=nodes, bow_ids=ids[:k].copy(), bow_vals=vals[:k].copy(), n_words=k)
 
     # -- the keyframe database query: shared words, L1 score, candidates (xfh_bow_score / xfh_bowdb_query*) -----------------------------------
-    BOWDB_OUT = (("common", np.int32), ("score", np.float64), ("status", np.uint8), ("list_slot", np.int32), ("list_acc", np.float32), ("list_best", np.int32),
-                 ("cand_slot", np.int32), ("cand_acc", np.float32))
+    BOWDB_TABLE = (("common", I32, ("B", "n")), ("score", F64, ("B", "n")), ("status", U8, ("B", "n")), ("list_slot", I32, ("B", "n")), ("list_acc", F32, ("B", "n")),
+                   ("list_best", I32, ("B", "n")), ("cand_slot", I32, ("B", "n")), ("cand_acc", F32, ("B", "n")), ("header", I32, ("B", capi.BOWDB_HEADER_INTS)),
+                   ("best_acc", F32, ("B",)))
+    BOWDB_OUT = tuple((name, dt) for name, dt, shape in BOWDB_TABLE if shape == ("B", "n"))
     BOWDB_HEADER = ("n_listed", "max_common", "min_common", "n_scored", "n_candidates")
 
     @staticmethod
@@ -667,28 +675,17 @@ class Context:
     def bowdb_query_layout(B: int, n_slots: int, guard: int = 0):
         """byte offsets of the outputs of bowdb_query_device inside one buffer (and its size under "bytes"); guard as in fuse_search_layout.
         The workspace and d_state are buffers of their own."""
-        al = lambda x: (x + 255) & ~255
-        o, off = {}, al(guard)
-        for name, dt in Context.BOWDB_OUT:
-            o[name] = off; off += al(np.dtype(dt).itemsize * B * n_slots) + al(guard)
-        for name, nbytes in (("header", 4 * capi.BOWDB_HEADER_INTS * B), ("best_acc", 4 * B)):
-            o[name] = off; off += al(nbytes) + al(guard)
-        o["bytes"] = off
-        return o
+        return Layout.of(Context.BOWDB_TABLE, guard, B=B, n=n_slots)
 
     @staticmethod
     def bowdb_query_parse(raw: np.ndarray, lay, B: int, n_slots: int):
         """the bytes of an output buffer of bowdb_query_device -> one dict per query (the arrays at full length, the header fields as ints)"""
+        a = lay.parse(raw)
+        assert a["common"].shape == (B, n_slots)
         res = []
         for b in range(B):
-            o = {}
-            for name, dt in Context.BOWDB_OUT:
-                w = np.dtype(dt).itemsize * n_slots
-                o[name] = raw[lay[name] + b * w: lay[name] + (b + 1) * w].view(dt)
-            h = raw[lay["header"] + 4 * capi.BOWDB_HEADER_INTS * b: lay["header"] + 4 * capi.BOWDB_HEADER_INTS * (b + 1)].view(np.int32)
-            o.update({k: int(h[i]) for i, k in enumerate(Context.BOWDB_HEADER)})
-            o["header"] = h
-            o["best_acc"] = raw[lay["best_acc"] + 4 * b: lay["best_acc"] + 4 * b + 4].view(np.float32)[0]
+            o = {k: v[b] for k, v in a.items()}
+            o.update({k: int(o["header"][i]) for i, k in enumerate(Context.BOWDB_HEADER)})
             res.append(o)
         return res
 
@@ -711,8 +708,8 @@ class Context:
         ng = np.ascontiguousarray(neigh, np.int32)
         ng = ng.reshape(n, -1) if ng.size else ng.reshape(n, 0)                                 # nn = 0: no neighbours at all
         nn = ng.shape[1]
-        sq = None if seq is None else np.ascontiguousarray(seq, np.uint32)
-        ex = None if exclude is None else np.ascontiguousarray(exclude, np.uint8)
+        sq = _opt(seq, np.uint32)
+        ex = _opt(exclude, np.uint8)
         assert len(qi) == len(qv) and dv.shape == di.shape and len(dn) == n and state.dtype == np.float32 and state.flags.c_contiguous and len(state) == n
         o = {name: np.zeros(n, dt) for name, dt in self.BOWDB_OUT}
         hd, ba = np.zeros(capi.BOWDB_HEADER_INTS, np.int32), np.zeros(1, np.float32)
@@ -726,7 +723,9 @@ class Context:
         return o
 
     # -- SearchByProjection of map points with a claim: the Sim3 and relocalisation forms (xfh_map_project / xfh_map_projection_search*) ----
-    MAPPROJ_OUT_INT = ("match_idx", "best_dist", "n_window", "n_tested", "level")
+    MAPPROJ_TABLE = (("match_idx", I32, ("B", "nq")), ("best_dist", I32, ("B", "nq")), ("n_window", I32, ("B", "nq")), ("n_tested", I32, ("B", "nq")),
+                     ("level", I32, ("B", "nq")), ("proj", F32, ("B", "nq", 3)), ("assigned", I32, ("B", "nt")), ("n_matches", I32, ("B",)), ("status", U8, ("B", "nq")))
+    MAPPROJ_OUT_INT = _names(MAPPROJ_TABLE, "nq")
 
     @staticmethod
     def map_project(Tcw, Ow, cam, bounds, th: float, scale_factors, ratio_max, form: int, xyz, normals, distances):
@@ -750,13 +749,7 @@ class Context:
     def map_projection_search_layout(B: int, nq: int, nt: int, guard: int = 0):
         """byte offsets of the outputs of map_projection_search_device inside one buffer (and its size under "bytes"); guard as in
         fuse_search_layout.  The workspace is a buffer of its own (map_projection_search_workspace_bytes)."""
-        al = lambda x: (x + 255) & ~255
-        o, off = {}, al(guard)
-        for name, nbytes in (("match_idx", 4 * B * nq), ("best_dist", 4 * B * nq), ("n_window", 4 * B * nq), ("n_tested", 4 * B * nq), ("level", 4 * B * nq),
-                             ("proj", 12 * B * nq), ("assigned", 4 * B * nt), ("n_matches", 4 * B), ("status", B * nq)):
-            o[name] = off; off += al(nbytes) + al(guard)
-        o["bytes"] = off
-        return o
+        return Layout.of(Context.MAPPROJ_TABLE, guard, B=B, nq=nq, nt=nt)
 
     def map_projection_search_device(self, form: int, B: int, nq: int, d_points, d_normals, d_distances, d_query_desc, d_query_flags, d_Tcw, d_Ow, cam, bounds,
                                      th: float, scale_factors, ratio_max, d_grids, d_targets, target_stride: int, target_shared: int, nt: int, d_workspace,
@@ -780,20 +773,22 @@ class Context:
         T = np.ascontiguousarray(Tcw, np.float32).reshape(12); O = np.ascontiguousarray(Ow, np.float32).reshape(3)
         sf = np.ascontiguousarray(scale_factors, np.float32); rm = np.ascontiguousarray(ratio_max, np.float32)
         nq, nt = len(p), len(k)
-        tk = None if taken is None else np.ascontiguousarray(taken, np.uint8)
+        tk = _opt(taken, np.uint8)
         assert len(nr) == nq and len(d) == nq and len(q) == nq and len(fl) == nq and len(tg) == nt and len(rm) >= len(sf) - 1 and (tk is None or len(tk) == nt)
         st = np.zeros(nq, np.uint8); oi = [np.zeros(nq, np.int32) for _ in range(5)]; proj = np.zeros((nq, 3), np.float32)
         asg = np.zeros(nt, np.int32); nm = np.zeros(1, np.int32)
         check(lib().xfh_map_projection_search(self.h, int(form), nq, p.ctypes.data, nr.ctypes.data, d.ctypes.data, q.ctypes.data, fl.ctypes.data, T.ctypes.data,
                                               O.ctypes.data, C.byref(cam), C.byref(capi.GridBounds(*bounds)), float(th), sf.ctypes.data, rm.ctypes.data, len(sf),
-                                              k.ctypes.data, tg.ctypes.data, nt, None if tk is None else tk.ctypes.data, int(init_dist), float(accept_max),
+                                              k.ctypes.data, tg.ctypes.data, nt, _ptr(tk), int(init_dist), float(accept_max),
                                               st.ctypes.data, *[o.ctypes.data for o in oi], proj.ctypes.data, asg.ctypes.data, nm.ctypes.data), self.h)
         r = dict(zip(self.MAPPROJ_OUT_INT, oi))
         r.update(status=st, proj=proj, assigned=asg, n_matches=int(nm[0]))
         return r
 
     # -- SearchBySim3: two keyframes' map points into each other (xfh_sim3_project / xfh_sim3_search*) ---------------------------
-    SIM3_OUT_INT = ("match", "best_dist", "n_window", "n_tested", "level")
+    SIM3_SIDE_TABLE = (("match", I32, ("B", "n")), ("best_dist", I32, ("B", "n")), ("n_window", I32, ("B", "n")), ("n_tested", I32, ("B", "n")), ("level", I32, ("B", "n")),
+                       ("proj", F32, ("B", "n", 3)), ("status", U8, ("B", "n")))
+    SIM3_OUT_INT = _names(SIM3_SIDE_TABLE, "n")
 
     @staticmethod
     def sim3_project(Tqw, M, cam, bounds, th: float, scale_factors, ratio_max, xyz, distances):
@@ -812,16 +807,8 @@ class Context:
     def sim3_search_layout(B: int, n1: int, n2: int, guard: int = 0):
         """byte offsets of the outputs of sim3_search_device inside one buffer (and its size under "bytes"): the per-side arrays under
         "match1", "status2", ..., then "match12" and "n_found"; guard as in fuse_search_layout"""
-        al = lambda x: (x + 255) & ~255
-        o, off = {}, al(guard)
-        for s, n in (("1", n1), ("2", n2)):
-            for name, nbytes in (("match", 4 * B * n), ("best_dist", 4 * B * n), ("n_window", 4 * B * n), ("n_tested", 4 * B * n), ("level", 4 * B * n),
-                                 ("proj", 12 * B * n), ("status", B * n)):
-                o[name + s] = off; off += al(nbytes) + al(guard)
-        for name, nbytes in (("match12", 4 * B * n1), ("n_found", 4 * B)):
-            o[name] = off; off += al(nbytes) + al(guard)
-        o["bytes"] = off
-        return o
+        side = lambda s: tuple((name + s, dt, tuple(d + s if d == "n" else d for d in shape)) for name, dt, shape in Context.SIM3_SIDE_TABLE)
+        return Layout.of(side("1") + side("2") + (("match12", I32, ("B", "n1")), ("n_found", I32, ("B",))), guard, B=B, n1=n1, n2=n2)
 
     @staticmethod
     def sim3_side(n: int, grid, desc, desc_stride: int, points, dist, mp_desc, flags, Tw, out, lay, s: str, proj: bool = True, kps=None):
@@ -863,8 +850,10 @@ class Context:
 
     # -- timing ---------------------------------------------------------------------------
     # -- SearchForInitialization with the reference's retraction order (xfh_init_accept / xfh_init_search*) --------------------------------
-    INIT_OUT_Q = ("claim_idx", "matches12", "best_dist", "second_dist", "n_window", "n_tested")
-    INIT_OUT_T = ("matches21", "matched_distance")
+    INIT_TABLE = (("claim_idx", I32, ("B", "nq")), ("matches12", I32, ("B", "nq")), ("best_dist", I32, ("B", "nq")), ("second_dist", I32, ("B", "nq")),
+                  ("n_window", I32, ("B", "nq")), ("n_tested", I32, ("B", "nq")), ("matches21", I32, ("B", "nt")), ("matched_distance", I32, ("B", "nt")),
+                  ("n_matches", I32, ("B",)), ("status", U8, ("B", "nq")), ("prev_out", F32, ("B", "nq", 2)))
+    INIT_OUT_Q, INIT_OUT_T = _names(INIT_TABLE, "nq"), _names(INIT_TABLE, "nt")
 
     @staticmethod
     def init_accept(best: int, second: int, th_low: int, nn_ratio: float) -> bool:
@@ -879,12 +868,7 @@ class Context:
     def init_search_layout(B: int, nq: int, nt: int, guard: int = 0):
         """byte offsets of the outputs of init_search_device inside one buffer (its size under "bytes", the library's list length under
         "K"); guard as in search_projection_layout.  The workspace is a buffer of its own (init_search_workspace_bytes)."""
-        al = lambda x: (x + 255) & ~255
-        o, off = {}, al(guard)
-        for name, nbytes in ([(k, 4 * B * nq) for k in Context.INIT_OUT_Q] + [(k, 4 * B * nt) for k in Context.INIT_OUT_T] +
-                             [("n_matches", 4 * B), ("status", B * nq), ("prev_out", 8 * B * nq)]):
-            o[name] = off; off += al(nbytes) + al(guard)
-        o["bytes"] = off
+        o = Layout.of(Context.INIT_TABLE, guard, B=B, nq=nq, nt=nt)
         o["K"] = int(lib().xfh_init_list_entries())
         return o
 
@@ -905,12 +889,12 @@ class Context:
         matches21, matched_distance, n_matches, prev_out); in_place: prev_out is the (copied) prev_matched array itself"""
         q = np.ascontiguousarray(query_desc, np.float32); pm = np.array(prev_matched, np.float32, order="C").reshape(-1, 2)
         k = np.ascontiguousarray(kps, KP_DTYPE); tg = np.ascontiguousarray(targets, np.float32)
-        fl = None if query_flags is None else np.ascontiguousarray(query_flags, np.uint8)
+        fl = _opt(query_flags, np.uint8)
         nq, nt = len(q), len(k)
         assert len(pm) == nq and len(tg) == nt and (fl is None or len(fl) == nq)
         st = np.zeros(nq, np.uint8); oq = [np.zeros(nq, np.int32) for _ in self.INIT_OUT_Q]; ot = [np.zeros(nt, np.int32) for _ in self.INIT_OUT_T]
         nm = np.zeros(1, np.int32); po = pm if in_place else np.zeros((nq, 2), np.float32)
-        check(lib().xfh_init_search(self.h, nq, q.ctypes.data, pm.ctypes.data, None if fl is None else fl.ctypes.data, float(window), k.ctypes.data,
+        check(lib().xfh_init_search(self.h, nq, q.ctypes.data, pm.ctypes.data, _ptr(fl), float(window), k.ctypes.data,
                                     C.byref(capi.GridBounds(*bounds)), tg.ctypes.data, nt, int(th_low), float(nn_ratio), st.ctypes.data,
                                     *[o.ctypes.data for o in oq + ot], nm.ctypes.data, po.ctypes.data), self.h)
         r = dict(zip(self.INIT_OUT_Q + self.INIT_OUT_T, oq + ot))
@@ -919,6 +903,12 @@ class Context:
 
     # -- PoseOptimization --------------------------------------------------------------------
     POSE_HEADER = ("n_initial", "n_bad", "ret", "rounds", "iterations", "trials", "rejected", "ldlt_failures")
+    POSE_TABLE = (("Tcw_out", F32, ("B", 12)), ("outlier", U8, ("B", "nt")), ("chi2", F32, ("B", "nt")), ("header", I32, ("B", 8)), ("final_chi2", F64, ("B",)))
+
+    @staticmethod
+    def pose_optimize_layout(B: int, nt: int, guard: int = 0):
+        """the outputs of pose_optimize_device inside one buffer, in the order the call takes them; guard as in fuse_search_layout"""
+        return Layout.of(Context.POSE_TABLE, guard, B=B, nt=nt)
 
     @staticmethod
     def pose_optimize_workspace_bytes(nt: int, B: int = 1) -> int:
@@ -934,16 +924,25 @@ class Context:
         """xfh_pose_optimize (host pointers, one frame) -> dict(ret, Tcw, outlier, chi2, header, final_chi2); ret is the reference's return value"""
         T = np.ascontiguousarray(Tcw, np.float32).reshape(12); xy = np.ascontiguousarray(xy_un, np.float32).reshape(-1, 2)
         a = np.ascontiguousarray(assigned, np.int32); p = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
-        ur = None if uright is None else np.ascontiguousarray(uright, np.float32)
+        ur = _opt(uright, np.float32)
         nt = len(a)
         assert len(xy) == nt and (ur is None or len(ur) == nt)
         To, ol, c2, hd, fc = np.zeros(12, np.float32), np.zeros(nt, np.uint8), np.zeros(nt, np.float32), np.zeros(8, np.int32), np.zeros(1, np.float64)
-        check(lib().xfh_pose_optimize(self.h, nt, len(p), T.ctypes.data, C.byref(cam), xy.ctypes.data, None if ur is None else ur.ctypes.data, a.ctypes.data,
+        check(lib().xfh_pose_optimize(self.h, nt, len(p), T.ctypes.data, C.byref(cam), xy.ctypes.data, _ptr(ur), a.ctypes.data,
                                       p.ctypes.data, float(inv_sigma2), To.ctypes.data, ol.ctypes.data, c2.ctypes.data, hd.ctypes.data, fc.ctypes.data), self.h)
         return dict(ret=int(hd[2]), Tcw=To.reshape(3, 4), outlier=ol, chi2=c2, header=dict(zip(self.POSE_HEADER, hd.tolist())), final_chi2=float(fc[0]))
 
     # -- OptimizeSim3 between the two Sim3 projection searches of loop detection (xfh_sim3_optimize*) ---------------------------
     SIM3_OPT_HEADER = ("n_corr", "n_in_kf2", "n_out_kf2", "n_bad", "n_bad_out_kf2", "n_more", "ret", "rounds", "iterations", "trials", "rejected", "ldlt_failures")
+
+    SIM3_OPT_TABLE = (("assigned_out", I32, ("B", "n1")), ("status", U8, ("B", "n1")), ("chi2", F32, ("B", "n1", 2)), ("state", F64, ("B", 8)), ("S12_out", F32, ("B", 13)),
+                      ("Tcw", F32, ("B", 12)), ("Ow", F32, ("B", 3)), ("header", I32, ("B", 16)), ("final_chi2", F64, ("B",)))
+
+    @staticmethod
+    def sim3_optimize_layout(B: int, n1: int, guard: int = 0):
+        """the outputs of sim3_optimize_device inside one buffer, in the order the call takes them (S12_out with stride 13); guard as in
+        fuse_search_layout"""
+        return Layout.of(Context.SIM3_OPT_TABLE, guard, B=B, n1=n1)
 
     @staticmethod
     def sim3_optimize_workspace_bytes(n1: int, B: int = 1) -> int:
@@ -973,7 +972,7 @@ class Context:
         tm = None if Tmw is None else f32(Tmw, 12)
         ao, st, c2, sv, so = np.zeros(n1, np.int32), np.zeros(n1, np.uint8), np.zeros((n1, 2), np.float32), np.zeros(8, np.float64), np.zeros(13, np.float32)
         To, Ow, hd, fc = np.zeros(12, np.float32), np.zeros(3, np.float32), np.zeros(16, np.int32), np.zeros(1, np.float64)
-        check(lib().xfh_sim3_optimize(self.h, n1, M1, nq, n2, *[a.ctypes.data for a in ins], None if tm is None else tm.ctypes.data, C.byref(cam1), C.byref(cam2),
+        check(lib().xfh_sim3_optimize(self.h, n1, M1, nq, n2, *[a.ctypes.data for a in ins], _ptr(tm), C.byref(cam1), C.byref(cam2),
                                       float(th2), 1 if fix_scale else 0, 1 if all_points else 0, float(inv_sigma2_1), float(inv_sigma2_2), ao.ctypes.data,
                                       st.ctypes.data, c2.ctypes.data, sv.ctypes.data, so.ctypes.data, None if tm is None else To.ctypes.data,
                                       None if tm is None else Ow.ctypes.data, hd.ctypes.data, fc.ctypes.data), self.h)
@@ -982,29 +981,23 @@ class Context:
 
     # -- CreateNewMapPoints: triangulation of the matched pairs (xfh_triangulate*) ----------------------------------------------
     TRIANG_HEADER = ("matched", "tri_attempts", "stereo_attempts", "accepted", "new", "new_stereo", "superseded", "reserved")
-    TRIANG_CLAIM_OUT = ("winner", "new_idx1", "new_b", "new_idx2", "new_xyz", "new_normal", "new_dist", "n_new")
+    TRIANG_TABLE = (("status", U8, ("B", "n1")), ("kind", U8, ("B", "n1")), ("xyz", F32, ("B", "n1", 3)), ("header", I32, ("B", 8)), ("winner", I32, ("n1",)),
+                    ("new_idx1", I32, ("n1",)), ("new_b", I32, ("n1",)), ("new_idx2", I32, ("n1",)), ("new_xyz", F32, ("n1", 3)), ("new_normal", F32, ("n1", 3)),
+                    ("new_dist", F32, ("n1", 3)), ("n_new", I32, (1,)))
+    TRIANG_CLAIM_OUT = _names(TRIANG_TABLE)[4:]                              # the claim's arrays: one set for the whole call, not one per neighbour
 
     @staticmethod
     def triangulate_layout(B: int, n1: int, guard: int = 0):
         """byte offsets of the outputs of triangulate_device inside one buffer (and its size under "bytes"); guard as in fuse_search_layout"""
-        al = lambda x: (x + 255) & ~255
-        o, off = {}, al(guard)
-        for name, nbytes in (("status", B * n1), ("kind", B * n1), ("xyz", 12 * B * n1), ("header", 32 * B), ("winner", 4 * n1), ("new_idx1", 4 * n1),
-                             ("new_b", 4 * n1), ("new_idx2", 4 * n1), ("new_xyz", 12 * n1), ("new_normal", 12 * n1), ("new_dist", 12 * n1), ("n_new", 4)):
-            o[name] = off; o[name + "_bytes"] = nbytes; off += al(nbytes) + al(guard)
-        o["bytes"] = off
-        return o
+        return Layout.of(Context.TRIANG_TABLE, guard, B=B, n1=n1)
 
     @staticmethod
     def triangulate_parse(raw: np.ndarray, lay, B: int, n1: int, claim: bool):
-        """the bytes of a buffer laid out by triangulate_layout -> dict of arrays"""
-        cut = lambda k, dt: raw[lay[k]:lay[k] + lay[k + "_bytes"]].view(dt).copy()
-        r = dict(status=cut("status", np.uint8).reshape(B, n1), kind=cut("kind", np.uint8).reshape(B, n1), xyz=cut("xyz", np.float32).reshape(B, n1, 3),
-                 header=cut("header", np.int32).reshape(B, 8))
+        """the bytes of a buffer laid out by triangulate_layout -> dict of arrays: without the claim its arrays are left out, with it n_new is an int"""
+        r = {k: v for k, v in lay.parse(raw).items() if claim or k not in Context.TRIANG_CLAIM_OUT}
+        assert r["status"].shape == (B, n1)
         if claim:
-            r.update(winner=cut("winner", np.int32), new_idx1=cut("new_idx1", np.int32), new_b=cut("new_b", np.int32), new_idx2=cut("new_idx2", np.int32),
-                     new_xyz=cut("new_xyz", np.float32).reshape(n1, 3), new_normal=cut("new_normal", np.float32).reshape(n1, 3),
-                     new_dist=cut("new_dist", np.float32).reshape(n1, 3), n_new=int(cut("n_new", np.int32)[0]))
+            r["n_new"] = int(r["n_new"][0])
         return r
 
     def triangulate_device(self, B: int, n1: int, n2: int, side1_shared: bool, cam, side1, side2, d_match12, d_out, sigma2: float = 1.0,
@@ -1036,11 +1029,10 @@ class Context:
         m = np.ascontiguousarray(match12, np.int32).reshape(B, n1)
         st, kd, xyz, hd = np.zeros((B, n1), np.uint8), np.zeros((B, n1), np.uint8), np.zeros((B, n1, 3), np.float32), np.zeros((B, 8), np.int32)
         co = [np.zeros(n1, np.int32) for _ in range(4)] + [np.zeros((n1, 3), np.float32) for _ in range(3)] + [np.zeros(1, np.int32)]
-        ptr = lambda a: None if a is None else a.ctypes.data
         flags = (capi.TRIANG_INERTIAL if inertial else 0) | (capi.TRIANG_CLAIM if claim else 0)
         check(lib().xfh_triangulate(self.h, B, n1, n2, flags, C.byref(cam), float(sigma2), float(ratio_factor), float(scale_last), float(far_th),
-                                    *[ptr(a) for a in s1], *[ptr(a) for a in s2], ptr(m), ptr(st), ptr(kd), ptr(xyz), ptr(hd),
-                                    *[ptr(a) if claim else None for a in co]), self.h)
+                                    *[_ptr(a) for a in s1], *[_ptr(a) for a in s2], _ptr(m), _ptr(st), _ptr(kd), _ptr(xyz), _ptr(hd),
+                                    *[_ptr(a) if claim else None for a in co]), self.h)
         r = dict(status=st, kind=kd, xyz=xyz, header=hd)
         if claim:
             r.update(zip(self.TRIANG_CLAIM_OUT, co)); r["n_new"] = int(co[7][0])
@@ -1065,7 +1057,9 @@ class Context:
     # -- MonocularInitialization: TwoViewReconstruction::Reconstruct (xfh_two_view*) -------------------------------------------------------
     TWO_VIEW_HEADER = ("N", "status", "model", "win_h", "win_f", "ngood0", "ngood1", "ngood2", "ngood3", "ngood4", "ngood5", "ngood6", "ngood7", "chosen",
                        "inliers_h", "inliers_f", "n_tri", "n_hyp", "n_matches_out")
-    TWO_VIEW_OUT = ("header", "floats", "inl_h", "inl_f", "tri", "p3d", "matches_out")
+    TWO_VIEW_TABLE = (("header", I32, ("B", capi.TWO_VIEW_HEADER_INTS)), ("floats", F32, ("B", capi.TWO_VIEW_FLOATS)), ("inl_h", U8, ("B", "n1")), ("inl_f", U8, ("B", "n1")),
+                      ("tri", U8, ("B", "n1")), ("p3d", F32, ("B", "n1", 3)), ("matches_out", I32, ("B", "n1")))
+    TWO_VIEW_OUT = _names(TWO_VIEW_TABLE)
 
     @staticmethod
     def two_view_cos(min_parallax_deg: float = 1.0) -> float:
@@ -1075,21 +1069,12 @@ class Context:
     @staticmethod
     def two_view_layout(B: int, n1: int, guard: int = 0):
         """byte offsets of the outputs of two_view_device inside one buffer (and its size under "bytes"); guard as in fuse_search_layout"""
-        al = lambda x: (x + 255) & ~255
-        o, off = {}, al(guard)
-        for name, nbytes in (("header", 4 * capi.TWO_VIEW_HEADER_INTS * B), ("floats", 4 * capi.TWO_VIEW_FLOATS * B), ("inl_h", B * n1), ("inl_f", B * n1),
-                             ("tri", B * n1), ("p3d", 12 * B * n1), ("matches_out", 4 * B * n1)):
-            o[name] = off; o[name + "_bytes"] = nbytes; off += al(nbytes) + al(guard)
-        o["bytes"] = off
-        return o
+        return Layout.of(Context.TWO_VIEW_TABLE, guard, B=B, n1=n1)
 
     @staticmethod
     def two_view_parse(raw: np.ndarray, lay, B: int, n1: int):
-        """the bytes of a buffer laid out by two_view_layout -> dict of arrays"""
-        cut = lambda k, dt: raw[lay[k]:lay[k] + lay[k + "_bytes"]].view(dt).copy()
-        return dict(header=cut("header", np.int32).reshape(B, -1), floats=cut("floats", np.float32).reshape(B, -1), inl_h=cut("inl_h", np.uint8).reshape(B, n1),
-                    inl_f=cut("inl_f", np.uint8).reshape(B, n1), tri=cut("tri", np.uint8).reshape(B, n1), p3d=cut("p3d", np.float32).reshape(B, n1, 3),
-                    matches_out=cut("matches_out", np.int32).reshape(B, n1))
+        """lay.parse(raw) under the name and arguments that callers of the hand-written layouts use"""
+        return lay.parse(raw)
 
     def two_view_device(self, B: int, n1: int, n2: int, cam, d_xy1, d_xy2, d_matches12, d_draws, draws_stride: int, iters: int, rand_max: int, d_workspace,
                         d_out, sigma: float = 1.0, min_parallax_cos: float | None = None, min_triangulated: int = 50, guard: int = 0):
@@ -1108,13 +1093,9 @@ class Context:
         n1 = m.shape[-1]
         x1, x2 = f32(xy1).reshape(B, n1, 2), f32(xy2).reshape(B, -1, 2)
         d = np.ascontiguousarray(draws, np.int32)
-        out = dict(header=np.zeros((B, capi.TWO_VIEW_HEADER_INTS), np.int32), floats=np.zeros((B, capi.TWO_VIEW_FLOATS), np.float32),
-                   inl_h=np.zeros((B, n1), np.uint8), inl_f=np.zeros((B, n1), np.uint8), tri=np.zeros((B, n1), np.uint8),
-                   p3d=np.zeros((B, n1, 3), np.float32), matches_out=m.reshape(B, n1).copy())
-        if prior is not None:
-            for k, v in prior.items():
-                out[k] = np.ascontiguousarray(v, out[k].dtype).reshape(out[k].shape).copy()
-        return B, n1, x2.shape[1], x1, x2, m, d, out
+        out = Context.two_view_layout(B, n1).zeros()
+        out["matches_out"] = m.reshape(B, n1).copy()
+        return B, n1, x2.shape[1], x1, x2, m, d, _with_prior(out, prior)
 
     @staticmethod
     def two_view_host(cam, xy1, xy2, matches12, draws, rand_max: int, sigma: float = 1.0, min_parallax_cos: float | None = None, min_triangulated: int = 50,
@@ -1171,7 +1152,10 @@ class Context:
 
     # -- LoopClosing::DetectCommonRegionsFromBoW: the merge of the BoW match lists and Sim3Solver (xfh_sim3_merge_matches*, xfh_sim3_solve*) ------------
     SIM3_SOLVE_HEADER = ("N", "status", "its", "winner", "n_inliers", "best", "best_count", "consumed")
-    SIM3_SOLVE_OUT = ("header", "floats", "inliers", "Tcw", "Ow")
+    SIM3_SOLVE_TABLE = (("header", I32, ("B", capi.SIM3_SOLVE_HEADER_INTS)), ("floats", F32, ("B", capi.SIM3_SOLVE_FLOATS)), ("inliers", U8, ("B", "n1")),
+                        ("Tcw", F32, ("B", 12)), ("Ow", F32, ("B", 3)))
+    SIM3_SOLVE_OUT = _names(SIM3_SOLVE_TABLE)
+    SIM3_MERGE_TABLE = (("matched", I32, ("n1",)), ("matched_kf", I32, ("n1",)), ("num_matches", I32, (1,)))
 
     @staticmethod
     def sim3_max_err(sigma2: float = 1.0) -> float:
@@ -1191,19 +1175,17 @@ class Context:
     @staticmethod
     def sim3_solve_layout(B: int, n1: int, guard: int = 0):
         """byte offsets of the outputs of sim3_solve_device inside one buffer (and its size under "bytes"); guard as in fuse_search_layout"""
-        al = lambda x: (x + 255) & ~255
-        o, off = {}, al(guard)
-        for name, nbytes in (("header", 4 * capi.SIM3_SOLVE_HEADER_INTS * B), ("floats", 4 * capi.SIM3_SOLVE_FLOATS * B), ("inliers", B * n1), ("Tcw", 48 * B),
-                             ("Ow", 12 * B)):
-            o[name] = off; o[name + "_bytes"] = nbytes; off += al(nbytes) + al(guard)
-        o["bytes"] = off
-        return o
+        return Layout.of(Context.SIM3_SOLVE_TABLE, guard, B=B, n1=n1)
 
     @staticmethod
     def sim3_solve_parse(raw: np.ndarray, lay, B: int, n1: int):
-        cut = lambda k, dt: raw[lay[k]:lay[k] + lay[k + "_bytes"]].view(dt).copy()
-        return dict(header=cut("header", np.int32).reshape(B, -1), floats=cut("floats", np.float32).reshape(B, -1), inliers=cut("inliers", np.uint8).reshape(B, n1),
-                    Tcw=cut("Tcw", np.float32).reshape(B, 12), Ow=cut("Ow", np.float32).reshape(B, 3))
+        """lay.parse(raw) under the name and arguments that callers of the hand-written layouts use"""
+        return lay.parse(raw)
+
+    @staticmethod
+    def sim3_merge_layout(n1: int, guard: int = 0):
+        """the outputs of sim3_merge_matches_device (d_matched, d_matched_kf, d_num_matches) inside one buffer; guard as in fuse_search_layout"""
+        return Layout.of(Context.SIM3_MERGE_TABLE, guard, n1=n1)
 
     def sim3_solve_device(self, B: int, n1: int, M: int, d_points, d_point1, d_matched, d_T1w, T1w_stride: int, d_T2w, cam1, cam2, d_iters_of_N, max_iters: int,
                           d_draws, draws_stride: int, rand_max: int, d_workspace, d_out, min_inliers: int = 15, fix_scale: bool = False, max_err1: float = 9.0,
@@ -1227,12 +1209,7 @@ class Context:
         t1 = t1.reshape(-1, 12)
         tb, d = np.ascontiguousarray(iters_of_N, np.int32), np.ascontiguousarray(draws, np.int32)
         assert len(tb) == n1 + 1 and t1.shape[0] in (1, B)
-        out = dict(header=np.zeros((B, capi.SIM3_SOLVE_HEADER_INTS), np.int32), floats=np.zeros((B, capi.SIM3_SOLVE_FLOATS), np.float32),
-                   inliers=np.zeros((B, n1), np.uint8), Tcw=np.zeros((B, 12), np.float32), Ow=np.zeros((B, 3), np.float32))
-        if prior is not None:
-            for k, v in prior.items():
-                out[k] = np.ascontiguousarray(v, out[k].dtype).reshape(out[k].shape).copy()
-        return B, n1, len(pts), pts, p1, m, t1, t2, tb, d, out
+        return B, n1, len(pts), pts, p1, m, t1, t2, tb, d, _with_prior(Context.sim3_solve_layout(B, n1).zeros(), prior)
 
     @staticmethod
     def sim3_solve_host(cam1, cam2, points, point1, matched, T1w, T2w, iters_of_N, draws, rand_max: int, min_inliers: int = 15, fix_scale: bool = False,
@@ -1246,7 +1223,7 @@ class Context:
         nm = None if num_matches is None else np.array([num_matches], np.int32)
         check(lib().xfh_sim3_solve_host(B, n1, M, pts.ctypes.data, p1.ctypes.data, m.ctypes.data, t1.ctypes.data, 0 if t1.shape[0] == 1 else 12, t2.ctypes.data,
                                         C.byref(cam1), C.byref(cam2), float(max_err1), float(max_err2), int(bool(fix_scale)), int(min_inliers), int(min_matches),
-                                        None if nm is None else nm.ctypes.data, tb.ctypes.data, max_iters, d.ctypes.data, 0 if d.ndim == 2 else max_iters * 3, rand_max,
+                                        _ptr(nm), tb.ctypes.data, max_iters, d.ctypes.data, 0 if d.ndim == 2 else max_iters * 3, rand_max,
                                         wp, *[out[k].ctypes.data for k in Context.SIM3_SOLVE_OUT]))
         return out
 
@@ -1287,7 +1264,7 @@ class Context:
         m, p2 = np.ascontiguousarray(match12, np.int32), np.ascontiguousarray(point2, np.int32)
         assert m.ndim == 2 and p2.ndim == 2 and m.shape[0] == p2.shape[0]
         n1 = m.shape[1]
-        return m.shape[0], n1, p2.shape[1], m, p2, np.zeros(n1, np.int32), np.zeros(n1, np.int32), np.zeros(1, np.int32)
+        return (m.shape[0], n1, p2.shape[1], m, p2, *Context.sim3_merge_layout(n1).zeros().values())
 
     @staticmethod
     def sim3_merge_matches_host(match12, point2, M: int):
@@ -1309,7 +1286,8 @@ class Context:
 
     # -- Tracking::Relocalization: MLPnPsolver between SearchByBoW and PoseOptimization (xfh_mlpnp_*) ------------------------------------------------------
     MLPNP_HEADER = ("N", "status", "its", "min_inliers", "winner", "n_inliers", "best", "best_count", "consumed", "refines", "planar")
-    MLPNP_OUT = ("header", "Tcw", "inliers", "assigned_out")
+    MLPNP_TABLE = (("header", I32, ("B", capi.MLPNP_HEADER_INTS)), ("Tcw", F32, ("B", 12)), ("inliers", U8, ("B", "n")), ("assigned_out", I32, ("B", "n")))
+    MLPNP_OUT = _names(MLPNP_TABLE)
     MLPNP_STATUS = ("TOO_FEW", "NONE", "BEST", "REFINED")
 
     @staticmethod
@@ -1322,18 +1300,12 @@ class Context:
     @staticmethod
     def mlpnp_layout(B: int, n: int, guard: int = 0):
         """byte offsets of the outputs of mlpnp_solve_device inside one buffer (and its size under "bytes"); guard as in fuse_search_layout"""
-        al = lambda x: (x + 255) & ~255
-        o, off = {}, al(guard)
-        for name, nbytes in (("header", 4 * capi.MLPNP_HEADER_INTS * B), ("Tcw", 48 * B), ("inliers", B * n), ("assigned_out", 4 * B * n)):
-            o[name] = off; o[name + "_bytes"] = nbytes; off += al(nbytes) + al(guard)
-        o["bytes"] = off
-        return o
+        return Layout.of(Context.MLPNP_TABLE, guard, B=B, n=n)
 
     @staticmethod
     def mlpnp_parse(raw: np.ndarray, lay, B: int, n: int):
-        cut = lambda k, dt: raw[lay[k]:lay[k] + lay[k + "_bytes"]].view(dt).copy()
-        return dict(header=cut("header", np.int32).reshape(B, -1), Tcw=cut("Tcw", np.float32).reshape(B, 12), inliers=cut("inliers", np.uint8).reshape(B, n),
-                    assigned_out=cut("assigned_out", np.int32).reshape(B, n))
+        """lay.parse(raw) under the name and arguments that callers of the hand-written layouts use"""
+        return lay.parse(raw)
 
     def mlpnp_solve_device(self, B: int, n: int, nq: int, d_xy_un, d_assigned, d_points, d_point_valid, cam, max_err: float, d_iters_of_N, d_min_inliers_of_N,
                            chunk: int, d_start_iter, max_iters: int, d_draws, draws_stride: int, rand_max: int, d_workspace, d_out, min_matches: int = 0,
@@ -1356,12 +1328,7 @@ class Context:
         ti, tm = np.ascontiguousarray(tables[0], np.int32), np.ascontiguousarray(tables[1], np.int32)
         d = np.ascontiguousarray(draws, np.int32)
         assert len(xy) == n and len(ti) == n + 1 and len(tm) == n + 1 and d.shape[-1] == 6
-        out = dict(header=np.zeros((B, capi.MLPNP_HEADER_INTS), np.int32), Tcw=np.zeros((B, 12), np.float32), inliers=np.zeros((B, n), np.uint8),
-                   assigned_out=np.zeros((B, n), np.int32))
-        if prior is not None:
-            for k, v in prior.items():
-                out[k] = np.ascontiguousarray(v, out[k].dtype).reshape(out[k].shape).copy()
-        return B, n, nq, xy, a, pts, va, ti, tm, d, out
+        return B, n, nq, xy, a, pts, va, ti, tm, d, _with_prior(Context.mlpnp_layout(B, n).zeros(), prior)
 
     @staticmethod
     def mlpnp_solve_host(cam, xy_un, assigned, points, tables, draws, rand_max: int, max_err: float = 5.991, chunk: int = 5, start_iter=None, point_valid=None,
@@ -1374,9 +1341,9 @@ class Context:
         wp = (ws.ctypes.data + 15) & ~15
         nm = None if n_matches is None else np.ascontiguousarray(n_matches, np.int32).reshape(B)
         st = None if start_iter is None else np.ascontiguousarray(start_iter, np.int32).reshape(B)
-        check(lib().xfh_mlpnp_solve_host(B, n, nq, xy.ctypes.data, a.ctypes.data, pts.ctypes.data, None if va is None else va.ctypes.data, C.byref(cam), float(max_err),
-                                         int(min_matches), None if nm is None else nm.ctypes.data, ti.ctypes.data, tm.ctypes.data, int(chunk),
-                                         None if st is None else st.ctypes.data, max_iters, d.ctypes.data, 0 if d.ndim == 2 else max_iters * 6, rand_max, wp,
+        check(lib().xfh_mlpnp_solve_host(B, n, nq, xy.ctypes.data, a.ctypes.data, pts.ctypes.data, _ptr(va), C.byref(cam), float(max_err),
+                                         int(min_matches), _ptr(nm), ti.ctypes.data, tm.ctypes.data, int(chunk),
+                                         _ptr(st), max_iters, d.ctypes.data, 0 if d.ndim == 2 else max_iters * 6, rand_max, wp,
                                          *[out[k].ctypes.data for k in Context.MLPNP_OUT]))
         return out
 
@@ -1385,7 +1352,7 @@ class Context:
         """xfh_mlpnp_solve (host pointers, one problem) -> the dict of mlpnp_solve_host with B = 1"""
         B, n, nq, xy, a, pts, va, ti, tm, d, out = self._mlpnp_arrays(xy_un, assigned, points, point_valid, tables, draws, prior)
         assert B == 1 and d.ndim == 2
-        check(lib().xfh_mlpnp_solve(self.h, n, nq, xy.ctypes.data, a.ctypes.data, pts.ctypes.data, None if va is None else va.ctypes.data, C.byref(cam), float(max_err),
+        check(lib().xfh_mlpnp_solve(self.h, n, nq, xy.ctypes.data, a.ctypes.data, pts.ctypes.data, _ptr(va), C.byref(cam), float(max_err),
                                     ti.ctypes.data, tm.ctypes.data, int(chunk), int(start_iter), d.shape[0], d.ctypes.data, rand_max,
                                     *[out[k].ctypes.data for k in self.MLPNP_OUT]), self.h)
         return out
@@ -1407,9 +1374,9 @@ class Context:
     def mlpnp_compute_pose(f, p, use=None, fold: bool = False):
         """bearing vectors [m][3] and points [m][3] (floats), use [m] bytes or None -> (Rt [3][4] doubles, planar)"""
         a, b = np.ascontiguousarray(f, np.float32), np.ascontiguousarray(p, np.float32)
-        u = None if use is None else np.ascontiguousarray(use, np.uint8)
+        u = _opt(use, np.uint8)
         Rt, planar = np.zeros(12, np.float64), C.c_int(0)
-        check(lib().xfh_mlpnp_compute_pose(len(a), a.ctypes.data, b.ctypes.data, None if u is None else u.ctypes.data, int(bool(fold)), Rt.ctypes.data, C.byref(planar)))
+        check(lib().xfh_mlpnp_compute_pose(len(a), a.ctypes.data, b.ctypes.data, _ptr(u), int(bool(fold)), Rt.ctypes.data, C.byref(planar)))
         return Rt.reshape(3, 4), planar.value
 
     @staticmethod
