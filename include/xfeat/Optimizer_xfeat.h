@@ -9,7 +9,8 @@
  * pose also comes back to the host, as pFrame->SetPose would want it.  This is not a graph optimiser: one SE3 vertex, unary edges, nothing else
  * (include/xfeat_hip.h has the contract line by line).  XFoptimizer::OptimizeSim3 is Optimizer::OptimizeSim3 (:2100-2381) in the same way: one
  * Sim3 vertex, two projection edges per correspondence, as one call of xfh_sim3_optimize_device between the two Sim3 projection searches of loop
- * detection.  Header only; needs nothing but xfeat_hip.h.
+ * detection.  XFoptimizer::LocalBundleAdjustment is Optimizer::LocalBundleAdjustment (:1188-1460, the graph, optimize(10) and vToErase) as one call of
+ * xfh_local_ba_device on the map's device tables.  Header only; needs nothing but xfeat_hip.h.
  */
 #ifndef XFEAT_OPTIMIZER_XFEAT_H
 #define XFEAT_OPTIMIZER_XFEAT_H
@@ -25,7 +26,7 @@ namespace ORB_SLAM3 {
 class XFoptimizer {
 public:
     explicit XFoptimizer(xfh_ctx* c) : ctx(c) {}
-    ~XFoptimizer() { if (d_buf) xfh_dev_free(d_buf); if (d_s3) xfh_dev_free(d_s3); }
+    ~XFoptimizer() { if (d_buf) xfh_dev_free(d_buf); if (d_s3) xfh_dev_free(d_s3); if (d_lba) xfh_dev_free(d_lba); }
     XFoptimizer(const XFoptimizer&) = delete;
     XFoptimizer& operator=(const XFoptimizer&) = delete;
 
@@ -147,6 +148,73 @@ public:
     double sim3State[8] = {};                                // quaternion (x, y, z, w), t, s of g2oS12 on return
     double sim3FinalChi2 = 0.0;
 
+    // ---- Optimizer::LocalBundleAdjustment (reference src/Optimizer.cc:1116-1498) as LocalMapping::Run calls it: the host keeps :1118-1186 (the three lists)
+    // and hands the problem over as indices into the map's two device tables; :1188-1460 is one call of xfh_local_ba_device.  The host-side vectors are
+    // copied to the device here (they are small: indices and observations); the tables are refined in place (write_back).
+    struct LocalBAInput {
+        float* d_poseTable; int poseRows;                       // [poseRows][12] row-major [R|t]
+        float* d_pointTable; int pointRows;                     // [pointRows][3]
+        std::vector<int> kfRow;                                 // lLocalKeyFrames, then lFixedCameras: the row of each in the pose table
+        std::vector<unsigned char> kfFixed;                     // 1 for lFixedCameras and for the initial keyframe (mnId == GetInitKFid())
+        std::vector<int> pointRow;                              // lLocalMapPoints: the row of each in the point table
+        std::vector<int> edgeBegin;                             // [points + 1]: the edges of point p are edgeBegin[p] .. edgeBegin[p + 1] - 1, in the
+        std::vector<int> edgeKF;                                // order of :1296 (observations of !isBad() keyframes of this map with leftIndex != -1);
+        std::vector<float> edgeObs;                             // index into kfRow; (kpUn.pt.x, kpUn.pt.y, mvuRight[leftIndex]) per edge
+    };
+    // Returns the status (XFH_LBA_OK, _ABORTED, _NOTHING_FREE).  Blocks until the header is on the host; the refined poses, points and the vToErase flags
+    // stay on the device (deviceTcw(), devicePoints(), deviceErase()) and come to the host on request.  After the call the host re-checks
+    // pMP->isBad() (:1422), erases the flagged observations, and calls SetPose / SetWorldPos / UpdateNormalAndDepth with the downloaded values.
+    int LocalBundleAdjustment(const LocalBAInput& in, const xfh_camera& cam, float invSigma2 = 1.0f, int iterations = 10, bool writeBack = true) {
+        const int nK = (int)in.kfRow.size(), nP = (int)in.pointRow.size(), nE = (int)in.edgeKF.size();
+        int nFree = 0;
+        for (unsigned char f : in.kfFixed) nFree += f ? 0 : 1;
+        const size_t ws = xfh_local_ba_workspace_bytes(nK, nP, nE, nFree);
+        if (ws == 0 || in.kfFixed.size() != (size_t)nK || in.edgeBegin.size() != (size_t)nP + 1 || in.edgeObs.size() != (size_t)nE * 3)
+            throw std::runtime_error("XFoptimizer::LocalBundleAdjustment: sizes out of range (more than XFH_LBA_MAX_FREE free keyframes?)");
+        auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+        const size_t K = (size_t)nK, P = (size_t)nP, E = (size_t)nE;
+        const size_t sz[] = {al(ws), al(K * 4), al(K), al(P * 4), al((P + 1) * 4), al(E * 4), al(E * 12), al(K * 48), al(P * 12), al(E), al(E * 4), 256, 256};
+        size_t need = 0;
+        for (size_t v : sz) need += v;
+        if (need > lba_bytes) {
+            if (d_lba) { xfh_synchronize(ctx); xfh_dev_free(d_lba); d_lba = nullptr; lba_bytes = 0; }
+            if (xfh_dev_alloc(&d_lba, need) != XFH_OK) throw std::runtime_error("XFoptimizer::LocalBundleAdjustment: out of device memory");
+            lba_bytes = need;
+        }
+        char* q[13];
+        q[0] = (char*)d_lba;
+        for (int i = 1; i < 13; ++i) q[i] = q[i - 1] + sz[i - 1];
+        d_lbaTcw = (float*)q[7]; d_lbaPoints = (float*)q[8]; d_lbaErase = (unsigned char*)q[9]; d_lbaChi2 = (float*)q[10];
+        lbaKF = nK; lbaPoints = nP; lbaEdges = nE;
+        int rc = xfh_synchronize(ctx);
+        if (rc == XFH_OK) rc = xfh_memcpy_h2d(q[1], in.kfRow.data(), K * 4);
+        if (rc == XFH_OK) rc = xfh_memcpy_h2d(q[2], in.kfFixed.data(), K);
+        if (rc == XFH_OK) rc = xfh_memcpy_h2d(q[3], in.pointRow.data(), P * 4);
+        if (rc == XFH_OK) rc = xfh_memcpy_h2d(q[4], in.edgeBegin.data(), (P + 1) * 4);
+        if (rc == XFH_OK) rc = xfh_memcpy_h2d(q[5], in.edgeKF.data(), E * 4);
+        if (rc == XFH_OK) rc = xfh_memcpy_h2d(q[6], in.edgeObs.data(), E * 12);
+        if (rc == XFH_OK) rc = xfh_local_ba_device(ctx, nK, nFree, nP, nE, in.d_poseTable, in.poseRows, in.d_pointTable, in.pointRows, (const int*)q[1],
+                                                   (const unsigned char*)q[2], (const int*)q[3], (const int*)q[4], (const int*)q[5], (const float*)q[6], &cam, invSigma2,
+                                                   iterations, writeBack ? 1 : 0, q[0], d_lbaTcw, d_lbaPoints, d_lbaErase, d_lbaChi2, (int*)q[11], (double*)q[12]);
+        if (rc == XFH_OK) rc = xfh_synchronize(ctx);
+        if (rc == XFH_OK) rc = xfh_memcpy_d2h(lbaHeader, q[11], XFH_LBA_HEADER_INTS * 4);
+        if (rc == XFH_OK) rc = xfh_memcpy_d2h(&lbaFinalChi2, q[12], 8);
+        if (rc != XFH_OK) throw std::runtime_error(std::string("XFoptimizer::LocalBundleAdjustment: ") + xfh_strerror(rc));
+        return lbaHeader[0];
+    }
+    // of the last LocalBundleAdjustment: the refined poses [keyframes][12] (a fixed keyframe's: its input), points [points][3], the vToErase flag and
+    // the chi2 of every edge, in device memory; and copies on request
+    const float* deviceTcw() const { return d_lbaTcw; }
+    const float* devicePoints() const { return d_lbaPoints; }
+    const unsigned char* deviceErase() const { return d_lbaErase; }
+    void localPoses(std::vector<float>& out) const { lbaGet(out, d_lbaTcw, (size_t)lbaKF * 12); }
+    void localPoints(std::vector<float>& out) const { lbaGet(out, d_lbaPoints, (size_t)lbaPoints * 3); }
+    void eraseFlags(std::vector<unsigned char>& out) const { lbaGet(out, d_lbaErase, (size_t)lbaEdges); }
+    void edgeChi2(std::vector<float>& out) const { lbaGet(out, d_lbaChi2, (size_t)lbaEdges); }
+    // status, free keyframes, fixed keyframes with an edge, mono edges, stereo edges, iterations, trials, rejected trials, factorisation failures, edges to erase
+    int lbaHeader[XFH_LBA_HEADER_INTS] = {};
+    double lbaFinalChi2 = 0.0;
+
     int nInitialCorrespondences() const { return header[0]; }
     int nBad() const { return header[1]; }
     // n_initial, n_bad, the return value, rounds run, Levenberg iterations, trials, rejected trials, factorisation failures
@@ -161,6 +229,13 @@ private:
     void* d_s3 = nullptr; size_t s3_bytes = 0;                       // OptimizeSim3's own buffer
     int* d_matches = nullptr; unsigned char* d_status = nullptr; float* d_chi2_pairs = nullptr; float* d_S12 = nullptr; float* d_Scw = nullptr; float* d_Ow = nullptr;
     int n_pairs = 0;
+    void* d_lba = nullptr; size_t lba_bytes = 0;                     // LocalBundleAdjustment's own buffer
+    float* d_lbaTcw = nullptr; float* d_lbaPoints = nullptr; unsigned char* d_lbaErase = nullptr; float* d_lbaChi2 = nullptr;
+    int lbaKF = 0, lbaPoints = 0, lbaEdges = 0;
+    template <class T> void lbaGet(std::vector<T>& out, const T* d, size_t count) const {
+        out.assign(count, T());
+        if (count > 0 && xfh_memcpy_d2h(out.data(), d, count * sizeof(T)) != XFH_OK) throw std::runtime_error("XFoptimizer: download failed");
+    }
 };
 
 }  // namespace ORB_SLAM3

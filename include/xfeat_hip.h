@@ -1726,6 +1726,96 @@ int xfh_sim3_optimize_host(int B, int n1, int M1, int nq, int n2, int side1_shar
                            int fix_scale, int all_points, float inv_sigma2_1, float inv_sigma2_2, void* workspace, int* assigned_out, uint8_t* pair_status,
                            float* chi2, double* state, float* S12_out, size_t S12_out_problem_stride, float* Tcw, float* Ow, int* header, double* final_chi2);
 
+/* ---- LocalBundleAdjustment: the Schur-complement Levenberg behind the triangulate -> fuse chain of LocalMapping, device resident ----------------------
+ * Optimizer::LocalBundleAdjustment (src/Optimizer.cc:1116-1498) from the graph to vToErase (:1188-1460): optimize(10) of OptimizationAlgorithmLevenberg over
+ * BlockSolver_6_3 with the Schur complement, then the three loops that fill vToErase.  Conventional Pinhole keyframes, mono and stereo (RGB-D)
+ * observations, octave 0, ONE problem per call.  The host keeps :1118-1186 (the three lists) and hands the problem over as indices into two device
+ * tables: d_pose_table [pose_rows][12] row-major [R|t] floats and d_point_table [point_rows][3], the map as the tracker's device calls read it.
+ *
+ * Problem.  nK keyframes d_kf_row [nK] (rows of the pose table); d_kf_fixed [nK] bytes, non-zero for lFixedCameras and for the initial keyframe
+ *   inside lLocalKeyFrames (:1220, :1237); n_free = the number of zero bytes, which the host knows and the call needs to size S (a device count
+ *   that differs gives status FREE_MISMATCH).  nP points d_point_row [nP].  nE edges in the order the reference creates them, point by point
+ *   (:1282-1403): the CSR d_edge_begin [nP + 1], d_edge_kf [nE] (index into the nK keyframes), d_edge_obs [nE][3] = (kpUn.pt.x, kpUn.pt.y,
+ *   mvuRight).  ur < 0 is a mono edge (EdgeSE3ProjectXYZ, delta (float)sqrt(5.991)), anything else -- a NaN too -- a stereo edge
+ *   (EdgeStereoSE3ProjectXYZ, the FLOAT invz of cam_project in the error and the double one in the Jacobian, delta (float)sqrt(7.815)).
+ *   Information = inv_sigma2 * I.  An edge is NO edge (inactive, erase 0, chi2 0) when its keyframe index is outside [0, nK), when the CSR names no
+ *   point for it (the first p with edge_begin[p + 1] > e, found in 32 fixed steps, must have edge_begin[p] <= e), or when its keyframe's or its point's
+ *   row is outside its table.  A keyframe whose row is outside the table counts as fixed and its Tcw_out is 12 zeros; such a point's points_out is
+ *   3 zeros; neither is written back.  A point without an edge is not a vertex: points_out = its input.
+ * Statuses, header[0].  OK; ABORTED: no keyframe with d_kf_fixed set has an edge (:1182); NOTHING_FREE: no free keyframe (a STATED DEVIATION: g2o
+ *   with zero poses under Schur is not modelled); FREE_MISMATCH.  In the last three every output equals its input, flags and chi2 are 0, final_chi2 0.
+ * Edge arithmetic.  The SE3 state, exp(u) * estimate, the error and the pose Jacobian are xfh_pose_optimize_device's.  The point Jacobian is
+ *   -projectJac(pc) * R (mono, OptimizableTypes.cpp:139-152) or types_six_dof_expmap.cpp:242-252 (stereo), R = toRotationMatrix of the pose.  An edge
+ *   adds A_l^T (rho1 w) A_l to its point's block Hll, -rho1 A_l^T (w e) to bl, and -- when its keyframe is free -- A_p^T (rho1 w) A_p to Hpp, -rho1
+ *   A_p^T (w e) to bp and W = A_p^T (rho1 w) A_l to the 6 x 3 cross block; each entry is summed over the edge's rows first.  A fixed keyframe
+ *   contributes to its points only.
+ * Per iteration.  Errors and the robust chi2 sum at the estimate, the blocks above.  Iteration 0: lambda = 1e-5 * max |diagonal| over the free
+ *   keyframes in index order, then the points in index order, with the NaN rule of xfh_pose_optimize_device; ni = 2.
+ * Per trial.  lambda goes on both diagonals.  Dinv_p = the closed-form cofactor inverse of Hll_p + lambda I (a singular block makes what it makes).
+ *   S = Hpp + lambda I - sum W Dinv W^T, b_S = b_p - sum (W Dinv) b_l.  The pose step: a dense unpivoted LDL^T of S in fp64 that fails at the first pivot
+ *   not > 0 (a STATED DEVIATION, as in the two existing optimisers, here standing in for SimplicialLDLT with an AMD ordering).  The point steps by
+ *   back-substitution x_l = Dinv (b_l - sum W^T x_p).  After a failed factorisation x (poses and points) keeps its previous values (zero before the first),
+ *   the update is applied all the same and tempChi = DBL_MAX.  computeScale runs over ALL unknowns, landmarks included.  rho, lambda, ni, the ten-trial
+ *   limit, rho == 0 and the three-bad-iterations stop are exactly xfh_pose_optimize_device's Levenberg paragraph; at most max_iterations x 10 trials.
+ * Classification.  erase = chi2 > 5.991 (7.815 stereo; doubles, as e->chi2() is compared there) || !isDepthPositive().  chi2 reads _error as the last
+ *   computeActiveErrors() left it: after a rejected last trial that is the error at the REJECTED estimate (the stale-error rule of the two existing
+ *   optimisers); the depth is computed afresh at the final (restored) estimate.  The host re-checks pMP->isBad() (:1422) when it reads the flags.
+ * Summation orders (part of the contract only in being FIXED; tests/ref_local_ba.py mirrors them):
+ *   - a point's Hll and bl: its edges' shares added to 0 in edge order (g2o's own order); the back-substitution subtracts edge by edge in edge order,
+ *     rows 0 .. 5 of W in turn;
+ *   - a keyframe's Hpp, bp and robust chi2: the 256-lane fold of xfh_pose_optimize_device over the keyframe's edges in edge order (lane l adds the
+ *     edges l, l + 256, ..; the xor butterfly 32 .. 1 in each wave of 64; the four waves in order);
+ *   - a block (i, j), i <= j, of sum W Dinv W^T and b_S: the same fold over keyframe i's edges; an edge's term is (W_e Dinv_p) W_e'^T summed over the
+ *     edges e' of the same point at keyframe j in edge order (one, in a proper graph);
+ *   - the chi2 of the whole graph: the same fold over the nK keyframe sums; computeScale: the same fold over the 6 n_free pose terms followed by one
+ *     term per point (its three terms added to 0);
+ *   - the LDL^T: every entry receives its terms in ascending column order; forward substitution ascending, back-substitution DESCENDING.
+ *   No floating-point atomic: two runs give identical bytes.  No bit claim against the reference: its order inside a point follows
+ *   std::map<KeyFrame*, ..>, pointer values.
+ * Out of scope: mpCamera2 / EdgeSE3ProjectXYZToBody, the inertial and merge forms, pbStopFlag in mid-optimisation (the host looks at it once before
+ *   the call, :1406).
+ *
+ *   xfh_lba_edge          host, stateless: one binary edge at pose7 = (qx, qy, qz, qw, tx, ty, tz) and point3 -> error[3], chi2, the pose Jacobian [3][6], the
+ *                         point Jacobian [3][3] (third rows zero and error[2] = 0 for a mono edge, obs3[2] < 0) and rho[1]; any output may be NULL.
+ *   xfh_lba_point_block   (H6 + lambda I)^-1, H6 = the upper triangle row by row -> Dinv9 row-major.
+ *   xfh_lba_solve         the LDL^T above on the lower triangle of S [n][n] (overwritten by L and d) -> 1 and x, or 0 with x untouched; n <= 768.
+ *   xfh_local_ba_workspace_bytes   bytes of d_workspace (0 for arguments the call would refuse).
+ *   xfh_local_ba_device   asynchronous on the ctx stream: nothing is read back, nothing is allocated.  A fixed schedule of 4 + 53 max_iterations + 2
+ *                         launches (536 for optimize(10)) around a control block in the workspace; each kernel returns at once when its step is not
+ *                         wanted.  No graph capture, no cooperative launch, no grid barrier; every loop has a bound that does not depend on the data.
+ *                         Outputs: d_Tcw_out [nK][12] (a fixed keyframe's: its input bits), d_points_out [nP][3], d_erase [nE] bytes, d_chi2 [nE] floats,
+ *                         d_header [10] ints: status, free keyframes, fixed keyframes that have an edge, mono edges, stereo edges, iterations, trials,
+ *                         rejected trials, factorisation failures, edges to erase; d_final_chi2: currentChi of the last iteration.  write_back = 1 also
+ *                         scatters Tcw_out of the free keyframes and points_out of the points with an edge into the two tables in place.
+ *                         XFH_ERR_INVALID_ARG before any launch: n_free > XFH_LBA_MAX_FREE (or < 0, or > nK); nK, nP or nE < 1 (or nK > 65535, nP > 2^22,
+ *                         nE > 2^24); pose_rows or point_rows < 1; max_iterations outside 1 .. 10; write_back outside 0 .. 1; a NULL pointer; a misaligned
+ *                         pointer (16 bytes for the workspace, 8 for d_final_chi2, 4 for floats and ints); an inv_sigma2 that is not finite or not > 0.
+ *                         Points, poses, observations, indices and the CSR may hold anything, NaN and Inf included: the call terminates and no load or
+ *                         store leaves the buffers the caller named.
+ *   xfh_local_ba          host-pointer form through the ctx staging arena (the tables are copied back when write_back is set).
+ *   xfh_local_ba_host     the whole rule on ONE host thread over host pointers (workspace included): the kernels' own lines, no ctx, no GPU. */
+#define XFH_LBA_MAX_FREE 128
+#define XFH_LBA_MAX_ITERATIONS 10
+#define XFH_LBA_HEADER_INTS 10
+enum { XFH_LBA_OK = 0, XFH_LBA_ABORTED = 1, XFH_LBA_NOTHING_FREE = 2, XFH_LBA_FREE_MISMATCH = 3 };
+int xfh_lba_edge(const double* pose7, const double* point3, const xfh_camera* cam, const float* obs3, float inv_sigma2, double* error3, double* chi2,
+                 double* jacobian_pose18, double* jacobian_point9, double* rho1);
+int xfh_lba_point_block(const double* H6, double lambda, double* Dinv9);
+int xfh_lba_solve(int n, double* S, const double* b, double* x);
+size_t xfh_local_ba_workspace_bytes(int nK, int nP, int nE, int n_free);
+int xfh_local_ba_device(xfh_ctx* ctx, int nK, int n_free, int nP, int nE, float* d_pose_table, int pose_rows, float* d_point_table, int point_rows,
+                        const int* d_kf_row, const uint8_t* d_kf_fixed, const int* d_point_row, const int* d_edge_begin, const int* d_edge_kf,
+                        const float* d_edge_obs, const xfh_camera* cam, float inv_sigma2, int max_iterations, int write_back, void* d_workspace, float* d_Tcw_out,
+                        float* d_points_out, uint8_t* d_erase, float* d_chi2, int* d_header, double* d_final_chi2);
+int xfh_local_ba(xfh_ctx* ctx, int nK, int n_free, int nP, int nE, float* pose_table, int pose_rows, float* point_table, int point_rows, const int* kf_row,
+                 const uint8_t* kf_fixed, const int* point_row, const int* edge_begin, const int* edge_kf, const float* edge_obs, const xfh_camera* cam,
+                 float inv_sigma2, int max_iterations, int write_back, float* Tcw_out, float* points_out, uint8_t* erase, float* chi2, int* header,
+                 double* final_chi2);
+int xfh_local_ba_host(int nK, int n_free, int nP, int nE, float* pose_table, int pose_rows, float* point_table, int point_rows, const int* kf_row,
+                      const uint8_t* kf_fixed, const int* point_row, const int* edge_begin, const int* edge_kf, const float* edge_obs, const xfh_camera* cam,
+                      float inv_sigma2, int max_iterations, int write_back, void* workspace, float* Tcw_out, float* points_out, uint8_t* erase, float* chi2,
+                      int* header, double* final_chi2);
+
 /* ---- MLPnPsolver (src/MLPnPsolver.cpp) as Tracking::Relocalization drives it (src/Tracking.cc:3678-3773) ------------------------------------------
  * The step between xfh_bow_search_device (shared = 2: the current frame against the B relocalisation candidates) and xfh_pose_optimize_device:
  * the PnP RANSAC over 6-point sets.  B problems per call, one candidate keyframe each; inputs as xfh_pose_optimize_device takes them: d_xy_un

@@ -33,7 +33,9 @@ enum {
     XFH_K_SIM3SOLVE_PREPARE = 45, XFH_K_SIM3SOLVE_FIT = 46, XFH_K_SIM3SOLVE_COUNT = 47, XFH_K_SIM3SOLVE_DECIDE = 48, XFH_K_SIM3SOLVE_MERGE = 49,
     XFH_K_MLPNP_PREPARE = 50, XFH_K_MLPNP_FIT = 51, XFH_K_MLPNP_COUNT = 52, XFH_K_MLPNP_RECORDS = 53, XFH_K_MLPNP_REFINE = 54, XFH_K_MLPNP_DECIDE = 55,
     XFH_K_SIM3_OPTIMIZE = 56,
-    XFH_K_COUNT = 57
+    XFH_K_LBA_PLAN = 57, XFH_K_LBA_LINEARIZE = 58, XFH_K_LBA_POINT_BUILD = 59, XFH_K_LBA_BEGIN = 60, XFH_K_LBA_SCHUR = 61, XFH_K_LBA_SOLVE = 62,
+    XFH_K_LBA_UPDATE = 63, XFH_K_LBA_EVALUATE = 64, XFH_K_LBA_DECIDE = 65, XFH_K_LBA_FINISH = 66,
+    XFH_K_COUNT = 67
 };
 /* layer_mask selects conv layers for XFH_K_CONV_*: 0 = every layer, else bit i = BasicLayer i
  * (0..22 in XFeatModel order) and bit 23 = block_fusion.2 */

@@ -236,6 +236,8 @@ struct S3MergeArgs;
 hipError_t launch_sim3_merge(xfh_ctx* c, const S3MergeArgs& a);
 struct MlArgs;
 hipError_t launch_mlpnp_solve(xfh_ctx* c, const MlArgs& a);                              // mlpnp.hip.h
+struct LbaArgs;
+hipError_t launch_local_ba(xfh_ctx* c, const LbaArgs& a);                                // lba.hip.h
 struct VocabArgs;
 hipError_t launch_bow_transform(xfh_ctx* c, const VocabArgs& a, int B);             // vocab_transform.hip.h
 struct BowDbArgs;
