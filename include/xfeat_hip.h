@@ -1755,7 +1755,10 @@ int xfh_sim3_optimize_host(int B, int n1, int M1, int nq, int n2, int side1_shar
  *   S = Hpp + lambda I - sum W Dinv W^T, b_S = b_p - sum (W Dinv) b_l.  The pose step: a dense unpivoted LDL^T of S in fp64 that fails at the first pivot
  *   not > 0 (a STATED DEVIATION, as in the two existing optimisers, here standing in for SimplicialLDLT with an AMD ordering).  The point steps by
  *   back-substitution x_l = Dinv (b_l - sum W^T x_p).  After a failed factorisation x (poses and points) keeps its previous values (zero before the first),
- *   the update is applied all the same and tempChi = DBL_MAX.  computeScale runs over ALL unknowns, landmarks included.  rho, lambda, ni, the ten-trial
+ *   the update is applied all the same and tempChi = DBL_MAX.  The pivots of S alone decide, as the matrix alone does in LinearSolverEigen::solve: an
+ *   infinite observation gives chi2 = e0 (w e0) + e1 (w e1) = Inf and rho1 = delta / sqrt(Inf) = 0, so H stays finite while b = 0 * Inf is NaN; no
+ *   pivot fails, x is NaN and the trial is rejected on a NaN rho.  (A STATED DEVIATION: the reference's chi2 is a dense information * error product,
+ *   whose 0 * Inf makes chi2, rho1 and H NaN for the same edge.)  computeScale runs over ALL unknowns, landmarks included.  rho, lambda, ni, the ten-trial
  *   limit, rho == 0 and the three-bad-iterations stop are exactly xfh_pose_optimize_device's Levenberg paragraph; at most max_iterations x 10 trials.
  * Classification.  erase = chi2 > 5.991 (7.815 stereo; doubles, as e->chi2() is compared there) || !isDepthPositive().  chi2 reads _error as the last
  *   computeActiveErrors() left it: after a rejected last trial that is the error at the REJECTED estimate (the stale-error rule of the two existing

@@ -1,6 +1,8 @@
 /*
  * xfeat_hip_bench.h -- measurement and debugging entry points of libxfeat_hip.so.  NOT part of the drop-in boundary
  * (include/xfeat_hip.h): nothing a SLAM consumer calls lives here.  bench.py, tools/ and tests/ use these through ctypes.
+ * Kernel timers, the match benchmarks, intermediate tensors, and single stages on caller-made input for tests: xfh_debug_select
+ * (tests/test_gpu_select.py) and xfh_debug_lba_solve (the LDL^T kernel of LocalBundleAdjustment, tests/test_gpu_lba_solve.py).
  */
 #ifndef XFEAT_HIP_BENCH_H
 #define XFEAT_HIP_BENCH_H
@@ -87,6 +89,13 @@ int xfh_debug_tensor(xfh_ctx* ctx, int id, int frame, float* out, size_t capacit
 int xfh_debug_select(xfh_ctx* ctx, const unsigned long long* keys, int n, int width, int lap0, int lap1, int form,
                      unsigned long long* sel_out, int* n_out, int* hdr_out);
 
+/* The factorisation stage of xfh_local_ba_device alone on a caller-made system (tests/test_gpu_lba_solve.py): k_lba_solve, the kernel the schedule
+ * launches and no copy of it, ONCE, as the TRIAL step of iteration 0, on a workspace laid out as the call lays it out (n / 6 free keyframes) in the ctx
+ * staging arena.  Every byte of that workspace is ws_fill (its low 8 bits) except the control block, S [n][n] row-major, b [n] and x [n], which hold what
+ * the caller hands in: x = "the previous solve's values".  On return S is as the kernel left it (the lower triangle L and d down to the column where it
+ * stopped, the strict upper triangle untouched), x the solution or -- after a failed factorisation -- its input bits, *solved the control block's flag
+ * (1, or 0 at the first pivot that is not > 0).  XFH_ERR_INVALID_ARG: n not a multiple of 6 in 6 .. 768, a NULL pointer.  Synchronous. */
+int xfh_debug_lba_solve(xfh_ctx* ctx, int n, double* S, const double* b, double* x, int ws_fill, int* solved);
 
 /* Counter calibration (MI355X_MICROARCH.md, HBM section: "calibrate on a known byte count in your own access pattern before
  * trusting an absolute"): `iters` launches of a kernel that moves exactly `nbytes` per launch (a buffer far larger than the

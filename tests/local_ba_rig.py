@@ -1,6 +1,9 @@
 """Seeded scenes for xfh_local_ba_device and its restatements (tests/ref_local_ba.py, tests/ref_local_ba_literal.py): keyframes on a baseline that see a
 cloud of points, mono and stereo, with noise, gross outliers, starts far from the optimum, keyframes of 0, 1, 255, 256 and 257 edges and the other
-cases the tests name.  SCENES is the table whose condition tests/test_local_ba_ref.py::test_rig_condition measures on the CPU and which the GPU tests
+cases the tests name; wide / wide_far (nK 266, 520 points, 3496 edges: chi2 folds of more than 256 terms, keyframes of 400, 511, 512, 513 and 520 edges),
+idle_keyframes (nK 300 the largest dimension, 295 keyframes without an edge), far_start at 1 and 3 iterations, outliers at inv_sigma2 = float32(1 / 1.44)
+and 4 (30 and 34 edges to erase against 31 at 1); FAILING, three scenes in which a NaN makes every factorisation fail and one in which an Inf leaves b_S
+NaN behind a factorisation that holds.  SCENES is the table whose condition tests/test_local_ba_ref.py::test_rig_condition measures on the CPU and which the GPU tests
 compare under LBA_TOL; run_host() runs a problem through xfh_local_ba_host, LbaRig on the device with the outputs, the workspace and both tables
 between guard bytes."""
 import collections
@@ -27,6 +30,8 @@ Tol = collections.namedtuple("Tol", "tcw points chi2 final")
 # coordinate, and of max(chi2, threshold)), final_chi2 relative to max(final_chi2, 5.991); not below 1 float step and 1e-13 relative.  Seen: Tcw_out 0.25
 # and points_out 0.002 of a step, chi2 5 steps (random scene 112), final_chi2 4.8e-8 (random scene 134): both between the rule and its libm-jittered runs, on scenes of 6 to 24 points with two to four
 # observations each.
+# On the scenes added for the wraps and the weights: wide chi2 0.25 of a step and final_chi2 3.1e-11, wide_far 0.5 and 8.2e-12, idle_keyframes 0 and 2.4e-13,
+# far_start_1it / _3it 0 and 9.3e-14, outliers_w0694 / _w4 0 and 5.9e-15; Tcw_out and points_out 0 on all of them.  FAILING: the forms agree NaN for NaN.
 # That test fails if it sees more than half of these.  Nothing from the device is in them.
 LBA_TOL = Tol(tcw=1, points=1, chi2=10, final=1e-7)
 
@@ -41,7 +46,7 @@ def _rot(rv):
 
 
 def make(seed, n_free, n_fixed, nP, per_point, kind="mixed", noise=0.4, pose_noise=0.01, point_noise=0.03, outliers=0.0, init_fixed=True, sees=None,
-         max_iterations=10, extra=None):
+         max_iterations=10, extra=None, inv_sigma2=1.0):
     """kind: mono | stereo | mixed.  Keyframe order: [the initial keyframe, fixed inside the local set] + free + fixed.  per_point: how many keyframes
     see a point (drawn), or None with sees = a bool matrix (nK, nP)."""
     rng = np.random.RandomState(seed)
@@ -82,7 +87,7 @@ def make(seed, n_free, n_fixed, nP, per_point, kind="mixed", noise=0.4, pose_noi
         pose_table[kf_row[k]] = np.concatenate([Rk, tk[:, None]], 1).reshape(12).astype(F)
     point_table[point_row] = (X + rng.normal(0, point_noise, X.shape)).astype(F)
     p = dict(pose_table=pose_table, point_table=point_table, kf_row=kf_row, kf_fixed=fixed, point_row=point_row, edge_begin=np.array(edge_begin, np.int32),
-             edge_kf=np.array(edge_kf, np.int32), edge_obs=np.array(edge_obs, F).reshape(-1, 3), cam=CAM, inv_sigma2=1.0, max_iterations=max_iterations)
+             edge_kf=np.array(edge_kf, np.int32), edge_obs=np.array(edge_obs, F).reshape(-1, 3), cam=CAM, inv_sigma2=float(F(inv_sigma2)), max_iterations=max_iterations)
     if extra:
         extra(p, rng)
     return p
@@ -122,6 +127,42 @@ def _no_fixed_edge(p, rng):
     p["edge_kf"][p["kf_fixed"][np.clip(p["edge_kf"], 0, len(p["kf_row"]) - 1)] != 0] = -1
 
 
+def _wide_sees():
+    """nK = 266, 520 points: the initial keyframe and the first fixed camera see every point, the free keyframes 1 .. 4 the first 400, 511, 512 and 513 (a
+    second and a third pass of the 256 lanes, by one lane and by whole waves), each of the other 260 fixed cameras two points"""
+    s = np.zeros((266, 520), bool)
+    s[0] = s[5] = True
+    for k, n in zip(range(1, 5), (400, 511, 512, 513)):
+        s[k, :n] = True
+    for k in range(6, 266):
+        s[k, (2 * k) % 520] = s[k, (2 * k + 1) % 520] = True
+    return s
+
+
+def _idle_sees():
+    """nK = 300, six points, 27 edges: nK is the largest of (nK, nP, nE); 295 keyframes have no edge"""
+    s = np.zeros((300, 6), bool)
+    s[0] = s[1] = s[299] = True
+    s[2, :4] = True
+    s[150, 1:] = True
+    return s
+
+
+def _nth_edge_of(p, k, n):
+    return int(np.nonzero(np.asarray(p["edge_kf"]) == k)[0][n])
+
+
+def _bad_obs(k, column, value):
+    """the sixth edge of keyframe k gets `value` in one entry of its observation"""
+    def extra(p, rng):
+        p["edge_obs"][_nth_edge_of(p, k, 5), column] = value
+    return extra
+
+
+def _nan_point(p, rng):
+    p["point_table"][p["point_row"][7], 2] = np.nan
+
+
 SCENES = {
     "one_free": lambda: make(1, 1, 1, 14, 2, "stereo", init_fixed=False),
     "two_free_mono": lambda: make(2, 2, 1, 40, 3, "mono"),
@@ -133,17 +174,34 @@ SCENES = {
     "outliers": lambda: make(8, 4, 2, 80, 4, "mixed", outliers=0.12),
     "special": lambda: make(9, 3, 2, 30, 3, "mixed", extra=_special),
     "seen_by_all": lambda: make(10, 3, 2, 25, 6, "mixed"),
+    # the strides and grids no scene above wraps: chi2 folds over nK = 266 and 300 terms, keyframes of 400 .. 520 edges, nK the largest dimension
+    "wide": lambda: make(40, 4, 261, 520, None, "mixed", sees=_wide_sees()),
+    "wide_far": lambda: make(40, 4, 261, 520, None, "mixed", sees=_wide_sees(), pose_noise=0.08, point_noise=0.5, outliers=0.05),
+    "idle_keyframes": lambda: make(42, 2, 297, 6, None, "mixed", sees=_idle_sees()),
+    "far_start_1it": lambda: make(7, 3, 2, 50, 4, "mixed", pose_noise=0.08, point_noise=0.5, max_iterations=1),
+    "far_start_3it": lambda: make(7, 3, 2, 50, 4, "mixed", pose_noise=0.08, point_noise=0.5, max_iterations=3),
+    # an information weight other than 1 (the workload's own is 1: octave 0)
+    "outliers_w0694": lambda: make(8, 4, 2, 80, 4, "mixed", outliers=0.12, inv_sigma2=1 / 1.44),
+    "outliers_w4": lambda: make(8, 4, 2, 80, 4, "mixed", outliers=0.12, inv_sigma2=4.0),
 }
 EARLY = {
     "aborted": lambda: make(20, 2, 1, 20, 3, "mixed", extra=_no_fixed_edge),
     "nothing_free": lambda: make(21, 0, 2, 20, 2, "mixed"),
+}
+# every factorisation fails (a NaN reaches S), or none does although b_S is NaN (the Inf: rho1 = delta / sqrt(Inf) = 0 keeps H finite and makes b = 0 * Inf):
+# keyframes 0 fixed (initial), 1 .. 3 free, 4 and 5 fixed
+FAILING = {
+    "nan_obs_free": lambda: make(41, 3, 2, 40, 4, "mixed", extra=_bad_obs(1, 0, np.nan)),
+    "nan_obs_fixed": lambda: make(41, 3, 2, 40, 4, "mixed", extra=_bad_obs(5, 0, np.nan)),
+    "nan_point": lambda: make(41, 3, 2, 40, 4, "mixed", extra=_nan_point),
+    "inf_obs_free": lambda: make(41, 3, 2, 40, 4, "mixed", extra=_bad_obs(1, 1, np.inf)),
 }
 LIMIT = {"limit_128": lambda: make(30, 128, 2, 300, 4, "mixed", max_iterations=2)}     # S is 768 x 768: the refusal limit itself
 
 
 @functools.lru_cache(maxsize=None)
 def scene(name):
-    return {**SCENES, **EARLY, **LIMIT}[name]()
+    return {**SCENES, **EARLY, **LIMIT, **FAILING}[name]()
 
 
 def random_small(k):
@@ -212,24 +270,34 @@ def forms_of(name):
 
 
 # ---- distances ----------------------------------------------------------------------------------------------------------------------------------------
+def _apart(a, b):
+    """|a - b| entry by entry; 0 where both hold the same value (the same infinity included) or both a NaN, inf where one alone holds a NaN"""
+    a, b = np.asarray(a, D), np.asarray(b, D)
+    na, nb = np.isnan(a), np.isnan(b)
+    with np.errstate(all="ignore"):
+        return np.where((a == b) | (na & nb), 0.0, np.where(na | nb, np.inf, np.abs(a - b)))
+
+
 def _steps(a, b, mag):
     a, b = np.asarray(a, D), np.asarray(b, D)
     if a.size == 0:
         return 0.0
     with np.errstate(all="ignore"):
-        return float(np.max(np.abs(a - b) / np.spacing(F(mag))))
+        return float(np.max(_apart(a, b) / np.spacing(F(mag))))
 
 
 def distances(a, b):
     Ta, Tb = np.asarray(a["Tcw_out"], D).reshape(-1, 3, 4), np.asarray(b["Tcw_out"], D).reshape(-1, 3, 4)
-    tmag = np.maximum(np.max(np.abs(Ta[:, :, 3]), initial=1.0), 1.0)
+    tmag = np.maximum(np.nanmax(np.abs(Ta[:, :, 3]), initial=1.0), 1.0)
     tcw = max(_steps(Ta[:, :, :3], Tb[:, :, :3], 1.0), _steps(Ta[:, :, 3], Tb[:, :, 3], tmag))
-    pmag = max(float(np.max(np.abs(a["points_out"]), initial=1.0)), 1.0)
+    pmag = max(float(np.nanmax(np.abs(a["points_out"]), initial=1.0)), 1.0)
     ca, cb = np.asarray(a["chi2"], D), np.asarray(b["chi2"], D)
     with np.errstate(all="ignore"):
-        chi = float(np.max(np.abs(ca - cb) / np.spacing(np.maximum(np.maximum(ca, cb), 5.991).astype(F)).astype(D), initial=0.0))
+        mag = np.where(np.isfinite(ca) & np.isfinite(cb), np.maximum(np.maximum(ca, cb), 5.991), 5.991)
+        chi = float(np.max(_apart(ca, cb) / np.spacing(mag.astype(F)).astype(D), initial=0.0))
     fa, fb = float(a["final_chi2"]), float(b["final_chi2"])
-    return dict(tcw=tcw, points=_steps(a["points_out"], b["points_out"], pmag), chi2=chi, final=abs(fa - fb) / max(fa, fb, 5.991))
+    fmag = max(fa, fb, 5.991) if np.isfinite(fa) and np.isfinite(fb) else 5.991
+    return dict(tcw=tcw, points=_steps(a["points_out"], b["points_out"], pmag), chi2=chi, final=float(_apart(fa, fb)) / fmag)
 
 
 def spread(forms):

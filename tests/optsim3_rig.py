@@ -31,11 +31,11 @@ def _to_world(T, Pc):
 
 
 def make(seed, n_pairs, n1, fix_scale=0, all_points=0, outliers=0, not_in_kf2=0, bad2=0, null1=0, null_assigned=0, behind=0, nan_z=0, noise=0.5,
-         start=(0.01, 0.03, 0.02), pin=None, spare=4, out_px=(30, 90)):
+         start=(0.01, 0.03, 0.02), pin=None, spare=4, out_px=(30, 90), w=(1.0, 1.0)):
     """-> a problem dict.  n_pairs good correspondences in KF2, then `outliers` more with a gross observation error, `not_in_kf2` more whose point is
     not in KF2 (an edge pair only with all_points), and keypoints that look matched but have no edge: bad2 (flag byte 0), null1 (point1 outside its
     range), null_assigned (assigned beyond nq), behind (z < 0 in camera 2), nan_z.  start = size of the perturbation (rotation, translation, log
-    scale).  pin: keypoint numbers that carry a good pair whatever the seed."""
+    scale).  pin: keypoint numbers that carry a good pair whatever the seed.  w = (inv_sigma2_1, inv_sigma2_2), drawn from nothing: the scene is the same."""
     rng = np.random.RandomState(seed)
     fx, fy, cx, cy = CAM
     n_edge = n_pairs + outliers + not_in_kf2
@@ -94,7 +94,7 @@ def make(seed, n_pairs, n1, fix_scale=0, all_points=0, outliers=0, not_in_kf2=0,
     st = R.oplus(np.r_[rng.randn(3) * start[0], rng.randn(3) * start[1], rng.randn() * start[2]], true, fix_scale)
     return dict(T1w=T1w, xy_un1=np.nan_to_num(xy1).astype(F), point1=point1, points1=points1, assigned=assigned, points2=points2, flags2=flags2, index2=index2,
                 xy_un2=np.nan_to_num(xy2).astype(F), T2w=T2w, S12=R.state_to(st), Tmw=Tmw, cam1=CAM, cam2=CAM, th2=TH2, fix_scale=fix_scale,
-                all_points=all_points, inv_sigma2_1=1.0, inv_sigma2_2=1.0)
+                all_points=all_points, inv_sigma2_1=float(F(w[0])), inv_sigma2_2=float(F(w[1])))
 
 
 def edge_pins(n1):
@@ -105,7 +105,10 @@ def edge_pins(n1):
 # name -> arguments of make().  Between them: fix_scale 0 and 1; all_points 0 and 1 with points not in KF2 (their obs2 is the normalised pair); bad
 # and NULL points on either side; z < 0 in camera 2 and a NaN z; 0 % outliers (n_more = 5) and 20 % (n_more = 10); n_corr - n_bad of exactly 9 and
 # exactly 10; no pair; one pair; n1 of 1, 255, 256, 257 and 1024 / 1025, the two sides of the size at which the kernel instance changes, and
-# XFH_GRID_MAX_N; pairs on the first and the last keypoint.  No scene has more than about 600 edges.
+# XFH_GRID_MAX_N; pairs on the first and the last keypoint.  No scene has more than about 600 edges.  out100_w, out100_w_swap and out100_fix_w carry
+# information weights (0.694444, 1.44), the swap, and the first again with a fixed scale: the rule's final_chi2 is 93.745 and 87.912 for the two orders
+# (85.249 at (1, 1)), so weights exchanged between the two edge directions cannot pass.  The spread of the float64 forms on the three: state 8.7e-9,
+# S12_out 0.125 and chi2 2.0 float32 steps, final_chi2 1.5e-10 -- under half of SIM3OPT_TOL, which test_spread_of_the_reference enforces.
 SCENES = {
     "none": dict(seed=1, n_pairs=0, n1=40, bad2=3, null1=3, null_assigned=2, behind=2, nan_z=0),
     "one_n1": dict(seed=2, n_pairs=1, n1=1),
@@ -125,6 +128,10 @@ SCENES = {
     "keep9_ws": dict(seed=4, n_pairs=9, n1=64, outliers=3, out_px=(60, 90), fix_scale=1, all_points=1),   # the two neighbours of ws300 in WS_BATCH3
     "out100_ws": dict(seed=9, n_pairs=80, n1=300, outliers=20, fix_scale=1, all_points=1, not_in_kf2=5, start=(0.02, 0.05, 0.0)),
     "max": dict(seed=15, n_pairs=200, n1=16384, outliers=40, pin={0, 16383}),
+    # information weights other than 1, different on the two sides (the workload's own are 1: octave 0); the swap has another final_chi2
+    "out100_w": dict(seed=8, n_pairs=80, n1=257, outliers=20, pin=edge_pins(257), bad2=4, null1=4, null_assigned=3, behind=3, w=(0.694444, 1.44)),
+    "out100_w_swap": dict(seed=8, n_pairs=80, n1=257, outliers=20, pin=edge_pins(257), bad2=4, null1=4, null_assigned=3, behind=3, w=(1.44, 0.694444)),
+    "out100_fix_w": dict(seed=9, n_pairs=80, n1=300, outliers=20, fix_scale=1, start=(0.02, 0.05, 0.0), w=(0.694444, 1.44)),
 }
 BATCH3 = ("out100", "keep9", "clean30")                                 # B = 3: different pair counts, the middle one returns early
 WS_BATCH3 = ("ws300", "keep9_ws", "out100_ws")                           # the same in the workspace instance (n1 = 3000)

@@ -83,8 +83,9 @@ def point_block(H6, lam):
         return np.stack([c00 * inv, c10 * inv, c20 * inv, c10 * inv, d4, d5, c20 * inv, d5, d8], -1)
 
 
-def ldlt_solve(S, b, x_old):
-    """the right-looking LDL^T on the lower triangle of S (a copy is factorised) -> ok, x, pivots [(d_k, |S_kk| before the updates)]"""
+def ldlt_factor(S, b, x_old):
+    """the right-looking LDL^T on the lower triangle of S (a copy is factorised) -> ok, x, pivots [(d_k, |S_kk| before the updates)], the copy as the
+    factorisation left it: L below the diagonal and d on it, down to the column at which it stopped (the copy's upper triangle means nothing)"""
     S = np.array(S, D)
     n = len(b)
     diag0 = np.abs(np.diag(S)).copy()
@@ -94,7 +95,7 @@ def ldlt_solve(S, b, x_old):
             dk = S[k, k]
             piv.append((float(dk), float(diag0[k])))
             if not dk > 0.0:
-                return False, np.array(x_old, D), piv
+                return False, np.array(x_old, D), piv, S
             S[k + 1:, k] = S[k + 1:, k] / dk
             col = S[k + 1:, k]
             S[k + 1:, k + 1:] = S[k + 1:, k + 1:] - col[:, None] * col[None, :] * dk
@@ -104,7 +105,12 @@ def ldlt_solve(S, b, x_old):
         y = y / np.diag(S)
         for k in range(n - 1, -1, -1):
             y[:k] = y[:k] - S[k, :k] * y[k]
-    return True, y, piv
+    return True, y, piv, S
+
+
+def ldlt_solve(S, b, x_old):
+    """-> ok, x, pivots of ldlt_factor"""
+    return ldlt_factor(S, b, x_old)[:3]
 
 
 def lambda_init(diag):

@@ -35,8 +35,10 @@ class Edge:
         self.error = np.array([float(er[0]), float(er[1]), float(er[2])], D)
 
     def chi2(self, w):
+        """sum_r e_r (w e_r), as include/xfeat_hip.h states it: the information is w I, and no product with one of its zeros is formed (an infinite
+        component makes chi2 Inf, not 0 * Inf)"""
         n = 3 if self.stereo else 2
-        return float(self.error[:n] @ (w * np.eye(n)) @ self.error[:n])
+        return float(sum(self.error[r] * (w * self.error[r]) for r in range(n)))
 
     def jacobians(self, cam):
         """linearizeOplus -> (rows x 3, rows x 6)"""
@@ -136,11 +138,11 @@ def literal(p):
                         bS[6 * i:6 * i + 6] -= Y @ bl[id(v)]
                         for j in seen:
                             S[6 * i:6 * i + 6, 6 * j:6 * j + 6] -= Y @ W[(j, id(v))].T
-                ok = bool(np.isfinite(S).all() and np.isfinite(bS).all())
+                ok = bool(np.isfinite(S).all())                               # LinearSolverEigen::solve judges the matrix alone: a NaN in b makes a NaN x
                 if ok:
                     try:
                         np.linalg.cholesky((S + S.T) / 2)
-                        x_pose = np.linalg.solve(S, bS)
+                        x_pose = np.linalg.solve(S, bS) if np.isfinite(bS).all() else np.full(6 * nF, np.nan)
                     except np.linalg.LinAlgError:
                         ok = False
                 if ok:

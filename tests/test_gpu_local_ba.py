@@ -5,8 +5,11 @@ Within LBA_TOL -- the spread of the float64 forms among themselves, measured on 
 and final_chi2.  The scenes reach 1, 2, 11, 22 and 128 free keyframes (the factorisation has no tile: one workgroup of 1024 lanes strides over the
 trailing matrix, which 11 free keyframes already cross; 128 is the refusal limit and S's full 768 x 768), keyframes of 0, 1, 255, 256 and 257 edges
 (the 256-lane fold), points seen once, twice and by every keyframe, a point without an edge, edge indices out of range, the initial keyframe fixed
-inside the local set, a start far from the optimum (rejected trials), gross outliers and a point that ends behind a camera.  No test asserts the
-device's trajectory of lambda."""
+inside the local set, a start far from the optimum (rejected trials), gross outliers and a point that ends behind a camera; chi2 folds over 266 and
+300 keyframes (a second step of the fold's stride), keyframes of 400 to 520 edges (a second and a third pass of the 256 lanes, whole waves of them),
+nK as the largest of (nK, nP, nE), max_iterations of 1 and 3, and information weights of 1 / 1.44 and 4.  G.FAILING: a NaN observation at a free and at a
+fixed keyframe and a NaN point -- all 100 factorisations fail, x stays zero, the header says so and every flag is the rule's -- and an Inf observation,
+after which no factorisation fails while b_S is NaN; their numbers are compared NaN for NaN.  No test asserts the device's trajectory of lambda."""
 import ctypes as C
 
 import numpy as np
@@ -19,7 +22,7 @@ from xfeatslam_amd import capi, local_ba
 pytestmark = pytest.mark.gpu
 F, D = np.float32, np.float64
 INVALID = 1
-ALL = list(G.SCENES) + list(G.EARLY) + list(G.LIMIT)
+ALL = list(G.SCENES) + list(G.EARLY) + list(G.LIMIT) + list(G.FAILING)
 
 
 @pytest.fixture(scope="module")

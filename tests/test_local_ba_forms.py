@@ -1,5 +1,6 @@
 """The rule of xfh_local_ba_device (tests/ref_local_ba.py) against the literal form (tests/ref_local_ba_literal.py: vertex and edge objects, sequential
-sums in g2o's order, push / pop, numpy.linalg for the point blocks and the reduced system) on the rig's scenes -- every decision equal -- and the spread
+sums in g2o's order, push / pop, numpy.linalg for the point blocks and the reduced system) on the rig's scenes, those of failing factorisations
+included -- every decision equal -- and the spread
 of the float64 forms among themselves (literal, rule, rule with jittered libm under three seeds, the library's host form), from which LBA_TOL of
 tests/local_ba_rig.py is taken.  Nothing from the device enters.  CPU only."""
 import numpy as np
@@ -10,7 +11,7 @@ import local_ba_rig as G
 STREAM = 200
 
 
-@pytest.mark.parametrize("name", list(G.SCENES) + list(G.EARLY) + list(G.LIMIT))
+@pytest.mark.parametrize("name", list(G.SCENES) + list(G.EARLY) + list(G.LIMIT) + list(G.FAILING))
 def test_rule_against_literal(name):
     """every erase flag, the status and the counts, and every accept / reject of every trial in every iteration, equal"""
     lit, rule = G.forms_of(name)[:2]

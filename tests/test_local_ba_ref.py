@@ -1,6 +1,7 @@
 """xfh_local_ba_host and the piece entry points (xfh_lba_edge, _point_block, _solve) against the Python rule (tests/ref_local_ba.py): the host form by
 bits on the rig and on 200 random small scenes, every piece against the rule and against an independent statement (central differences, numpy.linalg),
-a hand-made one-step case solved as ONE dense system without the Schur complement, every class of refusal, both early statuses, the sanitizer program,
+a hand-made one-step case solved as ONE dense system without the Schur complement, every class of refusal, both early statuses, the scenes in which every
+factorisation fails (a NaN) or none does although b is NaN (an Inf) with their written-out headers, the sanitizer program,
 and the condition the rig's scenes must hold for the GPU comparison to be a fair one.  CPU only."""
 import ctypes as C
 import os
@@ -31,6 +32,46 @@ def bits_equal(a, b):
 @pytest.mark.parametrize("name", list(G.SCENES) + list(G.EARLY) + list(G.LIMIT))
 def test_host_form_equals_the_rule_by_bits(name):
     assert bits_equal(G.host_of(name), G.rule_of(name)) == []
+
+
+def nan_matched(a, b):
+    """bits_equal where neither holds a NaN; a NaN for a NaN, whatever its bits (numpy's and the C++ default NaN differ in sign)"""
+    bad = []
+    for k in OUT + ("final_chi2",):
+        x, y = np.atleast_1d(np.asarray(a[k])), np.atleast_1d(np.asarray(b[k]))
+        if x.dtype.kind != "f":
+            if x.tobytes() != y.tobytes():
+                bad.append(k)
+            continue
+        nx, ny = np.isnan(x), np.isnan(y)
+        if not np.array_equal(nx, ny) or x[~nx].tobytes() != y[~ny].tobytes():
+            bad.append(k)
+    return bad
+
+
+# header: iterations, trials, rejected trials, factorisation failures; edges to erase; NaN chi2 among the outputs.  Where every factorisation fails x
+# stays zero, so every trial estimate IS the input: Tcw_out = the input, the flags are those of the input, a NaN chi2 is no flag and a NaN depth is one.
+FAILING_TABLE = {"nan_obs_free": ([10, 10, 10, 10], 128, 1), "nan_obs_fixed": ([10, 10, 10, 10], 128, 1), "nan_point": ([10, 10, 10, 10], 129, 4),
+                 "inf_obs_free": ([10, 10, 10, 0], 0, 160)}
+
+
+@pytest.mark.parametrize("name", list(G.FAILING))
+def test_failing_factorisations(name):
+    """a NaN observation at a free and at a fixed keyframe, a NaN point: S holds a NaN, all ten trials of all ten iterations fail at a pivot, the update
+    is applied all the same (x = 0) and tempChi = DBL_MAX.  An Inf observation: chi2 = Inf, rho1 = delta / sqrt(Inf) = 0, so H stays finite while
+    b = 0 * Inf is NaN -- no pivot fails, x is NaN, every trial is rejected on a NaN rho, and the stale-error rule leaves 160 NaN chi2.  The host form
+    equals the rule: header and flags exactly, the outputs by bits with NaNs matched by position."""
+    p, host, rule = G.scene(name), G.host_of(name), G.rule_of(name)
+    assert nan_matched(host, rule) == [], name
+    counts, erase, nans = FAILING_TABLE[name]
+    for got in (host, rule):
+        assert got["header"][0] == R.OK and got["header"][5:9].tolist() == counts and got["header"][9] == erase == int(got["erase"].sum()), (name, got["header"])
+        assert int(np.isnan(got["chi2"]).sum()) == nans, name
+        assert np.array_equal(got["Tcw_out"].view(np.uint32), np.asarray(p["pose_table"], F)[p["kf_row"]].view(np.uint32)), name
+        assert np.isnan(got["final_chi2"]) if name != "inf_obs_free" else got["final_chi2"] == np.inf, (name, got["final_chi2"])
+    e = int(np.nonzero(np.isnan(rule["chi2"]))[0][0])
+    if nans == 1:
+        assert not rule["erase"][e] and p["kf_fixed"][p["edge_kf"][e]] == (name == "nan_obs_fixed")
 
 
 def test_host_form_equals_the_rule_by_bits_on_200_random_scenes():
@@ -227,6 +268,16 @@ def test_rig_reaches_what_the_gpu_tests_name():
     assert behind, "no edge is erased for its depth alone"
     assert all(G.scene(n)["kf_fixed"][0] == 1 and G.scene(n)["kf_fixed"][1] == 0 for n in ("eleven_mixed", "outliers")), "the initial keyframe, fixed inside the local set"
     assert G.rule_of("far_start")["header"][7] > 0 and G.rule_of("outliers")["header"][9] > 10
+    # the wraps: chi2 folds of more than 256 terms, a second and a third pass of the 256 lanes over a keyframe's edges (by one lane and by whole waves),
+    # nK the largest dimension, and iteration limits other than 10 and 2
+    w, idle = G.scene("wide"), G.scene("idle_keyframes")
+    assert G.dims(w) == (266, 520, 3496) and np.bincount(w["edge_kf"], minlength=266)[:6].tolist() == [520, 400, 511, 512, 513, 520]
+    assert G.dims(idle) == (300, 6, 27) and max(G.dims(idle)) == 300 and int((np.bincount(idle["edge_kf"], minlength=300) == 0).sum()) == 295
+    assert G.rule_of("idle_keyframes")["header"][5:8].tolist() == [7, 15, 8] and G.rule_of("wide_far")["header"][9] > 100
+    assert G.rule_of("far_start_1it")["header"][5] == 1 and G.rule_of("far_start_3it")["header"][5] == 3
+    # weights other than 1 decide differently
+    assert [int(G.rule_of(n)["header"][9]) for n in ("outliers", "outliers_w0694", "outliers_w4")] == [31, 30, 34]
+    assert G.scene("outliers_w0694")["inv_sigma2"] == float(F(1 / 1.44)) and G.scene("outliers_w4")["inv_sigma2"] == 4.0
     assert any(ev[0] == "trial" and not ev[3] for ev in G.rule_of("far_start")["events"])
 
 

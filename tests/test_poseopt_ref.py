@@ -246,7 +246,7 @@ def test_rig_condition(models):
         print(n, a["header"].tolist(), a["reasons"], {k: f"{v:.1e}" for k, v in a["margins"].items()})
         assert min(a["margins"].values()) > MARGIN, (n, a["margins"])
         s = R.scene(n)
-        fresh = RP.literal(s["Tcw"], R.CAM, s["xy_un"], s["uright"], s["assigned"], s["points"], R.INV_SIGMA2, stale=False)
+        fresh = RP.literal(s["Tcw"], R.CAM, s["xy_un"], s["uright"], s["assigned"], s["points"], s["w"], stale=False)
         stale_visible += int((fresh["outlier"] != a["outlier"]).sum() + (fresh["chi2"].view(np.int32) != a["chi2"].view(np.int32)).sum())
     print(f"outputs that the stale-error rule changes, over the rig: {stale_visible}")
     lit = {n: m[0] for n, m in models.items()}
@@ -417,7 +417,10 @@ def test_header_helper_under_sanitizers(asan_exe):
     assert r.returncode == 0 and "asan_poseopt_test ok" in r.stdout, (r.stdout[-1000:], r.stderr[-3000:])
 
 
-@pytest.mark.parametrize("name", ["n2", "n9_mixed", "n63_mono_lost", "n64_stereo", "n65_mixed", "n257", "identical", "big"] + list(R.EDGE_SCENES) + list(R.MONO_SCENES))
+WEIGHTED = [n for n, kw in R.SCENES.items() if "w" in kw]
+
+
+@pytest.mark.parametrize("name", ["n2", "n9_mixed", "n63_mono_lost", "n64_stereo", "n65_mixed", "n257", "identical", "big"] + WEIGHTED + list(R.EDGE_SCENES) + list(R.MONO_SCENES))
 def test_the_kernels_loop_on_the_host_equals_the_rule(asan_exe, tmp_path, models, mono_models, name):
     """the state machine, the per-edge lines and the fold of k_pose_optimize, run by one thread of the sanitizer program: every output byte equals
     the rule's (the host's libm is the restatement's, so here even the doubles agree) -- on the all-mono scenes too, whose trajectory is decided in
@@ -425,7 +428,7 @@ def test_the_kernels_loop_on_the_host_equals_the_rule(asan_exe, tmp_path, models
     models = dict(models, **mono_models)
     s = R.scene(name)
     with open(tmp_path / "in.bin", "wb") as f:
-        f.write(struct.pack("<3i", s["nt"], s["nq"], int(s["uright"] is not None)) + s["Tcw"].astype(F).tobytes() + np.array(R.CAM, F).tobytes() + struct.pack("<f", R.INV_SIGMA2))
+        f.write(struct.pack("<3i", s["nt"], s["nq"], int(s["uright"] is not None)) + s["Tcw"].astype(F).tobytes() + np.array(R.CAM, F).tobytes() + struct.pack("<f", s["w"]))
         f.write(s["xy_un"].tobytes() + (s["uright"].tobytes() if s["uright"] is not None else b"") + s["assigned"].tobytes() + s["points"].tobytes())
     r = subprocess.run([asan_exe, str(tmp_path / "in.bin"), str(tmp_path / "out.bin")], capture_output=True, text=True, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0"))
     assert r.returncode == 0, (r.stdout[-1000:], r.stderr[-3000:])

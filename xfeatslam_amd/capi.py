@@ -312,6 +312,7 @@ SYMBOLS = [
     ("xfh_kernel_name", C.c_char_p, [_i]),
     ("xfh_debug_tensor", _i, [_vp, _i, _i, _vp, _sz, C.POINTER(_sz)]),
     ("xfh_debug_select", _i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    ("xfh_debug_lba_solve", _i, [_vp, _i, _vp, _vp, _vp, _i, _vp]),
 ]
 
 _lib = None

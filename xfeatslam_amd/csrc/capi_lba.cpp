@@ -1,8 +1,10 @@
-// capi_lba.cpp -- the entry points of include/xfeat_hip.h behind Optimizer::LocalBundleAdjustment (xfh_local_ba*, xfh_lba_edge, _point_block, _solve): the
+// capi_lba.cpp -- the entry points of include/xfeat_hip.h behind Optimizer::LocalBundleAdjustment (xfh_local_ba*, xfh_lba_edge, _point_block, _solve) and xfh_debug_lba_solve of
+// include/xfeat_hip_bench.h: the
 // pieces of the rule on the host (lba_math.h, the kernels' own lines), the whole rule on one host thread, the device form and the host-pointer form.
 #include "host_stage.h"
 #include "lba_math.h"
 #include <math.h>
+#include <string.h>
 
 static_assert(XFH_LBA_MAX_FREE_KF == XFH_LBA_MAX_FREE && XFH_LBA_HDR_INTS == XFH_LBA_HEADER_INTS && LBA_OK == XFH_LBA_OK && LBA_ABORTED == XFH_LBA_ABORTED &&
               LBA_NOTHING_FREE == XFH_LBA_NOTHING_FREE && LBA_FREE_MISMATCH == XFH_LBA_FREE_MISMATCH && XFH_LBA_ITERATIONS_MAX == XFH_LBA_MAX_ITERATIONS,
@@ -31,6 +33,16 @@ static LbaArgs lba_args(int nK, int n_free, int nP, int nE, float* pose_table, i
     a.w = (double)inv_sigma2;
     a.Tcw_out = Tcw_out; a.points_out = points_out; a.erase = erase; a.chi2 = chi2; a.header = header; a.final_chi2 = final_chi2; a.ws = (char*)ws;
     return a;
+}
+
+// the workspace image up, k_lba_solve once, the workspace image back (xfh_debug_lba_solve)
+static int lba_solve_staged(xfh_ctx* c, LbaArgs a, char* host, size_t bytes) {
+    HostStage s{c};
+    auto ws = s.add<char>(bytes, host, host, false);
+    if (const int rc = s.upload(); rc != XFH_OK) return rc;
+    a.ws = (char*)ws;
+    HIPCK(c, launch_lba_solve_alone(c, a));
+    return s.download();
 }
 
 extern "C" {
@@ -112,6 +124,30 @@ int xfh_local_ba(xfh_ctx* c, int nK, int n_free, int nP, int nE, float* pose_tab
                                        oT, oX, oe, oc, oh, of);
     if (rc != XFH_OK) return rc;
     return s.download();
+}
+
+// include/xfeat_hip_bench.h: k_lba_solve alone.  The workspace of a problem of one keyframe slot, one point and one edge with n / 6 free keyframes is made on
+// the host -- every byte ws_fill, then the control block at the TRIAL step of iteration 0 and S, b and x where lba_ws puts them -- and travels both ways whole.
+int xfh_debug_lba_solve(xfh_ctx* c, int n, double* S, const double* b, double* x, int ws_fill, int* solved) {
+    if (!c || n < 6 || n > 6 * XFH_LBA_MAX_FREE_KF || n % 6 != 0 || !S || !b || !x || !solved) return XFH_ERR_INVALID_ARG;
+    LbaArgs a = {};
+    a.nK = 1; a.nP = 1; a.nE = 1; a.n_free = n / 6; a.max_it = 1;
+    const size_t bytes = lba_ws(nullptr, a.nK, a.nP, a.nE, a.n_free).bytes, N = (size_t)n;
+    char* host = (char*)malloc(bytes);
+    if (!host) return XFH_ERR_OUT_OF_MEMORY;
+    memset(host, ws_fill & 255, bytes);
+    const LbaWs w = lba_ws(host, a.nK, a.nP, a.nE, a.n_free);
+    LbaCtl ctl = {};
+    ctl.act = LBA_TRIAL; ctl.iter = 0; ctl.max_it = 1; ctl.ni = 2.0; ctl.solved = -1;
+    *w.ctl = ctl;
+    memcpy(w.S, S, N * N * 8); memcpy(w.bS, b, N * 8); memcpy(w.xp, x, N * 8);
+    const int rc = lba_solve_staged(c, a, host, bytes);
+    if (rc == XFH_OK) {
+        memcpy(S, w.S, N * N * 8); memcpy(x, w.xp, N * 8);
+        *solved = w.ctl->solved;
+    }
+    free(host);
+    return rc;
 }
 
 }  // extern "C"

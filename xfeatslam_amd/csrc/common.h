@@ -238,6 +238,7 @@ struct MlArgs;
 hipError_t launch_mlpnp_solve(xfh_ctx* c, const MlArgs& a);                              // mlpnp.hip.h
 struct LbaArgs;
 hipError_t launch_local_ba(xfh_ctx* c, const LbaArgs& a);                                // lba.hip.h
+hipError_t launch_lba_solve_alone(xfh_ctx* c, const LbaArgs& a);                         // lba.hip.h (xfh_debug_lba_solve)
 struct VocabArgs;
 hipError_t launch_bow_transform(xfh_ctx* c, const VocabArgs& a, int B);             // vocab_transform.hip.h
 struct BowDbArgs;

@@ -248,3 +248,8 @@ hipError_t launch_local_ba(xfh_ctx* c, const LbaArgs& a) {
     launch_k(c, XFH_K_LBA_FINISH, -1, k_lba_header, dim3(1), dim3(64), 0, a);
     return hipGetLastError();
 }
+// xfh_debug_lba_solve: the schedule's k_lba_solve once, as the TRIAL step of iteration 0, on a workspace whose control block, S, b_S and x the caller made
+hipError_t launch_lba_solve_alone(xfh_ctx* c, const LbaArgs& a) {
+    launch_k(c, XFH_K_LBA_SOLVE, -1, k_lba_solve, dim3(1), dim3(XFH_LBA_SOLVE_THREADS), 0, a, 0);
+    return hipGetLastError();
+}
