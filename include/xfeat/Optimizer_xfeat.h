@@ -10,7 +10,9 @@
  * (include/xfeat_hip.h has the contract line by line).  XFoptimizer::OptimizeSim3 is Optimizer::OptimizeSim3 (:2100-2381) in the same way: one
  * Sim3 vertex, two projection edges per correspondence, as one call of xfh_sim3_optimize_device between the two Sim3 projection searches of loop
  * detection.  XFoptimizer::LocalBundleAdjustment is Optimizer::LocalBundleAdjustment (:1188-1460, the graph, optimize(10) and vToErase) as one call of
- * xfh_local_ba_device on the map's device tables.  Header only; needs nothing but xfeat_hip.h.
+ * xfh_local_ba_device on the map's device tables.  XFoptimizer::OptimizeEssentialGraph is Optimizer::OptimizeEssentialGraph (:1532-1779, the Sim3 pose graph
+ * of loop closing, optimize(20), the recovered poses and the corrected points) as one call of xfh_essential_graph_device on the same tables.  Header only;
+ * needs nothing but xfeat_hip.h.
  */
 #ifndef XFEAT_OPTIMIZER_XFEAT_H
 #define XFEAT_OPTIMIZER_XFEAT_H
@@ -26,7 +28,7 @@ namespace ORB_SLAM3 {
 class XFoptimizer {
 public:
     explicit XFoptimizer(xfh_ctx* c) : ctx(c) {}
-    ~XFoptimizer() { if (d_buf) xfh_dev_free(d_buf); if (d_s3) xfh_dev_free(d_s3); if (d_lba) xfh_dev_free(d_lba); }
+    ~XFoptimizer() { if (d_buf) xfh_dev_free(d_buf); if (d_s3) xfh_dev_free(d_s3); if (d_lba) xfh_dev_free(d_lba); if (d_eg) xfh_dev_free(d_eg); }
     XFoptimizer(const XFoptimizer&) = delete;
     XFoptimizer& operator=(const XFoptimizer&) = delete;
 
@@ -215,6 +217,76 @@ public:
     int lbaHeader[XFH_LBA_HEADER_INTS] = {};
     double lbaFinalChi2 = 0.0;
 
+    // ---- Optimizer::OptimizeEssentialGraph (reference src/Optimizer.cc:1501-1783) as LoopClosing::CorrectLoop calls it: the host keeps the walk over the map
+    // (:1532-1706: which keyframes, which edges pass minFeat / sInsertedEdges / hasChild, nIDr of every point) and hands the problem over as indices into
+    // the map's two device tables; the optimisation and the recovery (:1708-1779) are one call of xfh_essential_graph_device.  The host-side vectors are
+    // copied to the device here; the tables are corrected in place (write_back).
+    struct EssentialGraphInput {
+        float* d_poseTable; int poseRows;                       // [poseRows][12] row-major [R|t]
+        float* d_pointTable; int pointRows;                     // [pointRows][3]
+        std::vector<int> kfRow;                                 // vpKFs without the bad ones: the row of each in the pose table
+        std::vector<unsigned char> kfFixed;                     // 1 for mnId == pMap->GetInitKFid()
+        std::vector<int> correctedIndex, nonCorrectedIndex;     // per keyframe: its entry of CorrectedSim3 / NonCorrectedSim3 in sim3, or -1
+        std::vector<double> sim3;                               // [entries][8]: (qx, qy, qz, qw, tx, ty, tz, s) of a g2o::Sim3
+        std::vector<int> edgeI, edgeJ, edgeKind;                // vertex 0, vertex 1 (indices into kfRow) and the kind (0: a loop connection of :1577-1605,
+                                                                // 1: a spanning-tree, loop or covisibility edge of :1608-1706) in the reference's creation order
+        std::vector<int> pointRow, pointRef;                    // vpMPs without the bad ones: the row of each in the point table and the vertex of nIDr
+    };
+    // Returns the status (XFH_EG_OK, _NOTHING_FREE, _FREE_MISMATCH, _NO_EDGES).  SYNCHRONOUS, as xfh_essential_graph_device is: when it returns the header is
+    // on the host and the corrected poses and points are in device memory (deviceEgTcw(), deviceEgPoints()) and, with writeBack, in the tables.  After the call
+    // the host walks vpKFs and vpMPs once: SetPose(egPoses()), SetWorldPos(egMapPoints()) + UpdateNormalAndDepth, then pMap->IncreaseChangeIndex().
+    int OptimizeEssentialGraph(const EssentialGraphInput& in, bool bFixScale, bool writeBack = true, int iterations = XFH_EG_MAX_ITERATIONS) {
+        const int nV = (int)in.kfRow.size(), nE = (int)in.edgeI.size(), nP = (int)in.pointRow.size(), nS = (int)(in.sim3.size() / 8);
+        int nFree = 0;
+        for (unsigned char f : in.kfFixed) nFree += f ? 0 : 1;
+        const size_t ws = xfh_essential_graph_workspace_bytes(nV, nE, nFree);
+        if (ws == 0 || nP < 1 || nS < 1 || in.sim3.size() != (size_t)nS * 8 || in.kfFixed.size() != (size_t)nV || in.correctedIndex.size() != (size_t)nV ||
+            in.nonCorrectedIndex.size() != (size_t)nV || in.edgeJ.size() != (size_t)nE || in.edgeKind.size() != (size_t)nE || in.pointRef.size() != (size_t)nP)
+            throw std::runtime_error("XFoptimizer::OptimizeEssentialGraph: sizes out of range (more than XFH_EG_MAX_FREE free keyframes?)");
+        auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+        const size_t V = (size_t)nV, P = (size_t)nP, E = (size_t)nE;
+        const size_t sz[] = {al(ws), al(V * 4), al(V), al(V * 4), al(V * 4), al((size_t)nS * 64), al(E * 4), al(E * 4), al(E * 4), al(P * 4), al(P * 4),
+                             al(V * 64), al(V * 48), al(P * 12), al(E * 4), 256, 256};
+        const int NQ = (int)(sizeof(sz) / sizeof(sz[0]));
+        size_t need = 0;
+        for (size_t v : sz) need += v;
+        if (need > eg_bytes) {
+            if (d_eg) { xfh_synchronize(ctx); xfh_dev_free(d_eg); d_eg = nullptr; eg_bytes = 0; }
+            if (xfh_dev_alloc(&d_eg, need) != XFH_OK) throw std::runtime_error("XFoptimizer::OptimizeEssentialGraph: out of device memory");
+            eg_bytes = need;
+        }
+        char* q[17];
+        q[0] = (char*)d_eg;
+        for (int i = 1; i < NQ; ++i) q[i] = q[i - 1] + sz[i - 1];
+        d_egSim3 = (double*)q[11];
+        d_egTcw = (float*)q[12]; d_egPoints = (float*)q[13]; d_egChi2 = (float*)q[14];
+        egKF = nV; egPoints = nP; egEdges = nE;
+        int rc = xfh_synchronize(ctx);
+        const void* src[] = {in.kfRow.data(), in.kfFixed.data(), in.correctedIndex.data(), in.nonCorrectedIndex.data(), in.sim3.data(), in.edgeI.data(),
+                             in.edgeJ.data(), in.edgeKind.data(), in.pointRow.data(), in.pointRef.data()};
+        const size_t bytes_of[] = {V * 4, V, V * 4, V * 4, (size_t)nS * 64, E * 4, E * 4, E * 4, P * 4, P * 4};
+        for (int i = 0; i < 10 && rc == XFH_OK; ++i) rc = xfh_memcpy_h2d(q[1 + i], src[i], bytes_of[i]);
+        if (rc == XFH_OK) rc = xfh_essential_graph_device(ctx, nV, nFree, nE, nP, nS, in.d_poseTable, in.poseRows, in.d_pointTable, in.pointRows, (const int*)q[1],
+                                                          (const unsigned char*)q[2], (const int*)q[3], (const int*)q[4], (const double*)q[5], (const int*)q[6],
+                                                          (const int*)q[7], (const int*)q[8], (const int*)q[9], (const int*)q[10], bFixScale ? 1 : 0, iterations,
+                                                          writeBack ? 1 : 0, q[0], d_egSim3, d_egTcw, d_egPoints, d_egChi2, (int*)q[15], (double*)q[16]);
+        if (rc == XFH_OK) rc = xfh_memcpy_d2h(egHeader, q[15], XFH_EG_HEADER_INTS * 4);
+        if (rc == XFH_OK) rc = xfh_memcpy_d2h(&egFinalChi2, q[16], 8);
+        if (rc != XFH_OK) throw std::runtime_error(std::string("XFoptimizer::OptimizeEssentialGraph: ") + xfh_strerror(rc));
+        return egHeader[0];
+    }
+    // of the last OptimizeEssentialGraph, in device memory: the corrected poses [keyframes][12] = [R | t / s] and points [points][3]; and copies on request:
+    // egPoses(), egMapPoints(), egSim3() (the estimates [keyframes][8]) and egEdgeChi2().  LocalBundleAdjustment's getters keep speaking of LocalBundleAdjustment.
+    const float* deviceEgTcw() const { return d_egTcw; }
+    const float* deviceEgPoints() const { return d_egPoints; }
+    void egPoses(std::vector<float>& out) const { lbaGet(out, d_egTcw, (size_t)egKF * 12); }
+    void egMapPoints(std::vector<float>& out) const { lbaGet(out, d_egPoints, (size_t)egPoints * 3); }
+    void egSim3(std::vector<double>& out) const { lbaGet(out, d_egSim3, (size_t)egKF * 8); }
+    void egEdgeChi2(std::vector<float>& out) const { lbaGet(out, d_egChi2, (size_t)egEdges); }
+    // status, free keyframes, valid edges, loop-connection edges, iterations, trials, rejected trials, factorisation failures, corrected points
+    int egHeader[XFH_EG_HEADER_INTS] = {};
+    double egFinalChi2 = 0.0;
+
     int nInitialCorrespondences() const { return header[0]; }
     int nBad() const { return header[1]; }
     // n_initial, n_bad, the return value, rounds run, Levenberg iterations, trials, rejected trials, factorisation failures
@@ -232,6 +304,9 @@ private:
     void* d_lba = nullptr; size_t lba_bytes = 0;                     // LocalBundleAdjustment's own buffer
     float* d_lbaTcw = nullptr; float* d_lbaPoints = nullptr; unsigned char* d_lbaErase = nullptr; float* d_lbaChi2 = nullptr;
     int lbaKF = 0, lbaPoints = 0, lbaEdges = 0;
+    void* d_eg = nullptr; size_t eg_bytes = 0;                       // OptimizeEssentialGraph's own buffer
+    double* d_egSim3 = nullptr; float* d_egTcw = nullptr; float* d_egPoints = nullptr; float* d_egChi2 = nullptr;
+    int egKF = 0, egPoints = 0, egEdges = 0;
     template <class T> void lbaGet(std::vector<T>& out, const T* d, size_t count) const {
         out.assign(count, T());
         if (count > 0 && xfh_memcpy_d2h(out.data(), d, count * sizeof(T)) != XFH_OK) throw std::runtime_error("XFoptimizer: download failed");

@@ -1819,6 +1819,104 @@ int xfh_local_ba_host(int nK, int n_free, int nP, int nE, float* pose_table, int
                       float inv_sigma2, int max_iterations, int write_back, void* workspace, float* Tcw_out, float* points_out, uint8_t* erase, float* chi2,
                       int* header, double* final_chi2);
 
+/* ---- OptimizeEssentialGraph: the Sim3 pose graph behind the Sim3 Fuse of LoopClosing, on a blocked LDL^T, device resident --------------------------------
+ * Optimizer::OptimizeEssentialGraph(Map*, pLoopKF, pCurKF, NonCorrectedSim3, CorrectedSim3, LoopConnections, bFixScale) (src/Optimizer.cc:1501-1783) from
+ * the vertices to the corrected points (:1532-1779): optimize(20) of OptimizationAlgorithmLevenberg over BlockSolver_7_3 with setUserLambdaInit(1e-16), no
+ * Schur complement (nothing is marginalised), no robust kernel, the information matrix the identity.  ONE problem per call.  The host keeps the walk over
+ * the map -- everything that needs KeyFrame* / MapPoint* -- and hands the problem over as indices into the two device tables the tracker's calls read:
+ * d_pose_table [pose_rows][12] row-major [R|t] floats and d_point_table [point_rows][3].
+ *
+ * Vertices.  nV vertices in the order of vpKFs with bad keyframes left out: d_kf_row [nV] (rows of the pose table); d_kf_fixed [nV] bytes, non-zero for
+ *   mnId == GetInitKFid(); n_free = the number of zero bytes, which the host knows and the call needs to size H (a device count that differs gives status
+ *   FREE_MISMATCH).  d_corrected_index [nV] and d_noncorrected_index [nV] index d_sim3 [nS][8] doubles (qx, qy, qz, qw, tx, ty, tz, s), the entries of
+ *   CorrectedSim3 / NonCorrectedSim3 as CorrectLoop computed them; anything outside [0, nS) -- -1 by convention -- means "not in that map".
+ *   vScw[v] = the corrected entry, or else (Quaterniond(R), t, 1.0) of the pose-table row with R and t widened to double (:1551-1554); Smw[v] = the
+ *   non-corrected entry, or else vScw[v] (:1616-1621, :1632-1637).  The estimate starts at vScw[v].  A STATED DEVIATION: the reference takes
+ *   Tcw.unit_quaternion() of a Sophus SE3f; here the quaternion comes from the float rotation matrix by Eigen's Quaterniond(Matrix3d) branches, as
+ *   xfh_sim3_optimize_device forms its states.  A vertex whose row is outside the table and that has no corrected entry starts at the identity; it has no
+ *   edge and its row is never written.
+ * Edges.  nE edges in the reference's creation order -- per keyframe first all loop-connection edges (:1577-1605), then the spanning-tree edge, the loop
+ *   edges and the covisibility edges (:1608-1706): d_edge_i [nE] (vertex 0), d_edge_j [nE] (vertex 1), d_edge_kind [nE].  Kind 0 is a loop connection, Sji =
+ *   vScw[j] * vScw[i]^-1; every other kind a normal edge, Sji = Smw[j] * Smw[i]^-1.  The minFeat / sInsertedEdges / hasChild filters are the host's.  An edge
+ *   is NO edge (chi2 0) when an index is outside [0, nV), when both indices are the same, or when a vertex's row is outside the pose table.
+ * Points.  d_point_row [nP] (rows of the point table), d_point_ref [nP] the vertex of nIDr (:1759-1768).  A reference outside [0, nV) leaves points_out the
+ *   input; a row outside the table gives 3 zeros; neither is written back.
+ * Edge arithmetic.  EdgeSim3::computeError (types_seven_dof_expmap.h:106-114): error = ((C * v1) * v2^-1).log(), C the measurement.  Sim3::log follows
+ *   sim3.h:148-229 branch for branch: the eps = 1e-5 tests on sigma and d, deltaR, and W.lu().solve(t) as a partial-pivot LU of the 3 x 3 in a fixed order
+ *   (column by column the row with the largest |entry|, a later row only when strictly larger).  chi2 = e . e, the seven terms added in index order.  The
+ *   Jacobians are g2o's numeric ones (base_binary_edge.hpp:56-205): delta 1e-9, central differences through oplusImpl, as xfh_sim3_optimize_device states
+ *   them; with fix_scale the update's seventh entry is zeroed, so column 6 of both Jacobians is exactly 0.  A fixed vertex has no Jacobian and no block.
+ * System.  H [7 n_free][7 n_free] with the free vertices in vertex order, b [7 n_free].  An edge adds Ji^T Ji and Jj^T Jj to its vertices' diagonal blocks,
+ *   Ji^T Jj to the block of the pair, -Ji^T e and -Jj^T e to b; every entry of an edge's term is summed over the 7 rows first, in row order.
+ *   Summation orders (part of the contract only in being FIXED; tests/ref_essential_graph.py mirrors them): a vertex's diagonal block, its b and its share
+ *   of chi2 (the edges whose vertex 0 it is) take its edges in edge order through the 256-lane fold of xfh_pose_optimize_device (lane l adds the edges l,
+ *   l + 256, ..; the xor butterfly 32 .. 1 in each wave of 64; the four waves in order); an off-diagonal block takes the edges between that pair added to
+ *   0 in edge order; the chi2 of the graph is the same fold over the nV vertex shares, computeScale the same fold over the 7 n_free terms.  No
+ *   floating-point atomic: two runs give identical bytes.
+ * Levenberg.  Exactly the paragraph of xfh_pose_optimize_device / xfh_local_ba_device with these particulars: lambda at iteration 0 is 1e-16, the user
+ *   value, not 1e-5 max|diag|; computeScale runs over all 7 n_free unknowns; at most max_iterations <= XFH_EG_MAX_ITERATIONS iterations of at most 10
+ *   trials; after a failed factorisation x keeps its previous values (zero before the first), the update is applied all the same and tempChi = DBL_MAX;
+ *   chi2 [nE] reads _error as the last computeActiveErrors() left it (the stale-error rule).
+ * Solve.  The dense unpivoted fp64 LDL^T of xfh_lba_solve for any n <= 7 XFH_EG_MAX_FREE: it fails at the first pivot not > 0; every entry receives its terms
+ *   (L_ik * L_jk) * d_k in ascending k, each as two rounded products and one rounded subtraction; forward substitution ascending, back-substitution
+ *   DESCENDING.  On the device a left-looking blocked form over the whole GPU with those bits (xfeatslam_amd/csrc/essgraph.hip.h).  It stands in for
+ *   LinearSolverEigen (SimplicialLDLT with an AMD ordering): a STATED DEVIATION, as in the three existing optimisers.
+ * Recovery.  Sim3_out [nV][8] doubles: the estimates.  Tcw_out [nV][12] floats = [R | t / s], R from the normalised quaternion in double, rounded once
+ *   (:1747); a fixed vertex's row is its vScw recovered the same way.  points_out[p] = Swr_corrected.map(vScw[ref].map(P)) in double, rounded once
+ *   (:1771-1776).  write_back = 1 scatters both into the tables (rows inside the tables only; not under FREE_MISMATCH).  UpdateNormalAndDepth and
+ *   IncreaseChangeIndex stay with the host.
+ * Statuses, header[0].  OK; NOTHING_FREE; FREE_MISMATCH; NO_EDGES: no valid edge.  In the last three nothing is optimised: the outputs are the recovery of
+ *   the inputs, chi2 is 0, final_chi2 0.
+ * Limit.  XFH_EG_MAX_FREE = 192 free vertices: a system of 1344 x 1344 doubles, 14 MB of workspace, the largest size at which the call has been run and
+ *   measured (profiles/essential_graph.md) and its factorisation checked by bits against the column form.  The kernels have no bound of their own below 1024 free vertices (7168 x 7168, 411 MB), for which
+ *   the limit was designed; it is raised when a run at that size is on record.  More is refused with XFH_ERR_INVALID_ARG before any
+ *   launch and stays on the host's g2o: a capacity limit, not a speed claim.
+ * Out of scope: the merge form (:1785), OptimizeEssentialGraph4DoF, the inertial edges (:1709-1725).
+ *
+ *   xfh_sim3_log          host, stateless: Sim3::log of sim8 = (qx, qy, qz, qw, tx, ty, tz, s) -> (omega, upsilon, sigma).
+ *   xfh_eg_edge           host, stateless: one edge with measurement meas8 at the estimates Si8, Sj8 -> error [7], chi2, the Jacobians [7][7] row-major of
+ *                         vertex 0 and vertex 1 (zeros where free_i / free_j is 0); any output may be NULL.
+ *   xfh_eg_solve          the LDL^T above on the lower triangle of S [n][n] (overwritten by L and d) -> 1 and x, or 0 with x untouched; n <= 1344.  The bits
+ *                         of xfh_lba_solve where both take n.
+ *   xfh_essential_graph_workspace_bytes   bytes of d_workspace (0 for arguments the call would refuse).
+ *   xfh_essential_graph_device   SYNCHRONOUS: this call does not follow the fixed idle schedule of xfh_local_ba_device.  A factorisation is 2 x
+ *                         ceil(7 n_free / 64) launches, so the host launches one step at a time and reads a small control record back after every trial: at
+ *                         most max_iterations x 10 reads (200), about 21 in a converging run.  It is called once per loop closure from the LoopClosing
+ *                         thread; when it returns every output is written.  A HIP error at any read ends the loop and is returned.  No graph capture, no
+ *                         cooperative launch, no grid barrier; every loop has a bound that does not depend on the data.
+ *                         Outputs: d_Sim3_out [nV][8], d_Tcw_out [nV][12], d_points_out [nP][3], d_chi2 [nE] floats, d_header [9] ints: status, free
+ *                         vertices, valid edges, kind-0 edges, iterations, trials, rejected trials, factorisation failures, corrected points;
+ *                         d_final_chi2: currentChi of the last iteration.
+ *                         XFH_ERR_INVALID_ARG before any launch: n_free > XFH_EG_MAX_FREE (or < 0, or > nV); nV, nE, nP or nS < 1 (or nV > 65535,
+ *                         nE > 2^20, nP > 2^22, nS > 2^17); pose_rows or point_rows < 1; max_iterations outside 1 .. 20; write_back or fix_scale outside
+ *                         0 .. 1; a NULL pointer; a misaligned pointer (16 bytes for the workspace, 8 for doubles, 4 for floats and ints).  Poses, points,
+ *                         similarities and indices may hold anything, NaN and Inf included: the call terminates and no load or store leaves the buffers
+ *                         the caller named.
+ *   xfh_essential_graph   host-pointer form through the ctx staging arena (the tables are copied back when write_back is set).
+ *   xfh_essential_graph_host   the whole rule on ONE host thread over host pointers (workspace included): the kernels' own lines, no ctx, no GPU. */
+#define XFH_EG_MAX_FREE 192
+#define XFH_EG_MAX_ITERATIONS 20
+#define XFH_EG_HEADER_INTS 9
+enum { XFH_EG_OK = 0, XFH_EG_NOTHING_FREE = 1, XFH_EG_FREE_MISMATCH = 2, XFH_EG_NO_EDGES = 3 };
+int xfh_sim3_log(const double* sim8, double* log7);
+int xfh_eg_edge(const double* meas8, const double* Si8, const double* Sj8, int free_i, int free_j, int fix_scale, double* error7, double* chi2,
+                double* jacobian_i49, double* jacobian_j49);
+int xfh_eg_solve(int n, double* S, const double* b, double* x);
+size_t xfh_essential_graph_workspace_bytes(int nV, int nE, int n_free);
+int xfh_essential_graph_device(xfh_ctx* ctx, int nV, int n_free, int nE, int nP, int nS, float* d_pose_table, int pose_rows, float* d_point_table,
+                               int point_rows, const int* d_kf_row, const uint8_t* d_kf_fixed, const int* d_corrected_index, const int* d_noncorrected_index,
+                               const double* d_sim3, const int* d_edge_i, const int* d_edge_j, const int* d_edge_kind, const int* d_point_row,
+                               const int* d_point_ref, int fix_scale, int max_iterations, int write_back, void* d_workspace, double* d_Sim3_out, float* d_Tcw_out,
+                               float* d_points_out, float* d_chi2, int* d_header, double* d_final_chi2);
+int xfh_essential_graph(xfh_ctx* ctx, int nV, int n_free, int nE, int nP, int nS, float* pose_table, int pose_rows, float* point_table, int point_rows,
+                        const int* kf_row, const uint8_t* kf_fixed, const int* corrected_index, const int* noncorrected_index, const double* sim3, const int* edge_i,
+                        const int* edge_j, const int* edge_kind, const int* point_row, const int* point_ref, int fix_scale, int max_iterations, int write_back,
+                        double* Sim3_out, float* Tcw_out, float* points_out, float* chi2, int* header, double* final_chi2);
+int xfh_essential_graph_host(int nV, int n_free, int nE, int nP, int nS, float* pose_table, int pose_rows, float* point_table, int point_rows, const int* kf_row,
+                             const uint8_t* kf_fixed, const int* corrected_index, const int* noncorrected_index, const double* sim3, const int* edge_i,
+                             const int* edge_j, const int* edge_kind, const int* point_row, const int* point_ref, int fix_scale, int max_iterations, int write_back,
+                             void* workspace, double* Sim3_out, float* Tcw_out, float* points_out, float* chi2, int* header, double* final_chi2);
+
 /* ---- MLPnPsolver (src/MLPnPsolver.cpp) as Tracking::Relocalization drives it (src/Tracking.cc:3678-3773) ------------------------------------------
  * The step between xfh_bow_search_device (shared = 2: the current frame against the B relocalisation candidates) and xfh_pose_optimize_device:
  * the PnP RANSAC over 6-point sets.  B problems per call, one candidate keyframe each; inputs as xfh_pose_optimize_device takes them: d_xy_un

@@ -2,7 +2,8 @@
  * xfeat_hip_bench.h -- measurement and debugging entry points of libxfeat_hip.so.  NOT part of the drop-in boundary
  * (include/xfeat_hip.h): nothing a SLAM consumer calls lives here.  bench.py, tools/ and tests/ use these through ctypes.
  * Kernel timers, the match benchmarks, intermediate tensors, and single stages on caller-made input for tests: xfh_debug_select
- * (tests/test_gpu_select.py) and xfh_debug_lba_solve (the LDL^T kernel of LocalBundleAdjustment, tests/test_gpu_lba_solve.py).
+ * (tests/test_gpu_select.py), xfh_debug_lba_solve (the LDL^T kernel of LocalBundleAdjustment, tests/test_gpu_lba_solve.py) and xfh_debug_eg_solve (the
+ * blocked LDL^T of OptimizeEssentialGraph, tests/test_gpu_eg_solve.py).
  */
 #ifndef XFEAT_HIP_BENCH_H
 #define XFEAT_HIP_BENCH_H
@@ -37,7 +38,8 @@ enum {
     XFH_K_SIM3_OPTIMIZE = 56,
     XFH_K_LBA_PLAN = 57, XFH_K_LBA_LINEARIZE = 58, XFH_K_LBA_POINT_BUILD = 59, XFH_K_LBA_BEGIN = 60, XFH_K_LBA_SCHUR = 61, XFH_K_LBA_SOLVE = 62,
     XFH_K_LBA_UPDATE = 63, XFH_K_LBA_EVALUATE = 64, XFH_K_LBA_DECIDE = 65, XFH_K_LBA_FINISH = 66,
-    XFH_K_COUNT = 67
+    XFH_K_EG_PLAN = 67, XFH_K_EG_LINEARIZE = 68, XFH_K_EG_FILL = 69, XFH_K_EG_FACTOR = 70, XFH_K_EG_SUBST = 71, XFH_K_EG_EVALUATE = 72, XFH_K_EG_FINISH = 73,
+    XFH_K_COUNT = 74
 };
 /* layer_mask selects conv layers for XFH_K_CONV_*: 0 = every layer, else bit i = BasicLayer i
  * (0..22 in XFeatModel order) and bit 23 = block_fusion.2 */
@@ -96,6 +98,14 @@ int xfh_debug_select(xfh_ctx* ctx, const unsigned long long* keys, int n, int wi
  * stopped, the strict upper triangle untouched), x the solution or -- after a failed factorisation -- its input bits, *solved the control block's flag
  * (1, or 0 at the first pivot that is not > 0).  XFH_ERR_INVALID_ARG: n not a multiple of 6 in 6 .. 768, a NULL pointer.  Synchronous. */
 int xfh_debug_lba_solve(xfh_ctx* ctx, int n, double* S, const double* b, double* x, int ws_fill, int* solved);
+
+/* The solver of xfh_essential_graph_device alone on a caller-made system (tests/test_gpu_eg_solve.py): the blocked LDL^T (k_eg_ldlt_diag and
+ * k_eg_ldlt_panel per block column of 64) and k_eg_subst, the kernels the call launches and no copy of them, on S [n][n] row-major, b [n] and x [n] in the
+ * ctx staging arena.  Only the lower triangle of S is read.  On return the lower triangle of S holds L and d where the factorisation held (after a failed
+ * factorisation: the block columns finished before it, the rest as handed in), the strict upper triangle is untouched, x is the solution or -- after a
+ * failed factorisation -- its input bits, *solved is 1, or 0 at the first pivot that is not > 0.  The bits of xfh_eg_solve (include/xfeat_hip.h) for any
+ * n in 1 .. 1344 (7 XFH_EG_MAX_FREE).  XFH_ERR_INVALID_ARG: n outside that range, a NULL pointer.  Synchronous. */
+int xfh_debug_eg_solve(xfh_ctx* ctx, int n, double* S, const double* b, double* x, int* solved);
 
 /* Counter calibration (MI355X_MICROARCH.md, HBM section: "calibrate on a known byte count in your own access pattern before
  * trusting an absolute"): `iters` launches of a kernel that moves exactly `nbytes` per launch (a buffer far larger than the

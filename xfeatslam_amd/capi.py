@@ -29,7 +29,7 @@ ERR_EMPTY_IMAGE = 2
 ERR_NO_DEVICE = 7
 ERR_COMM = 11
 
-K = dict(NONE=0, MNN_GEMM=1, CONV_MFMA=2, CONV_DIRECT=3, NMS=4, SELECT=5, DESC=6, HEADS=7, DIST_I32=8, PREPROC=9, BEST2=10, DISTINCTIVE=11, MNN_GEMM_SEG=12, GRID_BUILD=13, SEARCH_WINDOW=14, FRAME_FINISH=15, PROJ_CANDIDATES=16, PROJ_RESOLVE=17, PROJ_COUNT=18, FUSE_SEARCH=19, TRIANGULATION_SEARCH=20, BOW_CANDIDATES=21, BOW_RESOLVE=22, MAPPROJ_CANDIDATES=23, SIM3_SEARCH=24, SIM3_AGREE=25, INIT_CANDIDATES=27, INIT_RESOLVE=28, INIT_FINAL=29, VOCAB_DESCEND=31, VOCAB_FINISH=32, BOWDB_SCORE=33, BOWDB_SELECT=34, POSE_OPTIMIZE=35, TRIANGULATE_PAIRS=36, TRIANGULATE_WINNER=37, TRIANGULATE_FINISH=38, TWOVIEW_PREPARE=39, TWOVIEW_FIT=40, TWOVIEW_SCORE=41, TWOVIEW_SELECT=42, TWOVIEW_CHECK_RT=43, TWOVIEW_FINAL=44, SIM3SOLVE_PREPARE=45, SIM3SOLVE_FIT=46, SIM3SOLVE_COUNT=47, SIM3SOLVE_DECIDE=48, SIM3SOLVE_MERGE=49, MLPNP_PREPARE=50, MLPNP_FIT=51, MLPNP_COUNT=52, MLPNP_RECORDS=53, MLPNP_REFINE=54, MLPNP_DECIDE=55, SIM3_OPTIMIZE=56, LBA_PLAN=57, LBA_LINEARIZE=58, LBA_POINT_BUILD=59, LBA_BEGIN=60, LBA_SCHUR=61, LBA_SOLVE=62, LBA_UPDATE=63, LBA_EVALUATE=64, LBA_DECIDE=65, LBA_FINISH=66)
+K = dict(NONE=0, MNN_GEMM=1, CONV_MFMA=2, CONV_DIRECT=3, NMS=4, SELECT=5, DESC=6, HEADS=7, DIST_I32=8, PREPROC=9, BEST2=10, DISTINCTIVE=11, MNN_GEMM_SEG=12, GRID_BUILD=13, SEARCH_WINDOW=14, FRAME_FINISH=15, PROJ_CANDIDATES=16, PROJ_RESOLVE=17, PROJ_COUNT=18, FUSE_SEARCH=19, TRIANGULATION_SEARCH=20, BOW_CANDIDATES=21, BOW_RESOLVE=22, MAPPROJ_CANDIDATES=23, SIM3_SEARCH=24, SIM3_AGREE=25, INIT_CANDIDATES=27, INIT_RESOLVE=28, INIT_FINAL=29, VOCAB_DESCEND=31, VOCAB_FINISH=32, BOWDB_SCORE=33, BOWDB_SELECT=34, POSE_OPTIMIZE=35, TRIANGULATE_PAIRS=36, TRIANGULATE_WINNER=37, TRIANGULATE_FINISH=38, TWOVIEW_PREPARE=39, TWOVIEW_FIT=40, TWOVIEW_SCORE=41, TWOVIEW_SELECT=42, TWOVIEW_CHECK_RT=43, TWOVIEW_FINAL=44, SIM3SOLVE_PREPARE=45, SIM3SOLVE_FIT=46, SIM3SOLVE_COUNT=47, SIM3SOLVE_DECIDE=48, SIM3SOLVE_MERGE=49, MLPNP_PREPARE=50, MLPNP_FIT=51, MLPNP_COUNT=52, MLPNP_RECORDS=53, MLPNP_REFINE=54, MLPNP_DECIDE=55, SIM3_OPTIMIZE=56, LBA_PLAN=57, LBA_LINEARIZE=58, LBA_POINT_BUILD=59, LBA_BEGIN=60, LBA_SCHUR=61, LBA_SOLVE=62, LBA_UPDATE=63, LBA_EVALUATE=64, LBA_DECIDE=65, LBA_FINISH=66, EG_PLAN=67, EG_LINEARIZE=68, EG_FILL=69, EG_FACTOR=70, EG_SUBST=71, EG_EVALUATE=72, EG_FINISH=73)
 T = dict(X=0, XSTAT=1, SKIP_POOL=2, FEATS=6, M1N=7, H1=8, K1H=9, RAW0=16, STAT0=48, SEL=80)
 
 
@@ -271,6 +271,13 @@ SYMBOLS = [
     ("xfh_local_ba_device", _i, [_vp] + [_i] * 4 + [_vp, _i, _vp, _i] + [_vp] * 6 + [C.POINTER(Camera), _f, _i, _i] + [_vp] * 7),
     ("xfh_local_ba", _i, [_vp] + [_i] * 4 + [_vp, _i, _vp, _i] + [_vp] * 6 + [C.POINTER(Camera), _f, _i, _i] + [_vp] * 6),
     ("xfh_local_ba_host", _i, [_i] * 4 + [_vp, _i, _vp, _i] + [_vp] * 6 + [C.POINTER(Camera), _f, _i, _i] + [_vp] * 7),
+    ("xfh_sim3_log", _i, [_vp, _vp]),
+    ("xfh_eg_edge", _i, [_vp, _vp, _vp, _i, _i, _i] + [_vp] * 4),
+    ("xfh_eg_solve", _i, [_i, _vp, _vp, _vp]),
+    ("xfh_essential_graph_workspace_bytes", _sz, [_i] * 3),
+    ("xfh_essential_graph_device", _i, [_vp] + [_i] * 5 + [_vp, _i, _vp, _i] + [_vp] * 10 + [_i] * 3 + [_vp] * 7),
+    ("xfh_essential_graph", _i, [_vp] + [_i] * 5 + [_vp, _i, _vp, _i] + [_vp] * 10 + [_i] * 3 + [_vp] * 6),
+    ("xfh_essential_graph_host", _i, [_i] * 5 + [_vp, _i, _vp, _i] + [_vp] * 10 + [_i] * 3 + [_vp] * 7),
     ("xfh_distinctive_csr", _i, [_vp, _vp, _i, _vp, _vp, _i, _vp, _vp]),
     ("xfh_distinctive_csr_device", _i, [_vp, _vp, _i, _vp, _vp, _i, _i, _vp, _vp]),
     ("xfh_comm_unique_id", _i, [_vp]),
@@ -313,6 +320,7 @@ SYMBOLS = [
     ("xfh_debug_tensor", _i, [_vp, _i, _i, _vp, _sz, C.POINTER(_sz)]),
     ("xfh_debug_select", _i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     ("xfh_debug_lba_solve", _i, [_vp, _i, _vp, _vp, _vp, _i, _vp]),
+    ("xfh_debug_eg_solve", _i, [_vp, _i, _vp, _vp, _vp, _vp]),
 ]
 
 _lib = None

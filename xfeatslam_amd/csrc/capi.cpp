@@ -86,7 +86,8 @@ const char* xfh_kernel_name(int id) {
                                          "k_sim3solve_prepare", "k_sim3solve_fit", "k_sim3solve_count", "k_sim3solve_decide", "k_sim3merge",
                                          "k_mlpnp_prepare", "k_mlpnp_fit", "k_mlpnp_count", "k_mlpnp_records", "k_mlpnp_refine", "k_mlpnp_decide", "k_sim3_optimize",
                                          "k_lba_plan", "k_lba_linearize", "k_lba_point_build", "k_lba_begin", "k_lba_schur", "k_lba_solve", "k_lba_update",
-                                         "k_lba_evaluate", "k_lba_decide", "k_lba_finish"};
+                                         "k_lba_evaluate", "k_lba_decide", "k_lba_finish",
+                                         "k_eg_plan", "k_eg_linearize", "k_eg_fill", "k_eg_factor", "k_eg_subst", "k_eg_evaluate", "k_eg_finish"};
     return (id >= 0 && id < XFH_K_COUNT) ? n[id] : "?";
 }
 

@@ -239,6 +239,12 @@ hipError_t launch_mlpnp_solve(xfh_ctx* c, const MlArgs& a);                     
 struct LbaArgs;
 hipError_t launch_local_ba(xfh_ctx* c, const LbaArgs& a);                                // lba.hip.h
 hipError_t launch_lba_solve_alone(xfh_ctx* c, const LbaArgs& a);                         // lba.hip.h (xfh_debug_lba_solve)
+struct EgArgs;
+hipError_t launch_eg_plan(xfh_ctx* c, const EgArgs& a);                                  // essgraph.hip.h: the plan, one BUILD, one TRIAL, the outputs
+hipError_t launch_eg_build(xfh_ctx* c, const EgArgs& a);
+hipError_t launch_eg_trial(xfh_ctx* c, const EgArgs& a);
+hipError_t launch_eg_finish(xfh_ctx* c, const EgArgs& a);
+hipError_t launch_eg_solve_alone(xfh_ctx* c, double* S, const double* b, double* x, int* ok, int n);   // essgraph.hip.h (xfh_debug_eg_solve)
 struct VocabArgs;
 hipError_t launch_bow_transform(xfh_ctx* c, const VocabArgs& a, int B);             // vocab_transform.hip.h
 struct BowDbArgs;
